@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the large-scale-chain Metropolis hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): 256x256 synthetic grid, 1024 chains per GPU, fp64,
 Matern(0.9125) spectral proposals, blocks 50-80 cells, sigma_mc = 5, Philox draws generated on the device.
@@ -16,7 +16,9 @@ anything touches the GPU in the parent, waits for them and exits non-zero if any
 starts its own workers too, largeScaleChain_multiprocessing_GPU.py:47, :84-85).  Backend "nccl" (= RCCL);
 GSM_DIST_BACKEND=gloo rehearses the same code path with the ranks sharing the visible GPUs.
 
-Prints ONE JSON line on rank 0 (see the driver contract): metric chain-steps/s, plus
+Prints ONE JSON line on rank 0 (see the driver contract): metric chain-steps/s (`value`), `ms_per_step` (wall time of one timed
+step), the accept rate and the final mean loss.  A plain run does only that: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs) and the line.  With --full the line also holds
   roofline      -- algorithmic HBM bytes (SURVEY.md 8d formula, summed exactly from the recorded blocks/accepts)
                    per launch of the dominant kernel / its average duration (HIP events on its own stream)
   cpu_baseline  -- the NumPy oracle (bit-validated restatement of the reference's CPU loop) under the reference's
@@ -24,6 +26,13 @@ Prints ONE JSON line on rank 0 (see the driver contract): metric chain-steps/s, 
   other_configs -- (N=1, default workload only) short measurements of BASELINE configs[3] (512x512, precomputed-Cholesky
                    generator, MFMA roofline), of one GPU's shard of configs[4] (1024x1024, fp32 state) and of configs[0] (the
                    small-scale chain, 64x64 grid x 4 chains) on the device, in the same run.
+(--no-cpu-baseline / --no-extras leave those two out of a --full run.)
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed back (rank 0's chains): loss.npy and
+accept.npy (chains x inner steps), blocks.npy (row, col, bh, bw of every proposal), beds.npy (the chain states after the
+step) and mean_field.npy (the posterior-mean field of the segment end), float64 / float32; where an array would exceed its
+share of 64 MB, a fixed seeded sample of chains.  Seeds and initial beds depend on the arguments only, so two builds run
+with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -171,8 +180,36 @@ def launch_ranks(n, argv):
     return rc
 
 
-def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, rank, world, dev, classes=2, headline=True):
-    """One workload, timed as the driver contract says; returns the result dict (rank 0) or None."""
+# --dump-outputs: bytes allowed per array (64 MB in all); a larger array is cut to a fixed seeded sample of its first axis
+DUMP_BUDGET = {"loss": 20_000_000, "accept": 10_000_000, "blocks": 8_000_000, "beds": 12_000_000, "mean_field": 14_000_000}
+
+
+def _first_axis_sample(n, row_bytes, budget):
+    """Indices kept along the first axis (n rows of row_bytes each): all of them if they fit, else a fixed seeded sample."""
+    k = max(1, min(n, budget // max(row_bytes, 1)))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, loss, acc, blk, beds, mean_field):
+    """The last timed step's results as DIR/<name>.npy: float64, float32 for accept masks and block records (integers) and for
+    f32 chain states.  loss, accept, blocks and beds have one row per chain, mean_field one per grid row."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": loss.double(), "accept": acc.float(), "blocks": blk.float(), "beds": beds,
+              "mean_field": mean_field.double()}
+    for name, t in arrays.items():
+        idx = _first_axis_sample(t.shape[0], t[0].numel() * t.element_size(), DUMP_BUDGET[name])
+        if len(idx) < t.shape[0]:
+            t = t[torch.as_tensor(idx, device=t.device)]
+        np.save(d / f"{name}.npy", t.cpu().numpy())
+
+
+def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, rank, world, dev, classes=2, headline=True,
+            roofline=True, dump_dir=None):
+    """One workload, timed as the driver contract says; returns the result dict (rank 0) or None.
+    roofline=False leaves out what only the roofline needs (kernel timing events, block records, byte sums)."""
     from mcmc_gpu_amd import parallel, synthetic
     dev_index = dev.index
     n_total = n_local * world
@@ -188,7 +225,8 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
     eng = ch._make_engine(rf, n_local, dev_index)
     eng.set_state(beds0)
     del beds0
-    eng.enable_timing(True)
+    if roofline:
+        eng.enable_timing(True)
     t_setup = time.perf_counter()
     if generator == "cholesky":
         from mcmc_gpu_amd import cholesky as chol
@@ -202,7 +240,7 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
     blk = torch.empty((n_local, inner, 4), dtype=torch.int32, device=dev)
     acc_all = torch.empty((n_local, n_timed), dtype=torch.uint8, device=dev)
     loss_all = torch.empty((n_local, n_timed), dtype=torch.float64, device=dev)
-    blk_all = torch.empty((n_local, n_timed, 4), dtype=torch.int32, device=dev) if rank == 0 else None
+    blk_all = torch.empty((n_local, n_timed, 4), dtype=torch.int32, device=dev) if rank == 0 and roofline else None
 
     def segment_end():
         """Per-chain caches to every rank, posterior-mean field, small results to the host."""
@@ -220,7 +258,8 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
     if warmup > 0:
         acc_all.zero_(); loss_all.zero_()
         segment_end()          # loads torch's reduce/copy kernels and RCCL channels outside the timed region
-        algorithmic_bytes(blk, acc, H, H, sbytes)
+        if roofline:
+            algorithmic_bytes(blk, acc, H, H, sbytes)
     torch.cuda.synchronize(dev)
     parallel.barrier()
     torch.cuda.synchronize(dev)
@@ -232,11 +271,12 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
         step0 += inner
         sl = slice(k * inner, (k + 1) * inner)
         acc_all[:, sl] = acc; loss_all[:, sl] = loss
-        if rank == 0:
-            blk_all[:, sl] = blk     # the roofline numerator is summed from these records after the timed region
-        tm = eng.last_timing()
-        t_step += tm["step_ms"] * tm["step_launches"]; n_step_l += tm["step_launches"]
-        t_prop += tm["proposal_ms"] * tm["proposal_launches"]; n_prop_l += tm["proposal_launches"]
+        if roofline:
+            if rank == 0:
+                blk_all[:, sl] = blk     # the roofline numerator is summed from these records after the timed region
+            tm = eng.last_timing()
+            t_step += tm["step_ms"] * tm["step_launches"]; n_step_l += tm["step_launches"]
+            t_prop += tm["proposal_ms"] * tm["proposal_launches"]; n_prop_l += tm["proposal_launches"]
     h_loss, h_acc_rate, h_mean = segment_end()
     torch.cuda.synchronize(dev)
     parallel.barrier()
@@ -244,12 +284,33 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, dev)
     fused = bool(eng.last_run_fused())
     strip = bool(eng.strip_active())          # chain_strip_kernel (two chains per CU) or chain_fused_kernel (one)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, acc, blk, eng.beds, h_mean)
     eng.close()
     del eng
     if rank != 0:
         return None
 
     chain_steps = n_total * n_timed
+    gen_txt = ("spectral (Matern 0.9125) proposals" if generator == "spectral" else
+               f"precomputed-Cholesky (Matern 0.9125, {classes} range classes) proposals")
+    tag = {("spectral", "f64", 256): "BASELINE configs[1]" if world == 1 else "BASELINE configs[2] at 8 GPUs: 1024 chains/GPU",
+           ("cholesky", "f64", 512): "BASELINE configs[3]",
+           ("spectral", "f32", 1024): "BASELINE configs[4], one GPU's shard"}.get((generator, state, H), "")
+    res = {
+        "metric": f"chain-steps/sec on {H}x{H} grid x {n_local} chains{' per GPU' if world > 1 else ''}; accept-rate parity",
+        "value": chain_steps / elapsed, "unit": "chain-steps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64" if state == "f64" else "f64 arithmetic on f32 state", "data": "synthetic",
+        "config": {"workload": f"largeScaleChain {H}x{H} grid, {n_local} chains/GPU, "
+                               f"{'fp64' if state == 'f64' else 'fp32 state / fp64 arithmetic'}, Philox {gen_txt}, blocks 50-80, "
+                               f"sigma_mc 5" + (f" ({tag})" if tag else ""),
+                   "chains_total": n_total, "mh_steps_per_bench_step": inner,
+                   "timed_seconds": elapsed, "setup_seconds_factors": t_setup if generator == "cholesky" else None},
+        "accept_rate": h_acc_rate, "final_loss_mean": float(h_loss.mean()),
+    }
+    if not roofline:
+        return res
     bytes_total, flops_total = 0, 0.0
     for k in range(steps):       # device-side sums, one bench step at a time (bounded temporaries)
         sl = slice(k * inner, (k + 1) * inner)
@@ -285,24 +346,9 @@ def measure(args, H, n_local, generator, state, inner, batch, steps, warmup, ran
             roof["issue_limits"] = dict(sq, source=src)
         if not fused:
             roof["step_kernel_ms"] = step_ms; roof["propose_kernel_ms"] = prop_ms
-    gen_txt = ("spectral (Matern 0.9125) proposals" if generator == "spectral" else
-               f"precomputed-Cholesky (Matern 0.9125, {classes} range classes) proposals")
-    tag = {("spectral", "f64", 256): "BASELINE configs[1]" if world == 1 else "BASELINE configs[2] at 8 GPUs: 1024 chains/GPU",
-           ("cholesky", "f64", 512): "BASELINE configs[3]",
-           ("spectral", "f32", 1024): "BASELINE configs[4], one GPU's shard"}.get((generator, state, H), "")
-    return {
-        "metric": f"chain-steps/sec on {H}x{H} grid x {n_local} chains{' per GPU' if world > 1 else ''}; accept-rate parity",
-        "value": chain_steps / elapsed, "unit": "chain-steps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64" if state == "f64" else "f64 arithmetic on f32 state", "data": "synthetic",
-        "config": {"workload": f"largeScaleChain {H}x{H} grid, {n_local} chains/GPU, "
-                               f"{'fp64' if state == 'f64' else 'fp32 state / fp64 arithmetic'}, Philox {gen_txt}, blocks 50-80, "
-                               f"sigma_mc 5" + (f" ({tag})" if tag else ""),
-                   "chains_total": n_total, "mh_steps_per_bench_step": inner, "steps_per_launch": steps_per_launch,
-                   "timed_seconds": elapsed, "setup_seconds_factors": t_setup if generator == "cholesky" else None},
-        "accept_rate": h_acc_rate, "final_loss_mean": float(h_loss.mean()),
-        "roofline": roof,
-    }
+    res["config"]["steps_per_launch"] = steps_per_launch
+    res["roofline"] = roof
+    return res
 
 
 # sgs_weights_kernel: vector wave-instructions per simulated cell at the driver configuration (48 neighbours: ring search + 49-step
@@ -438,9 +484,13 @@ def main():
     ap.add_argument("--inner", type=int, default=2048,
                     help="Metropolis steps per chain in one bench step (2048: --steps 20 times several seconds)")
     ap.add_argument("--batch", type=int, default=32, help="steps per kernel launch of the two-kernel pipeline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the CPU baseline and the other configurations (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[3] / configs[4]-shard lines")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the other configurations' lines")
     ap.add_argument("--gather-beds", action="store_true", help="also all-gather the final beds (512 MiB per GPU at 256^2)")
     ap.add_argument("--generator", choices=["spectral", "cholesky"], default="spectral",
                     help="proposal generator: the reference's spectral synthesis (headline) or precomputed Cholesky factors (BASELINE configs[3])")
@@ -477,7 +527,7 @@ def main():
 
     default_workload = (args.grid, args.chains, args.generator, args.state) == (256, 1024, "spectral", "f64")
     cpu_res = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(args.grid, args.cpu_budget)   # before the GPU is initialised: the pool forks
     rank, local_rank, world = parallel.init_distributed()
     dev_index = local_rank if torch.cuda.device_count() > local_rank else 0
@@ -486,7 +536,7 @@ def main():
 
     inner = args.inner if args.generator == "spectral" else min(args.inner, 256)
     out = measure(args, args.grid, args.chains, args.generator, args.state, inner, args.batch, args.steps, args.warmup,
-                  rank, world, dev, classes=args.classes)
+                  rank, world, dev, classes=args.classes, roofline=args.full, dump_dir=args.dump_outputs)
     if rank == 0:
         out["world_size"] = torch.distributed.get_world_size() if world > 1 else 1
         out["launcher"] = "self" if os.environ.get("GSM_BENCH_SELF_LAUNCHED") else ("torchrun" if world > 1 else "single process")
@@ -494,7 +544,7 @@ def main():
             out["backend"] = torch.distributed.get_backend()
         if cpu_res is not None:
             out["cpu_baseline"] = cpu_res
-    if world == 1 and default_workload and not args.no_extras:
+    if world == 1 and default_workload and args.full and not args.no_extras:
         extras = {}
         for name, kw in (("configs[3]", dict(H=512, n_local=1024, generator="cholesky", state="f64", inner=256, batch=128, steps=3, warmup=1)),
                          ("configs[4] one GPU's shard", dict(H=1024, n_local=512, generator="spectral", state="f32", inner=512, batch=32, steps=3, warmup=1))):

@@ -10,7 +10,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 cd $root
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $out/bench_profiled.json 2> $out/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $out/bench_profiled.json 2> $out/trace.err
 echo "trace rc=$?"
 python3 scripts/pmc_fused.py 2048 > $out/workload.jsonl 2> $out/workload.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 scripts/pmc_fused.py 2048 > $out/fetch.log 2>&1; echo "fetch rc=$?"
