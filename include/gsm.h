@@ -404,6 +404,43 @@ int gsm_sgs_commit(gsm_handle h, double* cur, double* next, uint32_t* resampled,
 #define GSM_KRIGING_SIMPLE 1
 int gsm_sgs_set_kriging(gsm_handle h, int32_t ktype, const double* global_mean);
 
+/* ---- interpolate.sgs on whole grids (gstatsim_custom/interpolate.py:92-191) --------------------------------------------
+ * Sequential Gaussian simulation of n_chains = R whole-grid realisations on one handle, in normal-score space.
+ *   grids    [dev, R*H*W] in/out        normal scores: the conditioning values, NaN at every cell without one; on return
+ *                                       every path cell holds its simulated value (NaN cells off the paths stay NaN)
+ *   path     [dev, total]               flat cell indices (row * W + col) in visiting order -- the caller's rng.shuffle of
+ *                                       the cells of sim_mask (interpolate.py:127) without the cells that hold a value;
+ *                                       realisation r's path is path[path_off[r] .. path_off[r + 1])
+ *   path_off [dev, R + 1]               int64 offsets; max_path >= the longest path
+ *   draws    [dev, total]               one number per path cell: draw_kind GSM_DRAW_NORMAL, a standard normal,
+ *                                       rng.normal(est, sqrt(var), 1) = est + sqrt(var) * z (interpolate.py:174);
+ *                                       GSM_DRAW_TRUNCATED, a uniform u (rng.random()): truncnorm.rvs(a, b, loc=est,
+ *                                       scale=sqrt(var)) = truncnorm.ppf(u, a, b) * scale + est with a, b = (lower - est) /
+ *                                       scale, (upper - est) / scale (interpolate.py:176-187; scipy 1.15's truncnorm has
+ *                                       no _rvs of its own).  Unused at cells whose bounds coincide
+ *   lower, upper [dev, H*W] or NULL     transformed bounds (GSM_DRAW_TRUNCATED only): a cell with lower == upper takes
+ *                                       lower and solves no system (interpolate.py:181-182)
+ *   x_axis, y_axis, lag_cov, lag_mi, lag_mj, hw, radius, num_points, sill   as in gsm_sgs_blocks.  The search widens by
+ *                                       100 km steps (interpolate.py:150-157): lag_mi / lag_mj must cover 2 ceil(r / |dx|)
+ *                                       for the widest radius r any visit reaches (or H - 1 / W - 1)
+ *   seg_cells                           path slots whose records (800 bytes each per realisation) are resident at once,
+ *                                       rounded up to a multiple of 64; the result does not depend on it
+ *   trace    [dev, total*3] or NULL     (number of neighbours, kriging estimate, kriging variance) per path cell; -1
+ *                                       neighbours where no system was solved (bounds coincide)
+ * Kriging type and, for simple kriging, the global mean of each realisation [dev, R] from gsm_sgs_set_kriging.
+ * Neighbour sets, tie order and solve as gsm_sgs_blocks; the truncated-normal ppf restates scipy's (csrc/truncnorm.h).
+ * Errors: GSM_E_ARG for H * W > 2^25 (25-bit slot / cell fields) or inconsistent arguments; GSM_E_DEVICE_DATA for a path
+ * cell that holds a value or is listed twice, a cell with no value anywhere, a singular system, a lag table too small, or a
+ * truncated draw outside scipy's domain (scale 0 or lower >= upper after standardising).  Synchronises the stream.
+ * Replaces: interpolate.sgs (gstatsim_custom/interpolate.py:92-191), neighbors (gstatsim_custom/neighbors.py:4-64),
+ * ok_solve / sk_solve (gstatsim_custom/_krige.py:5-81). */
+#define GSM_DRAW_NORMAL 0
+#define GSM_DRAW_TRUNCATED 1
+int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                 const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                 const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
+                 int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream);
+
 /* One batch of small-scale iterations in ONE call: for j < n_iters, in the order of chain_sgs.run's loop body
  * (MCMC.py:1741-1822) -- [gsm_qt_transform cur -> next] gsm_sgs_blocks_batch [gsm_sgs_finish | gsm_qt_transform next ->
  * proposed, gsm_sgs_loss, gsm_sgs_decide, gsm_sgs_commit(_map)] -- with iteration j's draws at windows + 4*n_chains*j,

@@ -1034,6 +1034,71 @@ extern "C" int gsm_sgs_set_kriging(gsm_handle h, int32_t ktype, const double* gl
   return GSM_OK;
 }
 
+extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                            const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                            const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
+                            int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream) {
+  if (!h) return GSM_E_ARG;
+  const char* who = "gsm_sgs_grid";
+  const std::string w(who);
+  if (!grids || !path || !path_off || !draws || !x_axis || !y_axis || !lag_cov) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  if (draw_kind != GSM_DRAW_NORMAL && draw_kind != GSM_DRAW_TRUNCATED) return fail(h, GSM_E_ARG, w + ": draw_kind must be GSM_DRAW_NORMAL or GSM_DRAW_TRUNCATED");
+  if ((draw_kind == GSM_DRAW_TRUNCATED) != (lower != nullptr) || (lower != nullptr) != (upper != nullptr))
+    return fail(h, GSM_E_ARG, w + ": bounds (lower and upper) go with GSM_DRAW_TRUNCATED and only with it");
+  if (hw < 1) return fail(h, GSM_E_ARG, w + ": search half-width (ceil(radius / grid spacing)) must be >= 1 cell");
+  if (num_points < 8 || num_points > 48) return fail(h, GSM_E_UNSUPPORTED, w + ": num_points must be in [8, 48]");
+  if (!(radius > 0.0)) return fail(h, GSM_E_ARG, w + ": radius must be > 0");
+  if (lag_mi < 0 || lag_mj < 0) return fail(h, GSM_E_ARG, w + ": lag table extents must be >= 0");
+  if (h->H > 32767 || h->W > 32767 || (int64_t)h->H * h->W > (1LL << 25))
+    return fail(h, GSM_E_ARG, w + ": at most 2^25 cells and 32767 per side (25-bit slot and cell fields in the records)");
+  if (h->n_chains > 65535) return fail(h, GSM_E_ARG, w + ": at most 65535 realisations per handle");
+  if (max_path < 0 || (int64_t)max_path > (int64_t)h->H * h->W) return fail(h, GSM_E_ARG, w + ": max_path must be in [0, H * W]");
+  if (seg_cells < 1) return fail(h, GSM_E_ARG, w + ": seg_cells must be >= 1");
+  if (h->sgs_ktype == GSM_KRIGING_SIMPLE && !h->sgs_gmean) return fail(h, GSM_E_STATE, w + ": simple kriging without global means");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t R = (size_t)h->n_chains, HW = (size_t)h->H * h->W;
+  const int seg_cap = (int)std::min<int64_t>(((int64_t)seg_cells + 63) / 64 * 64, std::max<int64_t>(64, ((int64_t)max_path + 63) / 64 * 64));
+  SgsGridArgs a{};
+  a.H = h->H; a.W = h->W; a.n_real = (int)R;
+  a.grid = grids; a.path = path; a.path_off = path_off; a.draw = draws; a.lo = lower; a.hi = upper; a.draw_kind = draw_kind;
+  a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov; a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points;
+  a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.radius = radius; a.sill = sill; a.trace = trace; a.err = h->d_err;
+  a.seg_cap = seg_cap; a.seg_len = seg_cap;
+  // scratch of the call: ranks [R][H*W], then per realisation seg_cap records (headers + 48 (value, weight) entries)
+  const size_t bytes = R * HW * sizeof(int32_t) + 256 + R * (size_t)seg_cap * (sizeof(SgsGridHdr) + 48 * sizeof(double2));
+  void* scratch = nullptr;
+  hipError_t e = hipMalloc(&scratch, bytes);
+  if (e != hipSuccess) return fail(h, GSM_E_HIP, w + ": records of " + std::to_string(seg_cap) + " slots x " + std::to_string(R) +
+                                                 " realisations: " + hipGetErrorString(e));
+  char* p = (char*)scratch;
+  a.rec_vw = (double2*)p; p += R * (size_t)seg_cap * 48 * sizeof(double2);
+  a.rec_hdr = (SgsGridHdr*)p; p += R * (size_t)seg_cap * sizeof(SgsGridHdr);
+  a.rank = (int32_t*)p;
+  e = launch_sgs_grid_ranks(a, max_path, st);
+  for (int s0 = 0; e == hipSuccess && s0 < max_path; s0 += seg_cap) {
+    a.seg0 = s0; a.seg_len = std::min(seg_cap, max_path - s0);
+    e = launch_sgs_grid_segment(a, st);
+  }
+  int32_t flag = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&flag, h->d_err, sizeof(flag), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  hipFree(scratch);
+  if (e != hipSuccess) return fail(h, GSM_E_HIP, w + ": " + hipGetErrorString(e));
+  if (!flag) return GSM_OK;
+  hipMemsetAsync(h->d_err, 0, sizeof(int32_t), st);
+  hipStreamSynchronize(st);
+  if (flag & 2) return fail(h, GSM_E_DEVICE_DATA, w + ": a path cell outside the grid, holding a value, or listed twice");
+  if (flag & 4) return fail(h, GSM_E_DEVICE_DATA, w + ": a cell to simulate has no value anywhere on the grid (the reference would widen "
+                                                   "its search radius for ever, interpolate.py:150-157)");
+  if (flag & 8) return fail(h, GSM_E_DEVICE_DATA, w + ": singular kriging system (a pivot below eps * N * max|diag|)");
+  if (flag & 64) return fail(h, GSM_E_ARG, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                            "(it must cover twice the widest search radius)");
+  if (flag & 128) return fail(h, GSM_E_DEVICE_DATA, w + ": truncated-normal draw outside scipy's domain (kriging variance 0, or "
+                                                     "lower >= upper after standardising)");
+  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+}
+
 extern "C" int gsm_sgs_check(gsm_handle h, void* stream) {
   if (!h) return GSM_E_ARG;
   HIPCHK(h, hipSetDevice(h->device));

@@ -222,6 +222,36 @@ struct SgsArgs {
                            //  or NaN-boxed (visiting slot << 16 | block-local index) where the neighbour is a cell simulated earlier in
                            //  the block; its kriging weight)
 };
+// interpolate.sgs on whole grids, many realisations at once (sgs_grid_kernel.hip)
+struct SgsGridHdr {          // one per (realisation, path slot of the segment), written by sgs_grid_weights_kernel
+  int32_t n;                 // neighbours; -3: the cell's bounds coincide (value = lower bound, no system); -2: invalid path entry; 0: error
+  int32_t cell;              // flat grid index of the cell
+  double sd;                 // sqrt(|kriging variance|)
+  double var;                // |kriging variance|
+  double c1;                 // ordinary: (1 - sum of the kriging weights) / n; simple: global mean * (1 - sum of the weights)
+};
+struct SgsGridArgs {
+  int H, W, n_real;
+  double* grid;            // [n_real][H*W] normal scores, NaN where a value is to be simulated; the path cells are rewritten
+  const int32_t* path;     // flat cell indices in visiting order, realisation r's at [path_off[r], path_off[r + 1])
+  const int64_t* path_off; // [n_real + 1]
+  const double* draw;      // [total] standard normal (draw_kind 0) or uniform (draw_kind 1) per path cell
+  const double* lo;        // [H*W] transformed lower / upper bounds, or nullptr (draw_kind 0)
+  const double* hi;
+  int draw_kind;
+  const double* xs; const double* ys; const double* lag;
+  int hw, mi, mj, num_points, ktype;
+  const double* gmean;     // [n_real] (simple kriging)
+  double radius, sill;
+  double* trace;           // optional [total*3]: (neighbours, estimate, variance) per path cell
+  int32_t* err;
+  int32_t* rank;           // [n_real][H*W]: -1 conditioning value, slot of a path cell, INT32_MAX never filled
+  int seg0, seg_len, seg_cap;   // this segment: slots [seg0, seg0 + seg_len); records per realisation (a multiple of 64)
+  SgsGridHdr* rec_hdr;     // [n_real*seg_cap]
+  double2* rec_vw;         // [n_real*seg_cap/64][48][64]: (value, or NaN-boxed (slot << 25 | cell) of a path cell; kriging weight)
+};
+hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
+hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st);      // weights, then values of one segment
 hipError_t launch_sgs_blocks(const SgsArgs& a, int launch_cells, hipStream_t st);
 hipError_t launch_sgs_weights(const SgsArgs& a, int launch_cells, hipStream_t st);     // ranks + records
 hipError_t launch_sgs_sequence(const SgsArgs& a, hipStream_t st);                      // value pass

@@ -1,0 +1,258 @@
+"""Device mirror of gstatsim_custom.interpolate.sgs (gstatsMCMC/gstatsim_custom/interpolate.py:92-191): sequential Gaussian
+simulation of a whole grid, the step that makes the chains' initial beds (T2_StatisticalAnalysis.ipynb calls it once per seed).
+
+    sgs       interpolate.sgs's arguments and return value, plus `device`
+    sgs_many  many realisations in one call, row r == sgs(..., seed=seeds[r]) bit for bit
+
+The host does what the reference does with its generator, in its order -- one rng.shuffle of the cells of sim_mask, then one
+standard normal per simulated cell (rng.normal(est, sd, 1) = est + sd * z) or, with bounds, one uniform per simulated cell whose
+bounds differ (truncnorm.rvs = truncnorm.ppf(uniform, a, b) * scale + est) -- and the normal-score transform with
+scikit-learn (utilities.gaussian_transformation, the same call).  Neighbour search, kriging and the sequential value pass
+run on the device (gsm_sgs_grid, csrc/sgs_grid_kernel.hip); nothing is computed on the CPU in their place.
+
+Numerics: the kriging systems are solved by Gauss-Jordan elimination where the reference calls numpy.linalg.lstsq, and the
+truncated-normal ppf is a restatement of scipy's (csrc/truncnorm.h), so values agree with the reference to ~1e-9 of the
+normal-score scale, not bit for bit.  Equidistant neighbour candidates are taken in ascending (row, col); the reference's
+argsort is unstable there.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import numbers
+
+import numpy as np
+
+from .sgs import _axes, _ptr, lag_cov_table
+
+__all__ = ["sgs", "sgs_many"]
+
+RECORD_BYTES = 800          # one path cell's record on the device: 48 (value, weight) pairs + a 32-byte header
+WIDEN_STEP = 100e3          # interpolate.py:155
+
+
+def _sanity_checks(xx, yy, grid, vario, radius, num_points, ktype, sim_mask):
+    """The argument errors of interpolate._sanity_checks (interpolate.py:265-330), same types and messages."""
+    for name, a in (("xx", xx), ("yy", yy), ("grid", grid)):
+        if not isinstance(a, np.ndarray) or a.ndim != 2:
+            raise ValueError(f"{name} must be a 2D NumPy array")
+    if xx.shape != yy.shape or xx.shape != grid.shape:
+        raise ValueError("xx, yy, and grid must have same shape")
+    missing = [k for k in ("major_range", "minor_range", "azimuth", "sill", "nugget", "vtype") if k not in vario.keys()]
+    if missing:
+        raise ValueError(f"Variogram missing {', '.join(missing)}")
+    if vario["vtype"].lower() not in ("matern", "exponential", "gaussian", "spherical"):
+        raise ValueError("vtype must be exponential, gaussian, spherical, or matern")
+    if vario["vtype"].lower() == "matern" and "s" not in vario.keys():
+        raise ValueError("Matern covariance requires the s parameter in the variogram")
+    if sim_mask is not None:
+        if not isinstance(sim_mask, np.ndarray):
+            raise ValueError("sim_mask must be None or a 2D array")
+        if sim_mask.shape != grid.shape:
+            raise ValueError("sim_mask shape must be same as grid if provided")
+    for k, v in vario.items():
+        if k == "vtype":
+            continue
+        if isinstance(v, numbers.Number):
+            if np.isnan(v):
+                raise ValueError(f"variogram parameter {k} is NaN")
+        elif isinstance(v, np.ndarray):
+            bad = np.isnan(v) if sim_mask is None else (sim_mask == True) & np.isnan(v)  # noqa: E712
+            if np.count_nonzero(bad) > 0:
+                raise ValueError(f"Variogram parameter {k} contains NaN" + ("" if sim_mask is None else " in sim_mask"))
+    if not isinstance(radius, numbers.Number):
+        raise ValueError("radius must be a number")
+    if not isinstance(num_points, numbers.Number):
+        raise ValueError("num_points must be a number")
+    if ktype not in ("ok", "sk"):
+        raise ValueError("ktype must be 'ok' or 'sk'")
+
+
+def _generator(seed):
+    """utilities.get_random_generator (utilities.py:50-70)."""
+    if seed is None:
+        return np.random.default_rng()
+    if isinstance(seed, int):
+        return np.random.default_rng(seed=seed)
+    if isinstance(seed, np.random.Generator):
+        return seed
+    raise ValueError("Seed should be an integer, a NumPy random Generator, or None")
+
+
+class _Plan:
+    """Everything of one call that does not depend on the seed: the fitted transformer, the grid in normal-score space, the
+    transformed bounds and the cells of sim_mask in the reference's (C) order."""
+
+    def __init__(self, xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil, rcond, bounds):
+        from sklearn.preprocessing import QuantileTransformer
+        _sanity_checks(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask)
+        if stencil is not None or rcond is not None:
+            raise NotImplementedError("the device SGS searches the circular stencil and solves with lstsq's default cut-off "
+                                      "(stencil=None, rcond=None)")
+        if any(isinstance(v, np.ndarray) for k, v in variogram.items() if k != "vtype"):
+            raise NotImplementedError("the device SGS takes scalar variogram parameters (one covariance table per call)")
+        if not 8 <= int(num_points) <= 48:
+            raise NotImplementedError("the device SGS takes 8 <= num_points <= 48")
+        grid = np.asarray(grid, dtype=np.float64)
+        self.H, self.W = grid.shape
+        self.cond = ~np.isnan(grid)
+        if not self.cond.any():
+            raise ValueError("grid holds no conditioning value (the reference's neighbour search would widen for ever)")
+        # utilities.gaussian_transformation (utilities.py:7-25)
+        self.nst = QuantileTransformer(n_quantiles=500, output_distribution="normal").fit(grid[self.cond].reshape(-1, 1))
+        self.grid_ns = np.full(grid.shape, np.nan)
+        np.place(self.grid_ns, self.cond, self.nst.transform(grid[self.cond].reshape(-1, 1)).squeeze())
+        self.global_mean = float(np.mean(self.grid_ns[self.cond]))
+        self.bounds = None if bounds is None else self._bounds(bounds, xx.shape)
+        if sim_mask is None:
+            sim_mask = np.full(xx.shape, True)
+        ii, jj = np.meshgrid(np.arange(self.H), np.arange(self.W), indexing="ij")
+        self.inds = np.array([ii[sim_mask].flatten(), jj[sim_mask].flatten()]).T
+        self.xs, self.ys, self.dx, self.dy = _axes(np.asarray(xx, dtype=np.float64), np.asarray(yy, dtype=np.float64))
+        self.vario = {k: (v if k == "vtype" else float(v)) for k, v in variogram.items()}
+        self.radius, self.num_points, self.ktype = float(radius), int(num_points), ktype
+
+    def _bounds(self, bounds, shape):
+        """interpolate._preprocess's bounds (interpolate.py:240-261): a number is transformed and broadcast, an array of the
+        grid's shape is transformed cell by cell; any other input is the reference's ValueError."""
+        try:
+            if len(bounds) != 2:
+                raise ValueError
+            out = []
+            for b in bounds:
+                if isinstance(b, numbers.Number):
+                    out.append(np.full(shape, self.nst.transform(np.array([b]).reshape(-1, 1)).squeeze()))
+                elif isinstance(b, np.ndarray):
+                    if b.shape != shape:
+                        raise ValueError
+                    out.append(self.nst.transform(b.reshape(-1, 1)).reshape(shape))
+                else:
+                    raise ValueError
+        except Exception:
+            raise ValueError("bounds must be None or a 2D numpy array") from None
+        return np.ascontiguousarray(out[0], dtype=np.float64), np.ascontiguousarray(out[1], dtype=np.float64)
+
+    def draws(self, rng):
+        """Consume `rng` as interpolate.sgs does: (path of flat cell indices, one number per path cell)."""
+        inds = self.inds.copy()
+        rng.shuffle(inds)                                                            # interpolate.py:127
+        flat = inds[:, 0] * self.W + inds[:, 1]
+        path = flat[~self.cond.ravel()[flat]]
+        if self.bounds is None:
+            d = rng.standard_normal(path.size)                                       # rng.normal(est, sd, 1), :174
+        else:
+            lo, hi = self.bounds
+            live = lo.ravel()[path] != hi.ravel()[path]                              # lo == hi: no draw, :181-182
+            d = np.zeros(path.size)
+            d[live] = rng.random(int(live.sum()))                                    # truncnorm.rvs: uniform(size=1), :185
+        return np.ascontiguousarray(path, dtype=np.int32), d
+
+
+def _lag_extents(plan, eng, torch):
+    """Lag table extents that the radius widening never runs off: every visit's radius stays below radius + 100 km k, with k
+    from the largest distance of a cell to simulate to the nearest conditioning value (gsm_min_dist_from_mask)."""
+    H, W = plan.H, plan.W
+    dev = eng.dev
+    xx = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(plan.xs[None, :], (H, W)))).to(dev)
+    yy = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(plan.ys[:, None], (H, W)))).to(dev)
+    mask = torch.as_tensor(plan.cond.astype(np.uint8).ravel()).to(dev)
+    dist = torch.empty(H * W, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        eng._check(eng.lib.gsm_min_dist_from_mask(eng.h, _ptr(xx), _ptr(yy), _ptr(mask), _ptr(dist), eng._stream()))
+    d = dist.cpu().numpy()[~plan.cond.ravel()]
+    d_max = float(d.max()) if d.size else 0.0
+    k = 0 if d_max < plan.radius else int(math.floor((d_max - plan.radius) / WIDEN_STEP)) + 1
+    r_max = plan.radius + WIDEN_STEP * k
+    hw_max = int(math.ceil(r_max / abs(plan.dx))) + 1
+    return min(2 * hw_max, H - 1), min(2 * hw_max, W - 1)
+
+
+def _segment_cells(R, max_path, torch, dev, extra_bytes):
+    free, _ = torch.cuda.mem_get_info(dev)
+    budget = (free - extra_bytes) // 2
+    s = int(budget // (R * RECORD_BYTES)) // 64 * 64
+    if s < 64:
+        raise MemoryError(f"not enough device memory for 64 path slots of records x {R} realisations")
+    return max(64, min(s, (max_path + 63) // 64 * 64))
+
+
+def _run(plan, gens, segment_cells=None, device=None, trace=False):
+    """Draw for every generator in turn, simulate all realisations in one gsm_sgs_grid call.  Returns the normal-score grids
+    [R, H, W] and, with trace, (paths, traces [total, 3])."""
+    import torch
+    from .engine import GsmEngine
+    plans = [plan.draws(g) for g in gens]
+    R, H, W = len(plans), plan.H, plan.W
+    lens = np.array([p.size for p, _ in plans], dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    max_path = int(lens.max()) if R else 0
+    eng = GsmEngine(H, W, R, device)
+    try:
+        dev, lib, h = eng.dev, eng.lib, eng.h
+        mi, mj = _lag_extents(plan, eng, torch)
+        if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
+            raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not fit "
+                              "the device; raise `radius` or add conditioning data")
+        hw = int(math.ceil(plan.radius / abs(plan.dx)))
+        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        grids = f64(plan.grid_ns)[None].repeat(R, 1, 1).contiguous()
+        d_path = torch.as_tensor(np.concatenate([p for p, _ in plans])).to(dev)
+        d_off = torch.as_tensor(off).to(dev)
+        d_draw = f64(np.concatenate([d for _, d in plans]))
+        d_lo = d_hi = None
+        if plan.bounds is not None:
+            d_lo, d_hi = f64(plan.bounds[0]), f64(plan.bounds[1])
+        d_xs, d_ys = f64(plan.xs), f64(plan.ys)
+        d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        d_gm = f64(np.full(R, plan.global_mean))
+        d_tr = torch.zeros((int(off[-1]), 3), dtype=torch.float64, device=dev) if trace else None
+        if segment_cells is None:
+            segment_cells = _segment_cells(R, max_path, torch, dev, 0)
+        with torch.cuda.device(dev):
+            eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
+            eng._check(lib.gsm_sgs_grid(h, _ptr(grids), _ptr(d_path), _ptr(d_off), max_path, _ptr(d_draw), _ptr(d_lo), _ptr(d_hi),
+                                        1 if plan.bounds is not None else 0, _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), mi, mj, hw,
+                                        plan.radius, plan.num_points, float(plan.vario["sill"]), int(segment_cells), _ptr(d_tr),
+                                        eng._stream()))
+        ns = grids.cpu().numpy()
+        extra = ([p for p, _ in plans], d_tr.cpu().numpy()) if trace else None
+    finally:
+        eng.close()
+    return ns, extra
+
+
+def _inverse(plan, ns):
+    return plan.nst.inverse_transform(ns.reshape(-1, 1)).squeeze().reshape(ns.shape)
+
+
+def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None, rcond=None,
+        bounds=None, seed=None, device=None):
+    """Sequential Gaussian simulation with ordinary ('ok') or simple ('sk') kriging on the device -- interpolate.sgs
+    (gstatsim_custom/interpolate.py:92-191): same arguments and return value (the simulated grid in data units), the generator
+    consumed exactly as the reference consumes it.  `device`: CUDA/HIP device index (default: torch's current device).
+    Not supported (NotImplementedError): a custom stencil, rcond other than None, per-cell variogram arrays, num_points
+    outside [8, 48], a grid that is not axis-aligned with uniform spacing.  A grid without any conditioning value raises
+    ValueError (the reference never terminates there); so does a truncated draw scipy would not make (kriging variance 0,
+    or bounds that leave no interval), raised from the device as GsmError."""
+    return sgs_many(xx, yy, grid, variogram, [seed], radius=radius, num_points=num_points, ktype=ktype, sim_mask=sim_mask,
+                    quiet=quiet, stencil=stencil, rcond=rcond, bounds=bounds, device=device)[0]
+
+
+def sgs_many(xx, yy, grid, variogram, seeds, *, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None,
+             rcond=None, bounds=None, segment_cells=None, device=None):
+    """len(seeds) realisations of interpolate.sgs in one device call: out[r] is bit for bit sgs(..., seed=seeds[r]) -- an int,
+    a numpy Generator (advanced exactly as the reference advances it, in the order of `seeds`) or None.  Returns [R, H, W];
+    list(out) is what largeScaleChain_mp takes as initial_beds.
+    One normal-score transformer is fitted for all rows.  That equals separate calls while the conditioning data hold at most
+    10 000 values: above that scikit-learn's QuantileTransformer fits on a random subsample (subsample=10_000, random_state=None),
+    so the reference's own fit differs from call to call there.
+    segment_cells: path slots whose records are resident at once (default: from the free device memory); it does not change
+    the result."""
+    plan = _Plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil, rcond, bounds)
+    if segment_cells is not None and int(segment_cells) < 1:
+        raise ValueError("segment_cells must be >= 1")
+    gens = [_generator(s) for s in seeds]
+    if not gens:
+        return np.zeros((0,) + plan.grid_ns.shape)
+    ns, _ = _run(plan, gens, segment_cells, device)
+    return _inverse(plan, ns)

@@ -1,0 +1,70 @@
+"""Throughput of interpolate.sgs_many on the device (gsm_sgs_grid): simulated cells per second over whole grids, 48 neighbours
+within 50 km, Matern, bounds on (T2_StatisticalAnalysis.ipynb's call), split into the host draw plan, the device call (weights
+and values; per-kernel times: run under rocprofv3 --kernel-trace --stats) and the inverse transform.
+
+    python scripts/sgs_grid_bench.py [--sizes 256,566] [--reals 10,64] [--out profiles/sgs_grid_bench.json]
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+
+def problem(n):
+    import interp_sgs_common as ic
+    xx, yy = np.meshgrid(np.arange(n) * 500.0, np.arange(n) * 500.0)
+    bed = ic.field(n, n, 3)
+    cond = np.zeros((n, n), bool)
+    cond[::10, :] = True                                      # flight lines 5 km apart, crossing lines every 7.5 km
+    cond[:, ::15] = True
+    grid = np.where(cond, bed, np.nan)
+    vario = dict(major_range=30e3, minor_range=30e3, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Matern", s=1.5)
+    bounds = (float(np.nanmin(grid)) - 200.0, bed + 500.0)
+    return xx, yy, grid, vario, bounds
+
+
+def main():
+    import torch
+    from mcmc_gpu_amd import interpolate
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="256,566")
+    ap.add_argument("--reals", default="10,64")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    rows = []
+    for n in [int(s) for s in args.sizes.split(",")]:
+        xx, yy, grid, vario, bounds = problem(n)
+        for R in [int(s) for s in args.reals.split(",")]:
+            t0 = time.perf_counter()
+            plan = interpolate._Plan(xx, yy, grid, vario, 50e3, 48, "ok", None, None, None, bounds)
+            t1 = time.perf_counter()
+            gens = [np.random.default_rng(s) for s in range(R)]
+            draws = [plan.draws(np.random.default_rng(s)) for s in range(R)]
+            t2 = time.perf_counter()
+            ns, _ = interpolate._run(plan, gens)
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            out = interpolate._inverse(plan, ns)
+            t4 = time.perf_counter()
+            cells = int(sum(p.size for p, _ in draws))
+            dev_s = (t3 - t2) - (t2 - t1)                     # _run draws again on the host before its device call
+            row = {"grid": f"{n}x{n}", "realisations": R, "simulated_cells": cells, "fit_ms": 1e3 * (t1 - t0),
+                   "draw_plan_ms": 1e3 * (t2 - t1), "device_ms": 1e3 * dev_s, "inverse_transform_ms": 1e3 * (t4 - t3),
+                   "cells_per_s_device": cells / dev_s, "cells_per_s_total": cells / (t4 - t0 - (t2 - t1)),
+                   "nan_cells": int(np.isnan(out).sum())}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "rows": rows}, indent=1))
+
+
+if __name__ == "__main__":
+    main()
