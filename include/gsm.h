@@ -202,7 +202,7 @@ int gsm_spectral_from_noise(gsm_handle h, int32_t n_fields, const int32_t* size_
 /* Philox mode end to end.  Spectral generator: the fused chain kernel (per chain-step the proposal is generated and
  * consumed inside one workgroup; nothing but chain state touches HBM), launched once per segment of at most 4096 steps
  * (scratch: one 140-byte scalar record per chain and step of a SEGMENT; `batch` is not used).  Cholesky generator, block
- * tables beyond the fused kernel's LDS budget, or GSM_FUSED=0 in the environment: batches of `batch` steps, proposals of
+ * tables beyond the fused kernel's LDS budget, or gsm_set_fused(h, 0): batches of `batch` steps, proposals of
  * batch k+1 generated on a second stream while batch k is stepped, scratch owned by the handle.
  * Both forms give bit-identical results, whatever the segment / batch size.  Outputs as gsm_run_replay plus blocks
  * [dev, n_chains*n_steps*4] = (row, col, bh, bw) (blocks_cache, MCMC.py:1264).  Synchronises the stream before returning.
@@ -213,8 +213,7 @@ int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int32_t batch, 
                    double* loss, uint8_t* accept, int32_t* blocks, void* stream);
 
 /* Select the launch structure of gsm_run_philox for the spectral generator on this handle: 1 = fused chain kernel
- * (default), 0 = two-kernel pipeline.  Identical results; kept for A/B measurements and tests.  Environment default:
- * GSM_FUSED. */
+ * (default), 0 = two-kernel pipeline.  Identical results; kept for A/B measurements and tests. */
 int gsm_set_fused(gsm_handle h, int32_t on);
 /* Which form the last gsm_run_philox call on this handle ran: 1 = fused chain kernel, 0 = the two-kernel pipeline. */
 int gsm_last_run_fused(gsm_handle h);
@@ -446,18 +445,14 @@ int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t
  * proposed, gsm_sgs_loss, gsm_sgs_decide, gsm_sgs_commit(_map)] -- with iteration j's draws at windows + 4*n_chains*j,
  * cell_off + cell_off_stride*j, cell_cnt + n_chains*j (or NULL), u + n_chains*j and records at loss_rec + j / acc_rec + j
  * (rec_stride = n_iters).  cell_base (HOST, n_iters entries, or NULL = 0): iteration j's cells / z start at
- * cells + 2*cell_base[j] / z + cell_base[j] (the tightly packed lists of replay mode).
- * use_graph != 0 (and cell_base == NULL, stream != NULL): the launch sequence is captured into a hipGraph the second time the
- * SAME batch (every byte of the struct -- zero it before filling -- and n_iters) is submitted and replayed afterwards: one
- * launch per batch instead of up to 7 per iteration; the device buffers must then be static and refilled in place
- * (gsm_sgs_draw_philox / gsm_sgs_draw_pcg64 do).  Asynchronous; gsm_sgs_check reports a raised device flag.
+ * cells + 2*cell_base[j] / z + cell_base[j] (the tightly packed lists of replay mode).  Asynchronous; gsm_sgs_check reports a
+ * raised device flag.
  * grid_finite != 0: the caller's promise that no cell of `cur` is NaN (it stays so: simulation fills every cell of a block).
  * A cell's neighbour set and kriging weights depend on WHERE values are, not on the values; with the promise the search reads no
  * grid value, the records name their cells, and the records of iteration j + 1 are made on a second stream of the handle while
  * iteration j runs its value pass, transforms, loss and decision (the longest kernel of an iteration leaves the critical path;
  * the value pass then reads the neighbours' values from the grid).  Same numbers as without the promise.  With NaN cells in
- * `cur` the promise is false and the neighbour sets would be wrong: leave it 0.
- * gsm_sgs_graph_replays: how many batches of this handle were graph launches (diagnostics / tests). */
+ * `cur` the promise is false and the neighbour sets would be wrong: leave it 0. */
 typedef struct gsm_sgs_batch {
   double* cur; double* next; double* proposed;            /* proposed: only with a transformer */
   const double* zcond; const double* trend;               /* trend NULL: not detrended */
@@ -470,11 +465,10 @@ typedef struct gsm_sgs_batch {
   uint32_t* resampled; double* loss; int32_t* bad; double* loss_prev; uint8_t* accept; double* loss_rec; uint8_t* acc_rec;
   double radius, sill;
   int64_t cell_off_stride;
-  int32_t qt_n, windowed, lag_mi, lag_mj, hw, num_points, max_cells, use_graph;
+  int32_t qt_n, windowed, lag_mi, lag_mj, hw, num_points, max_cells;
   int32_t grid_finite;                                    /* the caller's promise: no NaN in cur (see below) */
 } gsm_sgs_batch;
 int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* batch, int32_t n_iters, void* stream);
-int gsm_sgs_graph_replays(gsm_handle h);
 
 /* Setup-time distance transform: dist[i] = Euclidean distance from cell i (coordinates xx[i], yy[i]) to the nearest
  * cell with mask[i] != 0, all [dev, H*W].  Exact (brute force over the masked cells, same dx*dx + dy*dy, sqrt
@@ -487,13 +481,6 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
 /* Diagnostics: stream-copy n doubles src -> dst [dev] with the step kernel's access shape (8 bytes per lane,
  * coalesced).  A known byte count for calibrating rocprofv3's FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM). */
 int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream);
-
-/* Diagnostics: per-chain cycle totals of the step kernel's phases (8 x uint64 per chain, host buffer) from the last
- * launch.  Only in a library built with GSM_STAMPS=1 (a diagnostic build: the stamps cost cycles); the production build
- * returns GSM_E_UNSUPPORTED. */
-int gsm_debug_stamps(uint64_t* out, int32_t n_chains);
-/* Same for the fused chain kernel (16 x uint64 per chain). */
-int gsm_debug_stamps_fused(uint64_t* out, int32_t n_chains);
 
 /* Test hook: the device's standard-normal pairs (Philox4x32-10 counters (idx, stream, step), Box-Muller with the table-driven
  * log / sincos of the coefficient phase) for idx = idx0 .. idx0 + n - 1: out[2 i], out[2 i + 1] [dev].  Checked against

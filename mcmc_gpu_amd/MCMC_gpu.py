@@ -718,7 +718,7 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
                  if chain.update_in_region else None)
         stride = eng.field_stride
         if fused is None:
-            fused = eng.strip_active() and os.environ.get("GSM_PCG64_FUSED", "1") != "0"
+            fused = eng.strip_active()
         elif fused and not eng.strip_active():
             raise NotImplementedError("run_many_pcg64(fused=True): this block table does not go to the strip kernels")
         if batch is None:

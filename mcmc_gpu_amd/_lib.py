@@ -39,20 +39,12 @@ class GsmError(RuntimeError):
         self.code = code
 
 
-def _diag_flags() -> list[str]:
-    """Diagnostic defines taken from the environment (scripts/stamps*.py): part of the build's identity."""
-    diag = ["-DGSM_STAMPS"] if os.environ.get("GSM_STAMPS") else []
-    if os.environ.get("GSM_STAMP_TID"):
-        diag.append("-DGSM_STAMP_TID=" + os.environ["GSM_STAMP_TID"])
-    return diag
-
-
 def source_hash() -> str:
     """First 16 hex digits of the SHA-256 over the library sources (csrc/*.hip, csrc/*.h, include/gsm.h, by name) AND the
-    effective compiler flags (a diagnostic build -- GSM_STAMPS -- therefore never passes for the product build)."""
+    compiler flags."""
     import hashlib
     h = hashlib.sha256()
-    h.update(repr((HIPCC_FLAGS, sorted(EXTRA_FLAGS.items()), _diag_flags())).encode())
+    h.update(repr((HIPCC_FLAGS, sorted(EXTRA_FLAGS.items()))).encode())
     for p in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h")), key=lambda q: q.name) + [HEADER]:
         h.update(p.name.encode())
         h.update(p.read_bytes())
@@ -102,10 +94,8 @@ def _build_locked(force: bool, verbose: bool) -> Path:
         is_version = s == "gsm_version.hip"
         if not force and not is_version and obj.exists() and obj.stat().st_mtime > max(src.stat().st_mtime, hdr_t):
             continue
-        diag = _diag_flags()
-        if is_version:
-            diag.append(f'-DGSM_SRC_HASH="{src_hash}"')
-        cmd = [hipcc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(s, []), *diag, "-c", "-o", str(obj), str(src)]
+        defs = [f'-DGSM_SRC_HASH="{src_hash}"'] if is_version else []
+        cmd = [hipcc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(s, []), *defs, "-c", "-o", str(obj), str(src)]
         if verbose:
             print(" ".join(cmd))
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
@@ -142,7 +132,7 @@ class SgsBatch(C.Structure):
                                           "x_axis", "y_axis", "lag_cov", "windows", "cell_off", "cell_cnt", "cells", "z", "cell_base", "u",
                                           "resampled", "loss", "bad", "loss_prev", "accept", "loss_rec", "acc_rec")] +
                 [("radius", C.c_double), ("sill", C.c_double), ("cell_off_stride", C.c_int64)] +
-                [(k, C.c_int32) for k in ("qt_n", "windowed", "lag_mi", "lag_mj", "hw", "num_points", "max_cells", "use_graph", "grid_finite")])
+                [(k, C.c_int32) for k in ("qt_n", "windowed", "lag_mi", "lag_mj", "hw", "num_points", "max_cells", "grid_finite")])
 
 
 class Vario(C.Structure):
@@ -212,7 +202,6 @@ def load() -> C.CDLL:
     lib.gsm_sgs_blocks_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, vp, vp, i32, vp]
     lib.gsm_sgs_check.argtypes = [vp, vp]
     lib.gsm_sgs_iterate.argtypes = [vp, C.POINTER(SgsBatch), i32, vp]
-    lib.gsm_sgs_graph_replays.argtypes = [vp]
     lib.gsm_sgs_set_kriging.argtypes = [vp, i32, vp]
     lib.gsm_sgs_grid.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, i32, vp, vp]
     lib.gsm_draw_pcg64.argtypes = [vp, i32, C.POINTER(RfParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]

@@ -25,7 +25,6 @@
 #include "device_util.h"
 #include "proposal_device.h"
 #include <math.h>
-#include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
@@ -34,18 +33,6 @@ namespace gsm {
 using namespace dev;
 
 constexpr int kUPW = 32 / kNW;             // stage-1 units per wave (2 halves x at most 16 output tiles over 16 waves)
-
-#ifdef GSM_STAMPS
-// diagnostic build only (GSM_STAMPS=1 at build time): per-workgroup cycle totals of the phases, thread 0
-__device__ unsigned long long g_stamps_fused[4096 * 16];
-#ifndef GSM_STAMP_TID
-#define GSM_STAMP_TID 0
-#endif
-#define STAMP(slot) do { if (tid == GSM_STAMP_TID) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[slot] += t_ - st_last; st_last = t_; } } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#endif
 
 // work area: flux tiles, overlaid by the DFT planes + the [cos|sin] table during the proposal;
 // field tile: overlaid by the c2r table until the field is written
@@ -149,10 +136,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
   // are complete: vmcnt counts in order and every thread has since waited for younger loads of its own.
   int pr0 = 0, pr1 = 0, pc0 = 0, pc1 = 0;
 
-#ifdef GSM_STAMPS
-  unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
   const NoiseIn no_noise{nullptr, nullptr, nullptr};
   // the fields of a record the proposal stages use
   auto prop_rec = [&](crec_t r) {
@@ -163,7 +146,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     return q;
   };
   for (int s = 0; s < n_steps; ++s) {
-    STAMP(15);
     // Geometry of the thread's tile cells t, t + 1024, ... by (magic) division; ptid is laundered per phase so that the
     // derived values are recomputed instead of being kept live across phases.  (An incremental form without the
     // multiplies measured 1.8 % slower on the same box.)
@@ -195,7 +177,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       dma_to_lds<kNW, 0>(pa.tables + q.g_off, fld, 2 * pg.Kc * pg.M1, wave, lane);
       coef_items<kNT, false>(ptid, 0, pg.nrow * pg.ncol, true, pa, q, pg, seed, pa.step0 + s, lds, pa.lds_x_half, no_noise, mtab);
     }
-    STAMP(10);
     // ---- P0: chain state of the window -> registers, in flight during the two MFMA stages ------------------------------
     double vb[KT], ve[KT];
     // tile row | tile col << 8 | valid << 16 | in-window << 17 of the thread's cells: computed once per step, here
@@ -226,11 +207,9 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
         }
       }
     }
-    STAMP(0);
     // The table LDS-DMAs are older than the 2 KT state loads just issued: wait for everything but those (vmcnt counts in
     // order) and for this wave's LDS writes; then a bare barrier.  __syncthreads() would wait vmcnt(0), i.e. for HBM.
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(2 * KT) : "memory");
-    STAMP(2);
     // mean of the field = DC coefficient / n (proposal_device.h); read before T^T overlays the plane
     const double dc0 = lds[0];
     {
@@ -241,9 +220,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
         const PropScalars q = prop_rec(rec);
         dft_stage1<kNW, kUPW, true>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, lds + lds_xh4, uc, us);
       }
-      STAMP(1);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has finished reading the planes
-      STAMP(13);
       {
         const cargs_t K = kargs();
         const ProposeArgs pa = load_c(&K->P);
@@ -265,9 +242,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       const int ln = ptid & 63;
       dft_stage2<kNW, 1, true>(wave, ln, pa, q, pg, lds, fld, fe, fo);
       mask_prefetch<kNW, 1>(wave, ln, pa, q, pg, mreg);
-      STAMP(11);
       const double gain = standardise<kNW, 1>(wave, ln, q, pg, dc0, red2, fe, fo);     // contains a barrier
-      STAMP(14);
       const bool with_nugget = pa.rf.nugget_max > 0.0;
       emit_field<kNW, 1, true>(wave, ln, pa, q, pg, fe, fo, mreg, gain, with_nugget, fld, [bw](int y, int x) { return y * bw + x; });
       if (with_nugget) {
@@ -276,7 +251,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
         nugget_pass<kNT, false>(ptid, pa, q, pg, seed, pa.step0 + s, no_noise, fld, [bw](int y, int x) { return y * bw + x; }, mtab);
       }
     }
-    STAMP(12);
     // static operands of the thread's first phase-A cells: requested before the barrier that phase A begins with
     // (after it every wave would wait for them at the same time)
     constexpr int KBA = (KT > 4) ? 2 : KT;
@@ -295,7 +269,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // field tile complete
-    STAMP(3);
 
     // ---- A: candidate bed, fluxes -> LDS, guard ---------------------------------------------------------------------
     double v_new[KT];
@@ -387,9 +360,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
         C2[k] = ld_f64x2(r_st, inwin ? g * 16u : kOOB, off_sC);
       }
     }
-    STAMP(4);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS tiles complete; the loads above stay in flight
-    STAMP(5);
 
     // ---- D: residual stencil on the flux tiles ---------------------------------------------------------
     double e_new[KT];
@@ -445,7 +416,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       };
       if (interior) phase_d(std::true_type{}); else phase_d(std::false_type{});
     }
-    STAMP(6);
     // ---- R: reduce, decide (every thread evaluates the same numbers in the same order) ----------------
     {
       // one sum: the thread's change of energy, or +inf from a thread whose candidate grounds the ice (MCMC.py:1321-1329:
@@ -455,9 +425,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       const double w_delta = wave64_sum(delta);
       if (lane == 0) red[wave] = w_delta;
     }
-    STAMP(7);
     __syncthreads();
-    STAMP(8);
     const double sd = row16_sum(red[lane & 15]);
     double c_hi, c_err;
     two_sum(s_hi, sd, c_hi, c_err);
@@ -492,7 +460,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     } else {
       pr0 = pr1 = pc0 = pc1 = 0;
     }
-    STAMP(9);
     if (tid == 0) {
       const StepArgs a = load_c(&Ke->T);
       const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
@@ -505,18 +472,6 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     fa.T.loss_sum[2 * chain] = s_hi;
     fa.T.loss_sum[2 * chain + 1] = s_lo;
   }
-#ifdef GSM_STAMPS
-  if (tid == GSM_STAMP_TID && chain < 4096) for (int q = 0; q < 16; ++q) g_stamps_fused[chain * 16 + q] = st_acc[q];
-#endif
-}
-
-int debug_read_stamps_fused(unsigned long long* out, int n_chains) {
-#ifdef GSM_STAMPS
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_fused), sizeof(unsigned long long) * 16 * (size_t)n_chains) == hipSuccess ? 0 : -3;
-#else
-  (void)out; (void)n_chains;
-  return -4;
-#endif
 }
 
 template <typename TS, int KT>
@@ -636,7 +591,6 @@ hipError_t launch_chain_fused(const FusedArgs& a_in, hipStream_t st) {
     return launch_resampled_from_records(a_in, st);
   }
   FusedArgs a = a_in;
-  { static int dbg = -1; if (dbg < 0) { const char* v = getenv("GSM_PROPOSE_DBG"); dbg = v ? atoi(v) : 0; } a.P.dbg = dbg; }   // diagnostics only
   a.work_len = fused_work_len(a);
   a.fld_len = fused_fld_len(a);
   hipError_t e;

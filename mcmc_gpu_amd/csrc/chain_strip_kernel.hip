@@ -114,7 +114,6 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
   const uint32_t n_cells = (uint32_t)gH * (uint32_t)gW;
   const srec_t rec0 = (srec_t)(uintptr_t)(fa.P.scalars + (size_t)chain * fa.P.n_steps);
   const uint64_t seed = NOISE ? 0ull : fa.P.seeds[chain];
-  const int dbg = fa.P.dbg;      // diagnostics only (GSM_PROPOSE_DBG): 128 / 256 / 512 / 1024 skip phase D / phase A / the state loads / the commit
   for (int i = tid; i < kMathTabDoubles; i += kST) mtab[i] = fa.P.mathtab[i];
   if (tid < 16) red[tid] = 0.0;
   __syncthreads();
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
       if (tid >= kST - kMask1D) m1[tid - (kST - kMask1D)] = K->P.B.mask1d[rec->si * kMask1D + tid - (kST - kMask1D)];
       if (tid < 2 * s_bh) t1[(tid < s_bh) ? tid : kT1S + tid - s_bh] = g1[rec->t1h_off + tid];
       else if (tid >= 256 && tid < 256 + 2 * s_bw) {
-        const int i = tid - 256;
+        const int i = ptid - 256;      // laundered: tid + 128 would otherwise be hoisted out of the step loop and spilled
         const double v = g1[rec->t1w_off + i];
         t1[2 * kT1S + ((i < s_bw) ? i : kT1S + i - s_bw)] = (i < s_bw) ? v : -v;
       }
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
         const cargs_t K = kargs();
         const ProposeArgs pa = load_cs(&K->P);
         relaunder();
-        if (!(dbg & 2048)) dft_tt_write<kSW, kSUPW>(wave, ptid & 63, prop_geom(pa, s_bh, s_bw), lds, uc, us);
+        dft_tt_write<kSW, kSUPW>(wave, ptid & 63, prop_geom(pa, s_bh, s_bw), lds, uc, us);
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -208,9 +207,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
       relaunder();
       const int ln = ptid & 63;
       dft_stage2<kSW, kSMAXT, 2>(wave, ln, pa, q, pg, lds, t1 + 2 * kT1S, fe, fo);
-      double gain = 1.0;
-      if (dbg & 4096) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else gain = standardise<kSW, kSMAXT>(wave, ln, q, pg, dc0, red2, fe, fo, (pa.parseval && !((q.bh | q.bw) & 1)) ? red2 + 16 : nullptr);     // contains a barrier; even shapes: variance from the spectrum
+      const double gain = standardise<kSW, kSMAXT>(wave, ln, q, pg, dc0, red2, fe, fo, (pa.parseval && !((q.bh | q.bw) & 1)) ? red2 + 16 : nullptr);     // contains a barrier; even shapes: variance from the spectrum
       NoiseIn nz{nullptr, nullptr, nullptr};
       if (NOISE) {
         typedef const __attribute__((address_space(4))) FusedArgs* cfa_t;
@@ -240,20 +237,12 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     {
       double vb[kNR + 2], ve[kNR];
       double2 a2[strip::kNA];
-      if (dbg & 512) {
-#pragma unroll
-        for (int i = 0; i < kNR + 2; ++i) vb[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < kNR; ++i) ve[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < strip::kNA; ++i) a2[i] = make_double2(0.0, 0.0);
-      } else if (G.interior) strip::load_state<TS, true>(L, cfg.n, gW, r_bed, r_en, r_st, vb, ve, a2);
+      if (G.interior) strip::load_state<TS, true>(L, cfg.n, gW, r_bed, r_en, r_st, vb, ve, a2);
       else strip::load_state<TS, false>(L, cfg.n, gW, r_bed, r_en, r_st, vb, ve, a2);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // field tile complete; the state loads stay in flight
       const int ts = s_bw + 2;
       auto field = [&](int jj, bool) { return lds[L.tidx + jj * ts]; };      // unconditional: a lane without the cell discards the value
-      if (dbg & 256) { upd_bits = 0u; acc_old = 0.0; guard = false; }
-      else if (G.interior) strip::phase_a<TS, true>(L, cfg.n, gW, s_bw, r_st, field, lds, vb, ve, a2, upd_bits, acc_old, guard);
+      if (G.interior) strip::phase_a<TS, true>(L, cfg.n, gW, s_bw, r_st, field, lds, vb, ve, a2, upd_bits, acc_old, guard);
       else strip::phase_a<TS, false>(L, cfg.n, gW, s_bw, r_st, field, lds, vb, ve, a2, upd_bits, acc_old, guard);
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // candidate-bed tile complete
@@ -262,28 +251,21 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
       double acc_new;
       const cargs_t K = kargs();
       const strip::StepConsts SC{K->T.S.res, K->T.S.rcp_res, K->T.S.two_res, K->T.S.rcp_two_res};
-      if (dbg & 128) {
-        acc_new = 0.0;
-#pragma unroll
-        for (int i = 0; i < kNR; ++i) en[i] = 0.0;
-      } else if (G.interior) strip::phase_d<TS, FAST_DIV, true>(L, cfg.n, gW, s_bw, r_st, n_cells * 16u, SC, lds, en, acc_new);
+      if (G.interior) strip::phase_d<TS, FAST_DIV, true>(L, cfg.n, gW, s_bw, r_st, n_cells * 16u, SC, lds, en, acc_new);
       else strip::phase_d<TS, FAST_DIV, false>(L, cfg.n, gW, s_bw, r_st, n_cells * 16u, SC, lds, en, acc_new);
       double delta = acc_new - acc_old;
       if (guard) delta = INFINITY;
       const double w_delta = wave64_sum(delta);
       if (lane == 0) red[wave] = w_delta;
     }
-    if (dbg & 1024) {
-#pragma unroll
-      for (int i = 0; i < kNR; ++i) vn[i] = 0.0;
-    } else strip::read_candidate(L, cfg.n, s_bw, lds, vn);
+    strip::read_candidate(L, cfg.n, s_bw, lds, vn);
     const double s_hi = carry[0], s_lo = carry[1];
     double loss_prev = carry[2];
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const double sd = strip::waves_sum(red, lane);
     double c_hi, c_lo, loss_next;
     const bool acc = decide<FAST_DIV>(sd, s_hi, s_lo, two_sigma2, rcp_two_sigma2, loss_prev, rec->u, c_hi, c_lo, loss_next);
-    if (acc && !(dbg & 1024)) {
+    if (acc) {
       if (G.interior) strip::commit<TS, true, false>(L, cfg.n, gW, r_bed, r_en, r_en, vn, en, upd_bits);
       else strip::commit<TS, false, false>(L, cfg.n, gW, r_bed, r_en, r_en, vn, en, upd_bits);
       loss_prev = loss_next;
@@ -466,7 +448,6 @@ static hipError_t launch_fused_strip_t(const FusedArgs& a, hipStream_t st) {
 hipError_t launch_chain_strip(const FusedArgs& a_in, hipStream_t st) {
   if (!a_in.T.strip || a_in.P.tab_max <= 0) return hipErrorInvalidValue;
   FusedArgs a = a_in;
-  { static int dbg = -1; if (dbg < 0) { const char* v = getenv("GSM_PROPOSE_DBG"); dbg = v ? atoi(v) : 0; } a.P.dbg = dbg; }   // diagnostics only
   a.work_len = strip_main_len(a);
   a.fld_len = 0;
   return a.T.f32_state ? launch_fused_strip_t<float, false>(a, st) : launch_fused_strip_t<double, false>(a, st);
@@ -476,7 +457,6 @@ hipError_t launch_chain_strip(const FusedArgs& a_in, hipStream_t st) {
 hipError_t launch_chain_strip_noise(const FusedArgs& a_in, hipStream_t st) {
   if (!a_in.T.strip || a_in.P.tab_max <= 0 || !a_in.noise_re || !a_in.noise_im) return hipErrorInvalidValue;
   FusedArgs a = a_in;
-  a.P.dbg = 0;
   a.work_len = strip_main_len(a);
   a.fld_len = 0;
   return a.T.f32_state ? launch_fused_strip_t<float, true>(a, st) : launch_fused_strip_t<double, true>(a, st);

@@ -38,9 +38,7 @@ struct gsm_context {
   void* d_sgs_rec[kSgsDepth] = {}; size_t sgs_rec_cells[kSgsDepth] = {};
   double* d_sgs_next_acc = nullptr; size_t sgs_next_acc_cap = 0;                 // T(proposed) of every chain (sgs_loss_tail_kernel<true>)
   hipStream_t sgs_side = nullptr, sgs_side2 = nullptr; hipEvent_t sgs_ev[kSgsDepth + 2] = {};         // gsm_sgs_iterate's second stream (records of later iterations beside the current one)
-  // gsm_sgs_iterate: the captured launch sequence of one batch (hipGraph), keyed by the bytes of its gsm_sgs_batch + n_iters
   int sgs_ktype = 0; const double* sgs_gmean = nullptr;        // gsm_sgs_set_kriging
-  std::vector<char> sgs_graph_key; hipGraphExec_t sgs_graph_exec = nullptr; int sgs_graph_replays = 0;
   uint64_t* d_pcg_tab = nullptr;   // gsm_draw_pcg64: LCG jump table (kPcgJumpWords) + ziggurat tables (768 words)
   int32_t* d_k2_off = nullptr;
   double k2_resolution = 0.0;
@@ -70,7 +68,7 @@ struct gsm_context {
   // timing
   bool timing = false;
   int last_fused = 0;     // 1 when the last gsm_run_philox call went through the fused chain kernel
-  int use_fused = -1;     // -1: decide from GSM_FUSED at the first gsm_run_philox; 0 / 1: set by gsm_set_fused
+  int use_fused = 1;      // 0 / 1: set by gsm_set_fused
   double t_step_ms = 0, t_prop_ms = 0;
   int n_step_launch = 0, n_prop_launch = 0;
 };
@@ -152,7 +150,6 @@ extern "C" int gsm_destroy(gsm_handle h) {
   if (h->d_sgs_next_acc) hipFree(h->d_sgs_next_acc);
   if (h->sgs_side) hipStreamDestroy(h->sgs_side);
   if (h->sgs_side2) hipStreamDestroy(h->sgs_side2);
-  if (h->sgs_graph_exec) hipGraphExecDestroy(h->sgs_graph_exec);
   if (h->d_pcg_tab) hipFree(h->d_pcg_tab);
   if (h->d_k2_off) hipFree(h->d_k2_off);
   if (h->d_factors) hipFree(h->d_factors);
@@ -696,9 +693,8 @@ extern "C" int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int3
   if (batch > n_steps) batch = n_steps;
   { int rc2 = ensure_k2(h, rf, st); if (rc2) return rc2; }
   // Spectral generator: one fused launch (chain_fused_kernel.hip) -- proposals are generated and consumed on the CU,
-  // no field scratch, no second stream.  GSM_FUSED=0 keeps the two-kernel pipeline (also used by the Cholesky generator
-  // and by block tables beyond the fused kernel's LDS budget).
-  if (h->use_fused < 0) { const char* v = getenv("GSM_FUSED"); h->use_fused = v ? atoi(v) : 1; }
+  // no field scratch, no second stream.  gsm_set_fused(h, 0) keeps the two-kernel pipeline (also used by the Cholesky
+  // generator and by block tables beyond the fused kernel's LDS budget).
   h->last_fused = 0;
   if (h->use_fused && rf->generator == GSM_GEN_SPECTRAL) {
     // Segments of at most kFusedSegment steps: the per-(chain, step) scalar records (120 + 20 bytes) are sized by the
@@ -838,16 +834,6 @@ extern "C" int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int3
   return rc;
 }
 
-extern "C" int gsm_debug_stamps(uint64_t* out, int32_t n_chains) {
-  if (!out || n_chains < 1 || n_chains > 4096) return GSM_E_ARG;
-  return debug_read_stamps((unsigned long long*)out, n_chains);
-}
-
-extern "C" int gsm_debug_stamps_fused(uint64_t* out, int32_t n_chains) {
-  if (!out || n_chains < 1 || n_chains > 4096) return GSM_E_ARG;
-  return debug_read_stamps_fused((unsigned long long*)out, n_chains);
-}
-
 extern "C" int gsm_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int32_t n, double* out, void* stream) {
   if (!out || n < 1) return GSM_E_ARG;
   double tab[kMathTabDoubles];
@@ -952,9 +938,6 @@ static int sgs_fill(gsm_handle h, SgsArgs& a, double* grids, const double* zcond
   max_cells = (max_cells + 63) & ~63;                        // record stride: whole 64-cell chunks (sgs_sequence_kernel: one cell per lane)
   const size_t n = (size_t)h->n_chains, cells_cap = n * (size_t)max_cells;
   if (h->sgs_rec_cells[parity] < cells_cap) {
-    // a captured batch (gsm_sgs_iterate's hipGraph) holds the old scratch pointers: it must not be replayed
-    if (h->sgs_graph_exec) { hipGraphExecDestroy(h->sgs_graph_exec); h->sgs_graph_exec = nullptr; }
-    h->sgs_graph_key.clear();
     if (h->d_sgs_rec[parity]) { hipFree(h->d_sgs_rec[parity]); h->d_sgs_rec[parity] = nullptr; h->sgs_rec_cells[parity] = 0; }
     const size_t bytes = n * 1024 * 4 + n * 4 + 64 + cells_cap * (sizeof(SgsCellHdr) + 48 * sizeof(double2));
     hipError_t e = hipMalloc(&h->d_sgs_rec[parity], bytes);
@@ -1029,8 +1012,6 @@ extern "C" int gsm_sgs_set_kriging(gsm_handle h, int32_t ktype, const double* gl
   if (ktype != GSM_KRIGING_ORDINARY && ktype != GSM_KRIGING_SIMPLE) return fail(h, GSM_E_ARG, "gsm_sgs_set_kriging: ktype must be GSM_KRIGING_ORDINARY or GSM_KRIGING_SIMPLE");
   if (ktype == GSM_KRIGING_SIMPLE && !global_mean) return fail(h, GSM_E_ARG, "gsm_sgs_set_kriging: simple kriging needs the global mean of every chain");
   h->sgs_ktype = ktype; h->sgs_gmean = ktype == GSM_KRIGING_SIMPLE ? global_mean : nullptr;
-  h->sgs_graph_key.clear();                     // a captured batch baked the old choice into its launches
-  if (h->sgs_graph_exec) { hipGraphExecDestroy(h->sgs_graph_exec); h->sgs_graph_exec = nullptr; }
   return GSM_OK;
 }
 
@@ -1160,8 +1141,6 @@ extern "C" int gsm_sgs_draw_pcg64(gsm_handle h, uint64_t* chain_state, int32_t n
 static int sgs_parts_ensure(gsm_handle h) {
   const size_t need = (size_t)h->n_chains * sgs_loss_parts(h->S);
   if (h->sgs_part_cap >= need) return GSM_OK;
-  if (h->sgs_graph_exec) { hipGraphExecDestroy(h->sgs_graph_exec); h->sgs_graph_exec = nullptr; }     // captured with the old scratch
-  h->sgs_graph_key.clear();
   if (h->d_sgs_part_sum) { hipFree(h->d_sgs_part_sum); hipFree(h->d_sgs_part_bad); hipFree(h->d_sgs_ticket); h->d_sgs_part_sum = nullptr; h->d_sgs_part_bad = nullptr; h->d_sgs_ticket = nullptr; h->sgs_part_cap = 0; }
   HIPCHK(h, hipMalloc(&h->d_sgs_part_sum, need * sizeof(double)));
   HIPCHK(h, hipMalloc(&h->d_sgs_part_bad, need * sizeof(int32_t)));
@@ -1246,7 +1225,7 @@ extern "C" int gsm_sgs_commit(gsm_handle h, double* cur, double* next, uint32_t*
   return GSM_OK;
 }
 
-// ---- one batch of small-scale iterations in ONE call (and, when the buffers are static, one hipGraph launch) ----------------
+// ---- one batch of small-scale iterations in ONE call ------------------------------------------------------------------------
 static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void* st) {
   const int64_t n = h->n_chains;
   const bool qt = b->qt_n > 0;
@@ -1320,8 +1299,6 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
     const double lo = 1e-7 - 2.220446049250313e-16;               // as gsm_qt_transform
     qt_clip_min = ns::ndtri(lo); qt_clip_max = ns::ndtri(1.0 - lo);
     if (h->sgs_next_acc_cap < (size_t)map) {
-      if (h->sgs_graph_exec) { hipGraphExecDestroy(h->sgs_graph_exec); h->sgs_graph_exec = nullptr; }
-      h->sgs_graph_key.clear();
       if (h->d_sgs_next_acc) { hipFree(h->d_sgs_next_acc); h->d_sgs_next_acc = nullptr; h->sgs_next_acc_cap = 0; }
       HIPCHK(h, hipMalloc(&h->d_sgs_next_acc, (size_t)map * sizeof(double)));
       h->sgs_next_acc_cap = (size_t)map;
@@ -1338,7 +1315,7 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
       // takes the next `half` iterations' records (it then runs between depth - half and depth - 1 iterations ahead)
       if ((j + 1) % half == 0 && issued < n_iters) {
         HIPCHK(h, hipEventRecord(ev_seq, main_st));
-        must_wait[0] = must_wait[1] = true;                    // (a stream waits when it next gets work: no wait is left dangling in a capture)
+        must_wait[0] = must_wait[1] = true;                    // (a stream waits when it next gets work)
         if ((rc = enqueue_records(std::min<int32_t>(n_iters, j + depth)))) return rc;
       }
     } else {
@@ -1374,40 +1351,9 @@ extern "C" int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* b, int32_t n_i
     return fail(h, GSM_E_ARG, "gsm_sgs_iterate: the windowed finish needs energy / state and no transformer");
   if (!b->windowed && (!b->loss || !b->bad || !b->loss_prev)) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: loss / bad / loss_prev are NULL");
   if (b->cell_off_stride < h->n_chains) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: cell_off_stride must be >= n_chains");
-  hipStream_t st = (hipStream_t)stream;
   HIPCHK(h, hipSetDevice(h->device));
-  // Graph replay needs every pointer of the batch to be the same as at capture, a capturable (non-NULL) stream, and all lazy
-  // allocations of the launch path made: the first call with a given batch runs eagerly, the second captures, later ones replay.
-  const bool graphable = b->use_graph && st != nullptr && !b->cell_base;
-  if (!graphable) return sgs_issue(h, b, n_iters, stream);
-  std::vector<char> key(sizeof(gsm_sgs_batch) + sizeof(int32_t));
-  memcpy(key.data(), b, sizeof(gsm_sgs_batch));
-  memcpy(key.data() + sizeof(gsm_sgs_batch), &n_iters, sizeof(int32_t));
-  if (key != h->sgs_graph_key) {
-    if (h->sgs_graph_exec) { hipGraphExecDestroy(h->sgs_graph_exec); h->sgs_graph_exec = nullptr; }
-    h->sgs_graph_key = key;
-    return sgs_issue(h, b, n_iters, stream);
-  }
-  if (!h->sgs_graph_exec) {
-    HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    int rc = sgs_issue(h, b, n_iters, stream);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc || e != hipSuccess) {
-      if (g) hipGraphDestroy(g);
-      h->sgs_graph_key.clear();
-      return rc ? rc : fail(h, GSM_E_HIP, std::string("gsm_sgs_iterate: hipStreamEndCapture: ") + hipGetErrorString(e));
-    }
-    e = hipGraphInstantiate(&h->sgs_graph_exec, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    if (e != hipSuccess) { h->sgs_graph_exec = nullptr; h->sgs_graph_key.clear(); return fail(h, GSM_E_HIP, std::string("gsm_sgs_iterate: hipGraphInstantiate: ") + hipGetErrorString(e)); }
-  }
-  HIPCHK(h, hipGraphLaunch(h->sgs_graph_exec, st));
-  ++h->sgs_graph_replays;
-  return GSM_OK;
+  return sgs_issue(h, b, n_iters, stream);
 }
-
-extern "C" int gsm_sgs_graph_replays(gsm_handle h) { return h ? h->sgs_graph_replays : GSM_E_ARG; }
 
 extern "C" int gsm_struct_size(int32_t which) {
   return which == 0 ? (int)sizeof(gsm_rf_params) : which == 1 ? (int)sizeof(gsm_sgs_batch) : which == 2 ? (int)sizeof(gsm_vario) : -1;

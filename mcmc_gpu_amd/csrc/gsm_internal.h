@@ -131,7 +131,6 @@ struct ProposeArgs {
   const double* k2tab;     // (sqrt(kx^2 + ky^2) + 1e-10)^2 on ky <= bh/2, kx <= bw/2, one [nrow][ncol] table per block size
   const int32_t* k2_off;   // [n_sizes] offsets into k2tab
   PropScalars* scalars;    // device scratch, n_chains * n_steps records
-  int dbg;                 // diagnostics only (GSM_PROPOSE_DBG): bit0 cheap coefficients, bit1 skip stage 1, bit2 skip stage 2
   int parseval;            // the field's variance from the spectrum (Parseval) instead of from the field: same handles as split2 (the sum's order is that of
                            // 512-thread workgroups; proposal_device.h: coef_items, standardise)
   int split2;              // stage 2 of even block widths split by the parity of kx where the shape allows it (handles on the strip kernels: every kernel of
@@ -298,8 +297,6 @@ hipError_t launch_cov_assemble(int bh, int bw, double res, const gsm_vario& v, c
 hipError_t launch_step(const StepArgs& a, hipStream_t st);
 hipError_t launch_step_flux(const StepArgs& a, hipStream_t st);
 bool step_flux_supported(const StepArgs& a);
-int debug_read_stamps(unsigned long long* out, int n_chains);
-int debug_read_stamps_fused(unsigned long long* out, int n_chains);
 hipError_t launch_pack_flux_static(const StaticFields& S, double2* sA, double2* sB, double2* sC, hipStream_t st);
 hipError_t launch_init_loss(const StaticFields& S, int n_chains, const void* beds, void* energy, int f32_state,
                             double* loss_sum, double* loss0, hipStream_t st);

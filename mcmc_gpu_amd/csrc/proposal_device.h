@@ -2,9 +2,6 @@
 // (512 threads, two workgroups per CU) and the fused chain kernel.  See proposal_kernel.hip for the algorithm
 // (reference gstatsMCMC/MCMC.py:742-778, :176-254).
 #pragma once
-#ifndef PSTAMP
-#define PSTAMP(slot) do {} while (0)
-#endif
 #include "gsm_internal.h"
 #include "device_util.h"
 #include "philox.h"
@@ -243,7 +240,7 @@ __device__ __forceinline__ void coef_items(const int t, const int i_lo, const in
   const uint32_t m_nc = sc.m_nc;
   double pw = 0.0;
   const double* __restrict__ k2tab = a.k2tab + sc.pad;          // this shape's [nrow][ncol] table (pad = its offset)
-  for (int i = i_lo + t; i < i_hi && !(a.dbg & 32); i += NTH) {
+  for (int i = i_lo + t; i < i_hi; i += NTH) {
     const double k2 = k2tab[i];                                 // requested first: lands under the Box-Muller code
     const int ky = (int)__umulhi((uint32_t)i, m_nc);
     const int kx = i - ky * ncol;
@@ -262,14 +259,11 @@ __device__ __forceinline__ void coef_items(const int t, const int i_lo, const in
         bi = amp * (0.5 * (noise.im[kyc * bw + kx] - noise.im[ky * bw + nkx]));
       }
     } else {
-      if (a.dbg & 1) { amp = 1.0; g1 = ky; g2 = kx; h1 = 1.0; h2 = 2.0; }
-      else {
-        // the four normals of the item -- (g1, g2) for row ky, (h1, h2) for row bh - ky -- from one Philox block at counter
-        // ky * ncol + kx; evaluated unconditionally: one straight-line block, so the two Box-Muller chains interleave
-        normals4(seed, step, kStreamSpectrum, (uint32_t)(ky * ncol + kx), g1, g2, h1, h2, mt);
-        if (!paired) { h1 = 0.0; h2 = 0.0; }
-        amp = spectral_amp(P, sc, k2, mt);
-      }
+      // the four normals of the item -- (g1, g2) for row ky, (h1, h2) for row bh - ky -- from one Philox block at counter
+      // ky * ncol + kx; evaluated unconditionally: one straight-line block, so the two Box-Muller chains interleave
+      normals4(seed, step, kStreamSpectrum, (uint32_t)(ky * ncol + kx), g1, g2, h1, h2, mt);
+      if (!paired) { h1 = 0.0; h2 = 0.0; }
+      amp = spectral_amp(P, sc, k2, mt);
       if (FOLD_CK && kx != 0 && kx != hw) amp = 2.0 * amp;
       if (kx > 0 && kx < hw) {
         ar = amp * (g1 * M_SQRT1_2); ai = amp * (g2 * M_SQRT1_2);
@@ -346,7 +340,7 @@ __device__ __forceinline__ void dft_stage1(const int w, const int lane, const Pr
     for (int j = 0; j < UPW; j += 2) {
       const int pq = w + (j >> 1) * NW;
       v4f64 cE = {0.0, 0.0, 0.0, 0.0}, sE = cE, cO = cE, sO = cE;
-      if ((j + 1 < UPW) && pq < n_pairs && !(a.dbg & 2)) {
+      if ((j + 1 < UPW) && pq < n_pairs) {
         const int t = pq >> 1;
         const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
         const double* __restrict__ Ac = (pq & 1) ? Pi : Pr;
@@ -401,7 +395,7 @@ __device__ __forceinline__ void dft_stage1(const int w, const int lane, const Pr
     auto setup = [&](const int j) {
       Unit x{0, 0u, 0u, Pr, Mi, false};
       const int u = w + j * NW, t = u >> 1;
-      x.on = (j < UPW) && (t < n_t1) && !(a.dbg & 2);
+      x.on = (j < UPW) && (t < n_t1);
       if (x.on) {
         const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
         x.ao = l4 * SX + 16 * mt + l15;
@@ -473,7 +467,7 @@ __device__ __forceinline__ void dft_stage1(const int w, const int lane, const Pr
     v4f64 ac = {0.0, 0.0, 0.0, 0.0}, as = ac;
     const int u = w + j * NW;
     const int t = u >> 1;
-    if (t < n_t1 && !(a.dbg & 2)) {
+    if (t < n_t1) {
       const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
       const int ao = l4 * SX + 16 * mt + l15;
       const double* __restrict__ Ac = (u & 1) ? Pi : Pr;
@@ -614,7 +608,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
     for (int j = 0; j + 1 < MAXT; j += 2) {
       const int tp = w + (j >> 1) * NW;
       v4f64 eE = {0.0, 0.0, 0.0, 0.0}, oE = eE, eO = eE, oO = eE;
-      if (tp < n_tp && !(a.dbg & 4)) {
+      if (tp < n_tp) {
         const int nt = tile_div(tp, g.q_mt2), mt = tp - nt * n_mt2;
         const int ycol = 16 * mt + l15, x = 16 * nt + l15;
         uint32_t mE = 0u, mO = 0u, d8 = 0u;
@@ -665,7 +659,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
     auto setup = [&](const int j) {
       Tile x{TT, 0u, 0u, false};
       const int t = w + j * NW;
-      x.on = (j < MAXT) && (t < n_t2) && !(a.dbg & 4);
+      x.on = (j < MAXT) && (t < n_t2);
       if (x.on) {
         const int nt = tile_div(t, g.q_mt2), mt = t - nt * n_mt2;
         x.a_p = TT + l4 * ST + 16 * mt + l15;
@@ -734,7 +728,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
   for (int j = 0; j < MAXT; ++j) {
     v4f64 ae = {0.0, 0.0, 0.0, 0.0}, ao = ae;
     const int t = w + j * NW;
-    if (t < n_t2 && !(a.dbg & 4)) {
+    if (t < n_t2) {
       const int nt = tile_div(t, g.q_mt2), mt = t - nt * n_mt2;
       const double* a_p = TT + l4 * ST + 16 * mt + l15;
       const double* gc_p = GC + l4 * M1 + 16 * nt + l15;
@@ -885,7 +879,7 @@ __device__ __forceinline__ void emit_field(const int w, const int lane, const Pr
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int y = 16 * mt + l4 + 4 * q;
-      if (sx.ok && (y < bh) && !(a.dbg & 8)) {
+      if (sx.ok && (y < bh)) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           if (half == 1 && !(x > 0 && x < hw)) continue;

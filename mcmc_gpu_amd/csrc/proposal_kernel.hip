@@ -29,7 +29,6 @@
 #include "philox.h"
 #include "proposal_device.h"
 #include <math.h>
-#include <stdlib.h>
 
 namespace gsm {
 
@@ -118,7 +117,6 @@ __global__ __launch_bounds__(NT, (WIDE == 1) ? NT / 256 : 1) void propose_kernel
   const int s = blockIdx.x, chain = blockIdx.y;
   const int64_t rec = (int64_t)chain * a.n_steps + s;
   const PropScalars sc = a.scalars[rec];
-  if (a.dbg & 64) { if (threadIdx.x == 0) a.fields[rec * a.field_stride] = (double)sc.bh; return; }
   double* __restrict__ out = a.fields + rec * a.field_stride;
   propose_field<NT, false, WIDE>((int)threadIdx.x, a, sc, a.seeds[chain], a.step0 + s, plds, red, out,
                                  [bw = sc.bw](int y, int x) { return y * bw + x; });
@@ -242,17 +240,12 @@ hipError_t launch_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id,
   return hipGetLastError();
 }
 
-hipError_t launch_propose(const ProposeArgs& a_in, hipStream_t st) {
-  ProposeArgs a = a_in;
-  { static int dbg = -1; if (dbg < 0) { const char* v = getenv("GSM_PROPOSE_DBG"); dbg = v ? atoi(v) : 0; } a.dbg = dbg; }
+hipError_t launch_propose(const ProposeArgs& a, hipStream_t st) {
   const size_t lds = ((size_t)a.lds_main + 32 + kMathTabDoubles) * sizeof(double);
-  static int nt = -1;   // GSM_PROPOSE_NT=1024: the fused kernel's workgroup size (tests: bit-identical fields)
-  if (nt < 0) { const char* v = getenv("GSM_PROPOSE_NT"); nt = (v && atoi(v) == 1024) ? 1024 : 512; }
   static bool attr_set[kMaxDevices] = {};
   int attr_dev;
   if (attr_needed_on_this_device(attr_set, attr_dev)) {
     hipError_t e = hipFuncSetAttribute((const void*)propose_kernel<512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)propose_kernel<1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)propose_kernel<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     if (attr_dev >= 0) attr_set[attr_dev] = true;
@@ -261,7 +254,6 @@ hipError_t launch_propose(const ProposeArgs& a_in, hipStream_t st) {
   const int64_t nrec = (int64_t)a.n_chains * a.n_steps;
   hipLaunchKernelGGL(propose_scalars_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, a);
   if (wide_table(a)) hipLaunchKernelGGL((propose_kernel<512, 2>), dim3(a.n_steps, a.n_chains), dim3(512), lds, st, a);
-  else if (nt == 1024) hipLaunchKernelGGL((propose_kernel<1024, 1>), dim3(a.n_steps, a.n_chains), dim3(1024), lds, st, a);
   else hipLaunchKernelGGL((propose_kernel<512, 1>), dim3(a.n_steps, a.n_chains), dim3(512), lds, st, a);
   return hipGetLastError();
 }

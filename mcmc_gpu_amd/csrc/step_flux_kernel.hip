@@ -33,15 +33,6 @@ namespace gsm {
 
 using namespace dev;
 
-#ifdef GSM_STAMPS
-// diagnostic build only (GSM_STAMPS=1 at build time): per-workgroup cycle totals of the phases, wave 0
-__device__ unsigned long long g_stamps[4096 * 8];
-#define STAMP(slot) do { if (tid == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[slot] += t_ - st_last; st_last = t_; } } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#endif
-
 size_t step_flux_lds_bytes(int tile_cap) { return ((size_t)2 * tile_cap + 4 * kNW + 64) * sizeof(double); }
 
 // KT = tile cells per thread: (bh + 2)(bw + 2) <= KT * 1024 for every block of the table (host-checked).
@@ -78,12 +69,7 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
   double n_u = a.u[rin0];
   __syncthreads();
 
-#ifdef GSM_STAMPS
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_last = __builtin_amdgcn_s_memtime();
-#endif
   for (int s = 0; s < a.n_steps; ++s) {
-    STAMP(7);
     const int64_t rin = rin0 + s;
     const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
     const int si = n_si, row = n_row, col = n_col;
@@ -117,7 +103,6 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
     const int dr = r0 - hr0, dc = c0 - hc0;  // window origin inside the tile (0 or 1)
 
     // geometry of the thread's k-th tile cell (recomputed per phase: cheaper than 2 registers per cell)
-    STAMP(0);
     int ptid = tid;   // re-laundered at each phase so that the geometry is recomputed, not kept live across phases
     auto cell = [&](int k, int& i, int& lr, int& lc, uint32_t& g, bool& valid, bool& inwin) {
       i = ptid + k * kNT;
@@ -182,9 +167,7 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       asm volatile("" : "+v"(acc_old));   // pin the partial sum here (otherwise the adds sink to phase R and the
       __builtin_amdgcn_sched_barrier(0);   // loaded energies stay live across phase D)
     }
-    STAMP(1);
     __syncthreads();
-    STAMP(2);
 
     // ---- D: residual stencil on the flux tiles ---------------------------------------------------------
     double e_new[KT];
@@ -228,7 +211,6 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       }
     }
 
-    STAMP(3);
     // ---- R: reduce, decide (every thread evaluates the same numbers in the same order) ----------------
     {
       // one sum: the thread's change of energy, or +inf from a thread whose candidate grounds the ice (MCMC.py:1321-1329:
@@ -238,9 +220,7 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       const double w_delta = wave64_sum(delta);
       if (lane == 0) red[wave] = w_delta;
     }
-    STAMP(4);
     __syncthreads();
-    STAMP(5);
     const double sd = row16_sum(red[lane & 15]);
     double c_hi, c_err;
     two_sum(s_hi, sd, c_hi, c_err);
@@ -271,7 +251,6 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       a.accept[rout] = acc ? 1 : 0;
       if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = bh; a.blocks[4 * rout + 3] = bw; }
     }
-    STAMP(6);
     // End of step.  LDS needs no barrier here: the tiles are rewritten only after every wave has passed the R barrier
     // (its stencil reads are done), and `red` only after the next A barrier.  The global stores of an accepted step must
     // be visible to the next step's loads only if the next halo window touches this window.
@@ -286,9 +265,6 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
     a.loss_sum[2 * chain] = s_hi;
     a.loss_sum[2 * chain + 1] = s_lo;
   }
-#ifdef GSM_STAMPS
-  if (tid == 0 && chain < 4096) for (int q = 0; q < 8; ++q) g_stamps[chain * 8 + q] = st_acc[q];
-#endif
 }
 
 template <typename TS, int KT>
@@ -335,15 +311,6 @@ __global__ __launch_bounds__(256) void pack_flux_static_kernel(const StaticField
     sB[g] = make_double2(S.velx[g], S.vely[g]);
     sC[g] = make_double2(S.mc[g] == 1 ? S.dhdt[g] : __builtin_nan(""), S.smb[g]);
   }
-}
-
-int debug_read_stamps(unsigned long long* out, int n_chains) {
-#ifdef GSM_STAMPS
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 8 * (size_t)n_chains) == hipSuccess ? 0 : -3;
-#else
-  (void)out; (void)n_chains;
-  return -4;
-#endif
 }
 
 hipError_t launch_pack_flux_static(const StaticFields& S, double2* sA, double2* sB, double2* sC, hipStream_t st) {

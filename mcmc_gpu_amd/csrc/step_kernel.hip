@@ -315,9 +315,7 @@ size_t step_lds_bytes(int tile_cap) { return ((size_t)tile_cap + 3 * 16 + 64) * 
 
 template <typename TS, int NT, int KMAX, int MINW>
 static hipError_t launch_step_t(const StepArgs& a, hipStream_t st) {
-  size_t lds = step_lds_bytes(a.tile_cap);
-  { static long pad = -1; if (pad < 0) { const char* v = getenv("GSM_STEP_LDS_PAD"); pad = v ? atol(v) : 0; }
-    if ((size_t)pad > lds) lds = (size_t)pad; }
+  const size_t lds = step_lds_bytes(a.tile_cap);
   auto kfast = step_kernel<TS, NT, KMAX, true, MINW>;
   auto kslow = step_kernel<TS, NT, KMAX, false, MINW>;
   static bool attr_set[kMaxDevices] = {};
@@ -338,23 +336,15 @@ hipError_t launch_step(const StepArgs& a, hipStream_t st) {
   // (window cells <= KMAX * NT and tile cells <= (KMAX + 1) * NT)
   if (a.strip) return launch_step_strip(a, st);      // pairs with chain_strip_kernel (same sums)
   const int max_win = std::max(a.B.max_bh * a.B.max_bw, a.tile_cap - 1024);
-  static int variant = -1;
-  if (variant < 0) { const char* v = getenv("GSM_STEP_VARIANT"); variant = v ? atoi(v) : 3; }
-  // default: the flux-tile kernel (step_flux_kernel.hip); blocks beyond its two LDS tiles fall back to the bed-tile form
-  if (variant == 3 && step_flux_supported(a)) return launch_step_flux(a, st);
+  // the flux-tile kernel (step_flux_kernel.hip); blocks beyond its two LDS tiles fall back to the bed-tile form
+  if (step_flux_supported(a)) return launch_step_flux(a, st);
   if (a.f32_state) {
     if (max_win <= 1024 * 7) return launch_step_t<float, 1024, 7, 8>(a, st);
     if (max_win <= 1024 * 12) return launch_step_t<float, 1024, 12, 4>(a, st);
     if (max_win <= 1024 * 20) return launch_step_t<float, 1024, 20, 4>(a, st);
     return hipErrorInvalidValue;
   }
-  if (max_win <= 1024 * 7) {
-    switch (variant) {
-      case 0: return launch_step_t<double, 1024, 7, 4>(a, st);
-      case 2: return launch_step_t<double, 512, 13, 4>(a, st);
-      default: return launch_step_t<double, 1024, 7, 8>(a, st);   // <=64 VGPRs: 2 workgroups per CU (fastest measured)
-    }
-  }
+  if (max_win <= 1024 * 7) return launch_step_t<double, 1024, 7, 8>(a, st);   // <=64 VGPRs: 2 workgroups per CU (fastest measured)
   if (max_win <= 1024 * 12) return launch_step_t<double, 1024, 12, 4>(a, st);
   if (max_win <= 1024 * 20) return launch_step_t<double, 1024, 20, 4>(a, st);
   return hipErrorInvalidValue;  // gsm_set_blocks refuses such tables (LDS tile limit is reached first)

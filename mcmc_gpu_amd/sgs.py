@@ -335,9 +335,6 @@ class chain_sgs_gpu:
         return out[0]
 
 
-LAST_GRAPH_REPLAYS = 0      # batches of the last device-draw run_many_sgs call that were hipGraph launches (gsm_sgs_iterate)
-
-
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -371,8 +368,7 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
     # smallScaleChain_multiprocessing.py:493-496) runs on the device (gsm_qt_transform); any other transformer object is
     # called on the host once per iteration, where the reference calls it
     dev_qt = (nst is not None and type(nst).__name__ == 'QuantileTransformer' and getattr(nst, 'output_distribution', None) == 'normal'
-              and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1
-              and os.environ.get('GSM_SGS_HOST_TRANSFORM', '0') != '1')
+              and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1)
     host_nst = nst if (nst is not None and not dev_qt) else None
     track = chain.sample_loc is not None
     keep_all = not only_save_last_bed
@@ -455,9 +451,9 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
             d_isdata = torch.as_tensor(np.ascontiguousarray(cond_is_data, dtype=np.uint8)).to(dev)
         from ._lib import SgsBatch
 
-        def make_batch(d_win, d_off, off_stride, d_cnt, d_cells, d_z, d_us, d_lrec, d_arec, cell_base=None, use_graph=False):
+        def make_batch(d_win, d_off, off_stride, d_cnt, d_cells, d_z, d_us, d_lrec, d_arec, cell_base=None):
             """gsm_sgs_batch (include/gsm.h) of one batch of iterations: the loop body of chain_sgs.run (MCMC.py:1741-1822) is issued
-            by ONE gsm_sgs_iterate call -- and, with static buffers and use_graph, replayed as one hipGraph launch."""
+            by ONE gsm_sgs_iterate call."""
             b = SgsBatch()
             pv = lambda t: t.data_ptr() if t is not None else None
             b.cur, b.next, b.proposed = pv(cur), pv(nxt), pv(prop) if dev_qt else None
@@ -474,7 +470,7 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
             b.resampled, b.loss, b.bad, b.loss_prev, b.accept = pv(resampled), pv(d_loss), pv(d_bad), pv(d_lprev), pv(d_acc)
             b.loss_rec, b.acc_rec = pv(d_lrec), pv(d_arec)
             b.radius, b.sill = rad, float(vario["sill"])
-            b.lag_mi, b.lag_mj, b.hw, b.num_points, b.max_cells, b.use_graph = lag_mi, lag_mj, hw, npts, max_cells, int(use_graph)
+            b.lag_mi, b.lag_mj, b.hw, b.num_points, b.max_cells = lag_mi, lag_mj, hw, npts, max_cells
             b.grid_finite = int(grid_finite)
             return b
 
@@ -483,19 +479,14 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
         grid_finite = os.environ.get('GSM_SGS_OVERLAP', '1') != '0' and bool(torch.isfinite(cur).all())
         it_done = 0
         if philox and n_iter > 0:
-            # device draws refill the SAME buffers batch after batch: the launch sequence of a full batch CAN be a hipGraph
-            # (captured on a side stream -- the legacy default stream cannot be captured)
-            # GSM_SGS_GRAPH=1.  Off by default: measured, the replay of a captured batch is no faster than its launches (the queue never runs
-            # dry), and capturing + instantiating the 256 nodes of a batch costs about 35 ms -- a third of a 100-iteration run of 256 chains
-            use_graph = batch > 1 and os.environ.get('GSM_SGS_GRAPH', '0') != '0'
             i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
             kmax = min(batch, n_iter)
             # two sets of draw buffers: the draws of batch b + 1 (they depend on the generators only, never on the chains' state) are
-            # made on their own stream while batch b iterates.  A captured batch needs ONE set of static buffers: no second set then.
+            # made on their own stream while batch b iterates.
             # Only for few chains (4 chains, pcg64 mode: 38.7 -> 56.2 k chain-iterations/s): with the chip full (256 chains) the draw
             # kernel fits into the gap where the host downloads a batch's records, and drawing ahead measured 10 % slower (same box)
             ahead = os.environ.get('GSM_SGS_DRAW_AHEAD', '1' if n <= 64 else '0') != '0'
-            n_sets = 2 if (ahead and not use_graph) else 1
+            n_sets = 2 if ahead else 1
             sets = []
             for _ in range(n_sets):
                 sets.append(dict(win=i32(kmax * n * 4), blk=i32(kmax * n * 4), off=i32(kmax * n), cnt=i32(kmax * n),
@@ -537,7 +528,7 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
             if nxt_kb > 0 and n_sets == 2:
                 draw(sets[(n_batch + 1) % 2], it_done + kb, nxt_kb)   # the other set: the batch that used it is over (its records were downloaded)
             with torch.cuda.device(dev), torch.cuda.stream(side):
-                bt = make_batch(d_win, d_off, n, d_cnt, bs['cells'], bs['z'], d_us, d_lrec, d_arec, use_graph=use_graph)
+                bt = make_batch(d_win, d_off, n, d_cnt, bs['cells'], bs['z'], d_us, d_lrec, d_arec)
                 eng._check(lib.gsm_sgs_iterate(h, C.byref(bt), kb, side.cuda_stream))
                 eng._check(lib.gsm_sgs_check(h, side.cuda_stream))
                 lrec_h, arec_h, blk_h = d_lrec.cpu().numpy(), d_arec.cpu().numpy(), d_blk.cpu().numpy()
@@ -558,8 +549,6 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
             if it_done >= n_iter:
                 torch.cuda.current_stream(dev).wait_stream(side)
                 torch.cuda.current_stream(dev).wait_stream(draw_st)
-                global LAST_GRAPH_REPLAYS
-                LAST_GRAPH_REPLAYS = int(lib.gsm_sgs_graph_replays(h))
             if progress_bar is not None:
                 el = time.time() - t0
                 print(f"Chain {getattr(chain, 'chain_id', 0)} ({str(getattr(chain, 'seed', 'Unknown'))[:6]}): "

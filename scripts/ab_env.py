@@ -1,5 +1,5 @@
 """Same-box A/B of one library under two environments (a diagnostic switch read at launch time):
-    python scripts/ab_env.py GSM_PROPOSE_DBG=0 GSM_PROPOSE_DBG=16384
+    python scripts/ab_env.py GSM_SPLIT2=1 GSM_SPLIT2=0
 Prints the median bench value of AB_REPS short bench.py runs per setting, interleaved (see ab_lib.py for the box-to-box caveat)."""
 import json, os, subprocess, sys
 from pathlib import Path

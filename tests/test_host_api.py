@@ -42,6 +42,24 @@ def test_struct_restatements_have_the_librarys_layout():
     assert lib.gsm_struct_size(99) == -1
 
 
+def test_environment_switches_are_the_listed_ones():
+    """The GSM_* variables the package reads (getenv in csrc/, os.environ in its Python modules) are exactly the part of DESIGN.md
+    §1's list that the package reads: switches that a test uses as its reference, and GSM_LIB / GSM_DIST_BACKEND."""
+    import re
+    found = set()
+    for p in sorted(_lib.CSRC.iterdir()):
+        found |= set(re.findall(r'getenv\(\s*"(GSM_\w+)"', p.read_text()))
+    for p in sorted(_lib.PKG_DIR.glob("*.py")):
+        for line in p.read_text().splitlines():
+            if "os.environ" in line:
+                found |= set(re.findall(r"""['"](GSM_\w+)['"]""", line))
+    listed = {"GSM_STRIP", "GSM_SPLIT2", "GSM_FUSED_SEGMENT", "GSM_SGS_BATCH", "GSM_SGS_OVERLAP", "GSM_SGS_DRAW_AHEAD",
+              "GSM_SGS_TAIL_QT", "GSM_SGS_WINDOWED", "GSM_LIB", "GSM_DIST_BACKEND"}
+    assert found == listed
+    design = (_lib.PKG_DIR.parent / "DESIGN.md").read_text()
+    assert all(f"`{name}`" in design for name in listed)
+
+
 def test_create_without_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():
