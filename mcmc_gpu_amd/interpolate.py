@@ -14,6 +14,9 @@ Numerics: the kriging systems are solved by Gauss-Jordan elimination where the r
 truncated-normal ppf is a restatement of scipy's (csrc/truncnorm.h), so values agree with the reference to ~1e-9 of the
 normal-score scale, not bit for bit.  Equidistant neighbour candidates are taken in ascending (row, col); the reference's
 argsort is unstable there.
+
+Grids: axis-aligned with uniform spacing; either axis may ascend or descend (north-up rasters) and the cells need not be
+square (tests/test_gpu_interp_sgs_geometry.py: both signs of both axes, |dy| / |dx| from 0.5 to 2).
 """
 from __future__ import annotations
 
@@ -148,23 +151,41 @@ class _Plan:
         return np.ascontiguousarray(path, dtype=np.int32), d
 
 
+def _window_rows(ys, dx, dy):
+    """Row coordinates on which the Euclidean distance to a value bounds the reference's search from above.  A search finds a
+    value when it lies within the radius AND within hw = ceil(radius / |dx|) cells of the cell in rows and in columns
+    (neighbors.py:4-64 scans that window only).  Columns: |dj| |dx| <= d < radius <= hw |dx| always.  Rows: only while
+    |dy| >= |dx|; with closer rows a value can be inside the radius and outside the window.  On rows spread to |dx| apart,
+    d' = sqrt(dx_^2 + (di |dx|)^2) >= max(d, |di| |dx|), so d' < radius puts the value inside both."""
+    if abs(dy) >= abs(dx):
+        return ys
+    return np.arange(ys.size, dtype=np.float64) * abs(dx)
+
+
+def _lag_extents_from(d, radius, dx, H, W):
+    """Lag table extents (rows, columns) from d, the distance (on _window_rows) of every cell to simulate to the nearest
+    conditioning value: a cell's search widens by 100 km at most k times, k the least number with d < radius + 100 km k, and the
+    window of that search is ceil(r / |dx|) cells either way, so two chosen neighbours are at most twice that apart."""
+    d_max = float(np.max(d)) if np.size(d) else 0.0
+    k = 0 if d_max < radius else int(math.floor((d_max - radius) / WIDEN_STEP)) + 1
+    r_max = radius + WIDEN_STEP * k
+    hw_max = int(math.ceil(r_max / abs(dx))) + 1
+    return min(2 * hw_max, H - 1), min(2 * hw_max, W - 1)
+
+
 def _lag_extents(plan, eng, torch):
-    """Lag table extents that the radius widening never runs off: every visit's radius stays below radius + 100 km k, with k
-    from the largest distance of a cell to simulate to the nearest conditioning value (gsm_min_dist_from_mask)."""
+    """Lag table extents that the radius widening never runs off (_lag_extents_from), the distances from
+    gsm_min_dist_from_mask."""
     H, W = plan.H, plan.W
     dev = eng.dev
+    ys = _window_rows(plan.ys, plan.dx, plan.dy)
     xx = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(plan.xs[None, :], (H, W)))).to(dev)
-    yy = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(plan.ys[:, None], (H, W)))).to(dev)
+    yy = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(ys[:, None], (H, W)))).to(dev)
     mask = torch.as_tensor(plan.cond.astype(np.uint8).ravel()).to(dev)
     dist = torch.empty(H * W, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         eng._check(eng.lib.gsm_min_dist_from_mask(eng.h, _ptr(xx), _ptr(yy), _ptr(mask), _ptr(dist), eng._stream()))
-    d = dist.cpu().numpy()[~plan.cond.ravel()]
-    d_max = float(d.max()) if d.size else 0.0
-    k = 0 if d_max < plan.radius else int(math.floor((d_max - plan.radius) / WIDEN_STEP)) + 1
-    r_max = plan.radius + WIDEN_STEP * k
-    hw_max = int(math.ceil(r_max / abs(plan.dx))) + 1
-    return min(2 * hw_max, H - 1), min(2 * hw_max, W - 1)
+    return _lag_extents_from(dist.cpu().numpy()[~plan.cond.ravel()], plan.radius, plan.dx, H, W)
 
 
 def _segment_cells(R, max_path, torch, dev, extra_bytes):

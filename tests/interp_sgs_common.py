@@ -56,3 +56,74 @@ def t2_like():
     vario = dict(major_range=15000.0, minor_range=15000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Matern", s=1.5)
     kw = dict(radius=10e3, num_points=48, ktype="ok", bounds=(float(np.nanmin(grid)) - 100.0, surf))
     return xx, yy, grid, {"d": (vario, kw, [41])}
+
+
+def _lines(H, W, a, b):
+    cond = np.zeros((H, W), bool)
+    cond[::a, :] = True
+    cond[:, ::b] = True
+    return cond
+
+
+def _mesh(H, W, dx, dy, x_desc=False, y_desc=False):
+    x, y = np.arange(W) * dx, np.arange(H) * dy
+    return np.meshgrid(x[::-1].copy() if x_desc else x, y[::-1].copy() if y_desc else y)
+
+
+def geometry():
+    """Grids golden F14 leaves out, for tests against the CPU oracle (test_gpu_interp_sgs_geometry.py): square cells (distance
+    ties everywhere), descending axes (north-up rasters), cells far from square, several widenings of the radius, the
+    reference's default arguments (a 200-ring window), num_points that is no multiple of 8, a window that clips the rows
+    before the radius does.  id -> (xx, yy, grid, variogram, keyword arguments, seeds); seed 5 is the realisation on which
+    each case's reason for being here is asserted."""
+    exp_aniso = dict(major_range=8000.0, minor_range=5000.0, azimuth=30.0, sill=1.0, nugget=0.0, vtype="Exponential")
+    matern = dict(major_range=6000.0, minor_range=6000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Matern", s=1.5)
+    exp_far = dict(major_range=60e3, minor_range=60e3, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Exponential")
+    out = {}
+    # G1, G2, G8: F14's 40 x 44 layout (conditioning lines with a gap wider than the radius) on square cells
+    H, W = 40, 44
+    cond = _lines(H, W, 5, 7)
+    cond[8:34, 10:40] = False
+    grid = np.where(cond, field(H, W, 21), np.nan)
+    lo = float(np.nanmin(grid)) - 25.0                    # the bounds of small()'s case b
+    up = np.full((H, W), float(np.nanmax(grid)) + 50.0)
+    up[:, :W // 3] = np.nanquantile(grid, 0.7)
+    up[30:36, 2:9] = lo - 10.0
+    sim_mask = np.zeros((H, W), bool)
+    sim_mask[4:36, 6:40] = True
+    out["G1"] = (*_mesh(H, W, 500.0, 500.0, y_desc=True), grid, exp_aniso,
+                 dict(radius=3000.0, num_points=24, ktype="ok", bounds=(lo, up)), [5, 6, 7])
+    out["G2"] = (*_mesh(H, W, 500.0, 500.0, x_desc=True, y_desc=True), grid, matern,
+                 dict(radius=3000.0, num_points=16, ktype="sk", sim_mask=sim_mask), [5, 6])
+    out["G8"] = (*_mesh(H, W, 500.0, 500.0, x_desc=True), grid,
+                 dict(major_range=7000.0, minor_range=7000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Spherical"),
+                 dict(radius=4000.0, num_points=8, ktype="ok"), [5, 6])
+    # G3: rows half as far apart as columns -- the +-hw-cell window ends at 1.5 km in y, the radius at 3 km
+    H, W = 48, 40
+    out["G3"] = (*_mesh(H, W, 500.0, 250.0), np.where(_lines(H, W, 5, 7), field(H, W, 23), np.nan), exp_aniso,
+                 dict(radius=3000.0, num_points=48, ktype="ok"), [5, 6])
+    # G4: rows twice as far apart as columns, y descending, 20 points = 2 per octant
+    H, W = 36, 60
+    out["G4"] = (*_mesh(H, W, 500.0, 1000.0, y_desc=True), np.where(_lines(H, W, 5, 7), field(H, W, 24), np.nan), matern,
+                 dict(radius=4000.0, num_points=20, ktype="ok"), [5, 6])
+    # G5: data in one corner of a 240 km grid, radius 10 km: up to two widenings, systems of one neighbour
+    H = W = 48
+    cond = np.zeros((H, W), bool)
+    cond[:4, :4] = True
+    out["G5"] = (*_mesh(H, W, 5000.0, 5037.0), np.where(cond, field(H, W, 25), np.nan), exp_far,
+                 dict(radius=10e3, num_points=16, ktype="ok"), [5, 6, 7])
+    # G6: the reference's default radius and num_points: a 200-ring window, neighbours beyond 64 rings
+    H = W = 100
+    cond = np.zeros((H, W), bool)
+    cond[0, ::3] = True
+    cond[::4, 0] = True
+    out["G6"] = (*_mesh(H, W, 500.0, TIE_FREE_DY), np.where(cond, field(H, W, 26), np.nan), exp_far,
+                 dict(radius=100e3, num_points=20, ktype="ok"), [5])
+    # G7: data rows 4 km apart in y but 16 rows apart: inside the radius, outside the window -- searches come back empty and widen
+    H, W = 97, 64
+    cond = np.zeros((H, W), bool)
+    cond[::16, ::3] = True
+    out["G7"] = (*_mesh(H, W, 500.0, 250.0), np.where(cond, field(H, W, 27), np.nan),
+                 dict(major_range=6000.0, minor_range=6000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Exponential"),
+                 dict(radius=3000.0, num_points=16, ktype="ok"), [5, 6])
+    return out

@@ -172,3 +172,57 @@ def test_sgs_many_of_no_seed_is_empty():
     from mcmc_gpu_amd import interpolate
     xx, yy, grid, vario, kw, _, _ = _case("a")
     assert interpolate.sgs_many(xx, yy, grid, vario, [], radius=3000.0, num_points=16).shape == (0,) + grid.shape
+
+
+def _lag_case(cid):
+    if cid.startswith("small"):
+        xx, yy, grid, cases = ic.small()
+        vario, kw, seeds = cases[cid[-1]]
+        return xx, yy, grid, vario, kw, seeds[0]
+    xx, yy, grid, vario, kw, _ = ic.geometry()[cid]
+    return xx, yy, grid, vario, kw, 5
+
+
+@pytest.mark.parametrize("cid", ["small_a", "small_c", "G3", "G5", "G7"])
+def test_lag_table_reaches_every_lag_of_the_reference_search(cid):
+    """interpolate._lag_extents_from on KD-tree distances (what gsm_min_dist_from_mask returns, test_min_dist_device_equals_kdtree)
+    against the neighbours the oracle's search actually chooses: every lag between a cell and a chosen neighbour and between two
+    chosen neighbours fits the table.  G7: rows 250 m apart under a 3 km radius and a +-6-cell window -- values inside the radius
+    but outside the window, searches that come back empty and widen by 100 km.  The Euclidean distance alone (2062 m at most)
+    says no search widens there."""
+    import warnings
+    from scipy.spatial import cKDTree
+    import sgs_oracle as so
+    from mcmc_gpu_amd import interpolate
+    xx, yy, grid, vario, kw, seed = _lag_case(cid)
+    plan = interpolate._Plan(xx, yy, grid, vario, kw["radius"], kw["num_points"], kw["ktype"], kw.get("sim_mask"), None, None,
+                             kw.get("bounds"))
+    H, W = plan.H, plan.W
+    rows = interpolate._window_rows(plan.ys, plan.dx, plan.dy)
+    pts = np.stack([np.broadcast_to(plan.xs[None, :], (H, W)).ravel(), np.broadcast_to(rows[:, None], (H, W)).ravel()], axis=1)
+    d = cKDTree(pts[plan.cond.ravel()]).query(pts[~plan.cond.ravel()])[0]
+    mi, mj = interpolate._lag_extents_from(d, plan.radius, plan.dx, H, W)
+    # never smaller than the table of the Euclidean distance on the grid's own rows
+    pts0 = np.stack([xx.ravel(), yy.ravel()], axis=1)
+    d0 = cKDTree(pts0[plan.cond.ravel()]).query(pts0[~plan.cond.ravel()])[0]
+    mi0, mj0 = interpolate._lag_extents_from(d0, plan.radius, plan.dx, H, W)
+    assert mi >= mi0 and mj >= mj0
+    if abs(plan.dy) >= abs(plan.dx):
+        assert (mi, mj) == (mi0, mj0)
+    so.STABLE_TIES, so.NBR_LOG = True, []
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            so.sgs(xx, yy, plan.grid_ns, dict(vario), kw["radius"], kw["num_points"], kw["ktype"], sim_mask=kw.get("sim_mask"),
+                   rng=np.random.default_rng(seed), bounds=plan.bounds)
+        log = so.NBR_LOG
+    finally:
+        so.STABLE_TIES, so.NBR_LOG = False, None
+    need_i = need_j = 0
+    for i, j, nb in log:
+        if nb:
+            a = np.array(nb + [(i, j)])
+            need_i, need_j = max(need_i, int(np.ptp(a[:, 0]))), max(need_j, int(np.ptp(a[:, 1])))
+    assert 0 < need_i <= mi and 0 < need_j <= mj, (need_i, need_j, mi, mj)
+    if cid == "G7":
+        assert need_i > mi0, "the case no longer needs more rows than the Euclidean rule gives"
