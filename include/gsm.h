@@ -478,6 +478,60 @@ int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* batch, int32_t n_iters, v
 int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, const uint8_t* mask, double* dist,
                            void* stream);
 
+/* ---- posterior accumulator: moments of the bed over all chains and a thinned set of iterations --------------------------
+ * The reference looks inside a run through host caches of one chain: bed_cache[i] = bed_c (only_save_last_bed=False,
+ * MCMC.py:1198, :1362-1363) and sample_values[:, i] = bed_c at the sample points (set_sample_points_locations,
+ * MCMC.py:1174-1182, :1366), one whole-bed copy per iteration.  These entry points keep, on the device and for every chain of
+ * the handle, what statistics of bed_cache[burn_in::thin] need -- shifted sums per cell -- and copy the sample points.  The
+ * caller decides which iterations are snapshots and calls once per snapshot between two run calls; all arrays are caller-owned.
+ * `beds` is the handle's state array [dev, n_chains*H*W] in its state dtype (double, or float for dtype 1).
+ *
+ * gsm_posterior_accumulate: one snapshot into the sums of ONE sequence of every chain (a chain, or one half of it for
+ * split-R-hat).  ref [dev, n_chains*H*W], state dtype: each chain's bed at the first snapshot of the sequence being filled.  first != 0: ref = bed is
+ * written and s1 = d, s2 = d*d with d = bed - bed (0; NaN where the bed is not finite); otherwise d = bed - ref, s1 += d,
+ * s2 += d*d.  s1, s2 [dev, n_chains*H*W] fp64.  The shift keeps the variance (s2 - s1^2/N)/(N-1) free of cancellation against
+ * the bed's magnitude, and a cell that never changes has d == 0, hence s1 == s2 == 0 and variance 0, exactly.  beds, ref, s1
+ * and s2 must be 16-byte aligned (GSM_E_ARG otherwise).  sample_out [dev, n_chains*n_samples] fp64 (may be NULL) receives
+ * bed_c[sample_cells[p]] at c*n_samples + p, sample_cells [dev, n_samples] flat cell indices row*W+col (NaN for an index
+ * outside the grid).  48 bytes per chain-cell with fp64 state (8 bed, 8 ref, 16 read and 16 written of the sums), one pass.
+ * Replaces: bed_cache / sample_values of chain_crf.run (MCMC.py:1198, :1362-1366) as the input of per-chain moments.
+ *
+ * gsm_posterior_accumulate_pooled: the same snapshot into sums over ALL chains, when no per-chain statistic is wanted:
+ * S1[cell] += sum_c d, S2[cell] += sum_c d*d with d = bed_c - g, g [dev, H*W] fp64 one common reference field, S1, S2
+ * [dev, H*W] fp64.  Reads the beds only (8 bytes per chain-cell).  Chains are summed in index order within a part of the chain
+ * axis and the parts in part order (a second kernel; no atomics): bit-reproducible from run to run.
+ *
+ * gsm_posterior_sample: the sample points alone (a snapshot that belongs to no sequence).
+ *
+ * gsm_posterior_close: a finished sequence's sums become its statistics, in place: s1 = a_m = (ref_c - g) + s1 / N (the
+ * sequence mean minus the common field g [dev, H*W]), s2 = v_m = (s2 - s1^2 / N) / (N - 1) (its ddof=1 variance), N = n_per_seq.
+ * `ref` is then free for the next sequence of the same chains (gsm_posterior_accumulate with first != 0), so that every sequence
+ * is shifted by a bed of its own: a cell that is constant within a sequence has v_m == 0 exactly, also when it changed between
+ * the two halves of a chain.  GSM_E_ARG for NULL pointers or n_per_seq < 2.
+ *
+ * gsm_posterior_partials: reduction over this handle's sequences, per cell, to partials [dev, 3*H*W] fp64:
+ *   P0 = sum_m a_m, P1 = sum_m a_m^2, P2 = sum_m v_m,  a_m = (ref_c - g) + s1_m / N,  v_m = (s2_m - s1_m^2 / N) / (N - 1)
+ * with N = n_per_seq snapshots per sequence; a_m is sequence m's mean minus the common field g [dev, H*W] (which only keeps P1
+ * well conditioned), v_m its ddof=1 variance.  Sequence k < n_seq_per_chain (1 or 2) of chain c has its sums at
+ * s1 + k*seq_stride + c*H*W (likewise s2); the first n_closed sequences of every chain were closed (their arrays hold a_m, v_m),
+ * the others are open and `ref` is theirs.  The sum runs over chains in index order, k innermost.  Partials of several handles
+ * (ranks) add.  With M sequences in all: mean = g + P0/M, within-sequence variance W = P2/M, between-sequence variance over N
+ * B/N = (P1 - P0^2/M)/(M-1), pooled ddof=1 variance ((N-1) P2 + N (P1 - P0^2/M)) / (M N - 1), R-hat = sqrt(((N-1)/N W + B/N) / W).
+ * Errors: GSM_E_ARG for NULL pointers, n_per_seq < 2, n_seq_per_chain not 1 or 2, n_closed outside [0, n_seq_per_chain],
+ * seq_stride < n_chains*H*W with two sequences.
+ * Replaces: numpy statistics over bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
+ * All five are asynchronous on `stream`. */
+int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
+                             const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
+int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
+                                    const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
+int gsm_posterior_sample(gsm_handle h, const void* beds, const int32_t* sample_cells, int32_t n_samples, double* sample_out,
+                         void* stream);
+int gsm_posterior_close(gsm_handle h, const void* ref, const double* g, double* s1, double* s2, int32_t n_per_seq, void* stream);
+int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const double* s1, const double* s2,
+                           int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
+                           void* stream);
+
 /* Diagnostics: stream-copy n doubles src -> dst [dev] with the step kernel's access shape (8 bytes per lane,
  * coalesced).  A known byte count for calibrating rocprofv3's FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM). */
 int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream);

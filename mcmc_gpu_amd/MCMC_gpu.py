@@ -551,38 +551,81 @@ class chain_crf_gpu:
         return out + (sample_values,) if track else out
 
 
-def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0=0, return_device=False):
+def _result_tuples(eng, loss0, loss, acc, blk, n_iter):
+    """Per-chain 7-tuples shaped like chain.run(..., only_save_last_bed=True) from a finished Philox-mode engine."""
+    beds_out = eng.beds.double().cpu().numpy()
+    res = eng.resampled.cpu().numpy().astype(np.float64)
+    out = []
+    for c in range(eng.n_chains):
+        lc = np.concatenate([[loss0[c]], loss[c]])
+        sc = np.concatenate([[0.0], acc[c].astype(np.float64)])
+        bc = np.vstack([np.full((1, 4), np.nan), blk[c].astype(np.float64)])
+        out.append((beds_out[c], lc.copy(), np.zeros(int(n_iter)), lc, sc, res[c], bc))
+    return out
+
+
+def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
+    """The Philox run of run_many advanced from snapshot to snapshot: a run split into stretches reproduces the unsplit run bit
+    for bit (include/gsm.h, gsm_propose_philox), so the snapshots change no chain.  Iteration k is the bed after k proposals."""
+    from .posterior import PosteriorAccumulator, default_common_ref
+    g = opt['common_ref'] if opt['common_ref'] is not None else default_common_ref(chain.initial_bed)
+    ij = chain._sample_indices() if chain.sample_loc is not None else None
+    accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
+                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc)
+    n_chains = eng.n_chains
+    parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
+    done = 0                                   # eng.beds holds iteration `done`
+    for k in [int(v) for v in accum.snapshot_iterations] + [int(n_iter) - 1]:
+        if k > done:
+            parts.append(eng.run_philox(k - done, step0 + done, seeds, RF, batch=batch))
+            done = k
+        if accum.n_added < accum.T:
+            accum.add()
+    return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(3)), accum
+
+
+def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0=0, return_device=False, posterior=None):
     """Batched entry the reference lacks: n independent Philox-mode chains of one template (same static fields,
     same RandField) on one GPU.  Returns a list of per-chain 7-tuples shaped like chain.run(..., only_save_last_bed=True)
-    (what Pool.starmap returns in largeScaleChain_mp, largeScaleChain_multiprocessing_GPU.py:84-85)."""
+    (what Pool.starmap returns in largeScaleChain_mp, largeScaleChain_multiprocessing_GPU.py:84-85).
+
+    posterior: None, or a dict with `burn_in`, `thin` and optionally `split` (True), `rhat` (True), `common_ref` (the template's
+    initial bed) -- see mcmc_gpu_amd/posterior.py.  The run then stops at every snapshot iteration, folds all chains' beds into
+    running moments on the device, and the call returns (results, PosteriorSummary): mean, sd and split-R-hat maps over all
+    chains, and the thinned traces at chain.sample_loc if set_sample_points_locations was called.  `results` is what the call
+    returns without `posterior`.  With return_device=True the PosteriorAccumulator is returned in place of the summary (its
+    partials() can be merged over ranks first)."""
     if not isinstance(RF, RandField):
         raise TypeError('The arugment "RF" has to be an object of the class RandField')
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     if len(seeds) != n_chains:
         raise ValueError('need one seed per chain')
+    if posterior is not None:
+        from .posterior import check_options
+        posterior = check_options(posterior, n_iter)
     eng = chain._make_engine(RF, n_chains, device)
+    accum = None
     try:
         loss0 = eng.set_state(beds)
         n_steps = int(n_iter) - 1
-        if n_steps > 0:
-            loss, acc, blk = eng.run_philox(n_steps, step0, [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], RF, batch=batch)
+        seeds64 = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+        if posterior is not None:
+            (loss, acc, blk), accum = _run_with_posterior(chain, eng, RF, seeds64, n_iter, batch, step0, posterior)
+        elif n_steps > 0:
+            loss, acc, blk = eng.run_philox(n_steps, step0, seeds64, RF, batch=batch)
         else:
             loss = np.zeros((n_chains, 0)); acc = np.zeros((n_chains, 0), np.uint8); blk = np.zeros((n_chains, 0, 4), np.int32)
         if return_device:
-            return eng, loss0, loss, acc, blk
-        beds_out = eng.beds.double().cpu().numpy()
-        res = eng.resampled.cpu().numpy().astype(np.float64)
-    finally:
-        if not return_device:
-            eng.close()
-    out = []
-    for c in range(n_chains):
-        lc = np.concatenate([[loss0[c]], loss[c]])
-        sc = np.concatenate([[0.0], acc[c].astype(np.float64)])
-        bc = np.vstack([np.full((1, 4), np.nan), blk[c].astype(np.float64)])
-        out.append((beds_out[c], lc.copy(), np.zeros(int(n_iter)), lc, sc, res[c], bc))
-    return out
+            dev = (eng, loss0, loss, acc, blk)
+            return dev if accum is None else (dev, accum)
+        out = _result_tuples(eng, loss0, loss, acc, blk, n_iter)
+        summary = None if accum is None else accum.finalize()
+    except BaseException:
+        eng.close()
+        raise
+    eng.close()
+    return out if accum is None else (out, summary)
 
 
 def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, chunk=None, n_workers=None, device=None,

@@ -132,12 +132,33 @@ def _make_params(largeScaleChain, rf, i, initial_beds, rng_seeds, n_iters, outpu
     return chain_param, rf_param, run_param
 
 
-def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, n_workers):
+def _segment_label(prev, n_iter):
+    """The `{k}k` of the files _save_segment writes for a chain resumed from `prev`."""
+    label_count = prev.get('label_count', prev['cumulative']) if prev is not None else 0
+    return f'{(label_count + n_iter) // 1000}k'
+
+
+def _merge_posterior(accum, part, n_chains, base, label):
+    """Sum this rank's posterior partials with the other ranks', gather the sample traces, and let rank 0 write the summary."""
+    import torch.distributed as dist
+    total, M = parallel.all_reduce_posterior(part, accum.n_sequences)
+    sv = None
+    if accum.d_samples is not None:                # [T, local chains, points] on the device -> [n_chains, points, T]
+        sv = parallel.all_gather_chains(accum.d_samples.permute(1, 2, 0).contiguous(), n_chains).cpu().numpy()
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
+        base.mkdir(parents=True, exist_ok=True)
+        accum.finalize(total, M, sample_values=sv).save(base / f'posterior_{label}.npz')
+
+
+def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, n_workers,
+               posterior=None, n_chains=None):
     """The chains [lo, hi) of this rank: one libgsm_hip handle for all of them when they share n_iter (and, in Philox
     mode, the Philox step); otherwise chain by chain through lsc_run_wrapper."""
     base = Path(output_path) / 'LargeScaleChain'
     idx = list(range(lo, hi))
     same_len = len(set(int(n_iters[i]) for i in idx)) <= 1
+    if posterior is not None and not (same_len and idx):
+        raise ValueError('posterior= needs the same n_iter for every chain and at least one chain on every rank')
     if same_len and idx:
         n_iter = int(n_iters[lo])
         prevs = [_load_previous(_seed_folder(base, rng_seeds[i])) for i in idx]
@@ -147,7 +168,20 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
         ch_st = [p.get('chain_state', g) if p else g for p, g in zip(prevs, fresh)]
         steps0 = [int(p['philox']['step']) if (p and 'philox' in p) else 0 for p in prevs]
         seeds = [int(rng_seeds[i]) for i in idx]
-        if mode == 'philox' and len(set(steps0)) == 1:
+        accum = None
+        if posterior is not None and not (mode == 'philox' and len(set(steps0)) == 1):
+            raise ValueError("posterior= is built for Philox mode with all chains at the same Philox step (one shared handle); "
+                             f"this call is mode '{mode}' with steps {sorted(set(steps0))}")
+        if mode == 'philox' and len(set(steps0)) == 1 and posterior is not None:
+            dev, accum = MCMC_gpu.run_many(largeScaleChain, rf, beds, seeds, n_iter, batch=batch, step0=steps0[0],
+                                           return_device=True, posterior=posterior)
+            try:
+                local = MCMC_gpu._result_tuples(*dev, n_iter)
+                part = accum.partials()
+            finally:
+                dev[0].close()
+            steps1 = [steps0[0] + n_iter - 1] * len(idx)
+        elif mode == 'philox' and len(set(steps0)) == 1:
             local = MCMC_gpu.run_many(largeScaleChain, rf, beds, seeds, n_iter, batch=batch, step0=steps0[0])
             steps1 = [steps0[0] + n_iter - 1] * len(idx)
         elif mode == 'replay':
@@ -163,6 +197,9 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
             for k, i in enumerate(idx):
                 _save_segment(_seed_folder(base, rng_seeds[i]), local[k], n_iter, prevs[k], rf_st[k], ch_st[k],
                               {'key': seeds[k] & 0xFFFFFFFFFFFFFFFF, 'step': steps1[k]})
+            if accum is not None:
+                # only rank 0 writes, and its first chain is chain 0: the label is that of chain 0's files
+                _merge_posterior(accum, part, n_chains if n_chains is not None else len(idx), base, _segment_label(prevs[0], n_iter))
             return local
     local = []
     for i in idx:
@@ -221,7 +258,7 @@ def _self_launch(n_gpus, kw, which='largeScaleChain_mp'):
 
 
 def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, rng_seeds, n_iters,
-                       output_path='./Data/output', mode=None, batch=8, gather=True, n_gpus=None):
+                       output_path='./Data/output', mode=None, batch=8, gather=True, n_gpus=None, posterior=None):
     """Run n_chains large-scale chains and return the list of their result tuples (reference :22-104).
 
     mode 'replay' (default when largeScaleChain.rng_mode == 'replay'): every chain draws from its own NumPy
@@ -235,9 +272,23 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
 
     n_gpus: None = every visible GPU.  With more than one and no torch.distributed group in this process, the function
     starts its own ranks (one fresh process per GPU, RCCL) -- the caller brings no launcher, like the reference's driver;
-    under torchrun (or inside such a rank) the initialised group is used and this process runs its shard."""
+    under torchrun (or inside such a rank) the initialised group is used and this process runs its shard.
+
+    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`).  Philox mode with all
+    chains sharing n_iter and the Philox step only (any other combination is a ValueError).  Return value and per-seed
+    checkpoint files are unchanged; rank 0 also writes <output_path>/LargeScaleChain/posterior_{k}k.npz (posterior.
+    PosteriorSummary.load reads it; {k}k as in the first chain's bed_{k}k.npy) with the mean, sd and split-R-hat maps over the
+    chains of ALL ranks (one all-reduce of [3, H, W]) and the traces at the template's sample points.  The summary covers THIS
+    call's segment: iteration 0 is the bed the segment starts from, and accumulators are not carried across driver calls."""
     tic = time.time()
     mode = mode or getattr(largeScaleChain, 'rng_mode', 'replay')
+    if posterior is not None:
+        from .posterior import check_options
+        if mode != 'philox':
+            raise ValueError(f"posterior= is built for mode 'philox' only (shared-handle runs); got mode '{mode}'")
+        if len(set(int(v) for v in n_iters[:n_chains])) != 1:
+            raise ValueError('posterior= needs the same n_iter for every chain')
+        check_options(posterior, n_iters[0])
     import os
     import torch.distributed as dist
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
@@ -249,7 +300,7 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
         if n_gpus > 1:
             res = _self_launch(n_gpus, dict(n_chains=n_chains, n_workers=n_workers, largeScaleChain=largeScaleChain, rf=rf,
                                             initial_beds=initial_beds, rng_seeds=rng_seeds, n_iters=n_iters,
-                                            output_path=output_path, mode=mode, batch=batch, gather=True))
+                                            output_path=output_path, mode=mode, batch=batch, gather=True, posterior=posterior))
             print(f'Completed in {time.time() - tic:.2f} seconds')
             return res
     rank, world = (dist.get_rank(), dist.get_world_size()) if sharded else (0, 1)
@@ -257,7 +308,8 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     workers = n_workers
     if workers and workers > 0 and world > 1:
         workers = max(1, workers // world)
-    result = _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, workers)
+    result = _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, workers,
+                        posterior=posterior, n_chains=n_chains)
     if sharded and gather:
         result = _gather_results(result, n_chains, lo, hi)
     if rank == 0:

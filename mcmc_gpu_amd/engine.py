@@ -169,6 +169,75 @@ class GsmEngine:
             self._check(self.lib.gsm_residual(self.h, _ptr(b), _ptr(out), self._stream()))
         return out
 
+    # ---- posterior accumulator (gsm_posterior_*; mcmc_gpu_amd/posterior.py owns the tensors) ------------------------------
+    def _sample_args(self, sample_cells, sample_out):
+        if sample_out is None:
+            return _ptr(None), 0, _ptr(None)
+        if sample_cells is None or sample_cells.dtype != torch.int32 or sample_out.dtype != torch.float64 or \
+                sample_out.numel() != self.n_chains * sample_cells.numel() or not sample_out.is_contiguous():
+            raise ValueError("sample_cells must be an int32 device tensor and sample_out a contiguous float64 one of n_chains x n_samples")
+        return _ptr(sample_cells), int(sample_cells.numel()), _ptr(sample_out)
+
+    def _check_sums(self, n, **tensors):
+        for name, t in tensors.items():
+            if t.dtype != torch.float64 or t.numel() < n or not t.is_contiguous() or t.device != self.dev:
+                raise ValueError(f"{name} must be a contiguous float64 tensor of at least {n} elements on {self.dev}")
+
+    def posterior_accumulate(self, ref, s1, s2, first, sample_cells=None, sample_out=None):
+        """One snapshot of self.beds into the per-chain sums of one sequence: d = bed - ref, s1 += d, s2 += d * d (first: ref = bed is
+        written and the sums are set).  ref [n_chains, H, W] in the state dtype, s1 / s2 float64 of the same size.  Asynchronous."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        n = self.n_chains * self.H * self.W
+        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
+            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
+        self._check_sums(n, s1=s1, s2=s2)
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_accumulate(self.h, _ptr(self.beds), _ptr(ref), _ptr(s1), _ptr(s2), 1 if first else 0,
+                                                          *self._sample_args(sample_cells, sample_out), self._stream()))
+
+    def posterior_accumulate_pooled(self, g, s1, s2, sample_cells=None, sample_out=None):
+        """One snapshot of self.beds into sums over all chains: S1 += sum_c d, S2 += sum_c d * d, d = bed_c - g; g, s1, s2 [H, W] float64."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        self._check_sums(self.H * self.W, g=g, s1=s1, s2=s2)
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_accumulate_pooled(self.h, _ptr(self.beds), _ptr(g), _ptr(s1), _ptr(s2),
+                                                                 *self._sample_args(sample_cells, sample_out), self._stream()))
+
+    def posterior_sample(self, sample_cells, sample_out):
+        """sample_out[c, p] = self.beds[c] at flat cell sample_cells[p]."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_sample(self.h, _ptr(self.beds), *self._sample_args(sample_cells, sample_out), self._stream()))
+
+    def posterior_close(self, ref, g, s1, s2, n_per_seq):
+        """A finished sequence's sums become, in place, s1 = its mean minus g and s2 = its ddof=1 variance; `ref` is then free for
+        the chains' next sequence (posterior_accumulate with first=True)."""
+        n = self.n_chains * self.H * self.W
+        self._check_sums(self.H * self.W, g=g)
+        self._check_sums(n, s1=s1, s2=s2)
+        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
+            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_close(self.h, _ptr(ref), _ptr(g), _ptr(s1), _ptr(s2), int(n_per_seq), self._stream()))
+
+    def posterior_partials(self, ref, g, s1, s2, n_seq_per_chain, seq_stride, n_closed, n_per_seq):
+        """[3, H, W] device tensor (sum of sequence means minus g, of their squares, of sequence variances) over this handle's
+        n_chains * n_seq_per_chain sequences of n_per_seq snapshots; sequence k's sums start at s1.view(-1)[k * seq_stride]; the
+        first n_closed sequences of every chain were closed (posterior_close), `ref` belongs to the others."""
+        n = self.n_chains * self.H * self.W
+        self._check_sums(self.H * self.W, g=g)
+        self._check_sums((int(n_seq_per_chain) - 1) * int(seq_stride) + n if n_seq_per_chain in (1, 2) else n, s1=s1, s2=s2)
+        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
+            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
+        out = torch.empty((3, self.H, self.W), dtype=torch.float64, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_partials(self.h, _ptr(ref), _ptr(g), _ptr(s1), _ptr(s2), int(n_seq_per_chain), int(seq_stride),
+                                                        int(n_closed), int(n_per_seq), _ptr(out), self._stream()))
+        return out
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

@@ -87,6 +87,24 @@ def all_reduce_mean_field(local_sum: torch.Tensor, n_chains: int) -> torch.Tenso
     return t / float(n_chains)
 
 
+def all_reduce_posterior(partials: torch.Tensor, n_local_sequences: int):
+    """Posterior partials ([3, H, W] sums over this rank's sequences, posterior.PosteriorAccumulator.partials) and the sequence
+    count summed over ranks: one SUM all-reduce each.  Returns (partials_sum, M)."""
+    t = partials.clone()
+    m = torch.tensor([int(n_local_sequences)], dtype=torch.int64)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        if _via_host(t) or not t.is_cuda:
+            h = t.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM)
+            dist.all_reduce(m, op=dist.ReduceOp.SUM)
+            t = h.to(t.device)
+        else:
+            m = m.to(t.device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            dist.all_reduce(m, op=dist.ReduceOp.SUM)
+    return t, int(m.item())
+
+
 def barrier():
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.barrier()

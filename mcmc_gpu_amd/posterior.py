@@ -1,0 +1,237 @@
+"""Posterior mean, spread and split-R-hat of the bed over all chains of a run, accumulated on the device.
+
+The reference looks inside a run through host caches of ONE chain: bed_cache (only_save_last_bed=False, MCMC.py:1198, :1363)
+and sample_values (set_sample_points_locations, MCMC.py:1174-1182, :1366), one whole-bed copy per iteration.  Here the chains
+of a handle advance from snapshot to snapshot and a HIP kernel folds each snapshot into per-cell running sums that stay on the
+device (gsm_posterior_* of include/gsm.h); only [H, W] maps and the thinned traces at the sample points come back.
+
+Definitions.  Iterations are numbered as in the reference's caches: 0 is the initial bed, n_iter - 1 the last.
+  snapshots   iterations k with burn_in <= k < n_iter and (k - burn_in) % thin == 0; T of them.
+  sequences   split=False: every chain is one sequence of N = T snapshots.  split=True: the last 2N, N = T // 2, snapshots are
+              used (an odd T drops the first) and every chain gives two sequences, its first and second half: M = 2C.
+  per cell    mu_m, v_m: mean and ddof=1 variance of sequence m.  mean = mean of all M*N values; sd = sqrt of their ddof=1
+              variance; W = mean_m(v_m); B_over_N = var_m(mu_m, ddof=1); rhat = sqrt(((N-1)/N W + B_over_N) / W), NaN where
+              W == 0 (exactly the cells that are constant within every sequence).  A NaN bed value makes its cell NaN everywhere.
+  rhat=False  mean and sd only, from sums pooled over the chains: no per-chain storage.
+  sample_values[c, p, t]   bed of chain c at sample point p at snapshot t, for all T snapshots (also one that split drops).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, fields
+
+import numpy as np
+
+
+def snapshot_iterations(n_iter, burn_in, thin):
+    """The iterations of a run of n_iter iterations that are snapshots (ascending int64 array)."""
+    n_iter, burn_in, thin = int(n_iter), int(burn_in), int(thin)
+    if burn_in < 0:
+        raise ValueError("burn_in must be >= 0")
+    if thin < 1:
+        raise ValueError("thin must be >= 1")
+    return np.arange(burn_in, max(n_iter, burn_in), thin, dtype=np.int64)
+
+
+def sequence_plan(n_iter, burn_in, thin, split=True):
+    """(snapshot iterations, N snapshots per sequence, number of leading snapshots that belong to no sequence).  Raises
+    ValueError when the schedule gives fewer than 2 snapshots (4 with split): a variance needs two values per sequence."""
+    its = snapshot_iterations(n_iter, burn_in, thin)
+    T = int(its.size)
+    need = 4 if split else 2
+    if T < need:
+        raise ValueError(f"n_iter={int(n_iter)}, burn_in={int(burn_in)}, thin={int(thin)} give {T} snapshots; "
+                         f"split={bool(split)} needs at least {need}")
+    N = T // 2 if split else T
+    return its, N, T - (2 * N if split else N)
+
+
+@dataclass
+class PosteriorSummary:
+    """Maps are [H, W] float64.  rhat, within_var and between_var_over_n are None for a summary made with rhat=False;
+    sample_values [n_chains, n_points, T] and sample_loc are None without sample points."""
+    mean: np.ndarray
+    sd: np.ndarray
+    rhat: np.ndarray | None
+    within_var: np.ndarray | None
+    between_var_over_n: np.ndarray | None
+    n_chains: int
+    n_sequences: int
+    n_per_sequence: int
+    snapshot_iterations: np.ndarray
+    burn_in: int
+    thin: int
+    split: bool
+    sample_values: np.ndarray | None = None
+    sample_loc: np.ndarray | None = None
+
+    def save(self, path):
+        """One .npz; fields that are None are left out."""
+        np.savez_compressed(path, **{f.name: np.asarray(getattr(self, f.name)) for f in fields(self)
+                                     if getattr(self, f.name) is not None})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            kw = {f.name: (z[f.name] if f.name in z.files else None) for f in fields(cls)}
+        for k in ("n_chains", "n_sequences", "n_per_sequence", "burn_in", "thin"):
+            kw[k] = int(kw[k])
+        kw["split"] = bool(kw["split"])
+        return cls(**kw)
+
+
+def finalize(partials_sum, M, N, common_ref, rhat=True, **meta):
+    """PosteriorSummary from the partials summed over all handles / ranks (gsm_posterior_partials), the number of sequences
+    M behind them, the snapshots per sequence N and the common field g.  partials_sum [3, H, W]: with rhat, P0 = sum_m a_m,
+    P1 = sum_m a_m^2, P2 = sum_m v_m (a_m: sequence mean minus g, v_m: sequence variance); without, P0 = sum d, P1 = sum d^2
+    over all M*N values, d = bed - g.  meta: the remaining PosteriorSummary fields."""
+    P = np.asarray(partials_sum.detach().cpu().numpy() if hasattr(partials_sum, "detach") else partials_sum, dtype=np.float64)
+    g = np.asarray(common_ref, dtype=np.float64)
+    M, N = int(M), int(N)
+    if P.ndim != 3 or P.shape[0] != 3 or P.shape[1:] != g.shape:
+        raise ValueError(f"partials of shape {P.shape} do not match a common field of shape {g.shape}")
+    if N < 2 or M < 1:
+        raise ValueError("need at least one sequence of at least two snapshots")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if rhat:
+            if M < 2:
+                raise ValueError("rhat needs at least two sequences")
+            mean = g + P[0] / M
+            W = P[2] / M
+            ss_between = P[1] - P[0] * P[0] / M
+            B_over_N = ss_between / (M - 1)
+            var = ((N - 1) * P[2] + N * ss_between) / (M * N - 1)
+            r = np.sqrt(((N - 1) / N * W + B_over_N) / W)
+            r = np.where(W == 0, np.nan, r)
+        else:
+            n = M * N
+            mean = g + P[0] / n
+            var = (P[1] - P[0] * P[0] / n) / (n - 1)
+            W = B_over_N = r = None
+        sd = np.sqrt(var)
+    return PosteriorSummary(mean=mean, sd=sd, rhat=r, within_var=W, between_var_over_n=B_over_N, n_sequences=M, n_per_sequence=N, **meta)
+
+
+def default_common_ref(initial_bed):
+    """The template chain's initial bed with non-finite cells set to 0: the same on every rank because the template is."""
+    g = np.array(initial_bed, dtype=np.float64)
+    g[~np.isfinite(g)] = 0.0
+    return g
+
+
+class PosteriorAccumulator:
+    """Running moments of eng.beds over the snapshot schedule of one run.  Owns the torch tensors: with rhat, `ref`
+    [n_chains, H, W] in the state dtype (every chain's bed at the first snapshot of the sequence being filled) and 1 + split pairs of [n_chains, H, W] float64 sums (1 + 2 (1 + split) arrays of
+    the beds' shape); without, one [H, W] pair.  Call add() when eng.beds holds the next snapshot of the schedule, then
+    partials() (sum it over ranks) and finalize()."""
+
+    def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None):
+        import torch
+        self.eng = eng
+        self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
+        self.snapshot_iterations, self.N, self.dropped = sequence_plan(n_iter, burn_in, thin, self.split)
+        self.T = int(self.snapshot_iterations.size)
+        self.n_seq = 2 if self.split else 1
+        H, W, n = eng.H, eng.W, eng.n_chains
+        # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
+        g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
+        if g.shape != (H, W) or not np.isfinite(g).all():
+            raise ValueError(f"common_ref must be a finite array of shape {(H, W)}")
+        self.common_ref = g
+        cells = None if sample_cells is None else np.ascontiguousarray(sample_cells, dtype=np.int32).ravel()
+        if cells is not None and ((cells < 0).any() or (cells >= H * W).any()):
+            raise ValueError("sample cell outside the grid")
+        self.sample_loc = None if sample_loc is None else np.asarray(sample_loc)
+        self.n_samples = 0 if cells is None else int(cells.size)
+        # the second sequence's sums start on a 16-byte boundary whatever n_chains * H * W is
+        self.seq_stride = (n * H * W + 31) // 32 * 32
+        state_bytes = 8 if eng.state_dtype == torch.float64 else 4
+        need = (n * H * W * state_bytes + 2 * self.n_seq * self.seq_stride * 8) if self.rhat else 2 * H * W * 8
+        need += self.T * n * self.n_samples * 8
+        free = torch.cuda.mem_get_info(eng.dev)[0]
+        if need > free:
+            raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
+                              f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
+        dev = eng.dev
+        self.d_g = torch.as_tensor(g).to(dev)
+        if self.rhat:
+            self.ref = torch.empty((n, H, W), dtype=eng.state_dtype, device=dev)
+            self.s1 = torch.zeros((self.n_seq, self.seq_stride), dtype=torch.float64, device=dev)
+            self.s2 = torch.zeros((self.n_seq, self.seq_stride), dtype=torch.float64, device=dev)
+        else:
+            self.s1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+            self.s2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        self.d_cells = None if not self.n_samples else torch.as_tensor(cells).to(dev)
+        self.d_samples = None if not self.n_samples else torch.empty((self.T, n, self.n_samples), dtype=torch.float64, device=dev)
+        self.n_added = 0
+        self._partials = None
+
+    @property
+    def n_sequences(self):
+        """Sequences this accumulator contributes to M."""
+        return self.eng.n_chains * self.n_seq
+
+    def add(self):
+        """Fold eng.beds, which must hold the next snapshot of the schedule, into the sums (asynchronous)."""
+        eng, t = self.eng, self.n_added
+        if t >= self.T:
+            raise RuntimeError(f"all {self.T} snapshots of the schedule were added already")
+        if eng.beds is None:
+            raise RuntimeError("set_state() first")
+        smp = None if self.d_samples is None else self.d_samples[t]
+        if t < self.dropped:
+            if smp is not None:
+                eng.posterior_sample(self.d_cells, smp)
+        elif self.rhat:
+            j = t - self.dropped
+            k, first = j // self.N, j % self.N == 0
+            if first and k > 0:            # the finished half becomes (mean - g, variance); ref then serves this half
+                eng.posterior_close(self.ref, self.d_g, self.s1[k - 1], self.s2[k - 1], self.N)
+            eng.posterior_accumulate(self.ref, self.s1[k], self.s2[k], first, self.d_cells, smp)
+        else:
+            eng.posterior_accumulate_pooled(self.d_g, self.s1, self.s2, self.d_cells, smp)
+        self.n_added += 1
+        self._partials = None
+
+    def partials(self):
+        """[3, H, W] float64 device tensor of this handle's chains (see finalize); sums over ranks with all_reduce_posterior.
+        Kept, so that it can be read after the engine is closed."""
+        import torch
+        if self.n_added != self.T:
+            raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
+        if self._partials is None:
+            eng = self.eng
+            if self.rhat:
+                out = eng.posterior_partials(self.ref, self.d_g, self.s1, self.s2, self.n_seq, self.seq_stride, self.n_seq - 1, self.N)
+            else:
+                out = torch.stack([self.s1, self.s2, torch.zeros_like(self.s1)])
+            self._partials = out
+        return self._partials
+
+    def sample_values(self):
+        """[n_chains, n_points, T] numpy array of the traces, or None."""
+        return None if self.d_samples is None else np.ascontiguousarray(self.d_samples.permute(1, 2, 0).cpu().numpy())
+
+    def finalize(self, partials_sum=None, M=None, sample_values=None):
+        """PosteriorSummary from partials summed over ranks and their sequence count (default: this accumulator's own)."""
+        if partials_sum is None:
+            partials_sum, M = self.partials(), self.n_sequences
+        M = int(M)
+        return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
+                        snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
+                        sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc)
+
+
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref")
+
+
+def check_options(posterior, n_iter):
+    """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in."""
+    if not isinstance(posterior, dict):
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref")
+    unknown = set(posterior) - set(POSTERIOR_KEYS)
+    if unknown:
+        raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None)
+    opt.update(posterior)
+    sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
+    return opt

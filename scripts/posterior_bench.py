@@ -1,0 +1,159 @@
+"""Cost of the posterior accumulator (mcmc_gpu_amd/posterior.py) on the device.
+
+  kernels     bytes/s of one snapshot: the per-chain accumulate (48 B per chain-cell with fp64 state: 8 bed, 8 ref, 16 read and
+              16 written of the sums; 40 B with fp32 state) and the pooled form (its 8 / 4 B per chain-cell), each against
+              gsm_debug_stream_copy moving the same number of bytes in the same process.  Device events around `reps` calls,
+              after a warm-up; the median and the range are reported.  The bytes are what the algorithm needs, from the shapes.
+  end to end  wall time of MCMC_gpu.run_many (Philox mode, results left on the device) without `posterior` and with it at
+              several `thin`, rhat on and off: the overhead per snapshot.  The configurations alternate within each repeat.
+
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick]
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def _timed(fn, reps, warmup=3):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def _rate(name, nbytes, ms):
+    med = statistics.median(ms)
+    return {"what": name, "bytes": int(nbytes), "ms_median": med, "ms_min": min(ms), "ms_max": max(ms), "reps": len(ms),
+            "TB_per_s_median": nbytes / med / 1e9, "TB_per_s_range": [nbytes / max(ms) / 1e9, nbytes / min(ms) / 1e9]}
+
+
+def kernel_rows(n_chains, H, W, state, reps):
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        dev, n, sb = eng.dev, n_chains * H * W, 8 if state == "f64" else 4
+        eng.beds = (1000.0 + torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        ref = torch.empty_like(eng.beds)
+        s1 = torch.zeros(n, dtype=torch.float64, device=dev)
+        s2 = torch.zeros(n, dtype=torch.float64, device=dev)
+        eng.posterior_accumulate(ref, s1, s2, True)
+        per_chain = (2 * sb + 32) * n
+        acc = _rate(f"accumulate {n_chains}x{H}x{W} {state}", per_chain, _timed(lambda: eng.posterior_accumulate(ref, s1, s2, False), reps))
+
+        def copy_row(nbytes, label):
+            m = nbytes // 16                                   # doubles: 8 B read + 8 B written each
+            src = torch.ones(m, dtype=torch.float64, device=dev)
+            dst = torch.empty(m, dtype=torch.float64, device=dev)
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            r = _rate(label, 16 * m, _timed(lambda: eng._check(eng.lib.gsm_debug_stream_copy(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st)), reps))
+            del src, dst
+            return r
+
+        cp = copy_row(per_chain, f"stream copy of the accumulate's bytes ({n_chains}x{H}x{W} {state})")
+        acc["fraction_of_copy"] = acc["TB_per_s_median"] / cp["TB_per_s_median"]
+        rows += [acc, cp]
+        del ref, s1, s2
+        g = torch.full((H, W), 1000.0, dtype=torch.float64, device=dev)
+        p1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        pooled = sb * n
+        po = _rate(f"pooled accumulate {n_chains}x{H}x{W} {state}", pooled, _timed(lambda: eng.posterior_accumulate_pooled(g, p1, p2), reps))
+        cp2 = copy_row(pooled, f"stream copy of the pooled form's bytes ({n_chains}x{H}x{W} {state})")
+        po["fraction_of_copy"] = po["TB_per_s_median"] / cp2["TB_per_s_median"]
+        rows += [po, cp2]
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats):
+    import torch
+    from mcmc_gpu_amd import MCMC_gpu, synthetic
+    prob, ch, rf = synthetic.template(H)
+    beds = synthetic.initial_beds(prob, n_chains)
+    seeds = list(range(1000, 1000 + n_chains))
+    configs = [("no posterior", None)] + [(f"thin={t} rhat={r}", dict(burn_in=0, thin=t, rhat=r)) for t in thins for r in (True, False)]
+
+    def run(opt):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = MCMC_gpu.run_many(ch, rf, beds, seeds, n_iter, batch=32, return_device=True, posterior=opt)
+        dev, accum = out if opt is not None else (out, None)
+        if accum is not None:
+            accum.finalize()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        dev[0].close()
+        return dt, (accum.T if accum is not None else 0)
+
+    run(None)
+    run(configs[1][1])                                          # warm-up of both paths
+    wall = {name: [] for name, _ in configs}
+    snaps = {}
+    for _ in range(repeats):
+        for name, opt in configs:                              # alternating: drift of the shared box hits every configuration alike
+            dt, snaps[name] = run(opt)
+            wall[name].append(dt)
+    base = statistics.median(wall["no posterior"])
+    rows = []
+    for name, _ in configs:
+        med = statistics.median(wall[name])
+        row = {"what": f"run_many {n_chains}x{H}x{H}, {n_iter - 1} steps, {name}", "wall_s_median": med, "wall_s_min": min(wall[name]),
+               "wall_s_max": max(wall[name]), "repeats": repeats, "snapshots": snaps[name],
+               "chain_steps_per_s": n_chains * (n_iter - 1) / med}
+        if snaps[name]:
+            row["overhead_s"] = med - base
+            row["overhead_ms_per_snapshot"] = 1e3 * (med - base) / snaps[name]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def main():
+    import torch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true", help="small shapes: a rehearsal of the script, not a measurement")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
+    rows = []
+    if args.quick:
+        rows += kernel_rows(8, 64, 64, "f64", 3)
+        rows += kernel_rows(8, 64, 64, "f32", 3)
+        rows += end_to_end_rows(64, 8, 129, [64, 16], 1)
+    else:
+        rows += kernel_rows(1024, 256, 256, "f64", args.reps)
+        rows += kernel_rows(512, 1024, 1024, "f32", args.reps)
+        rows += end_to_end_rows(256, 1024, 20481, [2048, 256, 64], args.repeats)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d"), "rows": rows}, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
