@@ -1,0 +1,91 @@
+// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip).
+#include "gsm_context.h"
+
+using namespace gsm;
+
+static int posterior_setup(gsm_handle h, int64_t cell_blocks, int n_fields, int* parts) {
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->n_cu) {
+    HIPCHK(h, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (h->n_cu < 1) h->n_cu = 1;
+  }
+  if (!parts) return GSM_OK;
+  *parts = posterior_parts(cell_blocks, h->n_chains, h->n_cu);
+  const size_t need = (size_t)*parts * n_fields * h->H * h->W;
+  HIPCHK(h, h->d_post_slab.ensure(need));
+  return GSM_OK;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static int posterior_sample(gsm_handle h, const char* who, const void* beds, const int32_t* sample_cells, int32_t n_samples,
+                            double* sample_out, hipStream_t st) {
+  if (!sample_out) return GSM_OK;
+  if (!sample_cells || n_samples < 1) return fail(h, GSM_E_ARG, std::string(who) + ": sample_out without sample_cells / n_samples >= 1");
+  HIPCHK(h, launch_posterior_sample(beds, sample_cells, n_samples, h->n_chains, (int64_t)h->H * h->W, h->f32_state, sample_out, st));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
+                                        const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !ref || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: NULL pointer");
+  if (!aligned16(beds) || !aligned16(ref) || !aligned16(s1) || !aligned16(s2))
+    return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: beds, ref, s1 and s2 must be 16-byte aligned");
+  int rc = posterior_setup(h, 1, 0, nullptr);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_accumulate(beds, ref, s1, s2, (int64_t)h->n_chains * h->H * h->W, h->f32_state, first != 0, h->n_cu,
+                                        (hipStream_t)stream));
+  return posterior_sample(h, "gsm_posterior_accumulate", beds, sample_cells, n_samples, sample_out, (hipStream_t)stream);
+}
+
+extern "C" int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
+                                               const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !g || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: NULL pointer");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: beds must be 16-byte aligned");
+  const int64_t plane = (int64_t)h->H * h->W;
+  const int vec = h->f32_state ? (plane % 4 == 0 ? 4 : plane % 2 == 0 ? 2 : 1) : (plane % 2 == 0 ? 2 : 1);
+  int parts = 1;
+  int rc = posterior_setup(h, (plane / vec + 255) / 256, 2, &parts);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_pooled(beds, g, s1, s2, h->d_post_slab.get(), plane, h->n_chains, parts, h->f32_state, h->n_cu, (hipStream_t)stream));
+  return posterior_sample(h, "gsm_posterior_accumulate_pooled", beds, sample_cells, n_samples, sample_out, (hipStream_t)stream);
+}
+
+extern "C" int gsm_posterior_sample(gsm_handle h, const void* beds, const int32_t* sample_cells, int32_t n_samples, double* sample_out,
+                                    void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !sample_out) return fail(h, GSM_E_ARG, "gsm_posterior_sample: NULL pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  return posterior_sample(h, "gsm_posterior_sample", beds, sample_cells, n_samples, sample_out, (hipStream_t)stream);
+}
+
+extern "C" int gsm_posterior_close(gsm_handle h, const void* ref, const double* g, double* s1, double* s2, int32_t n_per_seq, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!ref || !g || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_close: NULL pointer");
+  if (n_per_seq < 2) return fail(h, GSM_E_ARG, "gsm_posterior_close: n_per_seq must be >= 2 (a variance needs two snapshots)");
+  if (h->n_chains > 65535) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_close: more than 65535 chains");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, launch_posterior_close(ref, g, s1, s2, (int64_t)h->H * h->W, h->n_chains, n_per_seq, h->f32_state, (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const double* s1, const double* s2,
+                                      int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
+                                      void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!ref || !g || !s1 || !s2 || !partials) return fail(h, GSM_E_ARG, "gsm_posterior_partials: NULL pointer");
+  if (n_seq_per_chain != 1 && n_seq_per_chain != 2) return fail(h, GSM_E_ARG, "gsm_posterior_partials: n_seq_per_chain must be 1 or 2");
+  if (n_per_seq < 2) return fail(h, GSM_E_ARG, "gsm_posterior_partials: n_per_seq must be >= 2 (a variance needs two snapshots)");
+  if (n_closed < 0 || n_closed > n_seq_per_chain) return fail(h, GSM_E_ARG, "gsm_posterior_partials: n_closed must be in [0, n_seq_per_chain]");
+  const int64_t plane = (int64_t)h->H * h->W;
+  if (n_seq_per_chain == 2 && seq_stride < (int64_t)h->n_chains * plane)
+    return fail(h, GSM_E_ARG, "gsm_posterior_partials: seq_stride smaller than n_chains * H * W");
+  int parts = 1;
+  int rc = posterior_setup(h, (plane + 255) / 256, 3, &parts);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_partials(ref, g, s1, s2, h->d_post_slab.get(), partials, plane, h->n_chains, n_seq_per_chain, seq_stride, n_closed, n_per_seq,
+                                      parts, h->f32_state, h->n_cu, (hipStream_t)stream));
+  return GSM_OK;
+}
