@@ -1,5 +1,6 @@
 """CPU suite of the posterior accumulator: the snapshot schedule, the finalisation of partials (one group of chains and ragged
-groups whose partials add), the cross-rank merge over gloo, the new symbols of the library and the summary file."""
+groups whose partials add), the cross-rank merge over gloo, the new symbols of the library and the summary file, and the kernels'
+summation order at the chain counts of tests/test_gpu_posterior_many_chains.py against the tolerances."""
 import os
 import socket
 import sys
@@ -82,6 +83,46 @@ def test_partials_of_ragged_groups_add(groups):
     many = posterior.finalize(tot, 2 * C, 5, g, **kw)
     for name in ("mean", "sd", "within_var", "between_var_over_n", "rhat"):
         np.testing.assert_allclose(getattr(many, name), getattr(one, name), rtol=1e-12, atol=0, equal_nan=True, err_msg=name)
+
+
+def test_split_plan_hand_computed_cases():
+    """The split rule on 256 compute units, worked by hand from the comments of posterior_kernel.hip."""
+    pl = pc.split_plan(128, 128, 390, True, 256)            # 4096 lanes of 4 cells = 16 cell blocks; 1024 / 16 = 64 parts
+    assert pl["pooled"] == dict(vec=4, parts=64, cpp=7, last=5, empty=8)
+    assert pl["partials"] == dict(vec=1, parts=16, cpp=25, last=15, empty=0)
+    assert pl["accumulate"] == dict(V=4, grid=2048, trips=2, last_trip_blocks=1072, last_block_groups=512, tail=0)   # 3120 blocks wanted
+    pl = pc.split_plan(127, 129, 101, False, 256)           # odd plane: one cell per lane in both forms
+    assert pl["pooled"] == pl["partials"] == dict(vec=1, parts=16, cpp=7, last=3, empty=1)
+    assert pl["accumulate"]["tail"] == 1 and pc.split_plan(127, 129, 101, True, 256)["accumulate"]["tail"] == 3
+    pl = pc.split_plan(64, 64, 5, False, 256)               # what the few-chain tests run: one chain per part
+    assert pl["pooled"] == dict(vec=2, parts=5, cpp=1, last=1, empty=0) and pl["accumulate"]["trips"] == 1
+    pl = pc.split_plan(256, 256, 1024, False, 256)          # production
+    assert (pl["pooled"]["parts"], pl["pooled"]["cpp"], pl["accumulate"]["trips"]) == (8, 128, 32)
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("T", [4, 5])
+@pytest.mark.parametrize("C,grid", [(390, (128, 128)), (101, (127, 129))])
+def test_kernel_summation_order_stays_within_the_tolerances(C, grid, T, split):
+    """The kernels' order of summation (pc.emulate_partials) with the parts and chains per part that an MI355X gives C chains
+    on `grid`, on 22 x 20 cells drawn as the GPU tests draw them: the reference and the order alone stay inside the tolerances."""
+    H, W = 22, 20
+    x, g = pc.many_chain_data(C, T, H, W, C + T)
+    plan = pc.split_plan(*grid, C, True, 256)
+    assert (plan["pooled"]["parts"], plan["pooled"]["cpp"]) == {390: (64, 7), 101: (16, 7)}[C]
+    assert (plan["partials"]["parts"], plan["partials"]["cpp"]) == {390: (16, 25), 101: (16, 7)}[C]
+    ref = pc.posterior_reference(x, split)
+    const = pc.constant_cells(H, W, split)
+    kw = dict(n_chains=C, snapshot_iterations=np.arange(T), burn_in=0, thin=1, split=split)
+    for rhat in (True, False):
+        form = plan["partials" if rhat else "pooled"]
+        P = pc.emulate_partials(x, g, split, rhat, form["parts"], form["cpp"])
+        s = posterior.finalize(P, ref["M"], ref["N"], g, rhat=rhat, **kw)
+        pc.check_maps(s, ref, rhat=rhat, label=f"emulated C={C} T={T} split={split} rhat={rhat}")
+        assert np.isnan(s.mean[5, 7]) and np.isnan(s.mean).sum() == 1
+        if rhat:
+            assert (s.within_var[const] == 0).all() and np.isnan(s.rhat[const]).all()
+            assert np.isfinite(s.rhat[~const]).sum() == H * W - const.sum() - 1
 
 
 def _free_port():
