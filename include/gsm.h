@@ -440,6 +440,35 @@ int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t
                  const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                  int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream);
 
+/* ---- interpolate.krige on a whole grid (gstatsim_custom/interpolate.py:13-89) -------------------------------------------
+ * The kriging estimate and its variance at n_cells cells of ONE grid, in normal-score space, on a handle created with
+ * n_chains = 1.  Kriging is gsm_sgs_grid without the sequence: the reference never adds an estimated cell to its conditioning
+ * mask, so every cell conditions on the measured values alone and all cells are solved side by side (one wavefront each).
+ *   grid     [dev, H*W]                 normal scores: the conditioning values, NaN at every cell without one; not written
+ *   cells    [dev, n_cells]             flat indices (row * W + col) of the cells to estimate -- the cells of sim_mask that
+ *                                       hold no value, in any order (the reference visits them in C order); each must be NaN
+ *                                       in `grid`.  n_cells = 0 is a no-op
+ *   x_axis, y_axis, lag_cov, lag_mi, lag_mj, hw, radius, num_points, sill   as in gsm_sgs_grid.  A cell with no value within
+ *                                       `radius` widens the search by 100 km steps (interpolate.py:65-71): lag_mi / lag_mj must
+ *                                       cover 2 ceil(r / |dx|) for the widest radius r any cell reaches (or H - 1 / W - 1)
+ *   est      [dev, n_cells]             kriging estimate of cells[k] at k: sum w v + (1 - sum w) * m, m the mean of the
+ *                                       neighbours' values (ordinary, _krige.py:42) or the global mean (simple, _krige.py:79)
+ *   var      [dev, n_cells]             sill - sum w rho, SIGNED (_krige.py:41, :78): the reference clips negative values to
+ *                                       zero afterwards (interpolate.py:83), and so does the caller
+ *   n_neighbours [dev, n_cells]         size of the solved system (1 .. num_points)
+ * Kriging type and, for simple kriging, the global mean [dev, 1] from gsm_sgs_set_kriging.  Neighbour sets, tie order
+ * (ascending (distance, row, column)) and solve as gsm_sgs_blocks.
+ * Limits: 8 <= num_points <= 48, H and W in [2, 32767], hw >= 1 (GSM_E_ARG / GSM_E_UNSUPPORTED as in gsm_sgs_grid).
+ * Errors found on the device, GSM_E_DEVICE_DATA with one text per cause: a listed cell outside the grid or holding a value; no
+ * value anywhere on the grid; a lag table too small ("lag covariance table"); a singular system.  Such a cell gets est = var =
+ * NaN and n_neighbours = 0; every other cell of the call is still completed.  Synchronises the stream.
+ * Replaces: interpolate.krige (gstatsim_custom/interpolate.py:13-89), neighbors (gstatsim_custom/neighbors.py:4-64),
+ * ok_solve / sk_solve (gstatsim_custom/_krige.py:5-81). */
+int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells,
+                   const double* x_axis, const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj,
+                   int32_t hw, double radius, int32_t num_points, double sill,
+                   double* est, double* var, int32_t* n_neighbours, void* stream);
+
 /* One batch of small-scale iterations in ONE call: for j < n_iters, in the order of chain_sgs.run's loop body
  * (MCMC.py:1741-1822) -- [gsm_qt_transform cur -> next] gsm_sgs_blocks_batch [gsm_sgs_finish | gsm_qt_transform next ->
  * proposed, gsm_sgs_loss, gsm_sgs_decide, gsm_sgs_commit(_map)] -- with iteration j's draws at windows + 4*n_chains*j,

@@ -1,4 +1,4 @@
-// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate) and whole-grid gsm_sgs_grid.
+// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid.
 #include "gsm_context.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -155,6 +155,38 @@ extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, co
                                             "(it must cover twice the widest search radius)");
   if (flag & 128) return fail(h, GSM_E_DEVICE_DATA, w + ": truncated-normal draw outside scipy's domain (kriging variance 0, or "
                                                      "lower >= upper after standardising)");
+  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+}
+
+extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
+                              const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
+                              int32_t num_points, double sill, double* est, double* var, int32_t* n_neighbours, void* stream) {
+  if (!h) return GSM_E_ARG;
+  const std::string w = "gsm_krige_grid";
+  if (n_cells < 0 || (int64_t)n_cells > (int64_t)h->H * h->W) return fail(h, GSM_E_ARG, w + ": n_cells must be in [0, H * W]");
+  if (n_cells == 0) return GSM_OK;
+  if (!grid || !cells || !x_axis || !y_axis || !lag_cov || !est || !var || !n_neighbours) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  if (int rc = sgs_check_search(h, w, hw, num_points, radius, lag_mi, lag_mj)) return rc;
+  if (h->H < 2 || h->W < 2 || h->H > 32767 || h->W > 32767) return fail(h, GSM_E_ARG, w + ": grid sides must be in [2, 32767]");
+  if (h->n_chains != 1) return fail(h, GSM_E_ARG, w + ": one grid per handle (create it with n_chains = 1)");
+  if (h->sgs_ktype == GSM_KRIGING_SIMPLE && !h->sgs_gmean) return fail(h, GSM_E_STATE, w + ": simple kriging without a global mean");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  KrigeGridArgs a{};
+  a.H = h->H; a.W = h->W; a.n_cells = n_cells; a.grid = grid; a.cells = cells;
+  a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov; a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points;
+  a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.radius = radius; a.sill = sill;
+  a.est = est; a.var = var; a.n = n_neighbours; a.err = h->d_err.get();
+  HIPCHK(h, launch_krige_grid(a, st));
+  int32_t flag = 0;
+  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
+  if (!flag) return GSM_OK;
+  if (flag & 2) return fail(h, GSM_E_DEVICE_DATA, w + ": a listed cell outside the grid or holding a value");
+  if (flag & 4) return fail(h, GSM_E_DEVICE_DATA, w + ": a cell to estimate has no value anywhere on the grid (the reference would widen "
+                                                   "its search radius for ever, interpolate.py:65-71)");
+  if (flag & 8) return fail(h, GSM_E_DEVICE_DATA, w + ": singular kriging system (a pivot below eps * N * max|diag|)");
+  if (flag & 64) return fail(h, GSM_E_DEVICE_DATA, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                                    "(it must cover twice the widest search radius)");
   return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
 }
 

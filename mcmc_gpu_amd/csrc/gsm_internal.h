@@ -249,6 +249,22 @@ struct SgsGridArgs {
   SgsGridHdr* rec_hdr;     // [n_real*seg_cap]
   double2* rec_vw;         // [n_real*seg_cap/64][48][64]: (value, or NaN-boxed (slot << 25 | cell) of a path cell; kriging weight)
 };
+// interpolate.krige: estimate and variance at listed cells of one grid (krige_grid_kernel.hip)
+struct KrigeGridArgs {
+  int H, W, n_cells;
+  int cell0;               // first entry of `cells` of this launch (set by launch_krige_grid)
+  const double* grid;      // [H*W] normal scores, NaN where there is no datum
+  const int32_t* cells;    // [n_cells] flat indices of the cells to estimate (each NaN in grid)
+  const double* xs; const double* ys; const double* lag;
+  int hw, mi, mj, num_points, ktype;
+  const double* gmean;     // [1] (simple kriging)
+  double radius, sill;
+  double* est;             // [n_cells] kriging estimate, in the order of `cells`; NaN where the cell raised an error
+  double* var;             // [n_cells] sill - sum w rho, signed
+  int32_t* n;              // [n_cells] neighbours; 0 where the cell raised an error
+  int32_t* err;
+};
+hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st);
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
 hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st);      // weights, then values of one segment
 hipError_t launch_sgs_blocks(const SgsArgs& a, int launch_cells, hipStream_t st);

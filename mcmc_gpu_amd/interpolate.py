@@ -1,14 +1,19 @@
-"""Device mirror of gstatsim_custom.interpolate.sgs (gstatsMCMC/gstatsim_custom/interpolate.py:92-191): sequential Gaussian
-simulation of a whole grid, the step that makes the chains' initial beds (T2_StatisticalAnalysis.ipynb calls it once per seed).
+"""Device mirror of gstatsim_custom.interpolate (gstatsMCMC/gstatsim_custom/interpolate.py): sequential Gaussian simulation of a
+whole grid (sgs, :92-191), the step that makes the chains' initial beds (T2_StatisticalAnalysis.ipynb calls it once per seed),
+and its deterministic twin, the kriging estimate and spread on the whole grid (krige, :13-89).
 
-    sgs       interpolate.sgs's arguments and return value, plus `device`
-    sgs_many  many realisations in one call, row r == sgs(..., seed=seeds[r]) bit for bit
+    sgs           interpolate.sgs's arguments and return value, plus `device`
+    sgs_many      many realisations in one call, row r == sgs(..., seed=seeds[r]) bit for bit
+    krige         interpolate.krige's arguments and return value, plus `device`
+    krige_scores  the same call in normal-score space: estimate, variance and neighbour count per cell
 
 The host does what the reference does with its generator, in its order -- one rng.shuffle of the cells of sim_mask, then one
 standard normal per simulated cell (rng.normal(est, sd, 1) = est + sd * z) or, with bounds, one uniform per simulated cell whose
 bounds differ (truncnorm.rvs = truncnorm.ppf(uniform, a, b) * scale + est) -- and the normal-score transform with
 scikit-learn (utilities.gaussian_transformation, the same call).  Neighbour search, kriging and the sequential value pass
-run on the device (gsm_sgs_grid, csrc/sgs_grid_kernel.hip); nothing is computed on the CPU in their place.
+run on the device (gsm_sgs_grid, csrc/sgs_grid_kernel.hip); nothing is computed on the CPU in their place.  Kriging has no
+generator and no sequence -- every cell conditions on the measured values alone -- so all its cells are searched, solved and
+finished side by side in one kernel (gsm_krige_grid, csrc/krige_grid_kernel.hip).
 
 Numerics: the kriging systems are solved by Gauss-Jordan elimination where the reference calls numpy.linalg.lstsq, and the
 truncated-normal ppf is a restatement of scipy's (csrc/truncnorm.h), so values agree with the reference to ~1e-9 of the
@@ -28,7 +33,7 @@ import numpy as np
 
 from .sgs import _axes, _ptr, lag_cov_table
 
-__all__ = ["sgs", "sgs_many"]
+__all__ = ["sgs", "sgs_many", "krige", "krige_scores"]
 
 RECORD_BYTES = 800          # one path cell's record on the device: 48 (value, weight) pairs + a 32-byte header
 WIDEN_STEP = 100e3          # interpolate.py:155
@@ -277,3 +282,104 @@ def sgs_many(xx, yy, grid, variogram, seeds, *, radius=100e3, num_points=20, kty
         return np.zeros((0,) + plan.grid_ns.shape)
     ns, _ = _run(plan, gens, segment_cells, device)
     return _inverse(plan, ns)
+
+
+# ---- interpolate.krige ----------------------------------------------------------------------------------------------------------
+def _krige_plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil):
+    return _Plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil, None, None)
+
+
+def _krige_cells(plan):
+    """The cells interpolate.krige solves a system for (interpolate.py:46-55): those of sim_mask that hold no value, in C order."""
+    flat = plan.inds[:, 0] * plan.W + plan.inds[:, 1]
+    return np.ascontiguousarray(flat[~plan.cond.ravel()[flat]], dtype=np.int32)
+
+
+def _krige_run(plan, cells=None, device=None):
+    """One gsm_krige_grid call on `cells` (default: _krige_cells).  Returns per listed cell the estimate, the SIGNED variance
+    (sill - sum w rho) and the neighbour count."""
+    import torch
+    from .engine import GsmEngine
+    if cells is None:
+        cells = _krige_cells(plan)
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    if cells.size == 0:
+        return np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int32)
+    H, W = plan.H, plan.W
+    eng = GsmEngine(H, W, 1, device)
+    try:
+        dev, lib, h = eng.dev, eng.lib, eng.h
+        mi, mj = _lag_extents(plan, eng, torch)
+        if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
+            raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not fit "
+                              "the device; raise `radius` or add conditioning data")
+        hw = int(math.ceil(plan.radius / abs(plan.dx)))
+        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        d_grid, d_cells = f64(plan.grid_ns), torch.as_tensor(cells).to(dev)
+        d_xs, d_ys = f64(plan.xs), f64(plan.ys)
+        d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        d_gm = f64(np.full(1, plan.global_mean))
+        d_est = torch.empty(cells.size, dtype=torch.float64, device=dev)
+        d_var = torch.empty(cells.size, dtype=torch.float64, device=dev)
+        d_n = torch.empty(cells.size, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
+            eng._check(lib.gsm_krige_grid(h, _ptr(d_grid), _ptr(d_cells), int(cells.size), _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), mi, mj,
+                                          hw, plan.radius, plan.num_points, float(plan.vario["sill"]), _ptr(d_est), _ptr(d_var),
+                                          _ptr(d_n), eng._stream()))
+        out = d_est.cpu().numpy(), d_var.cpu().numpy(), d_n.cpu().numpy()
+    finally:
+        eng.close()
+    return out
+
+
+def _score_maps(plan, cells, est, var, n):
+    """The per-cell results as interpolate.krige's grids in normal-score space (interpolate.py:40-41, :80-83): the estimate
+    over the transformed data (NaN stays where a cell is neither data nor solved), the variance 0 except at the solved cells
+    and clipped at 0 there, and the neighbour counts (0 where no system was solved)."""
+    est_ns = plan.grid_ns.copy()
+    var_ns = np.zeros(plan.grid_ns.shape)
+    n_map = np.zeros(plan.grid_ns.shape, dtype=np.int32)
+    est_ns.ravel()[cells] = est
+    var_ns.ravel()[cells] = np.where(var < 0, 0, var)
+    n_map.ravel()[cells] = n
+    return est_ns, var_ns, n_map
+
+
+def _data_maps(plan, est_ns, var_ns):
+    """interpolate.py:85-87: both grids through the transformer's inverse_transform, the standard deviation too."""
+    return _inverse(plan, est_ns), _inverse(plan, np.sqrt(var_ns))
+
+
+def _scores(plan, device=None):
+    cells = _krige_cells(plan)
+    return _score_maps(plan, cells, *_krige_run(plan, cells, device))
+
+
+def krige_scores(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None,
+                 device=None):
+    """interpolate.krige in normal-score space: (est_ns, var_ns, n_neighbours), three [H, W] maps.  est_ns: the transformed
+    data with the kriging estimate at every cell of sim_mask that holds no value (NaN elsewhere).  var_ns: the kriging variance
+    there, clipped at 0 as interpolate.py:83 does, 0 at every other cell; sqrt(var_ns) is the kriging standard deviation in
+    scores.  n_neighbours (int32): the size of each cell's system, 0 where none was solved.  Arguments, errors and limits as
+    krige."""
+    return _scores(_krige_plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil), device)
+
+
+def krige(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None, device=None):
+    """Ordinary ('ok') or simple ('sk') kriging on the device -- interpolate.krige (gstatsim_custom/interpolate.py:13-89): same
+    arguments and return value, (sim_trans, std_trans), two [H, W] maps in data units.  `device`: CUDA/HIP device index
+    (default: torch's current device).  The reference's own krige raises TypeError at its current HEAD (it unpacks seven values
+    from a _preprocess that returns eight); this is that function with the call repaired.
+    sim_trans is the kriging mean: the data's round trip through the transformer at the conditioning cells, the back-transformed
+    estimate at the cells of sim_mask, NaN elsewhere.
+    std_trans reproduces the reference to the letter, quirk included: it is inverse_transform(sd), the data QUANTILE whose
+    normal score equals the kriging standard deviation -- the data median where sd = 0 (every conditioning cell), higher values
+    where the data constrain less.  It is not a standard deviation in data units.  krige_scores returns the quantity that means
+    something (the variance in normal-score space) and the neighbour counts.
+    Not supported (NotImplementedError): a custom stencil, per-cell variogram arrays, num_points outside [8, 48], a grid that
+    is not axis-aligned with uniform spacing.  A grid without any conditioning value raises ValueError (the reference never
+    terminates there)."""
+    plan = _krige_plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil)
+    est_ns, var_ns, _ = _scores(plan, device)
+    return _data_maps(plan, est_ns, var_ns)

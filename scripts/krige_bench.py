@@ -1,0 +1,107 @@
+"""Throughput of interpolate.krige on the device (gsm_krige_grid): estimated cells per second over a whole grid, 48 neighbours
+within 50 km, Matern (the grid of scripts/sgs_grid_bench.py), with gsm_sgs_grid on the same grid and arguments in the same
+process as the yardstick: its weights pass runs the same search and solve per cell.
+
+    cells_per_s_device      HIP events around gsm_krige_grid (the whole call: one kernel and the error word's read-back)
+    cells_per_s_total       interpolate.krige end to end: transformer fit, lag table, uploads, device call, inverse transform
+    sgs_device_ms           the gsm_sgs_grid call, --reals realisations (ranks, weights pass, value pass)
+The weights pass cannot be timed from outside gsm_sgs_grid (the value pass follows it on the same stream): for the per-cell
+rates of krige_grid_kernel against sgs_grid_weights_kernel run this script under `rocprofv3 --kernel-trace --stats` and
+divide `cells` and `sgs_cells` by the two kernels' total times in kernel_stats.csv.
+
+    python scripts/krige_bench.py [--size 566] [--reals 8] [--repeats 5] [--out profiles/krige_bench.json]
+"""
+import argparse
+import json
+import math
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT / "scripts"))
+
+
+def device_call_ms(plan, repeats):
+    """gsm_krige_grid alone, uploads outside the timed window: milliseconds of every repeat after one warm-up call."""
+    import torch
+    from mcmc_gpu_amd import interpolate
+    from mcmc_gpu_amd.engine import GsmEngine
+    from mcmc_gpu_amd.sgs import _ptr, lag_cov_table
+    cells = interpolate._krige_cells(plan)
+    eng = GsmEngine(plan.H, plan.W, 1)
+    try:
+        dev = eng.dev
+        mi, mj = interpolate._lag_extents(plan, eng, torch)
+        hw = int(math.ceil(plan.radius / abs(plan.dx)))
+        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        d_grid, d_cells, d_xs, d_ys = f64(plan.grid_ns), torch.as_tensor(cells).to(dev), f64(plan.xs), f64(plan.ys)
+        d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        d_gm = f64(np.full(1, plan.global_mean))
+        d_est = torch.empty(cells.size, dtype=torch.float64, device=dev)
+        d_var = torch.empty_like(d_est)
+        d_n = torch.empty(cells.size, dtype=torch.int32, device=dev)
+        eng._check(eng.lib.gsm_sgs_set_kriging(eng.h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
+        ms = []
+        for k in range(repeats + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng._check(eng.lib.gsm_krige_grid(eng.h, _ptr(d_grid), _ptr(d_cells), int(cells.size), _ptr(d_xs), _ptr(d_ys), _ptr(d_lag),
+                                              mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]), _ptr(d_est),
+                                              _ptr(d_var), _ptr(d_n), eng._stream()))
+            e1.record()
+            torch.cuda.synchronize()
+            if k:
+                ms.append(e0.elapsed_time(e1))
+        n = d_n.cpu().numpy()
+    finally:
+        eng.close()
+    return cells.size, ms, float(n.mean())
+
+
+def main():
+    import torch
+    from mcmc_gpu_amd import interpolate
+    from sgs_grid_bench import problem
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=566)
+    ap.add_argument("--reals", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    n = args.size
+    xx, yy, grid, vario, _ = problem(n)
+    kw = dict(radius=50e3, num_points=48, ktype="ok")
+    plan = interpolate._krige_plan(xx, yy, grid, vario, kw["radius"], kw["num_points"], kw["ktype"], None, None)
+    cells, ms, mean_n = device_call_ms(plan, args.repeats)
+    interpolate.krige(xx, yy, grid, vario, **kw)                             # warm
+    t0 = time.perf_counter()
+    sim, std = interpolate.krige(xx, yy, grid, vario, **kw)
+    t1 = time.perf_counter()
+    # the yardstick: gsm_sgs_grid, same grid, variogram, radius and num_points, no bounds
+    R = args.reals
+    draws = [plan.draws(np.random.default_rng(s)) for s in range(R)]
+    t2 = time.perf_counter()
+    [plan.draws(np.random.default_rng(s)) for s in range(R)]
+    t3 = time.perf_counter()
+    interpolate._run(plan, [np.random.default_rng(s) for s in range(R)])
+    torch.cuda.synchronize()
+    t4 = time.perf_counter()
+    sgs_cells = int(sum(p.size for p, _ in draws))
+    sgs_dev_s = (t4 - t3) - (t3 - t2)                                        # _run draws again on the host before its device call
+    row = {"grid": f"{n}x{n}", "cells": int(cells), "mean_neighbours": mean_n, "device_ms": ms, "device_ms_median": float(np.median(ms)),
+           "cells_per_s_device": cells / (1e-3 * float(np.median(ms))), "total_ms": 1e3 * (t1 - t0),
+           "cells_per_s_total": cells / (t1 - t0), "nan_cells": int(np.isnan(sim).sum() + np.isnan(std).sum()),
+           "sgs_realisations": R, "sgs_cells": sgs_cells, "sgs_device_ms": 1e3 * sgs_dev_s}
+    print(json.dumps(row), flush=True)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "row": row}, indent=1))
+
+
+if __name__ == "__main__":
+    main()
