@@ -561,6 +561,31 @@ int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const
                            int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
                            void* stream);
 
+/* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
+ * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an
+ * experimental variogram with any bins (isotropic or directional) is host arithmetic on one small table per field: for every
+ * offset of the half plane di in [0, mi], dj in [-mj, mj]
+ *   sum   [dev, n_fields*(mi+1)*(2*mj+1)] fp64    sum of (z[i, j] - z[i+di, j+dj])^2 over the cells (i, j) with both cells inside
+ *                                                 the grid and both values present, at (r*(mi+1) + di)*(2*mj+1) + dj + mj
+ *   count [dev, same extent] int64                the number of those pairs
+ * The entries (0, dj <= 0) are zero: (0, -dj) holds the same pairs.  Semivariance of an offset: sum / (2 count).
+ *   fields [dev, n_fields*H*W] fp64               row-major; NaN or an infinity marks a missing cell; not written
+ *   mask   [dev, H*W] uint8, or NULL              shared by all fields: a 0 makes the cell count as missing
+ *   mi, mj                                        mi >= H or mj >= W is legal: offsets beyond the grid hold 0 / 0
+ *   rows_per_part                                 0 = the library's default, a function of (H, W, mi, mj) alone.  The rows of a
+ *                                                 field are summed in parts of this many rows (so that one field fills the device)
+ *                                                 and the parts are added in part order by a second kernel
+ * No atomics; neither the split nor the order of any sum depends on n_fields or on the device: the same call twice gives the
+ * same bits, and field r of a batched call gives the bits of the call on that field alone.  Each term is computed in fp64 with
+ * three roundings (difference, square, addition).  Asynchronous on `stream`; all arrays are caller-owned (the partials of a
+ * split live in the handle).
+ * Errors: GSM_E_ARG for NULL fields / sum / count, n_fields < 1, mi < 0 or mj < 0, rows_per_part < 0, more than 65535 parts;
+ * GSM_E_UNSUPPORTED for mi or mj above 2^20 or an offset table of more than about 2^33 entries.
+ * Replaces: the pair sums inside skgstat.Variogram as the reference calls it (gstatsim_custom/utilities.py:102, variograms;
+ * MCMC.py:305, fit_variogram), which take scattered points and compare every pair's distance with the bin edges. */
+int gsm_variogram_map(gsm_handle h, const double* fields, int32_t n_fields, const uint8_t* mask, int32_t mi, int32_t mj,
+                      int32_t rows_per_part, double* sum, int64_t* count, void* stream);
+
 /* Diagnostics: stream-copy n doubles src -> dst [dev] with the step kernel's access shape (8 bytes per lane,
  * coalesced).  A known byte count for calibrating rocprofv3's FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM). */
 int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream);

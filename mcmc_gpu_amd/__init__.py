@@ -6,4 +6,4 @@ C ABI of include/gsm.h (libgsm_hip.so).  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "variogram"]

@@ -100,6 +100,7 @@ struct gsm_context {
   gsm::DevBuf<int32_t> d_err;
   int n_cu = 0;                                               // compute units of the device (grid sizing of the posterior kernels)
   gsm::DevBuf<double> d_post_slab;                            // gsm_posterior_*: per-part sums before they are combined in part order
+  gsm::DevBuf<double> d_vario_sum; gsm::DevBuf<int64_t> d_vario_count;   // gsm_variogram_map: per-part sums and counts before they are combined in part order
   // philox-mode scratch (two buffers)
   struct Scratch {
     gsm::DevBuf<int32_t> size_idx, centre;

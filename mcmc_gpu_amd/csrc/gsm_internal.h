@@ -355,5 +355,12 @@ hipError_t launch_posterior_close(const void* ref, const double* g, double* s1, 
                                   int f32_state, hipStream_t st);
 hipError_t launch_posterior_sample(const void* beds, const int32_t* cells, int n_samples, int n_chains, int64_t plane, int f32_state,
                                    double* out, hipStream_t st);
+// variogram_kernel.hip
+constexpr int kVariogramMaxLag = 1 << 20;
+int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part
+int variogram_default_rows_per_part(int H, int W, int mi, int mj);     // a function of the shape alone: results do not depend on the batch or the device
+int variogram_parts(int H, int rows_per_part);
+hipError_t launch_variogram_map(const double* fields, int n_fields, const uint8_t* mask, int H, int W, int mi, int mj, int rows_per_part,
+                                double* psum, int64_t* pcount, double* sum, int64_t* count, hipStream_t st);
 
 }  // namespace gsm
