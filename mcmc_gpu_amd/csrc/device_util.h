@@ -1,5 +1,5 @@
 // Device helpers shared by the step kernels and the proposal code (gfx950 only): buffer-descriptor loads/stores with
-// 32-bit per-lane offsets, DPP reductions, exact division, compensated sums.
+// 32-bit per-lane offsets, DPP reductions, lane broadcast, exact division, compensated sums.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,16 +87,20 @@ __device__ __forceinline__ double row16_sum(double x) {
   x += dpp_f64<0x140, 0xF>(x);   // row_mirror
   return x;
 }
+// lane l's value of v (l wave-uniform), in every lane: two v_readlane
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+  const v2i32 b = __builtin_bit_cast(v2i32, v);
+  v2i32 o;
+  o.x = __builtin_amdgcn_readlane(b.x, l);
+  o.y = __builtin_amdgcn_readlane(b.y, l);
+  return __builtin_bit_cast(double, o);
+}
 // sum over the 64 lanes, returned wave-uniform
 __device__ __forceinline__ double wave64_sum(double x) {
   x = row16_sum(x);
   x += dpp_f64<0x142, 0xA>(x);   // row_bcast:15 into rows 1 and 3
   x += dpp_f64<0x143, 0xC>(x);   // row_bcast:31 into rows 2 and 3
-  const v2i32 b = __builtin_bit_cast(v2i32, x);
-  v2i32 o;
-  o.x = __builtin_amdgcn_readlane(b.x, 63);
-  o.y = __builtin_amdgcn_readlane(b.y, 63);
-  return __builtin_bit_cast(double, o);
+  return readlane_f64(x, 63);
 }
 
 

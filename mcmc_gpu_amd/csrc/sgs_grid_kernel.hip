@@ -15,11 +15,12 @@
 //   sgs_grid_rank_kernel / sgs_grid_slot_kernel  per realisation the visiting rank of every cell, int32 [R][H*W]: -1 for a
 //                        conditioning value, the slot for a path cell, INT32_MAX for a NaN cell that is never filled (outside
 //                        sim_mask);
-//   sgs_grid_weights_kernel  one wavefront per (realisation, path slot) of a segment, all side by side: the block kernel's ring
-//                        search (a cell qualifies when its rank is below the slot), radius widening, kriging system and
-//                        Gauss-Jordan solve (sgs_search.h) -> a record per cell.  A neighbour is either a value (conditioning
-//                        data, or a path cell whose bounds coincide) or an earlier path cell, NaN-boxed (slot << 25 | cell);
-//                        no simulated value is read, so a segment's records do not wait for the values before it;
+//   sgs_grid_weights_kernel  one wavefront per (realisation, path slot) of a segment, all side by side: the ring search with its
+//                        radius widening (a cell qualifies when its rank is below the slot), then the kriging system and its
+//                        Gauss-Jordan solve -- both sgs_search.h's, shared with the block kernel -> a record per cell.
+//                        A neighbour is either a value (conditioning data, or a path cell whose bounds coincide) or an
+//                        earlier path cell, NaN-boxed (slot << 25 | cell); no simulated value is read, so a segment's
+//                        records do not wait for the values before it;
 //   sgs_grid_values_kernel   one workgroup of four waves per realisation walks the segment's slots in 64-cell chunks, as
 //                        sgs_sequence_kernel does: the four waves gather each cell's known part (values of earlier chunks come
 //                        from the realisation's grid in global memory, written by wave 0 of the same workgroup before the
@@ -43,12 +44,6 @@ constexpr uint64_t kGridPendingTag = 0xFFFC000000000000ull;     // bits 50..63 s
 constexpr int kGridFieldBits = 25;
 constexpr uint32_t kGridFieldMask = (1u << kGridFieldBits) - 1u;
 
-__device__ __forceinline__ double grid_readlane_f64(double v, int l) {
-  const dev::v2i32 b = __builtin_bit_cast(dev::v2i32, v);
-  dev::v2i32 o;
-  o.x = __builtin_amdgcn_readlane(b.x, l); o.y = __builtin_amdgcn_readlane(b.y, l);
-  return __builtin_bit_cast(double, o);
-}
 // a value written by another wave of this workgroup: read from L2, past this CU's L1
 __device__ __forceinline__ double load_l2(const double* p) {
   return __builtin_bit_cast(double, __hip_atomic_load((unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -100,167 +95,18 @@ __global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs 
   }
   const double* __restrict__ g = a.grid + (size_t)r * HW;
   const int i0 = cell / W, j0 = cell - i0 * W;
-  const int k8 = a.num_points / 8;
-  const double x0 = a.xs[j0], y0 = a.ys[i0];
-  const double sx = a.xs[1] - a.xs[0], sy = a.ys[1] - a.ys[0];
-  const double adx = fabs(sx), ady = fabs(sy), dmin = fmin(adx, ady);
-  const double inv_cert = 1.0 / (dmin * (1.0 - 1e-6));
-  const double fac_x = fmin(1.0, ady / adx), fac_y = fmin(1.0, adx / ady);
-  double radius = a.radius;
-  int hw = a.hw;
-  int n = 0;
-  for (;;) {                                                     // radius widening (interpolate.py:150-157): usually one trip
-    const int ilo = max(0, i0 - hw), ihi = min(H - 1, i0 + hw), jlo = max(0, j0 - hw), jhi = min(W - 1, j0 + hw);
-    const int e_up = i0 - ilo, e_dn = ihi - i0, e_lf = j0 - jlo, e_rt = jhi - j0;
-    const int r_max = max(max(e_up, e_dn), max(e_lf, e_rt));
-    const int e_ypos = (sy > 0.0) ? e_up : e_dn, e_yneg = (sy > 0.0) ? e_dn : e_up;
-    const int e_xpos = (sx > 0.0) ? e_lf : e_rt, e_xneg = (sx > 0.0) ? e_rt : e_lf;
-    for (int q = lane; q < 8 * kSgsCertMax / 2; q += 64) (&L.cert[0][0])[q] = 0u;
-    if (lane < 8) { L.len[lane] = 0; L.cum[lane] = 0; }
-    __syncthreads();
-    int my_ext = 0;
-    double my_fac = 1.0;
-    if (lane < 8) {
-      const bool xprim = (lane == 3 || lane == 4 || lane == 7 || lane == 0);
-      my_fac = xprim ? fac_x : fac_y;
-      my_ext = (lane == 3 || lane == 4) ? e_xpos : (lane == 7 || lane == 0) ? e_xneg : (lane == 5 || lane == 6) ? e_ypos : e_yneg;
-    }
-    unsigned done_mask = 0;
-    int R = 0;
-    bool long_list = false;
-    auto probe = [&](int di, int dj, bool ok) {
-      const int i = i0 + di, j = j0 + dj;
-      ok = ok && i >= ilo && i <= ihi && j >= jlo && j <= jhi;
-      const int ic = min(max(i, ilo), ihi), jc = min(max(j, jlo), jhi);
-      const int rk = rank[ic * W + jc];
-      const double ddx = x0 - a.xs[jc], ddy = y0 - a.ys[ic];
-      const double d = sqrt(ddx * ddx + ddy * ddy);
-      const int s = octant(ddy, ddx);
-      // rk: -1 = conditioning data, < slot = filled before this cell
-      const bool ins = ok && rk < slot && d < radius && !((done_mask >> s) & 1u);
-      if (ins) {
-        const int pos = atomicAdd(&L.len[s], 1);
-        long_list |= pos + 1 > kSgsListCap - 64;
-        L.list_d[s][pos] = d; L.list_g[s][pos] = i * W + j;
-        const double qf = d * inv_cert;
-        if (qf < (double)kSgsCertMax) { const int qi = (int)qf; atomicAdd(&L.cert[s][qi >> 1], 1u << (16 * (qi & 1))); }
-      }
-      __syncthreads();
-      if (__ballot(long_list)) {
-        for (int s = 0; s < 8; ++s)
-          if (L.len[s] > kSgsListCap - 64) sgs_prune_sector(L, s, k8, lane);
-        long_list = false;
-      }
-    };
-    while (R < r_max && done_mask != 0xFFu) {
-      const int R_lo = R + 1;
-      int R_hi;
-      if (R == 0) {
-        R_hi = min(3, r_max);
-        const int side_w = 2 * R_hi + 1, cells_in_pass = side_w * side_w;
-        for (int t0 = 0; t0 < cells_in_pass; t0 += 64) {
-          const int t = t0 + lane;
-          const int di = t / side_w - R_hi, dj = t % side_w - R_hi;
-          probe(di, dj, t < cells_in_pass && !(di == 0 && dj == 0));
-        }
-      } else {
-        R_hi = R_lo;
-        const int cells_in_pass = 8 * R_hi;
-        const float inv_side = 1.0f / (float)(2 * R_hi);
-        for (int t0 = 0; t0 < cells_in_pass; t0 += 64) {
-          const int t = t0 + lane;
-          const int side = (int)(((float)t + 0.5f) * inv_side), o = t - side * 2 * R_hi;
-          int di, dj;
-          ring_cell(R_hi, 2 * side + (o >= R_hi ? 1 : 0), o >= R_hi ? o - R_hi : o, di, dj);
-          probe(di, dj, t < cells_in_pass);
-        }
-      }
-      R = R_hi;
-      bool fin = false;
-      if (lane < 8) {
-        int c = L.cum[lane];
-        for (int q = R_lo; q <= R && q < kSgsCertMax; ++q) c += (int)((L.cert[lane][q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
-        L.cum[lane] = c;
-        fin = c >= k8 || (double)my_ext <= floor((double)R * my_fac + 1e-6);
-      }
-      done_mask |= (unsigned)(__ballot(fin) & 0xFFull);
-      __syncthreads();
-    }
-    {
-      const int my_s = lane >> 3;
-      int tot = 0, my_base = 0, my_len = 0;
-      for (int s = 0; s < 8; ++s) {
-        const int len = L.len[s];
-        if (s == my_s) { my_base = tot; my_len = len; }
-        tot += min(len, k8);
-      }
-      for (int e = lane & 7; e < my_len; e += 8) {
-        const double d = L.list_d[my_s][e];
-        const int gg = L.list_g[my_s][e];
-        int rr = 0;
-        for (int q = 0; q < my_len; ++q) {
-          const double dq = L.list_d[my_s][q];
-          const int gq = L.list_g[my_s][q];
-          rr += (dq < d || (dq == d && gq < gg)) ? 1 : 0;
-        }
-        if (rr < k8) L.nb_g[my_base + rr] = gg;
-      }
-      n = tot;
-    }
-    __syncthreads();
-    if (n > 0) break;
-    if (ilo == 0 && jlo == 0 && ihi == H - 1 && jhi == W - 1 &&
-        radius * radius > ((double)(W - 1) * adx) * ((double)(W - 1) * adx) + ((double)(H - 1) * ady) * ((double)(H - 1) * ady)) break;
-    radius += 100e3;
-    hw = (int)fmin(ceil(radius / adx), 1.0e6);
-  }
-  if (n == 0) {                                                  // no value anywhere on the grid: the reference would loop forever
-    if (lane == 0) { atomicOr(a.err, 4); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; }
-    return;
-  }
-  if (lane < n) { const int gg = L.nb_g[lane]; const int rr = gg / W; L.nb_rc[lane] = (rr << 16) | (gg - rr * W); }
-  __syncthreads();
-  // ---- kriging system, one row per lane (sgs_weights_kernel's) ----
+  // rank: -1 = conditioning data, < slot = filled before this cell
+  const int n = octant_ring_search(L, [rank, slot, W](int ic, int jc) { return rank[ic * W + jc] < slot; }, i0, j0, H, W, a.xs, a.ys,
+                                   a.radius, a.hw, a.num_points / 8, lane);
+  // a cell that fails gets no value: n = 0 in its record
+  auto give_up = [&](int32_t flag) {
+    if (lane == 0) { atomicOr(a.err, flag); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; }
+  };
+  if (n == 0) { give_up(4); return; }                            // no value anywhere on the grid: the reference would loop forever
   const bool lagr = a.ktype == 0;
-  const int mi = a.mi, mj = a.mj, lag_w = 2 * mj + 1;
-  const double* __restrict__ lag = a.lag;
-  double rw[50];
-  const int my_rc = (lane < n) ? L.nb_rc[lane] : 0;
-  const int my_i = my_rc >> 16, my_j = my_rc & 0xFFFF;
-  bool lag_ok = true;
-#pragma unroll
-  for (int j = 0; j < 48; ++j) {
-    double v = 0.0;
-    if (j < n) {
-      if (lane < n) {
-        const int rc = L.nb_rc[j];
-        const int di = my_i - (rc >> 16), dj = my_j - (rc & 0xFFFF);
-        if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v = lag[(di + mi) * lag_w + dj + mj];
-      } else if (lane == 48 && lagr) v = 1.0;
-    }
-    rw[j] = v;
-  }
-  {
-    double v48 = 0.0, v49 = 0.0;
-    if (lane < n) {
-      const int di = my_i - i0, dj = my_j - j0;
-      v48 = lagr ? 1.0 : 0.0;
-      if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v49 = lag[(di + mi) * lag_w + dj + mj];
-    } else if (lane == 48 && lagr) v49 = 1.0;
-    rw[48] = v48; rw[49] = v49;
-  }
-  if (__ballot(!lag_ok)) { if (lane == 0) { atomicOr(a.err, 64); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; } return; }
-  const double rho_l = rw[49];
-  const double c00 = lag[mi * lag_w + mj];
-  const double tol = 2.220446049250313e-16 * (double)(n + 1) * fabs(c00), tol_l = 2.220446049250313e-16 * (double)(n + 1) / fabs(c00);
-  double mypiv = 1.0;
-  bool singular = false;
-  GjStep<0>::run(rw, lane, n, lagr, tol, tol_l, mypiv, singular);
-  if (singular) {
-    if (lane == 0) { atomicOr(a.err, 8); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; }
-    return;
-  }
-  const double w_l = (lane < n) ? rw[49] / mypiv : 0.0;
+  double w_l, rho_l;
+  int my_i, my_j;                                                // the neighbour's (row, column): only the block kernel's record needs it
+  if (const int e = krige_solve<false>(L, n, i0, j0, H, W, a.lag, a.mi, a.mj, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
   double var = a.sill - dev::wave64_sum(w_l * rho_l);
   var = fabs(var);                                               // interpolate.py:168
   const double sw = dev::wave64_sum(w_l);
@@ -360,11 +206,11 @@ __global__ __launch_bounds__(64 * kGridSeqWaves) void sgs_grid_values_kernel(con
       const int nk = __builtin_amdgcn_readlane(n, k);
       double vk = 0.0;
       if (nk > 0) {                                              // cell k's estimate is complete: every cell it lists came before
-        const double ek = grid_readlane_f64(est, k), sk = grid_readlane_f64(hd.sd, k), dk = grid_readlane_f64(dr, k);
-        if (bounded) vk = grid_truncnorm_draw(ek, sk, grid_readlane_f64(lo_c, k), grid_readlane_f64(hi_c, k), dk, a.err);
+        const double ek = dev::readlane_f64(est, k), sk = dev::readlane_f64(hd.sd, k), dk = dev::readlane_f64(dr, k);
+        if (bounded) vk = grid_truncnorm_draw(ek, sk, dev::readlane_f64(lo_c, k), dev::readlane_f64(hi_c, k), dk, a.err);
         else vk = ek + sk * dk;                                  // rng.normal(est, sqrt(var), 1), interpolate.py:174
       } else if (nk == -3) {
-        vk = grid_readlane_f64(lo_c, k);
+        vk = dev::readlane_f64(lo_c, k);
       } else if (nk == 0) {
         vk = NAN;                                                // error flagged by the weights pass
       }

@@ -15,7 +15,9 @@
 // values themselves.  So the simulation of a block is split in two:
 //   sgs_weights_kernel   one wavefront per (chain, cell), all cells of all chains side by side: octant search, ordinary-kriging
 //                        system, weights and kriging variance -> a record per cell (neighbour list with the values that are
-//                        known already, weights, standard deviation);
+//                        known already, weights, standard deviation).  The search and the solve described below are
+//                        sgs_search.h's octant_ring_search and krige_solve, which sgs_grid_kernel.hip and krige_grid_kernel.hip
+//                        call too; this kernel says which cells qualify and writes the record;
 //   sgs_sequence_kernel  one wavefront per chain walks the cells in visiting order: est = mean + sum w (v - mean),
 //                        value = est + sd * z, the only sequential part (a 48-term dot product per cell).
 //
@@ -57,7 +59,6 @@ constexpr uint64_t kSgsPendingTag = 0x7FF8C0DE00000000ull;   // neighbour record
 constexpr uint64_t kSgsWindowTag = 0x7FF8C0DF00000000ull;    // | block-local index: conditioning data inside the block (sgs_sequence_kernel's overlay holds it)
 constexpr uint64_t kSgsGridTag = 0x7FF8C0E000000000ull;      // | flat grid index: a cell outside the block, read from the grid by sgs_sequence_kernel
 
-__device__ __forceinline__ double wave_sum_f64(double v) { return dev::wave64_sum(v); }     // DPP tree, wave-uniform result
 // two sums over the 64 lanes at once, results wave-uniform.  The halves are folded first -- v_permlane32_swap (gfx950) exchanges the
 // upper 32 lanes of `a` with the lower 32 of `b`, so a' + b' carries a[l] + a[l + 32] in lanes 0..31 and b[l] + b[l + 32] in lanes
 // 32..63 -- and ONE chain of row reductions then sums both: 25 instructions instead of the 52 of two full wave reductions (the
@@ -124,204 +125,26 @@ __global__ __launch_bounds__(64) void sgs_weights_kernel(const SgsArgs a) {
   const int32_t* rank = a.rank + (size_t)chain * kSgsMaxWin;
   if (rank[(i0 - r0) * ww + (j0 - c0)] != slot) { if (lane == 0) { a.rec_hdr[rec].n = -1; a.rec_hdr[rec].op = (i0 - r0) * ww + (j0 - c0); } return; }       // conditioned already (MCMC.py:141)
   const double* __restrict__ g = a.grid + (size_t)chain * H * W;
-  const int k8 = a.num_points / 8;
-  const double x0 = a.xs[j0], y0 = a.ys[i0];
-  const double sx = a.xs[1] - a.xs[0], sy = a.ys[1] - a.ys[0];
-  const double adx = fabs(sx), ady = fabs(sy), dmin = fmin(adx, ady);
-  const double inv_cert = 1.0 / (dmin * (1.0 - 1e-6));          // certification ring of a distance: floor(d * inv_cert)
-  const double fac_x = fmin(1.0, ady / adx), fac_y = fmin(1.0, adx / ady);
-  double radius = a.radius;
-  int hw = a.hw;
-  int n = 0;
-  for (;;) {                                                     // radius widening (MCMC.py:150-156): usually one trip
-    const int ilo = max(0, i0 - hw), ihi = min(H - 1, i0 + hw), jlo = max(0, j0 - hw), jhi = min(W - 1, j0 + hw);
-    // cells towards smaller / larger row and column that the window holds
-    const int e_up = i0 - ilo, e_dn = ihi - i0, e_lf = j0 - jlo, e_rt = jhi - j0;
-    const int r_max = max(max(e_up, e_dn), max(e_lf, e_rt));
-    // sector s: extent (in cells) along its primary axis on its side.  dy = y0 - y > 0 <=> rows with smaller y.
-    const int e_ypos = (sy > 0.0) ? e_up : e_dn, e_yneg = (sy > 0.0) ? e_dn : e_up;
-    const int e_xpos = (sx > 0.0) ? e_lf : e_rt, e_xneg = (sx > 0.0) ? e_rt : e_lf;
-    for (int q = lane; q < 8 * kSgsCertMax / 2; q += 64) (&L.cert[0][0])[q] = 0u;
-    if (lane < 8) { L.len[lane] = 0; L.cum[lane] = 0; }
-    __syncthreads();
-    int my_ext = 0;
-    double my_fac = 1.0;
-    if (lane < 8) {
-      const bool xprim = (lane == 3 || lane == 4 || lane == 7 || lane == 0);
-      my_fac = xprim ? fac_x : fac_y;
-      my_ext = (lane == 3 || lane == 4) ? e_xpos : (lane == 7 || lane == 0) ? e_xneg : (lane == 5 || lane == 6) ? e_ypos : e_yneg;
-    }
-    unsigned done_mask = 0;                                      // wave-uniform: sectors complete or exhausted
-    int R = 0;
-    bool long_list = false;
-    // one candidate cell per lane: everything is computed for every lane at clamped (always valid) indices; ONE predicate guards the insertion
-    auto probe = [&](int di, int dj, bool ok) {
-      const int i = i0 + di, j = j0 + dj;
-      ok = ok && i >= ilo && i <= ihi && j >= jlo && j <= jhi;
-      const int ic = min(max(i, ilo), ihi), jc = min(max(j, jlo), jhi);
-      const bool inwin = ic >= r0 && ic < r1 && jc >= c0 && jc < c1;
-      const int rk = rank[inwin ? (ic - r0) * ww + (jc - c0) : 0];
-      const double gv = a.defer ? 0.0 : g[ic * W + jc];          // defer: every cell outside the block holds a value (the caller's promise)
-      const double ddx = x0 - a.xs[jc], ddy = y0 - a.ys[ic];
-      const double d = sqrt(ddx * ddx + ddy * ddy);
-      const int s = octant(ddy, ddx);
-      // rk: -1 = conditioning data, < slot = simulated before this cell
-      const bool ins = ok && (inwin ? rk < slot : !isnan(gv)) && d < radius && !((done_mask >> s) & 1u);
-      if (ins) {
-        const int pos = atomicAdd(&L.len[s], 1);
-        long_list |= pos + 1 > kSgsListCap - 64;
-        L.list_d[s][pos] = d; L.list_g[s][pos] = i * W + j;
-        const double qf = d * inv_cert;
-        if (qf < (double)kSgsCertMax) { const int qi = (int)qf; atomicAdd(&L.cert[s][qi >> 1], 1u << (16 * (qi & 1))); }
-      }
-      __syncthreads();
-      // a list that could not take another full pass is cut back to the k8 nearest (nothing beyond them can be selected); the lane
-      // whose insertion took a list over that mark knows: the eight lengths are only looked at then
-      if (__ballot(long_list)) {
-        for (int s = 0; s < 8; ++s)
-          if (L.len[s] > kSgsListCap - 64) sgs_prune_sector(L, s, k8, lane);
-        long_list = false;
-      }
-    };
-    while (R < r_max && done_mask != 0xFFu) {
-      // one pass = rings R+1 .. R_hi: the 7 x 7 window first (rings 1-3 = 48 cells), then ring by ring
-      const int R_lo = R + 1;
-      int R_hi;
-      if (R == 0) {
-        R_hi = min(3, r_max);
-        const int side_w = 2 * R_hi + 1, cells_in_pass = side_w * side_w;
-        for (int t0 = 0; t0 < cells_in_pass; t0 += 64) {
-          const int t = t0 + lane;
-          const int di = t / side_w - R_hi, dj = t % side_w - R_hi;
-          probe(di, dj, t < cells_in_pass && !(di == 0 && dj == 0));
-        }
-      } else {
-        R_hi = R_lo;
-        const int cells_in_pass = 8 * R_hi;
-        const float inv_side = 1.0f / (float)(2 * R_hi);
-        for (int t0 = 0; t0 < cells_in_pass; t0 += 64) {
-          const int t = t0 + lane;
-          // t / (2 R_hi) without an integer division: (t + 1/2) / (2 R_hi) is at least 1 / (4 R_hi) away from an integer, fp32 is exact enough
-          const int side = (int)(((float)t + 0.5f) * inv_side), o = t - side * 2 * R_hi;
-          int di, dj;
-          ring_cell(R_hi, 2 * side + (o >= R_hi ? 1 : 0), o >= R_hi ? o - R_hi : o, di, dj);
-          probe(di, dj, t < cells_in_pass);
-        }
-      }
-      R = R_hi;
-      bool fin = false;
-      if (lane < 8) {
-        int c = L.cum[lane];
-        for (int q = R_lo; q <= R && q < kSgsCertMax; ++q) c += (int)((L.cert[lane][q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
-        L.cum[lane] = c;
-        fin = c >= k8 || (double)my_ext <= floor((double)R * my_fac + 1e-6);
-      }
-      done_mask |= (unsigned)(__ballot(fin) & 0xFFull);
-      __syncthreads();
-    }
-    // selection: per sector the k8 nearest in ascending (distance, cell); sectors concatenated in angle order
-    // all eight sectors at once, eight lanes each (a sector's list rarely holds more than a few dozen candidates: one sector after
-    // the other left most lanes idle): lane = 8 * sector + e mod 8 ranks its candidates against the whole list of its sector
-    {
-      const int my_s = lane >> 3;
-      int tot = 0, my_base = 0, my_len = 0;
-      for (int s = 0; s < 8; ++s) {
-        const int len = L.len[s];
-        if (s == my_s) { my_base = tot; my_len = len; }
-        tot += min(len, k8);
-      }
-      for (int e = lane & 7; e < my_len; e += 8) {
-        const double d = L.list_d[my_s][e];
-        const int gg = L.list_g[my_s][e];
-        int r = 0;
-        for (int q = 0; q < my_len; ++q) {
-          const double dq = L.list_d[my_s][q];
-          const int gq = L.list_g[my_s][q];
-          r += (dq < d || (dq == d && gq < gg)) ? 1 : 0;
-        }
-        if (r < k8) L.nb_g[my_base + r] = gg;
-      }
-      n = tot;
-    }
-    __syncthreads();
-    if (n > 0) break;
-    // nothing within the radius: the reference adds 100 km and rebuilds the stencil (window = ceil(radius / |dx|) cells)
-    if (ilo == 0 && jlo == 0 && ihi == H - 1 && jhi == W - 1 &&
-        radius * radius > ((double)(W - 1) * adx) * ((double)(W - 1) * adx) + ((double)(H - 1) * ady) * ((double)(H - 1) * ady)) break;
-    radius += 100e3;
-    hw = (int)fmin(ceil(radius / adx), 1.0e6);
-  }
-  if (n == 0) {                                                  // no value anywhere on the grid: the reference would loop forever
-    if (lane == 0) { atomicOr(a.err, 4); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].op = (i0 - r0) * ww + (j0 - c0); }
-    return;
-  }
-  if (lane < n) { const int gg = L.nb_g[lane]; const int rr = gg / W; L.nb_rc[lane] = (rr << 16) | (gg - rr * W); }
-  __syncthreads();
-  // ---- kriging system, one row per lane in registers: ordinary kriging [Sigma 1; 1' 0] w = [rho; 1] (_krige.py:25-37) or, with
-  // a.ktype == 1, simple kriging Sigma w = rho (_krige.py:66-73: no Lagrange row / column) ------------------------------------
+  // rk: -1 = conditioning data, < slot = simulated before this cell
+  auto qualifies = [&](int ic, int jc) {
+    const bool inwin = ic >= r0 && ic < r1 && jc >= c0 && jc < c1;
+    const int rk = rank[inwin ? (ic - r0) * ww + (jc - c0) : 0];
+    const double gv = a.defer ? 0.0 : g[ic * W + jc];            // defer: every cell outside the block holds a value (the caller's promise)
+    return inwin ? rk < slot : !isnan(gv);
+  };
+  const int n = octant_ring_search(L, qualifies, i0, j0, H, W, a.xs, a.ys, a.radius, a.hw, a.num_points / 8, lane);
+  // a cell that fails gets no values: n = 0 in its record
+  auto give_up = [&](int32_t flag) {
+    if (lane == 0) { atomicOr(a.err, flag); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].op = (i0 - r0) * ww + (j0 - c0); }
+  };
+  if (n == 0) { give_up(4); return; }                            // no value anywhere on the grid: the reference would loop forever
   const bool lagr = a.ktype == 0;
-  const int mi = a.mi, mj = a.mj, lag_w = 2 * mj + 1;
-  const double* __restrict__ lag = a.lag;
-  double r[50];
-  const int my_rc = (lane < n) ? L.nb_rc[lane] : 0;
-  const int my_i = my_rc >> 16, my_j = my_rc & 0xFFFF;
-  bool lag_ok = true;
-  if (mi >= H - 1 && mj >= W - 1) {
-    // the table spans every lag of the grid (lag_extents: grids up to 2048 x 2048 lags): no range test, and the index of the pair
-    // (this lane's neighbour, neighbour j) is one subtraction -- (my_i + mi) lag_w + my_j + mj minus neighbour j's i lag_w + j
-    const int my_base = (my_i + mi) * lag_w + my_j + mj;
-    __syncthreads();
-    if (lane < n) L.nb_rc[lane] = my_i * lag_w + my_j;           // the (row, col) pairs are in registers by now
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 48; ++j) {
-      double v = 0.0;
-      if (j < n) {                                               // wave-uniform
-        if (lane < n) v = lag[my_base - L.nb_rc[j]];
-        else if (lane == 48 && lagr) v = 1.0;
-      }
-      r[j] = v;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 48; ++j) {
-      double v = 0.0;
-      if (j < n) {                                               // wave-uniform
-        if (lane < n) {
-          const int rc = L.nb_rc[j];
-          const int di = my_i - (rc >> 16), dj = my_j - (rc & 0xFFFF);
-          if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v = lag[(di + mi) * lag_w + dj + mj];
-        } else if (lane == 48 && lagr) v = 1.0;
-      }
-      r[j] = v;
-    }
-  }
-  {
-    double v48 = 0.0, v49 = 0.0;
-    if (lane < n) {
-      const int di = my_i - i0, dj = my_j - j0;
-      v48 = lagr ? 1.0 : 0.0;
-      if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v49 = lag[(di + mi) * lag_w + dj + mj];
-    } else if (lane == 48 && lagr) v49 = 1.0;
-    r[48] = v48; r[49] = v49;
-  }
-  if (__ballot(!lag_ok)) { if (lane == 0) { atomicOr(a.err, 64); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].op = (i0 - r0) * ww + (j0 - c0); } return; }
-  const double rho_l = r[49];
-  const double c00 = lag[mi * lag_w + mj];
-  // relative pivot test: eps * N * max|diag| for the covariance pivots (conditional variances), eps * N / max|diag| for the
-  // Lagrange pivot -1' Sigma^-1 1
-  const double tol = 2.220446049250313e-16 * (double)(n + 1) * fabs(c00), tol_l = 2.220446049250313e-16 * (double)(n + 1) / fabs(c00);
-  double mypiv = 1.0;
-  bool singular = false;
-  GjStep<0>::run(r, lane, n, lagr, tol, tol_l, mypiv, singular);
-  if (singular) {
-    if (lane == 0) { atomicOr(a.err, 8); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].op = (i0 - r0) * ww + (j0 - c0); }
-    return;
-  }
-  const double w_l = (lane < n) ? r[49] / mypiv : 0.0;
-  double var = a.sill - wave_sum_f64(w_l * rho_l);
+  double w_l, rho_l;
+  int my_i, my_j;
+  if (const int e = krige_solve<true>(L, n, i0, j0, H, W, a.lag, a.mi, a.mj, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
+  double var = a.sill - dev::wave64_sum(w_l * rho_l);
   var = fabs(var);
-  const double sw = wave_sum_f64(w_l);
+  const double sw = dev::wave64_sum(w_l);
   // ---- the cell's record ---------------------------------------------------------------------------------------------
   if (lane < kSgsMaxPts) {
     double2 vw = make_double2(0.0, 0.0);
@@ -369,12 +192,6 @@ __global__ __launch_bounds__(64) void sgs_weights_kernel(const SgsArgs a) {
 // A cell whose kriging system failed (n == 0, error flag raised by sgs_weights_kernel) gets NaN, and so does every later
 // cell of its chunk and every cell that lists one of those.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const dev::v2i32 b = __builtin_bit_cast(dev::v2i32, v);
-  dev::v2i32 o;
-  o.x = __builtin_amdgcn_readlane(b.x, l); o.y = __builtin_amdgcn_readlane(b.y, l);
-  return __builtin_bit_cast(double, o);
-}
 constexpr int kSeqWaves = 4;
 __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsArgs a) {
   __shared__ double overlay[kSgsMaxWin];
@@ -475,7 +292,7 @@ __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsA
 #pragma unroll
       for (int u = 0; u < 8; ++u) { const double tt = tile[(k8 + u) * 64 + lane]; t[u] = ((mask >> (k8 + u)) & 1ull) ? tt : 0.0; }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) val = __fma_rn(t[u], readlane_f64(val, k8 + u), val);     // lane k8 + u is final: every cell it lists came before
+      for (int u = 0; u < 8; ++u) val = __fma_rn(t[u], dev::readlane_f64(val, k8 + u), val);     // lane k8 + u is final: every cell it lists came before
     }
     if (n == -1) {                                              // conditioned already: nothing drawn for it (MCMC.py:141)
       if (a.trace) { a.trace[3 * (k_lo + j)] = -1.0; a.trace[3 * (k_lo + j) + 1] = overlay[op]; a.trace[3 * (k_lo + j) + 2] = 0.0; }

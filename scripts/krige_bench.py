@@ -1,6 +1,7 @@
 """Throughput of interpolate.krige on the device (gsm_krige_grid): estimated cells per second over a whole grid, 48 neighbours
 within 50 km, Matern (the grid of scripts/sgs_grid_bench.py), with gsm_sgs_grid on the same grid and arguments in the same
-process as the yardstick: its weights pass runs the same search and solve per cell.
+process as the yardstick: its weights pass calls the same search and solve per cell (octant_ring_search and krige_solve of
+csrc/sgs_search.h).
 
     cells_per_s_device      HIP events around gsm_krige_grid (the whole call: one kernel and the error word's read-back)
     cells_per_s_total       interpolate.krige end to end: transformer fit, lag table, uploads, device call, inverse transform

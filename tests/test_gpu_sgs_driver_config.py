@@ -74,15 +74,10 @@ def _one_iteration_inputs(ch, prob, rngs, cond_is_data):
     return wins, offs, np.ascontiguousarray(np.concatenate(cells)), np.concatenate(zs)
 
 
-@pytest.mark.parametrize("npts,rad,blocks,n_iter", [(16, 4000.0, (3, 8, 3, 8), 2000), (48, 30e3, (5, 20, 5, 20), 120)])
-def test_device_neighbour_sets_are_valid_octant_searches(npts, rad, blocks, n_iter):
-    """The property that holds whatever breaks ties (neighbors.py:50-60): for every simulated cell of a long run (8 chains, square
-    500 m grid, so equidistant candidates abound) the device's neighbour set holds, per 45-degree sector, min(k8, available)
-    cells, all with a value when the cell is visited and closer than the radius, and no unselected candidate of the sector is
-    closer than a selected one.  Uses gsm_sgs_blocks' neighbour trace."""
-    import torch
+def _h32_problem(rad, blocks):
+    """The 32 x 32 problem of the two tests below (square 500 m cells, 8 chains, exponential variogram): problem, chain, variogram,
+    sill, axes and spacings, search half-width in cells, the chains' beds and generators."""
     from mcmc_gpu_amd import sgs
-    from mcmc_gpu_amd.engine import GsmEngine, _ptr
     H, n = 32, 8
     prob = sc.problem(H)
     ch = sgs.chain_sgs_gpu(prob["xx"], prob["yy"], prob["bed"], prob["surf"], prob["velx"], prob["vely"], prob["dhdt"], prob["smb"],
@@ -92,6 +87,21 @@ def test_device_neighbour_sets_are_valid_octant_searches(npts, rad, blocks, n_it
     vario = dict(azimuth=0, nugget=0.0, major_range=6000.0, minor_range=6000.0, sill=sill, vtype="Exponential")
     xs, ys, dx, dy = sgs._axes(prob["xx"], prob["yy"])
     hw = int(np.ceil(rad / abs(dx)))
+    beds = np.stack([prob["bed"] + np.random.default_rng(70 + c).normal(0, 3, (H, H)) for c in range(n)])
+    rngs = [np.random.default_rng(500 + c) for c in range(n)]
+    return H, n, prob, ch, vario, sill, xs, ys, dx, dy, hw, beds, rngs
+
+
+@pytest.mark.parametrize("npts,rad,blocks,n_iter", [(16, 4000.0, (3, 8, 3, 8), 2000), (48, 30e3, (5, 20, 5, 20), 120)])
+def test_device_neighbour_sets_are_valid_octant_searches(npts, rad, blocks, n_iter):
+    """The property that holds whatever breaks ties (neighbors.py:50-60): for every simulated cell of a long run (8 chains, square
+    500 m grid, so equidistant candidates abound) the device's neighbour set holds, per 45-degree sector, min(k8, available)
+    cells, all with a value when the cell is visited and closer than the radius, and no unselected candidate of the sector is
+    closer than a selected one.  Uses gsm_sgs_blocks' neighbour trace."""
+    import torch
+    from mcmc_gpu_amd import sgs
+    from mcmc_gpu_amd.engine import GsmEngine, _ptr
+    H, n, prob, ch, vario, sill, xs, ys, dx, dy, hw, beds, rngs = _h32_problem(rad, blocks)
     k8 = npts // 8
     cond = prob["cond_bed"]
     is_data = ~np.isnan(cond)
@@ -100,8 +110,6 @@ def test_device_neighbour_sets_are_valid_octant_searches(npts, rad, blocks, n_it
     f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
     mi, mj = sgs.lag_extents(hw, H, H)
     d_lag, d_xs, d_ys, d_zc = f64(sgs.lag_cov_table(vario, hw, dx, dy, mi, mj)), f64(xs), f64(ys), f64(cond)
-    beds = np.stack([prob["bed"] + np.random.default_rng(70 + c).normal(0, 3, (H, H)) for c in range(n)])
-    rngs = [np.random.default_rng(500 + c) for c in range(n)]
     ii, jj = np.meshgrid(np.arange(H), np.arange(H), indexing="ij")
     max_cells = (blocks[1] - 1) * (blocks[3] - 1)
     checked = tied_cut = 0
@@ -156,6 +164,58 @@ def test_device_neighbour_sets_are_valid_octant_searches(npts, rad, blocks, n_it
     finally:
         eng.close()
     assert checked > 1000 and tied_cut > 0          # the run did meet cuts between equidistant candidates
+
+
+@pytest.mark.parametrize("ktype", ["ok", "sk"])
+def test_block_sgs_is_the_same_with_a_whole_grid_and_a_window_lag_table(ktype):
+    """sgs_weights_kernel loads the rows of its kriging systems in one of two ways (krige_solve in sgs_search.h): by one subtraction
+    per pair when the lag table spans every lag of the grid, by (row, column) differences with a range test otherwise.  Same problem
+    as the test above at 16 neighbours within 4000 m (half-width 8 cells), 8 chains, blocks 3-8; every cell outside a block holds a
+    value, so no search widens and two neighbours of a cell are at most 16 cells apart.  The table at extents (H - 1, W - 1) takes
+    the first path, the table at (16, 16) the second; they hold the same numbers at the same lags, so grid, trace and neighbour
+    trace must be identical bit for bit, in ordinary and in simple kriging."""
+    import torch
+    from mcmc_gpu_amd import sgs
+    from mcmc_gpu_amd.engine import GsmEngine, _ptr
+    npts, rad, blocks = 16, 4000.0, (3, 8, 3, 8)
+    H, n, prob, ch, vario, sill, xs, ys, dx, dy, hw, beds, rngs = _h32_problem(rad, blocks)
+    assert hw == 8
+    tables = {(H - 1, H - 1): sgs.lag_cov_table(vario, hw, dx, dy, H - 1, H - 1), (2 * hw, 2 * hw): sgs.lag_cov_table(vario, hw, dx, dy, 2 * hw, 2 * hw)}
+    lo = H - 1 - 2 * hw
+    assert np.array_equal(tables[(H - 1, H - 1)][lo:lo + 4 * hw + 1, lo:lo + 4 * hw + 1], tables[(2 * hw, 2 * hw)])
+    is_data = ~np.isnan(prob["cond_bed"])
+    assert np.isfinite(beds).all()
+    max_cells = (blocks[1] - 1) * (blocks[3] - 1)
+    eng = GsmEngine(H, H, n)
+    dev = eng.dev
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    d_xs, d_ys, d_zc = f64(xs), f64(ys), f64(prob["cond_bed"])
+    d_gm = f64([np.mean(b) for b in beds])
+    simulated = 0
+    try:
+        eng._check(eng.lib.gsm_sgs_set_kriging(eng.h, 1 if ktype == "sk" else 0, _ptr(d_gm)))
+        for it in range(4):
+            wins, offs, cells, z = _one_iteration_inputs(ch, prob, rngs, is_data)
+            tot = int(offs[-1])
+            keep = (torch.as_tensor(wins).to(dev), torch.as_tensor(offs).to(dev), torch.as_tensor(cells).to(dev), f64(z))
+            res = []
+            for (mi, mj), table in tables.items():
+                grid, d_lag = f64(beds), f64(table)
+                nbr = torch.full((tot, 48), -2, dtype=torch.int32, device=dev)
+                tr = torch.zeros((tot, 3), dtype=torch.float64, device=dev)
+                eng._check(eng.lib.gsm_sgs_blocks(eng.h, _ptr(grid), _ptr(d_zc), _ptr(keep[0]), _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), mi, mj, hw,
+                                                  float(rad), npts, sill, _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), max_cells, _ptr(tr),
+                                                  _ptr(nbr), eng._stream()))
+                res.append((grid.cpu().numpy(), tr.cpu().numpy(), nbr.cpu().numpy()))
+            (g_a, t_a, nb_a), (g_b, t_b, nb_b) = res
+            assert np.array_equal(nb_a, nb_b), "neighbour trace"
+            assert np.array_equal(t_a, t_b), "trace"
+            assert np.array_equal(g_a, g_b), "grid"
+            assert np.isfinite(g_a).all() and not np.array_equal(g_a, beds)
+            simulated += int((t_a[:, 0] > 0).sum())
+    finally:
+        eng.close()
+    assert simulated > 100
 
 
 @pytest.mark.parametrize("vtype,vrange", [("Gaussian", 700.0), ("Gaussian", 1000.0), ("Gaussian", 1500.0), ("Gaussian", 2200.0),
