@@ -1,6 +1,11 @@
 """-m gpu: the fused chain kernel (gsm_run_philox, spectral generator) against the two-kernel pipeline and against
 gsm_propose_philox + gsm_run_replay on the same Philox counters.  All three must agree bit for bit: the fused kernel
-generates every proposal inside the workgroup that consumes it, with the same arithmetic."""
+generates every proposal inside the workgroup that consumes it, with the same arithmetic.
+
+Which kernels these are: every block table here passes strip_table_ok, so with GSM_STRIP at its default both sides of every
+comparison below are the strip family (chain_strip_kernel against step_strip_kernel + propose_kernel).  The flux-tile pairing
+(chain_fused_kernel against step_flux_kernel) runs the same bodies in a GSM_STRIP=0 child of tests/test_gpu_flux_tile_oracle.py,
+which also pins step_flux_kernel's NaN rule and thickness guard to the oracle."""
 import numpy as np
 import pytest
 
@@ -108,7 +113,10 @@ def test_fused_segments_reproduce_unsplit_run():
 def test_fused_nan_fields_and_thickness_guard_equal_two_kernel_pipeline():
     """NaN holes in the bed, a NaN velocity patch, a NaN dhdt cell (nansum semantics, MCMC.py:1041, :1328) and a surface
     lowered so far in one corner that proposals there trip the thickness guard (loss = inf, MCMC.py:1321-1329): the fused
-    kernel's NaN-coded operands must give what the mask-byte kernels give (which replay tests pin to the oracle)."""
+    kernel must give what the two-kernel pipeline gives.  By default both are strip kernels (this 64 x 64 table passes
+    strip_table_ok), whose replay side test_gpu_parity pins to the oracle.  The flux-tile pairing -- chain_fused_kernel's NaN-coded
+    operands against step_flux_kernel's -- is this same body in the GSM_STRIP=0 child of tests/test_gpu_flux_tile_oracle.py, where
+    test_nan_cells_follow_nansum_semantics and test_thickness_guard_rejects pin step_flux_kernel to the oracle."""
     from mcmc_gpu_amd.engine import GsmEngine
     rfp = orc.standard_rf_params()
     prob, cfg, pairs, masks, _ = orc.standard_setup(64)
