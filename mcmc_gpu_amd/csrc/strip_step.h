@@ -74,7 +74,7 @@ __host__ inline bool table_ok(int max_bh, int max_bw) {
 }
 
 // t / d for t < 64, 1 <= d <= 8 (multipliers 2^15 / d + 1 packed in two constants)
-__device__ __forceinline__ int small_div(int t, int d) {
+__host__ __device__ __forceinline__ int small_div(int t, int d) {
   const uint64_t lo = 32769ull | (16385ull << 16) | (10923ull << 32) | (8193ull << 48);     // d = 1 .. 4
   const uint64_t hi = 6554ull | (5462ull << 16) | (4682ull << 32) | (4097ull << 48);        // d = 5 .. 8
   const uint32_t m = (uint32_t)(((d <= 4) ? lo : hi) >> (16 * ((d - 1) & 3))) & 0xFFFFu;
@@ -88,7 +88,7 @@ struct Window {
   int bw;                  // block width (row stride of the proposal field)
   bool interior;           // a halo ring on all four sides lies inside the grid
 };
-__device__ __forceinline__ Window make_window(int H, int W, int row, int col, int bh, int bw) {
+__host__ __device__ __forceinline__ Window make_window(int H, int W, int row, int col, int bh, int bw) {
   Window g;
   const int r0 = max(0, row - bh / 2), r1 = min(H, row + bh / 2);
   const int c0 = max(0, col - bw / 2), c1 = min(W, col + bw / 2);
@@ -118,7 +118,7 @@ struct Lane {
   int lo, hi;              // border windows: iterations whose row exists and is needed: lo .. hi (hi < lo: none)
   int jtop, jbot;          // border windows: iteration of grid row 0 / H - 1
 };
-__device__ __forceinline__ Lane lane_setup(const int lane, const int wave, const Cfg& c, const Window& g, const int H, const int W) {
+__host__ __device__ __forceinline__ Lane lane_setup(const int lane, const int wave, const Cfg& c, const Window& g, const int H, const int W) {
   Lane L;
   const int C = 1 << c.cs;
   const int sub = lane >> c.cs, l = lane & (C - 1);
@@ -144,7 +144,7 @@ __device__ __forceinline__ Lane lane_setup(const int lane, const int wave, const
   L.tidx = (g.mr0 + wr0 + 1) * (g.bw + 2) + g.mc0 + wc + 1;
   return L;
 }
-__device__ __forceinline__ bool has(const Lane& L, const uint32_t f) { return (L.flags & f) != 0u; }
+__host__ __device__ __forceinline__ bool has(const Lane& L, const uint32_t f) { return (L.flags & f) != 0u; }
 
 // Row predicates are one 32-bit compare each.  Left alone, the compiler computes every one of them once per step and keeps
 // the lane masks (two scalar registers each, several per row) alive from the loads to the commit -- hundreds of spilled
@@ -188,13 +188,13 @@ __device__ __forceinline__ void row_offsets(const Lane& L, const int jj, const i
   else { off = (L.cell0 + (uint32_t)(jj * W)) * cb; soff = 0u; }
 }
 // border windows: the row of iteration jj exists in the grid and the lane needs it
-__device__ __forceinline__ bool row_exists(const Lane& L, const int jj) { return jj >= L.lo && jj <= L.hi; }
-__device__ __forceinline__ bool row_own(const Lane& L, const int jj) { return (jj >= 1) && (jj <= kNR) && (jj <= L.rows); }
+__host__ __device__ __forceinline__ bool row_exists(const Lane& L, const int jj) { return jj >= L.lo && jj <= L.hi; }
+__host__ __device__ __forceinline__ bool row_own(const Lane& L, const int jj) { return (jj >= 1) && (jj <= kNR) && (jj <= L.rows); }
 // phase A writes the tile cell of iteration jj: the lane's own cells (candidate bed) and the cells of the halo ring around
 // the window (bed); cells inside the window that belong to another strip are that strip's to write.  w0, w1, w2: the
 // answer for iteration 0, for the own rows, for iteration rows + 1 (lane masks, fixed for the step).
 struct WriteMasks { bool w0, w1, w2; };
-__device__ __forceinline__ WriteMasks write_masks(const Lane& L) {
+__host__ __device__ __forceinline__ WriteMasks write_masks(const Lane& L) {
   WriteMasks m;
   const bool valid = has(L, kFValid), colin = has(L, kFColIn);
   m.w0 = valid && !(has(L, kFTopIn) && colin);
@@ -203,7 +203,7 @@ __device__ __forceinline__ WriteMasks write_masks(const Lane& L) {
   return m;
 }
 template <bool INTERIOR>
-__device__ __forceinline__ bool cell_written(const Lane& L, const WriteMasks& m, const int jj) {
+__host__ __device__ __forceinline__ bool cell_written(const Lane& L, const WriteMasks& m, const int jj) {
   bool w = (jj == 0) ? m.w0 : ((jj <= L.rows && m.w1) || (jj - 1 == L.rows && m.w2));
   if (!INTERIOR) w = w && row_exists(L, jj);
   return w;

@@ -1,0 +1,267 @@
+"""Cases of tests/test_gpu_strip_oracle.py: one block table per decomposition of the strip kernels (chain_strip_kernel,
+step_strip_kernel, strip_step.h) against the oracle.  GSM_STRIP defaults to 1, so the cases run in the test's own process;
+every case asserts strip_active() == 1.
+
+strip::config restated here (strip_step.h), by the width ww of the clipped window; a workgroup of 8 waves x 64 lanes is dealt
+as g column groups x sr row strips of n = ceil(wh / sr) rows, n <= kNR = 16:
+  ww <= 62: 64 lanes, g 1, sr 8;  63-70: 16 lanes, g 5, sr 6;  71-90: 32 lanes, g 3, sr 5;  91-124: 64 lanes, g 2, sr 4;
+  125-248: 64 lanes, g 4, sr 2  (block widths stop at kT1S = 128, so g 8 / sr 1 is out of reach).
+Each table's widths lie in one interval; its heights are the tallest the 80 KiB LDS bound of strip_table_ok admits.  Windows
+clip (centres anywhere), so a table also runs the decompositions of narrower windows: every case derives the decomposition of
+each step from its recorded block and centre and asserts how many steps ran the table's own one."""
+import functools
+
+import numpy as np
+
+import mcmc_oracle as orc
+from flux_tile_oracle_cases import _bars, oracle_chains_from
+from gpu_common import oracle_chains, replay_inputs
+
+KNR, KNA = 16, 4           # strip_step.h: owned rows per strip at most; slots of phase A's (wupd, surf) ring
+
+# name: (H, W, bw_min, bw_max, bh_min, bh_max, own (g, sr), deepest n of the own decomposition)
+TABLES = {
+    "strip_g1": (104, 72, 40, 62, 64, 94, (1, 8), 12),
+    "strip_l16": (96, 80, 64, 70, 50, 80, (5, 6), 14),
+    "strip_l32": (96, 100, 72, 90, 50, 80, (3, 5), 16),
+    "strip_g2": (60, 136, 92, 124, 18, 48, (2, 4), 12),
+    "strip_g4": (44, 140, 126, 128, 8, 32, (4, 2), 16),
+}
+N_CHAINS = 2
+N_STEPS = 60               # proposals per chain, replay cases
+
+
+def config(wh, ww):
+    """(g, sr, n) of a wh x ww window: strip::config."""
+    g, sr = (1, 8) if ww <= 62 else (5, 6) if ww <= 70 else (3, 5) if ww <= 90 else (2, 4) if ww <= 124 else (4, 2) if ww <= 248 else (8, 1)
+    return g, sr, -(-wh // sr)
+
+
+def window(row, col, bh, bw, H, W):
+    """(r0, r1, c0, c1, interior) of a step: make_window; interior = the halo ring lies inside the grid."""
+    r0, r1, c0, c1 = orc.window_bounds(int(row), int(col), int(bh), int(bw), H, W)[:4]
+    return r0, r1, c0, c1, (r0 > 0 and r1 < H and c0 > 0 and c1 < W)
+
+
+def _setup(name, block_type="CRF_weight"):
+    H, W, bw0, bw1, bh0, bh1, own, deepest = TABLES[name]
+    prob, cfg, _, _, rfp = orc.standard_setup(H, W, block_min=bw0, block_max=bw1, block_type=block_type, update_in_region=False)
+    pairs = orc.block_pairs(bw0, bw1, bh0, bh1)
+    masks = orc.edge_masks(pairs, [2, 0, 6, 1], 49900.0, prob["resolution"])
+    return H, W, own, deepest, prob, cfg, pairs, masks, rfp
+
+
+def _engine(H, W, n_chains, cfg, pairs, masks, state):
+    from mcmc_gpu_amd.engine import GsmEngine
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    eng.set_static(cfg.surf, cfg.velx, cfg.vely, cfg.dhdt, cfg.smb, cfg.crf_data_weight, cfg.grounded_ice_mask,
+                   cfg.mc_region_mask, cfg.resolution, cfg.sigma_mc)
+    eng.set_blocks(pairs, masks)
+    assert eng.strip_active() == 1, "strip_table_ok refuses the table"
+    return eng
+
+
+def decompositions(blocks, H, W):
+    """Per step (row, col, bh, bw): ((g, sr), n, interior)."""
+    out = []
+    for row, col, bh, bw in np.asarray(blocks).reshape(-1, 4):
+        r0, r1, c0, c1, interior = window(row, col, bh, bw, H, W)
+        g, sr, n = config(r1 - r0, c1 - c0)
+        out.append(((g, sr), n, interior))
+    return out
+
+
+def conditions(name, blocks, rate):
+    """What keeps a case from passing vacuously.  The accept rate lies in [0.2, 0.9]; windows hang over all four edges of the
+    grid; at least 10 steps ran the table's own decomposition, at least 3 of them with an interior window (the INTERIOR
+    instantiation) and at least 3 with a clipped one, and the deepest strip among them has the table's n."""
+    H, W, _, _, _, _, own, deepest = TABLES[name]
+    b = np.asarray(blocks).reshape(-1, 4)
+    row, col, bh, bw = (b[:, i] for i in range(4))
+    sides = {"top": row - bh / 2 < 0, "bottom": row + bh / 2 > H, "left": col - bw / 2 < 0, "right": col + bw / 2 > W}
+    dec = decompositions(b, H, W)
+    mine = [(n, interior) for d, n, interior in dec if d == own]
+    n_int = sum(1 for _, interior in mine if interior)
+    others = sorted({d for d, _, _ in dec if d != own})
+    deep = max((n for n, _ in mine), default=0)
+    print(f"    {name}: accept rate {rate:.2f}, windows over top / bottom / left / right " + " / ".join(str(int(v.sum())) for v in sides.values()) +
+          f", own decomposition {own}: {len(mine)} steps ({n_int} interior), deepest n {deep}, others run {others}", flush=True)
+    assert 0.2 <= rate <= 0.9, f"accept rate {rate}"
+    assert all(v.any() for v in sides.values()), {k: bool(v.any()) for k, v in sides.items()}
+    assert len(mine) >= 10 and n_int >= 3 and len(mine) - n_int >= 3, (len(mine), n_int)
+    assert deep == deepest, f"deepest n {deep}, expected {deepest}"
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_outs(name, f32):
+    """The oracle's chains on a table (seeds 7 and 8), computed once per state dtype and left unchanged by the cases that share them."""
+    H, W, own, deepest, prob, cfg, pairs, masks, rfp = _setup(name)
+    return oracle_chains(prob, cfg, pairs, masks, rfp, N_CHAINS, N_STEPS + 1, state_f32=f32)
+
+
+def oracle_conditions(name, outs):
+    conditions(name, np.concatenate([o[6][1:] for o in outs]), float(np.mean([o[4][1:].mean() for o in outs])))
+
+
+def replay_table(name, state="f64"):
+    """Replay of the oracle's draws, two chains, windows clipped on every edge.  fp32 state (RowIO<float> on strips up to kNR
+    rows deep): the bars of test_gpu_parity.test_f32_state_mode_matches_its_oracle_and_tracks_fp64."""
+    H, W, own, deepest, prob, cfg, pairs, masks, rfp = _setup(name)
+    f32 = state == "f32"
+    outs = oracle_outs(name, f32)
+    oracle_conditions(name, outs)
+    eng = _engine(H, W, N_CHAINS, cfg, pairs, masks, state)
+    loss0 = eng.set_state(np.stack([orc.chain_initial_bed(prob, c) for c in range(N_CHAINS)]))
+    loss, acc = eng.run_replay(*replay_inputs(eng, outs))
+    assert eng.beds.dtype.itemsize == eng.energy.dtype.itemsize == (4 if f32 else 8)
+    _bars(eng, outs, loss0, loss, acc)
+    eng.close()
+    if f32:
+        outs64 = oracle_outs(name, False)
+        for c in range(N_CHAINS):
+            assert (outs64[c][4] != outs[c][4]).sum() <= 1
+            np.testing.assert_allclose(outs[c][3][:50], outs64[c][3][:50], rtol=1e-6)
+
+
+def nan_inputs(name):
+    """The NaN cells of flux_tile_oracle_cases.nan_inputs, their coordinates scaled as fractions of H and of W separately: a
+    NaN patch in velx and a NaN cell in dhdt (static fields, seen by both chains), NaN holes in the initial bed of chain 1."""
+    H, W, own, deepest, prob, cfg, pairs, masks, rfp = _setup(name)
+    kr, kc = (lambda v: v * H // 64), (lambda v: v * W // 64)
+    cfg.velx = cfg.velx.copy(); cfg.velx[kr(30):kr(33), kc(40):kc(44)] = np.nan
+    cfg.dhdt = cfg.dhdt.copy(); cfg.dhdt[kr(12), kc(12)] = np.nan
+    beds0 = np.stack([orc.chain_initial_bed(prob, c) for c in range(N_CHAINS)])
+    beds0[1, kr(20):kr(22), kc(20):kc(25)] = np.nan
+    beds0[1, kr(45), kc(50)] = np.nan
+    return H, W, prob, cfg, pairs, masks, rfp, beds0
+
+
+def replay_table_nan(name):
+    """NaN residuals are ignored by the loss (nansum), NaN thickness never trips the guard: the chains replay exactly and the NaN
+    cells of the bed are still NaN, and the only NaN, at the end."""
+    H, W, prob, cfg, pairs, masks, rfp, beds0 = nan_inputs(name)
+    outs = oracle_chains_from(beds0, prob, cfg, pairs, masks, rfp, N_STEPS + 1)
+    assert all(np.isfinite(o[3]).all() for o in outs)
+    oracle_conditions(name, outs)
+    eng = _engine(H, W, N_CHAINS, cfg, pairs, masks, "f64")
+    loss0 = eng.set_state(beds0)
+    loss, acc = eng.run_replay(*replay_inputs(eng, outs))
+    _bars(eng, outs, loss0, loss, acc, equal_nan=True)
+    final = eng.beds.cpu().numpy()
+    assert np.array_equal(np.isnan(final), np.isnan(beds0)) and np.isnan(final[1]).sum() >= 11 and not np.isnan(final[0]).any()
+    eng.close()
+
+
+def guard_windows(name):
+    """The two windows of guard_table, for the table's largest block: (label, row, col, interior).  The clipped one loses 3 rows
+    and 2 columns against the bottom right corner of the grid, which leaves its width in the table's own interval."""
+    H, W, bw0, bw1, bh0, bh1, own, deepest = TABLES[name]
+    bh, bw = bh1 // 2 * 2, bw1 // 2 * 2
+    return bh, bw, [("interior", bh // 2 + 2, bw // 2 + 3, True), ("clipped bottom right", H - bh // 2 + 3, W - bw // 2 + 2, False)]
+
+
+def guard_table(name):
+    """flux_tile_oracle_cases.guard_table on the strip kernels: zero velocities make the loss independent of the bed, so only the
+    thickness guard (surf - bed_next <= 0 -> loss = inf) can reject while u is tiny.  The guard cell is the last own row and last
+    own column of the window of the table's largest block: the last column group and the last row strip, and a row deeper than
+    kNA in its strip, so that phase A reads surf from a refilled slot of its (wupd, surf) ring.  Once with the halo ring inside the
+    grid (INTERIOR), once with the window clipped against the bottom right corner."""
+    H, W, own, deepest, prob, cfg, pairs, masks, rfp = _setup(name, block_type="RF")
+    cfg.velx = np.zeros_like(cfg.velx)
+    cfg.vely = np.zeros_like(cfg.vely)
+    cfg.crf_data_weight = None
+    bh, bw, wins = guard_windows(name)
+    si = pairs.shape[1] - 1
+    assert (int(pairs[1, si]), int(pairs[0, si])) == (bh, bw) == (int(pairs[1].max()), int(pairs[0].max()))
+    bed0 = orc.chain_initial_bed(prob, 0)
+    mc0 = orc.mc_residual(bed0, cfg.surf, cfg.velx, cfg.vely, cfg.dhdt, cfg.smb, cfg.resolution)
+    lp0 = orc.gaussian_loss(mc0, cfg.mc_region_mask, cfg.sigma_mc)[0]
+    for label, row, col, want_interior in wins:
+        r0, r1, c0, c1, mr0, _, mc0_, _ = orc.window_bounds(row, col, bh, bw, H, W)
+        interior = r0 > 0 and r1 < H and c0 > 0 and c1 < W
+        g, sr, n = config(r1 - r0, c1 - c0)
+        last_rows = (r1 - r0) - (sr - 1) * n                  # rows of the last row strip
+        print(f"    {name} {label}: window rows [{r0}, {r1}) cols [{c0}, {c1}), decomposition {(g, sr)}, n {n}, last strip {last_rows} rows", flush=True)
+        assert interior == want_interior and (g, sr) == own and KNA < last_rows <= n <= KNR
+        gr, gc = r1 - 1, c1 - 1                               # the guard cell, and its place in the block
+        fr, fc = mr0 + gr - r0, mc0_ + gc - c0
+        thick = (cfg.surf - bed0)[gr, gc]
+        f_ok = np.zeros((bh, bw)); f_ok[fr, fc] = thick - 1e-9   # 1 nm of ice left: allowed
+        f_bad = np.zeros((bh, bw)); f_bad[fr, fc] = thick        # thickness == 0: guard
+        u = np.array([[1e-300, 1e-300, 0.999]])
+        eng = _engine(H, W, 1, cfg, pairs, masks, "f64")
+        eng.set_state(bed0[None])
+        loss, acc = eng.run_replay(np.full((1, 3), si, int), np.array([[[row, col]] * 3]), u, eng.pack_fields([[f_bad, f_ok, f_bad]]))
+        bed, mc, lp, exp_acc = bed0, mc0, lp0, []
+        for f, uu in zip((f_bad, f_ok, f_bad), u[0]):
+            a, bed, mc, lp, _ = orc.mh_step(cfg, bed, mc, lp, f, row, col, uu)
+            exp_acc.append(a)
+        assert exp_acc == [False, True, False]
+        assert acc[0].tolist() == [0, 1, 0], f"{label}: accepts {acc[0].tolist()}"
+        assert np.array_equal(eng.beds[0].cpu().numpy(), bed) and bed[gr, gc] != bed0[gr, gc], label
+        np.testing.assert_allclose(loss[0], [lp] * 3, rtol=1e-12)
+        eng.close()
+
+
+def philox_table(name, state, fields_vs_oracle=False):
+    """flux_tile_oracle_cases.philox_table on the strip kernels: gsm_run_philox on the fused chain kernel == gsm_propose_philox +
+    gsm_run_replay == the two-kernel pipeline with another batch size, bit for bit; centres anywhere, so that windows clip."""
+    H, W, own, deepest, prob, cfg, pairs, masks, _ = _setup(name)
+    n_chains, n = 3, 24
+    rfp = orc.standard_rf_params(); rfp.resolution = prob["resolution"]
+    eng = _engine(H, W, n_chains, cfg, pairs, masks, state)
+    eng.set_centres(np.ones((H, W), dtype=np.uint8))
+    seeds = [61, 2 ** 40 + 62, 63]
+    beds0 = np.stack([orc.chain_initial_bed(prob, c) for c in range(n_chains)])
+
+    def state_now():
+        return (eng.beds.cpu().numpy().copy(), eng.resampled.cpu().numpy().copy(), eng.energy.cpu().numpy().copy())
+
+    eng.set_fused(True)
+    eng.set_state(beds0)
+    loss, acc, blk = eng.run_philox(n, 9, seeds, rfp, batch=n)
+    fused = eng.last_run_fused()
+    dec = decompositions(blk, H, W)
+    mine = [interior for d, _, interior in dec if d == own]
+    print(f"    {name} {state}: last_run_fused() == {fused}, accept rate {acc.mean():.2f}, own decomposition {own}: {len(mine)} steps "
+          f"({sum(mine)} interior), others run {sorted({d for d, _, _ in dec if d != own})}", flush=True)
+    assert fused == 1
+    st_a = state_now()
+    assert st_a[0].dtype.itemsize == (4 if state == "f32" else 8)
+    assert 0.2 <= acc.mean() <= 0.95
+    row, col, bh, bw = (blk[..., i] for i in range(4))
+    assert ((row - bh // 2 < 0) | (row + bh // 2 > H) | (col - bw // 2 < 0) | (col + bw // 2 > W)).any()
+    # the Philox oracle gives the blocks of these 72 steps without a device: 72 / 23 / 29 / 33 / 4 steps on the tables' own decompositions
+    assert len(mine) >= 3, "fewer than 3 steps ran the table's own decomposition"
+
+    eng.set_state(beds0)
+    p = eng.propose_philox(n, 9, seeds, rfp)
+    si, ce = p["size_idx"].cpu().numpy(), p["centre"].cpu().numpy()
+    loss_r, acc_r = eng.run_replay(si, ce, p["u"].cpu().numpy(), p["fields"])
+    assert np.array_equal(loss, loss_r) and np.array_equal(acc, acc_r)
+    assert np.array_equal(blk[..., :2], ce) and np.array_equal(blk[..., 2], pairs[1][si]) and np.array_equal(blk[..., 3], pairs[0][si])
+    for x, y in zip(st_a, state_now()):
+        assert np.array_equal(x, y)
+
+    eng.set_fused(False)
+    eng.set_state(beds0)
+    loss_p, acc_p, blk_p = eng.run_philox(n, 9, seeds, rfp, batch=7)
+    assert eng.last_run_fused() == 0
+    assert np.array_equal(loss, loss_p) and np.array_equal(acc, acc_p) and np.array_equal(blk, blk_p)
+    for x, y in zip(st_a, state_now()):
+        assert np.array_equal(x, y)
+
+    if fields_vs_oracle:         # the proposal fields against the Philox oracle, as test_gpu_philox.test_proposals_256_blocks_match_oracle
+        import philox_oracle as po
+        centres = np.arange(H * W)
+        for c in range(2):
+            for s in range(6):
+                e = po.proposal(seeds[c], 9 + s, rfp, pairs, masks, centres, W, prob["resolution"])
+                assert int(si[c, s]) == e["size_idx"] and tuple(ce[c, s].tolist()) == e["centre"]
+                fbh, fbw = e["field"].shape
+                f = p["fields"][c, s, : fbh * fbw].cpu().numpy().reshape(fbh, fbw)
+                np.testing.assert_allclose(f, e["field"], rtol=0, atol=po.field_atol(e))
+    eng.close()
+
+
+FIELDS_VS_ORACLE = ("strip_l32", "strip_g4")     # 15 stage-2 tiles of the 16 allowed; bh != bw by a factor of 4 to 16

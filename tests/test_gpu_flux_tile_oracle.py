@@ -2,7 +2,8 @@
 (step_kernel) -- the families that run every grid above about 295 x 295, BASELINE configs[3] and configs[4] among them.
 
 The oracle cannot run such a grid in seconds, and at the 16-256 grids of the oracle tests the strip kernels take every table
-(tests/test_gpu_strip.py), so those tests pin the strip family only.  GSM_STRIP=0 routes a small grid to the other two; the
+(tests/test_gpu_strip.py), so those tests pin the strip family only (table by table: tests/test_gpu_strip_oracle.py).  GSM_STRIP=0
+routes a small grid to the other two; the
 switch is read once per process, so each group of cases runs in a fresh child (tests/flux_tile_oracle_cases.py: main).
 
   group A  the bodies of the oracle tests of test_gpu_parity, test_gpu_fullsize, test_gpu_fused and test_gpu_philox, unchanged

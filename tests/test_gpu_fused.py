@@ -5,7 +5,9 @@ generates every proposal inside the workgroup that consumes it, with the same ar
 Which kernels these are: every block table here passes strip_table_ok, so with GSM_STRIP at its default both sides of every
 comparison below are the strip family (chain_strip_kernel against step_strip_kernel + propose_kernel).  The flux-tile pairing
 (chain_fused_kernel against step_flux_kernel) runs the same bodies in a GSM_STRIP=0 child of tests/test_gpu_flux_tile_oracle.py,
-which also pins step_flux_kernel's NaN rule and thickness guard to the oracle."""
+which also pins step_flux_kernel's NaN rule and thickness guard to the oracle.  The tables here are 8-16 cell blocks and the
+50-80 headline blocks: the strip family's fused == replay == two-kernel comparison on every decomposition of strip::config, and
+its NaN rule and thickness guard against the oracle on strips deeper than 2 rows, are in tests/test_gpu_strip_oracle.py."""
 import numpy as np
 import pytest
 

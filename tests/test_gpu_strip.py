@@ -3,7 +3,9 @@
 operation (reference gstatsMCMC/MCMC.py:1279-1360, Topography.py:592-600): beds, energies, accept masks, blocks and resampled
 counts must be identical; the loss differs by the order of the window sums only (tolerance 1e-12 relative, stated here).
 The proposal fields of both runs are made equal with GSM_SPLIT2=0 (handles on the strip kernels otherwise split stage 2 of the
-inverse DFT by the parity of kx, which the one-slot-per-wave flux-tile fused kernel cannot: last-bit differences in the fields)."""
+inverse DFT by the parity of kx, which the one-slot-per-wave flux-tile fused kernel cannot: last-bit differences in the fields).
+The strip family against the ORACLE, one block table per decomposition of strip::config (the 4 x 64-lane one included, which no
+table here reaches): tests/test_gpu_strip_oracle.py; its integer geometry on the host: tests/test_strip_geometry.py."""
 import os
 import subprocess
 import sys
