@@ -71,6 +71,14 @@ class GsmEngine:
     def _f64(self, a):
         return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
 
+    def call(self, fn, *args, stream=None):
+        """fn(handle, *args, stream) under the device guard, its return code checked.  Tensors and None become pointers; `stream`
+        is a torch stream (default: the current one)."""
+        args = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+        st = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        with torch.cuda.device(self.dev):
+            self._check(fn(self.h, *args, st))
+
     # ------------------------------------------------------------------------------------------
     def set_static(self, surf, velx, vely, dhdt, smb, crf_weight, update_mask, mc_mask, resolution, sigma_mc):
         shp = (self.H, self.W)

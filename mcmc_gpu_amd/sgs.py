@@ -28,6 +28,7 @@ import math
 import os
 import sys
 import time
+from collections import namedtuple
 from copy import deepcopy
 
 import numpy as np
@@ -339,6 +340,425 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def host_draws(chain, rngs, cond_is_data, it0, kb, n):
+    """The host draws of iterations it0 .. it0 + kb - 1 of n chains, packed for one gsm_sgs_iterate call.  Contract: chain c's
+    generator rngs[c] is consumed for its kb iterations consecutively and the loop is chain-major -- what chain_sgs.run would
+    consume chain by chain; the draws do not depend on the chains' state.  The packing is iteration-major: wins[j, c] and us[j, c]
+    belong to iteration it0 + j of chain c, `cells` and `z` hold the cells and normals in (j, c) order, offs[j] is iteration j's
+    prefix over the chains (offs[j, n] = its cell count) and bases[j] the running total, so that chain c's cells of iteration j are
+    cells[bases[j] + offs[j, c] : bases[j] + offs[j, c + 1]].  Returns (packed arrays, block records [n, kb, 4])."""
+    wins = np.empty((kb, n, 4), np.int32); offs = np.zeros((kb, n + 1), np.int32); us = np.empty((kb, n))
+    blocks = np.empty((n, kb, 4), np.int64)
+    inds = [[None] * n for _ in range(kb)]; zs = [[None] * n for _ in range(kb)]
+    for c in range(n):                     # per chain in iteration order: each chain owns its generator
+        for j in range(kb):
+            blocks[c, j], wins[j, c], inds[j][c], zs[j][c], us[j, c] = chain._draw_iteration(rngs[c], cond_is_data)
+    for j in range(kb):
+        offs[j, 1:] = np.cumsum([a.shape[0] for a in inds[j]])
+    bases = np.concatenate([[0], np.cumsum(offs[:, n], dtype=np.int64)])
+    tot = int(bases[kb])
+    cells = np.ascontiguousarray(np.concatenate([a for row in inds for a in row]) if tot else np.zeros((1, 2), np.int32))
+    z = np.concatenate([a for row in zs for a in row]) if tot else np.zeros(1)
+    return dict(it0=it0, kb=kb, wins=wins, offs=offs, us=us, bases=bases, cells=cells, z=z), blocks
+
+
+# The draws of some iterations as gsm_sgs_iterate / gsm_sgs_blocks_batch read them.  Device draws: views of a buffer set, blk the
+# block records, cell counts in cnt, off_stride n.  Uploaded host draws: blk and cnt None, off_stride n + 1, cell_base on the host.
+_Draws = namedtuple('_Draws', 'win blk off cnt cells z us off_stride cell_base')
+
+
+class _SgsRun:
+    """What run_many_sgs computes once per call, and the operations its three iteration drivers share.
+    Host plan (no device needed): axes, hw, vario, lag extents and table, max_cells, trend, z_cond, cond_is_data, the transformer
+    kind (None, 'device_qt': scikit-learn's on the device, 'host_nst': any other object, called on the host), keep_all, track,
+    windowed, batch, grid_finite, the draw source ('replay', 'pcg64' or 'philox').
+    Device state (None where it does not apply): cur / nxt / prop, resampled, d_loss / d_bad, d_lprev / d_acc, d_energy / d_state
+    (windowed iteration end), d_q / d_ref (transformer tables), d_region / d_isdata, d_gen or d_seeds and the draw buffer sets.
+    Records: loss_cache, step_cache, blocks_cache, bed_cache, sample_values."""
+
+    def __init__(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source,
+                 philox_seeds, philox_iter0):
+        from .engine import GsmEngine
+        self._plan(chain, initial_beds, rngs, int(n_iter), only_save_last_bed, source)
+        self.info_per_iter, self.progress_bar, self.philox_iter0 = max(int(info_per_iter), 1), progress_bar, int(philox_iter0)
+        self.eng = GsmEngine(self.H, self.W, self.n, device)
+        try:
+            self._device_state(philox_seeds)
+        except BaseException:
+            self.eng.close()
+            raise
+        self.t0 = time.time()
+
+    def close(self):
+        self.eng.close()
+
+    def _plan(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, source):
+        H, W = chain.xx.shape
+        n = len(initial_beds)
+        self.chain, self.rngs, self.source, self.n, self.n_iter, self.H, self.W = chain, rngs, source, n, n_iter, H, W
+        self.xs, self.ys, self.dx, self.dy = _axes(np.asarray(chain.xx, dtype=np.float64), np.asarray(chain.yy, dtype=np.float64))
+        self.rad, self.npts = float(chain.sgs_param[1]), int(chain.sgs_param[0])
+        self.hw = int(math.ceil(self.rad / abs(self.dx)))
+        self.vario = chain._vario()
+        self.lag_mi, self.lag_mj = lag_extents(self.hw, H, W)
+        self.lag = lag_cov_table(self.vario, self.hw, self.dx, self.dy, self.lag_mi, self.lag_mj)
+        self.max_cells = min(1024, max(1, (int(chain.block_max_x) - 1) * (int(chain.block_max_y) - 1)))
+        self.trend = np.asarray(chain.trend, dtype=np.float64) if chain.detrend_map else None
+        detrended = lambda a: np.asarray(a, dtype=np.float64) - self.trend if self.trend is not None else np.array(a, dtype=np.float64)
+        nst = self.nst = chain.nst_trans if chain.do_transform else None
+        cond_c = detrended(chain.cond_bed)
+        self.z_cond = nst.transform(cond_c.reshape(-1, 1)).reshape(H, W) if nst is not None else cond_c
+        self.cond_is_data = ~np.isnan(self.z_cond)
+        # scikit-learn's QuantileTransformer with normal output and one feature (what the reference's drivers attach,
+        # smallScaleChain_multiprocessing.py:493-496) runs on the device (gsm_qt_transform); any other transformer object is
+        # called on the host once per iteration, where the reference calls it
+        if nst is None:
+            self.transformer = None
+        elif (type(nst).__name__ == 'QuantileTransformer' and getattr(nst, 'output_distribution', None) == 'normal'
+              and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1):
+            self.transformer = 'device_qt'
+        else:
+            self.transformer = 'host_nst'
+        self.track = chain.sample_loc is not None
+        self.keep_all = not only_save_last_bed
+        # no transformer: only the block and its one-cell halo change per iteration -> carried squared residuals, windowed loss,
+        # and loss / guard / acceptance test / commit in ONE launch (gsm_sgs_finish); the reference recomputes the whole map
+        # (gsm_sgs_finish keeps block + halo in LDS: 36 x 36 cells; a longer, thinner block takes the whole-map path)
+        self.windowed = (nst is None and os.environ.get('GSM_SGS_WINDOWED', '1') != '0' and
+                         (int(chain.block_max_x) + 1) * (int(chain.block_max_y) + 1) <= 1296)
+        # Without a host-side transformer and without per-iteration bed records nothing of an iteration has to come back to the
+        # host before the next one: the draws do not depend on the chain state (chain_sgs.run consumes chain.rng in the same order
+        # whatever is accepted), so a batch of iterations is drawn ahead and simulated / scored / decided / committed on the device
+        # back to back by ONE gsm_sgs_iterate call.  A batch ends with a host round trip (device flag, record download) and restarts
+        # the pipeline of records made ahead -- with few chains 128 instead of 32 iterations per batch is +7 % (4 chains: 66.6 ->
+        # 71.0 k chain-iterations/s); with the chip full it changes nothing and the draw buffers grow with batch x chains
+        one_by_one = self.transformer == 'host_nst' or self.keep_all or self.track
+        self.batch = 1 if one_by_one else int(os.environ.get('GSM_SGS_BATCH', '128' if n <= 64 else '32'))
+        # two sets of draw buffers: the device draws of batch b + 1 (they depend on the generators only, never on the chains' state)
+        # are made on their own stream while batch b iterates.
+        # Only for few chains (4 chains, pcg64 mode: 38.7 -> 56.2 k chain-iterations/s): with the chip full (256 chains) the draw
+        # kernel fits into the gap where the host downloads a batch's records, and drawing ahead measured 10 % slower (same box)
+        self.draw_ahead = os.environ.get('GSM_SGS_DRAW_AHEAD', '1' if n <= 64 else '0') != '0'
+        self.bed0 = np.stack([detrended(b) for b in initial_beds])
+        # no NaN in the beds (and none can appear: every cell of a block is simulated): gsm_sgs_iterate may then make the records of
+        # iteration j + 1 while iteration j is still running (include/gsm.h: grid_finite).  GSM_SGS_OVERLAP=0 turns that off.
+        self.grid_finite = os.environ.get('GSM_SGS_OVERLAP', '1') != '0' and bool(np.isfinite(self.bed0).all())
+        # records; every driver starts at iteration 0 and overwrites the record of the initial state there (module docstring)
+        self.loss_cache = np.zeros((n, n_iter)); self.step_cache = np.zeros((n, n_iter)); self.blocks_cache = np.full((n, n_iter, 4), np.nan)
+        self.bed_cache = self.sample_values = self.ij = None
+        if self.keep_all:
+            self.bed_cache = np.zeros((n, n_iter, H, W))
+            self.bed_cache[:, 0] = self.bed0
+        if self.track:
+            from .MCMC_gpu import chain_crf_gpu
+            self.ij = chain_crf_gpu._sample_indices(chain)          # the large-scale chain's lookup: same attributes (xx, yy, sample_loc)
+            self.sample_values = np.zeros((n, self.ij.shape[0], n_iter))
+            for c in range(n):
+                self.sample_values[c, :, 0] = np.asarray(initial_beds[c])[self.ij[:, 0], self.ij[:, 1]]
+
+    def _device_state(self, philox_seeds):
+        import torch
+        chain, eng, n, H, W = self.chain, self.eng, self.n, self.H, self.W
+        dev, f64 = eng.dev, eng._f64
+        self.lib, self.dev = eng.lib, dev
+        eng.set_static(chain.surf, chain.velx, chain.vely, chain.dhdt, chain.smb, None, chain.grounded_ice_mask,
+                       chain.mc_region_mask, chain.resolution, chain.sigma_mc)
+        self.d_xs, self.d_ys, self.d_lag, self.d_zcond = f64(self.xs), f64(self.ys), f64(self.lag), f64(self.z_cond)
+        self.d_trend = f64(self.trend) if self.trend is not None else None
+        self.cur = f64(self.bed0)
+        self.nxt = self.cur.clone()
+        self.bed_host = self.bed0 if self.transformer == 'host_nst' else None     # host-side transformer: the chains' state lives here
+        self.bed_next = None                                     # ... and its proposals in data space
+        self.d_q = self.d_ref = self.prop = None
+        self.nq = 0
+        if self.transformer == 'device_qt':
+            self.d_q, self.d_ref = f64(self.nst.quantiles_[:, 0]), f64(self.nst.references_)
+            self.nq = int(self.d_q.numel())
+            self.prop = self.cur.clone()                         # proposed beds in data space (inverse transform of nxt)
+        self.resampled = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
+        self.d_loss = torch.empty(n, dtype=torch.float64, device=dev)
+        self.d_bad = torch.empty(n, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev)
+        self.loss_prev, _ = self.loss(self.cur, st)
+        self.loss_cache[:, 0] = self.loss_prev
+        self.d_lprev = f64(self.loss_prev)
+        self.d_acc = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.d_energy = self.d_state = None
+        if self.windowed:
+            self.d_energy = torch.empty((n, H, W), dtype=torch.float64, device=dev)
+            self.d_state = torch.empty((n, 4), dtype=torch.float64, device=dev)
+            eng.call(self.lib.gsm_sgs_state_init, self.cur, self.d_trend, self.d_energy, self.d_state, stream=st)
+        self.d_gen = self.d_seeds = self.d_region = self.d_isdata = None
+        self.draw_sets = []
+        if self.source == 'replay':
+            return
+        if self.source == 'pcg64':
+            self.d_gen = torch.as_tensor(eng.pack_pcg64_states(list(self.rngs)).view(np.int64)).to(dev)
+        else:
+            self.d_seeds = torch.as_tensor(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in philox_seeds], dtype=np.uint64).view(np.int64)).to(dev)
+        if chain.update_in_region:
+            self.d_region = torch.as_tensor(np.ascontiguousarray(chain.region_mask == 1, dtype=np.uint8)).to(dev)
+        self.d_isdata = torch.as_tensor(np.ascontiguousarray(self.cond_is_data, dtype=np.uint8)).to(dev)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        kn = min(self.batch, self.n_iter) * n
+        for _ in range(2 if self.draw_ahead else 1):
+            self.draw_sets.append(dict(win=i32(kn * 4), blk=i32(kn * 4), off=i32(kn), cnt=i32(kn), cells=i32(kn * self.max_cells, 2),
+                                       z=torch.empty(kn * self.max_cells, dtype=torch.float64, device=dev),
+                                       us=torch.empty(kn, dtype=torch.float64, device=dev)))
+
+    # ---- the library calls, each on the stream it is given -----------------------------------------------------------------
+    def qt(self, src, dst, inverse, st):
+        self.eng.call(self.lib.gsm_qt_transform, self.d_q, self.d_ref, self.nq, src, dst, int(src.numel()), int(inverse), stream=st)
+
+    def loss(self, t, st):
+        """loss and thickness-guard flag per chain of the beds t (full grid), on the host"""
+        self.eng.call(self.lib.gsm_sgs_loss, t, self.d_trend, self.d_loss, self.d_bad, stream=st)
+        return self.d_loss.cpu().numpy().copy(), self.d_bad.cpu().numpy().copy()
+
+    def check(self, st):
+        self.eng.call(self.lib.gsm_sgs_check, stream=st)
+
+    def draw(self, it0, kb, bs, st):
+        """the device draws of iterations it0 .. it0 + kb - 1 into the buffer set bs"""
+        d, ch = self.views(bs, kb), self.chain
+        args = (kb, self.d_region, self.d_isdata, int(ch.block_min_x), int(ch.block_max_x), int(ch.block_min_y), int(ch.block_max_y),
+                self.max_cells, d.win, d.blk, d.off, d.cnt, d.cells, d.z, d.us)
+        if self.source == 'pcg64':
+            self.eng.call(self.lib.gsm_sgs_draw_pcg64, self.d_gen, *args, stream=st)
+        else:
+            self.eng.call(self.lib.gsm_sgs_draw_philox, self.d_seeds, self.philox_iter0 + it0, *args, stream=st)
+        return d
+
+    def views(self, bs, kb):
+        n = self.n
+        return _Draws(win=bs['win'][:kb * n * 4].view(kb, n, 4), blk=bs['blk'][:kb * n * 4].view(kb, n, 4), off=bs['off'][:kb * n].view(kb, n),
+                      cnt=bs['cnt'][:kb * n].view(kb, n), cells=bs['cells'], z=bs['z'], us=bs['us'][:kb * n].view(kb, n),
+                      off_stride=n, cell_base=None)
+
+    def host_draws(self, it0, kb):
+        """the host draws of iterations it0 .. it0 + kb - 1 (block records stored), packed"""
+        d, self.blocks_cache[:, it0:it0 + kb] = host_draws(self.chain, self.rngs, self.cond_is_data, it0, kb, self.n)
+        return d
+
+    def upload(self, d):
+        """packed host draws on the device; the tuple keeps the tensors alive"""
+        import torch
+        up = lambda a: torch.as_tensor(a).to(self.dev)
+        return _Draws(win=up(d['wins']), blk=None, off=up(d['offs']), cnt=None, cells=up(d['cells']), z=up(d['z']), us=up(d['us']),
+                      off_stride=self.n + 1, cell_base=d['bases'])
+
+    def make_batch(self, d, d_lrec, d_arec):
+        """gsm_sgs_batch (include/gsm.h) of the iterations whose draws are d: the loop body of chain_sgs.run (MCMC.py:1741-1822) is
+        issued by ONE gsm_sgs_iterate call."""
+        from ._lib import SgsBatch
+        b = SgsBatch()
+        pv = lambda t: t.data_ptr() if t is not None else None
+        b.cur, b.next, b.proposed = pv(self.cur), pv(self.nxt), pv(self.prop)
+        b.zcond, b.trend = pv(self.d_zcond), pv(self.d_trend)
+        b.qt_quantiles, b.qt_references, b.qt_n = pv(self.d_q), pv(self.d_ref), self.nq
+        b.energy, b.state, b.windowed = pv(self.d_energy), pv(self.d_state), int(self.windowed)
+        b.x_axis, b.y_axis, b.lag_cov = pv(self.d_xs), pv(self.d_ys), pv(self.d_lag)
+        b.windows, b.cell_off, b.cell_cnt, b.cells, b.z, b.u = pv(d.win), pv(d.off), pv(d.cnt), pv(d.cells), pv(d.z), pv(d.us)
+        b.cell_off_stride = d.off_stride
+        if d.cell_base is not None:
+            b.cell_base = d.cell_base.ctypes.data
+        b.resampled, b.loss, b.bad, b.loss_prev, b.accept = pv(self.resampled), pv(self.d_loss), pv(self.d_bad), pv(self.d_lprev), pv(self.d_acc)
+        b.loss_rec, b.acc_rec = pv(d_lrec), pv(d_arec)
+        b.radius, b.sill = self.rad, float(self.vario["sill"])
+        b.lag_mi, b.lag_mj, b.hw, b.num_points, b.max_cells = self.lag_mi, self.lag_mj, self.hw, self.npts, self.max_cells
+        b.grid_finite = int(self.grid_finite)
+        return b
+
+    def iterate(self, d, kb, d_lrec, d_arec, st):
+        """kb iterations on the draws d, decided on the device; losses and accept flags into d_lrec / d_arec [n, kb]"""
+        self.eng.call(self.lib.gsm_sgs_iterate, C.byref(self.make_batch(d, d_lrec, d_arec)), kb, stream=st)
+
+    def simulate(self, d, st):
+        """the blocks of ONE iteration simulated into nxt"""
+        self.eng.call(self.lib.gsm_sgs_blocks_batch, self.nxt, self.d_zcond, d.win, self.d_xs, self.d_ys, self.d_lag, self.lag_mi, self.lag_mj,
+                      self.hw, self.rad, self.npts, float(self.vario["sill"]), d.off, d.cnt, d.cells, d.z, self.max_cells, stream=st)
+
+    # ---- records --------------------------------------------------------------------------------------------------------------
+    def store(self, it0, kb, loss, acc, blocks=None):
+        """the records [n, kb] of iterations it0 .. it0 + kb - 1 (blocks [kb, n, 4] as the device draws record them)"""
+        self.loss_cache[:, it0:it0 + kb] = loss
+        self.step_cache[:, it0:it0 + kb] = acc
+        if blocks is not None:
+            self.blocks_cache[:, it0:it0 + kb] = blocks.transpose(1, 0, 2)
+
+    def beds_on_host(self):
+        return self.bed_host if self.bed_host is not None else self.cur.cpu().numpy()
+
+    def store_bed(self, it):
+        """per-iteration bed and sample-point records (chain_sgs.run, MCMC.py:1814-1822)"""
+        if not (self.keep_all or self.track):
+            return
+        bed_c = self.beds_on_host()
+        if self.keep_all:
+            self.bed_cache[:, it] = bed_c + self.trend if self.trend is not None else bed_c
+        if self.track:
+            for c in range(self.n):
+                self.sample_values[c, :, it] = bed_c[c][self.ij[:, 0], self.ij[:, 1]]
+
+    def progress(self, done):
+        if self.progress_bar is None:
+            return
+        el = time.time() - self.t0
+        print(f"Chain {getattr(self.chain, 'chain_id', 0)} ({str(getattr(self.chain, 'seed', 'Unknown'))[:6]}): "
+              f"{100 * (done - 1) / max(self.n_iter - 1, 1):3.0f}% | it/s: {done / max(el, 1e-9):7.2f} | n: {self.n_iter} | "
+              f"loss: {self.loss_cache[0, done - 1]:.3e} | acc: {self.step_cache[0, :done].sum() / done:.4f}", file=sys.stdout, flush=True)
+
+    def results(self):
+        """the reference's result tuple per chain; in pcg64 mode the generators continue where the device left them, as after NumPy calls"""
+        bed_c = self.beds_on_host()
+        res = self.resampled.cpu().numpy().astype(np.float64)
+        if self.source == 'pcg64':
+            for g, st in zip(self.rngs, self.eng.unpack_pcg64_states(self.d_gen.cpu().numpy().view(np.uint64))):
+                g.bit_generator.state = st
+        out = []
+        for c in range(self.n):
+            last = bed_c[c] + self.trend if self.trend is not None else bed_c[c]
+            tup = (self.bed_cache[c] if self.keep_all else last, self.loss_cache[c].copy(), np.zeros(self.n_iter), self.loss_cache[c],
+                   self.step_cache[c], res[c], self.blocks_cache[c])
+            out.append(tup + (self.sample_values[c],) if self.track else tup)
+        return out
+
+    # ---- driver 1: device draws, batches decided on the device ---------------------------------------------------------------
+    def drive_device_draws(self):
+        """Batch b iterates on the side stream while (two buffer sets) batch b + 1 is drawn on the draw stream; with one set the next
+        draws follow the batch's record download.  kb is 1 with per-iteration bed records."""
+        import torch
+        n, n_iter, batch, dev, sets = self.n, self.n_iter, self.batch, self.dev, self.draw_sets
+        kmax = min(batch, n_iter)
+        b_lrec = torch.empty(n * kmax, dtype=torch.float64, device=dev); b_arec = torch.empty(n * kmax, dtype=torch.uint8, device=dev)
+        main = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(main)
+        draw_st = torch.cuda.Stream(dev) if len(sets) == 2 else side
+        draw_st.wait_stream(main)
+        self.draw(0, kmax, sets[0], draw_st)
+        it_done = n_batch = 0
+        while it_done < n_iter:
+            kb = min(batch, n_iter - it_done)
+            d = self.views(sets[n_batch % len(sets)], kb)
+            d_lrec, d_arec = b_lrec[:n * kb].view(n, kb), b_arec[:n * kb].view(n, kb)
+            side.wait_stream(draw_st)                                  # this batch's draws
+            nxt_kb = min(batch, n_iter - it_done - kb)
+            if nxt_kb > 0 and len(sets) == 2:                          # the other set: the batch that used it is over (its records were downloaded)
+                self.draw(it_done + kb, nxt_kb, sets[(n_batch + 1) % 2], draw_st)
+            self.iterate(d, kb, d_lrec, d_arec, side)
+            self.check(side)
+            with torch.cuda.stream(side):
+                lrec_h, arec_h, blk_h = d_lrec.cpu().numpy(), d_arec.cpu().numpy(), d.blk.cpu().numpy()
+            if nxt_kb > 0 and len(sets) == 1:
+                self.draw(it_done + kb, nxt_kb, sets[0], draw_st)
+            n_batch += 1
+            self.store(it_done, kb, lrec_h, arec_h, blk_h)
+            self.store_bed(it_done)                                    # kb == 1 where there is anything to store
+            it_done += kb
+            if it_done >= n_iter:
+                main.wait_stream(side)
+                main.wait_stream(draw_st)
+            self.progress(it_done)
+
+    # ---- driver 2: host draws, batches decided on the device, pipelined -------------------------------------------------------
+    def drive_host_draw_batches(self):
+        """The host draws of batch b + 1 are made while the device works on batch b (its launches are asynchronous): gsm_sgs_check
+        and the record download of batch b come after the draws of b + 1."""
+        import torch
+        st = torch.cuda.current_stream(self.dev)
+        running = self._launch(self.host_draws(0, min(self.batch, self.n_iter)), st)
+        it_done = running[1]
+        while it_done < self.n_iter:
+            hd = self.host_draws(it_done, min(self.batch, self.n_iter - it_done))      # overlaps the device work of `running`
+            self._finish(running, st)
+            running = self._launch(hd, st)
+            it_done += running[1]
+        self._finish(running, st)
+
+    def _launch(self, hd, st):
+        """one batch of packed host draws uploaded and started; the returned tuple keeps its tensors alive until _finish"""
+        import torch
+        kb, d = hd['kb'], self.upload(hd)
+        d_lrec = torch.empty((self.n, kb), dtype=torch.float64, device=self.dev)
+        d_arec = torch.empty((self.n, kb), dtype=torch.uint8, device=self.dev)
+        self.iterate(d, kb, d_lrec, d_arec, st)
+        return hd['it0'], kb, d, d_lrec, d_arec
+
+    def _finish(self, running, st):
+        it0, kb, _, d_lrec, d_arec = running
+        self.check(st)
+        self.store(it0, kb, d_lrec.cpu().numpy(), d_arec.cpu().numpy())
+        self.progress(it0 + kb)
+
+    # ---- driver 3: one iteration at a time, decided on the host ---------------------------------------------------------------
+    def drive_one_by_one(self):
+        """The loop of chain_sgs.run (MCMC.py:1741-1822) launch by launch: full-grid loss, acceptance test on the host.  The
+        transformer kind picks the three operations around the simulation: to scores, score the proposal, commit."""
+        import torch
+        st = torch.cuda.current_stream(self.dev)
+        to_scores, score_proposal, commit = {None: (self._plain_to_scores, self._plain_score, self._plain_commit),
+                                             'device_qt': (self._qt_to_scores, self._qt_score, self._qt_commit),
+                                             'host_nst': (self._host_to_scores, self._host_score, self._host_commit)}[self.transformer]
+        for it in range(self.n_iter):
+            if self.source == 'replay':
+                hd = self.host_draws(it, 1)
+                d, wins, us = self.upload(hd), hd['wins'][0], hd['us'][0]
+            else:
+                d = self.draw(it, 1, self.draw_sets[0], st)
+                wins, us = d.win.cpu().numpy()[0], d.us.cpu().numpy()[0]
+                self.blocks_cache[:, it] = d.blk.cpu().numpy()[0]
+            to_scores(st)
+            self.simulate(d, st)
+            self.check(st)
+            loss_next, bad = score_proposal(st)
+            loss_next = np.where(bad > 0, np.inf, loss_next)
+            with np.errstate(over='ignore', invalid='ignore'):
+                p_acc = np.where(self.loss_prev > loss_next, 1.0, np.minimum(1.0, np.exp(self.loss_prev - loss_next)))
+            acc = us <= p_acc
+            commit(d, wins, acc, torch.as_tensor(acc.astype(np.uint8)).to(self.dev), st)
+            self.loss_prev = np.where(acc, loss_next, self.loss_prev)
+            self.store(it, 1, self.loss_prev[:, None], acc[:, None])
+            self.store_bed(it)
+            if it % self.info_per_iter == 0 or it == self.n_iter - 1:
+                self.progress(it + 1)
+
+    def _plain_to_scores(self, st):
+        pass                                                            # no transformer: nxt holds the beds themselves
+
+    def _plain_score(self, st):
+        return self.loss(self.nxt, st)
+
+    def _plain_commit(self, d, wins, acc, d_acc, st):
+        self.eng.call(self.lib.gsm_sgs_commit, self.cur, self.nxt, self.resampled, d.win, d_acc, stream=st)
+
+    def _qt_to_scores(self, st):
+        self.qt(self.cur, self.nxt, 0, st)
+
+    def _qt_score(self, st):
+        self.qt(self.nxt, self.prop, 1, st)
+        return self.loss(self.prop, st)
+
+    def _qt_commit(self, d, wins, acc, d_acc, st):
+        self.eng.call(self.lib.gsm_sgs_commit_map, self.cur, self.prop, self.resampled, d.win, d_acc, stream=st)
+
+    def _host_maps(self, fn, beds):
+        return np.stack([fn(beds[c].reshape(-1, 1)).reshape(self.H, self.W) for c in range(self.n)])
+
+    def _host_to_scores(self, st):
+        self.nxt.copy_(self.eng._f64(self._host_maps(self.nst.transform, self.bed_host)))       # the caller's transformer on the whole map (MCMC.py:1766)
+
+    def _host_score(self, st):
+        self.bed_next = self._host_maps(self.nst.inverse_transform, self.nxt.cpu().numpy())        # MCMC.py:1777
+        return self.loss(self.eng._f64(self.bed_next), st)
+
+    def _host_commit(self, d, wins, acc, d_acc, st):
+        for c in np.flatnonzero(acc):
+            self.bed_host[c] = self.bed_next[c]
+            r0, r1, c0, c1 = wins[c]
+            self.resampled[c, r0:r1, c0:c1] += 1
+
+
 def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=100, progress_bar=None, device=None,
                  philox_seeds=None, philox_iter0=0, pcg64=False):
     """n small-scale chains of one template (same static fields, variogram, block sizes) in ONE handle.  rngs: one NumPy
@@ -347,371 +767,25 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
     replay mode (rngs' own PCG64 streams, bit for bit) are made on the device and the generators are left where NumPy would leave
     them.
     Returns (list of result tuples, rngs)."""
-    import torch
-    from .engine import GsmEngine
-    H, W = chain.xx.shape
     n = len(initial_beds)
     if len(rngs) != n:
         raise ValueError('need one random generator per chain')
-    n_iter = int(n_iter)
-    xs, ys, dx, dy = _axes(np.asarray(chain.xx, dtype=np.float64), np.asarray(chain.yy, dtype=np.float64))
-    rad, npts = float(chain.sgs_param[1]), int(chain.sgs_param[0])
-    hw = int(math.ceil(rad / abs(dx)))
-    vario = chain._vario()
-    detrend = bool(chain.detrend_map)
-    trend = np.asarray(chain.trend, dtype=np.float64) if detrend else None
-    nst = chain.nst_trans if chain.do_transform else None
-    cond_c = np.asarray(chain.cond_bed, dtype=np.float64) - trend if detrend else np.asarray(chain.cond_bed, dtype=np.float64).copy()
-    z_cond = nst.transform(cond_c.reshape(-1, 1)).reshape(H, W) if nst is not None else cond_c
-    cond_is_data = ~np.isnan(z_cond)
-    # scikit-learn's QuantileTransformer with normal output and one feature (what the reference's drivers attach,
-    # smallScaleChain_multiprocessing.py:493-496) runs on the device (gsm_qt_transform); any other transformer object is
-    # called on the host once per iteration, where the reference calls it
-    dev_qt = (nst is not None and type(nst).__name__ == 'QuantileTransformer' and getattr(nst, 'output_distribution', None) == 'normal'
-              and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1)
-    host_nst = nst if (nst is not None and not dev_qt) else None
-    track = chain.sample_loc is not None
-    keep_all = not only_save_last_bed
-
-    eng = GsmEngine(H, W, n, device)
+    if pcg64 and philox_seeds is not None:
+        raise ValueError("choose one of philox_seeds / pcg64")
+    if philox_seeds is not None and len(philox_seeds) != n:
+        raise ValueError('need one Philox seed per chain')
+    source = 'pcg64' if pcg64 else 'philox' if philox_seeds is not None else 'replay'
+    run = _SgsRun(chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source, philox_seeds, philox_iter0)
     try:
-        dev = eng.dev
-        eng.set_static(chain.surf, chain.velx, chain.vely, chain.dhdt, chain.smb, None, chain.grounded_ice_mask,
-                       chain.mc_region_mask, chain.resolution, chain.sigma_mc)
-        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        d_xs, d_ys = f64(xs), f64(ys)
-        lag_mi, lag_mj = lag_extents(hw, H, W)
-        d_lag = f64(lag_cov_table(vario, hw, dx, dy, lag_mi, lag_mj))
-        max_cells = min(1024, max(1, (int(chain.block_max_x) - 1) * (int(chain.block_max_y) - 1)))
-        d_zcond = f64(z_cond)
-        d_trend = f64(trend) if detrend else None
-        bed_c = np.stack([np.asarray(b, dtype=np.float64) - trend if detrend else np.asarray(b, dtype=np.float64) for b in initial_beds])
-        cur = f64(bed_c)
-        nxt = cur.clone()
-        if dev_qt:
-            d_q = f64(nst.quantiles_[:, 0]); d_ref = f64(nst.references_); nq = int(d_q.numel())
-            prop = cur.clone()                                   # proposed beds in data space (inverse transform of nxt)
-        def qt(src, dst, inverse):
-            eng._check(lib.gsm_qt_transform(h, _ptr(d_q), _ptr(d_ref), nq, _ptr(src), _ptr(dst), int(src.numel()), int(inverse), eng._stream()))
-        resampled = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
-        d_loss = torch.empty(n, dtype=torch.float64, device=dev)
-        d_bad = torch.empty(n, dtype=torch.int32, device=dev)
-        lib, h = eng.lib, eng.h
-
-        def loss_of(t):
-            eng._check(lib.gsm_sgs_loss(h, _ptr(t), _ptr(d_trend), _ptr(d_loss), _ptr(d_bad), eng._stream()))
-            return d_loss.cpu().numpy().copy(), d_bad.cpu().numpy().copy()
-
-        loss_prev, _ = loss_of(cur)
-        # no transformer: only the block and its one-cell halo change per iteration -> carried squared residuals, windowed loss,
-        # and loss / guard / acceptance test / commit in ONE launch (gsm_sgs_finish); the reference recomputes the whole map
-        # (gsm_sgs_finish keeps block + halo in LDS: 36 x 36 cells; a longer, thinner block takes the whole-map path)
-        windowed = (nst is None and os.environ.get('GSM_SGS_WINDOWED', '1') != '0' and
-                    (int(chain.block_max_x) + 1) * (int(chain.block_max_y) + 1) <= 1296)
-        if windowed:
-            d_energy = torch.empty((n, H, W), dtype=torch.float64, device=dev)
-            d_state = torch.empty((n, 4), dtype=torch.float64, device=dev)
-            eng._check(lib.gsm_sgs_state_init(h, _ptr(cur), _ptr(d_trend), _ptr(d_energy), _ptr(d_state), eng._stream()))
-        loss_cache = np.zeros((n, n_iter)); step_cache = np.zeros((n, n_iter)); blocks_cache = np.full((n, n_iter, 4), np.nan)
-        loss_cache[:, 0] = loss_prev
-        if keep_all:
-            bed_cache = np.zeros((n, n_iter, H, W))
-            bed_cache[:, 0] = bed_c
-        if track:
-            loc = np.asarray(chain.sample_loc)
-            ij = np.zeros(loc.shape, dtype=np.int64)
-            for k in range(loc.shape[0]):
-                i_, j_ = np.where((chain.xx == loc[k, 0]) & (chain.yy == loc[k, 1]))
-                ij[k] = [int(i_[0]), int(j_[0])]
-            sample_values = np.zeros((n, ij.shape[0], n_iter))
-            for c in range(n):
-                sample_values[c, :, 0] = np.asarray(initial_beds[c])[ij[:, 0], ij[:, 1]]
-        t0 = time.time()
-        # Without a normal-score transformer and without per-iteration bed records nothing of an iteration has to come back
-        # to the host before the next one: the draws do not depend on the chain state (chain_sgs.run consumes chain.rng in
-        # the same order whatever is accepted), so a batch of iterations is drawn ahead, uploaded once, and simulated /
-        # scored / decided (gsm_sgs_decide) / committed on the device back to back.
-        philox = philox_seeds is not None
-        if pcg64 and philox:
-            raise ValueError("choose one of philox_seeds / pcg64")
-        from .engine import GsmEngine
-        if pcg64:
-            d_gen = torch.as_tensor(GsmEngine.pack_pcg64_states(list(rngs)).view(np.int64)).to(dev)
-        philox = philox or pcg64          # both draw on the device: same loop below
-        # iterations per gsm_sgs_iterate call: a batch ends with a host round trip (device flag, record download) and restarts the pipeline
-        # of records made ahead -- with few chains 128 instead of 32 iterations per batch is +7 % (4 chains: 66.6 -> 71.0 k chain-iterations/s);
-        # with the chip full it changes nothing and the draw buffers grow with batch x chains
-        batch = int(os.environ.get('GSM_SGS_BATCH', '128' if n <= 64 else '32')) if (host_nst is None and not keep_all and not track) else 1
-        if philox:
-            if not pcg64:
-                if len(philox_seeds) != n:
-                    raise ValueError('need one Philox seed per chain')
-                d_seeds = torch.as_tensor(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in philox_seeds], dtype=np.uint64).view(np.int64)).to(dev)
-            d_region = torch.as_tensor(np.ascontiguousarray(chain.region_mask == 1, dtype=np.uint8)).to(dev) if chain.update_in_region else None
-            d_isdata = torch.as_tensor(np.ascontiguousarray(cond_is_data, dtype=np.uint8)).to(dev)
-        from ._lib import SgsBatch
-
-        def make_batch(d_win, d_off, off_stride, d_cnt, d_cells, d_z, d_us, d_lrec, d_arec, cell_base=None):
-            """gsm_sgs_batch (include/gsm.h) of one batch of iterations: the loop body of chain_sgs.run (MCMC.py:1741-1822) is issued
-            by ONE gsm_sgs_iterate call."""
-            b = SgsBatch()
-            pv = lambda t: t.data_ptr() if t is not None else None
-            b.cur, b.next, b.proposed = pv(cur), pv(nxt), pv(prop) if dev_qt else None
-            b.zcond, b.trend = pv(d_zcond), pv(d_trend)
-            if dev_qt:
-                b.qt_quantiles, b.qt_references, b.qt_n = pv(d_q), pv(d_ref), nq
-            if windowed:
-                b.energy, b.state, b.windowed = pv(d_energy), pv(d_state), 1
-            b.x_axis, b.y_axis, b.lag_cov = pv(d_xs), pv(d_ys), pv(d_lag)
-            b.windows, b.cell_off, b.cell_cnt, b.cells, b.z, b.u = pv(d_win), pv(d_off), pv(d_cnt), pv(d_cells), pv(d_z), pv(d_us)
-            b.cell_off_stride = off_stride
-            if cell_base is not None:
-                b.cell_base = cell_base.ctypes.data
-            b.resampled, b.loss, b.bad, b.loss_prev, b.accept = pv(resampled), pv(d_loss), pv(d_bad), pv(d_lprev), pv(d_acc)
-            b.loss_rec, b.acc_rec = pv(d_lrec), pv(d_arec)
-            b.radius, b.sill = rad, float(vario["sill"])
-            b.lag_mi, b.lag_mj, b.hw, b.num_points, b.max_cells = lag_mi, lag_mj, hw, npts, max_cells
-            b.grid_finite = int(grid_finite)
-            return b
-
-        # no NaN in the beds (and none can appear: every cell of a block is simulated): gsm_sgs_iterate may then make the records of
-        # iteration j + 1 while iteration j is still running (include/gsm.h: grid_finite).  GSM_SGS_OVERLAP=0 turns that off.
-        grid_finite = os.environ.get('GSM_SGS_OVERLAP', '1') != '0' and bool(torch.isfinite(cur).all())
-        it_done = 0
-        if philox and n_iter > 0:
-            i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-            kmax = min(batch, n_iter)
-            # two sets of draw buffers: the draws of batch b + 1 (they depend on the generators only, never on the chains' state) are
-            # made on their own stream while batch b iterates.
-            # Only for few chains (4 chains, pcg64 mode: 38.7 -> 56.2 k chain-iterations/s): with the chip full (256 chains) the draw
-            # kernel fits into the gap where the host downloads a batch's records, and drawing ahead measured 10 % slower (same box)
-            ahead = os.environ.get('GSM_SGS_DRAW_AHEAD', '1' if n <= 64 else '0') != '0'
-            n_sets = 2 if ahead else 1
-            sets = []
-            for _ in range(n_sets):
-                sets.append(dict(win=i32(kmax * n * 4), blk=i32(kmax * n * 4), off=i32(kmax * n), cnt=i32(kmax * n),
-                                 cells=i32(kmax * n * max_cells, 2), z=torch.empty(kmax * n * max_cells, dtype=torch.float64, device=dev),
-                                 us=torch.empty(kmax * n, dtype=torch.float64, device=dev)))
-            b_lrec = torch.empty(n * kmax, dtype=torch.float64, device=dev); b_arec = torch.empty(n * kmax, dtype=torch.uint8, device=dev)
-            d_lprev = f64(loss_prev); d_acc = torch.empty(n, dtype=torch.uint8, device=dev)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            draw_st = torch.cuda.Stream(dev) if n_sets == 2 else side
-            draw_st.wait_stream(torch.cuda.current_stream(dev))
-
-            def views(bs, kb):
-                return (bs['win'][:kb * n * 4].view(kb, n, 4), bs['blk'][:kb * n * 4].view(kb, n, 4), bs['off'][:kb * n].view(kb, n),
-                        bs['cnt'][:kb * n].view(kb, n), bs['us'][:kb * n].view(kb, n))
-
-            def draw(bs, it0, kb):
-                """the draws of iterations it0 .. it0 + kb - 1 into the buffer set bs, on the draw stream"""
-                d_win, d_blk, d_off, d_cnt, d_us = views(bs, kb)
-                with torch.cuda.device(dev), torch.cuda.stream(draw_st):
-                    args = (kb, _ptr(d_region), _ptr(d_isdata), int(chain.block_min_x), int(chain.block_max_x), int(chain.block_min_y),
-                            int(chain.block_max_y), max_cells, _ptr(d_win), _ptr(d_blk), _ptr(d_off), _ptr(d_cnt), _ptr(bs['cells']), _ptr(bs['z']),
-                            _ptr(d_us), draw_st.cuda_stream)
-                    if pcg64:
-                        eng._check(lib.gsm_sgs_draw_pcg64(h, _ptr(d_gen), *args))
-                    else:
-                        eng._check(lib.gsm_sgs_draw_philox(h, _ptr(d_seeds), int(philox_iter0) + it0, *args))
-            if host_nst is None:
-                draw(sets[0], 0, min(batch, n_iter))
-        # (a transformer of another kind than scikit-learn's is called on the host once per iteration: the loop further down)
-        n_batch = 0
-        while philox and host_nst is None and it_done < n_iter:
-            kb = min(batch, n_iter - it_done)
-            bs = sets[n_batch % n_sets]
-            d_win, d_blk, d_off, d_cnt, d_us = views(bs, kb)
-            d_lrec, d_arec = b_lrec[:n * kb].view(n, kb), b_arec[:n * kb].view(n, kb)
-            side.wait_stream(draw_st)                                  # this batch's draws
-            nxt_kb = min(batch, n_iter - it_done - kb)
-            if nxt_kb > 0 and n_sets == 2:
-                draw(sets[(n_batch + 1) % 2], it_done + kb, nxt_kb)   # the other set: the batch that used it is over (its records were downloaded)
-            with torch.cuda.device(dev), torch.cuda.stream(side):
-                bt = make_batch(d_win, d_off, n, d_cnt, bs['cells'], bs['z'], d_us, d_lrec, d_arec)
-                eng._check(lib.gsm_sgs_iterate(h, C.byref(bt), kb, side.cuda_stream))
-                eng._check(lib.gsm_sgs_check(h, side.cuda_stream))
-                lrec_h, arec_h, blk_h = d_lrec.cpu().numpy(), d_arec.cpu().numpy(), d_blk.cpu().numpy()
-            if nxt_kb > 0 and n_sets == 1:
-                draw(sets[0], it_done + kb, nxt_kb)
-            n_batch += 1
-            loss_cache[:, it_done:it_done + kb] = lrec_h
-            step_cache[:, it_done:it_done + kb] = arec_h
-            blocks_cache[:, it_done:it_done + kb] = blk_h.transpose(1, 0, 2)
-            if keep_all or track:                      # per-iteration bed records (chain_sgs.run, MCMC.py:1814-1822): kb == 1 here
-                bed_c = cur.cpu().numpy()
-                if keep_all:
-                    bed_cache[:, it_done] = bed_c + trend if detrend else bed_c
-                if track:
-                    for c in range(n):
-                        sample_values[c, :, it_done] = bed_c[c][ij[:, 0], ij[:, 1]]
-            it_done += kb
-            if it_done >= n_iter:
-                torch.cuda.current_stream(dev).wait_stream(side)
-                torch.cuda.current_stream(dev).wait_stream(draw_st)
-            if progress_bar is not None:
-                el = time.time() - t0
-                print(f"Chain {getattr(chain, 'chain_id', 0)} ({str(getattr(chain, 'seed', 'Unknown'))[:6]}): "
-                      f"{100 * (it_done - 1) / max(n_iter - 1, 1):3.0f}% | it/s: {it_done / max(el, 1e-9):7.2f} | n: {n_iter} | "
-                      f"loss: {loss_cache[0, it_done - 1]:.3e} | acc: {step_cache[0, :it_done].sum() / it_done:.4f}", file=sys.stdout, flush=True)
-        # Replay batches: the host draws of batch b + 1 are made while the device works on batch b (its launches are
-        # asynchronous; gsm_sgs_check and the record download of batch b come after the draws of b + 1).
-        def host_draws(it0, kb):
-            wins = np.empty((kb, n, 4), np.int32); offs = np.zeros((kb, n + 1), np.int32); us = np.empty((kb, n))
-            cells, zs, bases = [], [], np.zeros(kb + 1, np.int64)
-            for c in range(n):                     # per chain in iteration order: each chain owns its generator
-                for j in range(kb):
-                    blk, win, inds, z, us[j, c] = chain._draw_iteration(rngs[c], cond_is_data)
-                    blocks_cache[c, it0 + j] = blk
-                    wins[j, c] = win
-                    cells.append((j, c, inds)); zs.append((j, c, z))
-            cells.sort(key=lambda t: (t[0], t[1])); zs.sort(key=lambda t: (t[0], t[1]))
-            k = 0
-            for j in range(kb):
-                for c in range(n):
-                    offs[j, c + 1] = offs[j, c] + cells[k][2].shape[0]; k += 1
-                bases[j + 1] = bases[j] + offs[j, n]
-            tot = int(bases[kb])
-            cells_all = np.ascontiguousarray(np.concatenate([t[2] for t in cells]) if tot else np.zeros((1, 2), np.int32))
-            z_all = np.concatenate([t[2] for t in zs]) if tot else np.zeros(1)
-            return dict(it0=it0, kb=kb, wins=wins, offs=offs, us=us, bases=bases, cells=cells_all, z=z_all)
-
-        def launch(d):
-            kb, bases = d['kb'], d['bases']
-            d_win = torch.as_tensor(d['wins']).to(dev); d_off = torch.as_tensor(d['offs']).to(dev); d_us = torch.as_tensor(d['us']).to(dev)
-            d_cells = torch.as_tensor(d['cells']).to(dev); d_z = torch.as_tensor(d['z']).to(dev)
-            d_lrec = torch.empty((n, kb), dtype=torch.float64, device=dev); d_arec = torch.empty((n, kb), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                bt = make_batch(d_win, d_off, n + 1, None, d_cells, d_z, d_us, d_lrec, d_arec, cell_base=np.ascontiguousarray(bases, dtype=np.int64))
-                eng._check(lib.gsm_sgs_iterate(h, C.byref(bt), kb, eng._stream()))
-            d['keep'] = (d_win, d_off, d_us, d_cells, d_z)      # alive until the batch is finished
-            d['lrec'], d['arec'] = d_lrec, d_arec
-
-        def finish(d):
-            with torch.cuda.device(dev):
-                eng._check(lib.gsm_sgs_check(h, eng._stream()))
-            it0, kb = d['it0'], d['kb']
-            loss_cache[:, it0:it0 + kb] = d['lrec'].cpu().numpy()
-            step_cache[:, it0:it0 + kb] = d['arec'].cpu().numpy()
-            if progress_bar is not None:
-                done = it0 + kb
-                el = time.time() - t0
-                print(f"Chain {getattr(chain, 'chain_id', 0)} ({str(getattr(chain, 'seed', 'Unknown'))[:6]}): "
-                      f"{100 * (done - 1) / max(n_iter - 1, 1):3.0f}% | it/s: {done / max(el, 1e-9):7.2f} | n: {n_iter} | "
-                      f"loss: {loss_cache[0, done - 1]:.3e} | acc: {step_cache[0, :done].sum() / done:.4f}", file=sys.stdout, flush=True)
-
-        if batch > 1 and it_done < n_iter:
-            d_lprev = f64(loss_prev); d_acc = torch.empty(n, dtype=torch.uint8, device=dev)
-            running = host_draws(0, min(batch, n_iter))
-            launch(running)
-            it_done = running['kb']
-            while it_done < n_iter:
-                nxt_draws = host_draws(it_done, min(batch, n_iter - it_done))      # overlaps the device work of `running`
-                finish(running)
-                launch(nxt_draws)
-                running = nxt_draws
-                it_done += running['kb']
-            finish(running)
-        for it in range(it_done, n_iter):
-            if philox:
-                # device draws of ONE iteration (a host-side transformer sits between the draws and the simulation)
-                bs = sets[0]
-                d_win, d_blk1 = bs['win'][:n * 4].view(n, 4), bs['blk'][:n * 4].view(n, 4)
-                d_off, d_cnt, d_us1, d_cells, d_z = bs['off'][:n], bs['cnt'][:n], bs['us'][:n], bs['cells'], bs['z']
-                with torch.cuda.device(dev):
-                    if pcg64:
-                        eng._check(lib.gsm_sgs_draw_pcg64(h, _ptr(d_gen), 1, _ptr(d_region), _ptr(d_isdata),
-                                                          int(chain.block_min_x), int(chain.block_max_x), int(chain.block_min_y), int(chain.block_max_y),
-                                                          max_cells, _ptr(d_win), _ptr(d_blk1), _ptr(d_off), _ptr(d_cnt), _ptr(d_cells), _ptr(d_z),
-                                                          _ptr(d_us1), eng._stream()))
-                    else:
-                        eng._check(lib.gsm_sgs_draw_philox(h, _ptr(d_seeds), int(philox_iter0) + it, 1, _ptr(d_region), _ptr(d_isdata),
-                                                           int(chain.block_min_x), int(chain.block_max_x), int(chain.block_min_y), int(chain.block_max_y),
-                                                           max_cells, _ptr(d_win), _ptr(d_blk1), _ptr(d_off), _ptr(d_cnt), _ptr(d_cells), _ptr(d_z),
-                                                           _ptr(d_us1), eng._stream()))
-                wins, us = d_win.cpu().numpy(), d_us1.cpu().numpy()
-                blocks_cache[:, it] = d_blk1.cpu().numpy()
-            else:
-                wins = np.empty((n, 4), np.int32); offs = np.zeros(n + 1, np.int32); us = np.empty(n)
-                cells, zs = [], []
-                for c in range(n):
-                    blk, win, inds, z, us[c] = chain._draw_iteration(rngs[c], cond_is_data)
-                    blocks_cache[c, it] = blk
-                    wins[c] = win
-                    cells.append(inds); zs.append(z)
-                    offs[c + 1] = offs[c] + inds.shape[0]
-                d_win = torch.as_tensor(wins).to(dev)
-                d_off = torch.as_tensor(offs).to(dev)
-                d_cnt = None
-                d_cells = torch.as_tensor(np.ascontiguousarray(np.concatenate(cells) if offs[-1] else np.zeros((1, 2), np.int32))).to(dev)
-                d_z = torch.as_tensor(np.concatenate(zs) if offs[-1] else np.zeros(1)).to(dev)
-            if dev_qt:
-                qt(cur, nxt, 0)
-            elif host_nst is not None:
-                # the caller's transformer on the whole map, where the reference calls it (MCMC.py:1766)
-                nxt.copy_(f64(np.stack([nst.transform(bed_c[c].reshape(-1, 1)).reshape(H, W) for c in range(n)])))
-            with torch.cuda.device(dev):
-                eng._check(lib.gsm_sgs_blocks_batch(h, _ptr(nxt), _ptr(d_zcond), _ptr(d_win), _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), lag_mi, lag_mj, hw,
-                                                    rad, npts, float(vario["sill"]), _ptr(d_off), _ptr(d_cnt), _ptr(d_cells), _ptr(d_z), max_cells,
-                                                    eng._stream()))
-                eng._check(lib.gsm_sgs_check(h, eng._stream()))
-            if dev_qt:
-                qt(nxt, prop, 1)
-                loss_next, bad = loss_of(prop)
-            elif host_nst is not None:
-                newsim = nxt.cpu().numpy()
-                bed_next = np.stack([nst.inverse_transform(newsim[c].reshape(-1, 1)).reshape(H, W) for c in range(n)])   # MCMC.py:1777
-                d_next = f64(bed_next)
-                loss_next, bad = loss_of(d_next)
-            else:
-                loss_next, bad = loss_of(nxt)
-            loss_next = np.where(bad > 0, np.inf, loss_next)
-            with np.errstate(over='ignore', invalid='ignore'):
-                p_acc = np.where(loss_prev > loss_next, 1.0, np.minimum(1.0, np.exp(loss_prev - loss_next)))
-            acc = us <= p_acc
-            d_acc = torch.as_tensor(acc.astype(np.uint8)).to(dev)
-            if dev_qt:
-                with torch.cuda.device(dev):
-                    eng._check(lib.gsm_sgs_commit_map(h, _ptr(cur), _ptr(prop), _ptr(resampled), _ptr(d_win), _ptr(d_acc), eng._stream()))
-            elif host_nst is not None:
-                for c in np.flatnonzero(acc):
-                    bed_c[c] = bed_next[c]
-                    r0, r1, c0, c1 = wins[c]
-                    resampled[c, r0:r1, c0:c1] += 1
-            else:
-                with torch.cuda.device(dev):
-                    eng._check(lib.gsm_sgs_commit(h, _ptr(cur), _ptr(nxt), _ptr(resampled), _ptr(d_win), _ptr(d_acc), eng._stream()))
-            loss_prev = np.where(acc, loss_next, loss_prev)
-            loss_cache[:, it] = loss_prev
-            step_cache[:, it] = acc
-            if keep_all or track:
-                if host_nst is None:
-                    bed_c = cur.cpu().numpy()
-                if keep_all:
-                    bed_cache[:, it] = bed_c + trend if detrend else bed_c
-                if track:
-                    for c in range(n):
-                        sample_values[c, :, it] = bed_c[c][ij[:, 0], ij[:, 1]]
-            if progress_bar is not None and (it % max(int(info_per_iter), 1) == 0 or it == n_iter - 1):
-                el = time.time() - t0
-                print(f"Chain {getattr(chain, 'chain_id', 0)} ({str(getattr(chain, 'seed', 'Unknown'))[:6]}): "
-                      f"{100 * it / max(n_iter - 1, 1):3.0f}% | it/s: {(it + 1) / max(el, 1e-9):7.2f} | n: {n_iter} | "
-                      f"loss: {loss_cache[0, it]:.3e} | acc: {step_cache[0, :it + 1].sum() / (it + 1):.4f}", file=sys.stdout, flush=True)
-        if host_nst is None:
-            bed_c = cur.cpu().numpy()
-        res = resampled.cpu().numpy().astype(np.float64)
-        if pcg64:                                  # the generators continue where the device left them, as after NumPy calls
-            for g, st in zip(rngs, GsmEngine.unpack_pcg64_states(d_gen.cpu().numpy().view(np.uint64))):
-                g.bit_generator.state = st
+        if run.source != 'replay' and run.transformer != 'host_nst':
+            run.drive_device_draws()                 # batch is 1 with keep_all / track
+        elif run.source == 'replay' and run.batch > 1:
+            run.drive_host_draw_batches()            # batch is 1 with a host-side transformer, keep_all / track or GSM_SGS_BATCH=1
+        else:
+            run.drive_one_by_one()                   # a host-side transformer in any draw mode; replay with batch 1
+        return run.results(), rngs
     finally:
-        eng.close()
-    out = []
-    for c in range(n):
-        last = bed_c[c] + trend if detrend else bed_c[c]
-        tup = (bed_cache[c] if keep_all else last, loss_cache[c].copy(), np.zeros(n_iter), loss_cache[c], step_cache[c], res[c],
-               blocks_cache[c])
-        out.append(tup + (sample_values[c],) if track else tup)
-    return out, rngs
+        run.close()
 
 
 def init_msc_chain_by_instance(param_dict):

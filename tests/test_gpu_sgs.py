@@ -399,23 +399,31 @@ def test_windowed_iteration_end_equals_the_full_grid_path(monkeypatch):
         assert 0.05 < acc < 0.95
 
 
-def test_philox_mode_keeps_per_iteration_records():
-    """chain_sgs.run's full signature in Philox mode (MCMC.py:1599, :1814-1829): only_save_last_bed=False returns the bed of every
-    iteration, sample locations their values -- the same chain as the last-bed-only run."""
+@pytest.mark.parametrize("mode", ["philox", "replay", "pcg64"])
+def test_philox_mode_keeps_per_iteration_records(mode):
+    """chain_sgs.run's full signature in every draw mode (MCMC.py:1599, :1814-1829): only_save_last_bed=False returns the bed of every
+    iteration, sample locations their values -- the same chain as the last-bed-only run.  Device draws (philox, pcg64): both runs
+    are batches decided on the device (one iteration per batch with records), equal bit for bit.  Replay: the last-bed run is
+    batched and decided on the device, the run with records goes iteration by iteration and is decided on the host -- the pair of
+    test_batched_iterations_equal_one_by_one: accept masks, blocks and the final bed identical, losses equal up to summation order."""
     from mcmc_gpu_amd import synthetic
     n_iter = 60
     outs = []
     for keep in (False, True):
         prob, ch = synthetic.sgs_template(32, transform=True, light=True)
         ch.set_random_generator(rng_seed=4242)
-        ch.set_rng_mode('philox')
+        ch.set_rng_mode(mode)
         if keep:
             loc = np.array([[prob["xx"][5, 7], prob["yy"][5, 7]], [prob["xx"][20, 11], prob["yy"][20, 11]]])
             ch.set_sample_points_locations(loc)
         outs.append(ch.run(n_iter, only_save_last_bed=not keep, info_per_iter=10 ** 9, plot=False, progress_bar=None))
     last, full = outs
     assert len(full) == 8 and full[0].shape == (n_iter, 32, 32)
-    assert np.array_equal(full[4], last[4]) and np.array_equal(full[6], last[6]) and np.array_equal(full[3], last[3])
+    assert np.array_equal(full[4], last[4]) and np.array_equal(full[6], last[6])
+    if mode == "replay":
+        np.testing.assert_allclose(full[3], last[3], rtol=1e-12)
+    else:
+        assert np.array_equal(full[3], last[3])
     assert np.array_equal(full[0][-1], last[0])
     tr = ch.trend if ch.detrend_map else np.zeros((32, 32))
     np.testing.assert_allclose(full[7][0, 1:], full[0][1:, 5, 7] - tr[5, 7], rtol=0, atol=1e-9)      # sample values are detrended beds
@@ -561,6 +569,55 @@ def test_transformer_of_another_class_runs_on_the_host_in_every_draw_mode(mode):
     np.testing.assert_allclose(a[3], b[3], rtol=1e-9)
     np.testing.assert_allclose(a[0], b[0], rtol=0, atol=1e-7)
     assert 0.05 < a[4].mean() < 0.95
+
+
+def test_host_side_transformer_keeps_per_iteration_records():
+    """A transformer of another class than scikit-learn's (called on the host, the chains' state kept there) with
+    only_save_last_bed=False and sample points, host draws: the same chain as its last-bed-only run -- accept mask, blocks and
+    counts identical, the last recorded bed is that run's bed, the bed changes exactly on accepted iterations and the sample values
+    are the detrended recorded beds."""
+    from mcmc_gpu_amd import synthetic
+    n_iter = 40
+    outs = []
+    for keep in (False, True):
+        prob, ch = synthetic.sgs_template(32, transform=True, light=True)
+        ch.set_normal_transformation(_WrappedTransformer(ch.nst_trans), do_transform=True)
+        ch.set_random_generator(rng_seed=2024)
+        ch.set_rng_mode('replay')
+        if keep:
+            ch.set_sample_points_locations(np.array([[prob["xx"][5, 7], prob["yy"][5, 7]], [prob["xx"][20, 11], prob["yy"][20, 11]]]))
+        outs.append(ch.run(n_iter, only_save_last_bed=not keep, info_per_iter=10 ** 9, plot=False, progress_bar=None))
+    last, full = outs
+    assert len(full) == 8 and full[0].shape == (n_iter, 32, 32) and full[7].shape == (2, n_iter)
+    assert np.array_equal(full[4], last[4]) and np.array_equal(full[6], last[6]) and np.array_equal(full[5], last[5])
+    assert np.array_equal(full[0][-1], last[0])
+    assert 0 < full[4].sum() < n_iter
+    moved = np.abs(np.diff(full[0], axis=0)).max(axis=(1, 2)) > 0
+    assert np.array_equal(moved, full[4][1:].astype(bool))
+    np.testing.assert_allclose(full[7][0, 1:], full[0][1:, 5, 7] - ch.trend[5, 7], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(full[7][1, 1:], full[0][1:, 20, 11] - ch.trend[20, 11], rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("mode,batch,percents", [("replay", None, [100]), ("replay", "1", [0, 45, 91, 100]), ("philox", None, [100])])
+def test_progress_lines_of_the_three_iteration_drivers(capsys, monkeypatch, mode, batch, percents):
+    """progress_bar=True, 12 iterations, info_per_iter=5: the batched drivers (host draws; device draws) print one line per batch
+    -- one batch here --, the iteration-by-iteration driver (GSM_SGS_BATCH=1) at iterations 0, 5, 10 and at the last one.  Line
+    counts and percentages as the runner printed them before its loops were split."""
+    import re
+    from mcmc_gpu_amd import synthetic
+    if batch is not None:
+        monkeypatch.setenv("GSM_SGS_BATCH", batch)
+    prob, ch = synthetic.sgs_template(32, transform=False, light=True)
+    ch.set_random_generator(rng_seed=31)
+    ch.set_rng_mode(mode)
+    capsys.readouterr()
+    out = ch.run(12, only_save_last_bed=True, info_per_iter=5, plot=False, progress_bar=True)
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    pat = re.compile(r"^Chain \S+ \(.{1,6}\): +(\d+)% \| it/s: +\d+\.\d\d \| n: 12 \| loss: \d\.\d{3}e[+-]\d+ \| acc: [01]\.\d{4}$")
+    got = [pat.match(ln) for ln in lines]
+    assert all(got), lines
+    assert [int(m.group(1)) for m in got] == percents
+    assert float(lines[-1].split("acc: ")[1]) == pytest.approx(out[4].mean(), abs=5e-5)
 
 
 def test_checkpoint_labels_follow_the_reference_when_n_iter_is_not_a_multiple_of_1000(tmp_path):

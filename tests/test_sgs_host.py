@@ -99,3 +99,29 @@ def test_sgs_function_argument_errors_are_the_references():
         sgs.sgs(xx, yy, np.full(grid.shape, np.nan), vario, seed=1, **kw)      # 2304 cells to simulate: not one block
     full = np.where(np.isnan(grid), 0.0, grid)
     assert np.array_equal(sgs.sgs(xx, yy, full, vario, seed=1, **kw), full)    # nothing to simulate: the grid comes back
+
+
+@pytest.mark.parametrize("kb", [4, 1])
+def test_packed_host_draws_equal_draw_iteration_chain_by_chain(kb):
+    """sgs.host_draws packs kb iterations of n chains for one gsm_sgs_iterate call: every generator is consumed as kb consecutive
+    _draw_iteration calls chain by chain (final states equal), and the packing is iteration-major -- wins / us by [j, c], the
+    cells and normals of (j, c) at cells[bases[j] + offs[j, c] : bases[j] + offs[j, c + 1]]."""
+    g, prob, cfg, ch = sc.setup("a")
+    n, seeds = 3, (11, 12, 13)
+    is_data = ~np.isnan(prob["cond_bed"])
+    rngs = [np.random.default_rng(s) for s in seeds]
+    d, blocks = sgs.host_draws(ch, rngs, is_data, 7, kb, n)
+    assert d["it0"] == 7 and d["kb"] == kb and blocks.shape == (n, kb, 4)
+    assert d["offs"].shape == (kb, n + 1) and d["bases"].shape == (kb + 1,) and d["bases"][0] == 0
+    for c, s in enumerate(seeds):
+        rng = np.random.default_rng(s)
+        for j in range(kb):
+            blk, win, inds, z, u = ch._draw_iteration(rng, is_data)
+            assert np.array_equal(blocks[c, j], blk)
+            assert np.array_equal(d["wins"][j, c], win) and d["us"][j, c] == u
+            lo, hi = d["bases"][j] + d["offs"][j, c], d["bases"][j] + d["offs"][j, c + 1]
+            assert inds.shape[0] > 0 and np.array_equal(d["cells"][lo:hi], inds) and np.array_equal(d["z"][lo:hi], z)
+        assert rngs[c].bit_generator.state == rng.bit_generator.state
+    for j in range(kb):
+        assert d["offs"][j, 0] == 0 and d["offs"][j, n] == d["bases"][j + 1] - d["bases"][j]
+    assert d["cells"].shape == (d["bases"][kb], 2) and d["cells"].dtype == np.int32 and d["z"].shape == (d["bases"][kb],)
