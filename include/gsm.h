@@ -98,6 +98,7 @@ int gsm_set_static(gsm_handle h, const double* surf, const double* velx, const d
 /* Proposal block table: n_sizes (bh, bw) pairs [host] and their edge masks packed back to back [dev],
  * mask i starting at mask_offsets[i] doubles [host, n_sizes entries].  Masks are needed only by the
  * Philox proposal generator; replay mode receives fields that already carry the mask.
+ * A new table drops the factors registered with gsm_set_factors (they belong to the old one): call it again.
  * Replaces: RandField.set_block_sizes / set_weight_param (MCMC.py:524-566, :568-623). */
 int gsm_set_blocks(gsm_handle h, int32_t n_sizes, const int32_t* bh, const int32_t* bw,
                    const double* edge_masks_packed, const int64_t* mask_offsets, void* stream);
@@ -252,6 +253,8 @@ int gsm_cholesky_upper(gsm_handle h, double* a, int32_t n, int64_t ld, double ji
 /* Precomputed factors of the Cholesky proposal generator: for block size i and range class r,
  * factors[i*n_classes + r] [host array of dev pointers] is U = chol(Sigma + jitter I)^T, upper triangular,
  * row-major [Npad][Npad] with Npad = N rounded up to 64 and zero padding.  The matrices stay caller-owned.
+ * Call after gsm_set_blocks, and again after every later gsm_set_blocks (GSM_E_STATE from the generator otherwise).
+ * n_sizes * n_classes <= 4096, else GSM_E_UNSUPPORTED.
  * With rf->generator == GSM_GEN_CHOLESKY, gsm_propose_philox / gsm_run_philox draw f = scale * (L z) * edge_mask
  * (z ~ N(0, I) from Philox, size and range class uniform) instead of the spectral field.
  * The reference has no such generator (README.md:21-23 lists it as future work); this is north_star's. */

@@ -122,6 +122,11 @@ extern "C" int gsm_set_blocks(gsm_handle h, int32_t n_sizes, const int32_t* bh, 
   }
   if (step_lds_bytes(cap) > 160 * 1024)
     return fail(h, GSM_E_UNSUPPORTED, "gsm_set_blocks: (bh+2)*(bw+2) window does not fit the 160 KiB LDS tile");
+  // the factors of gsm_set_factors and the Cholesky generator's scratch belong to the table that is replaced from here on:
+  // one pointer per (size, class) of THAT table, buffers sized by its largest block.  gsm_set_factors is due again.
+  h->d_factors.reset();
+  h->n_classes = 0;
+  for (auto& c : h->chol) c = gsm_context::CholScratch();
   HIPCHK(h, h->d_bh.assign(bh, (size_t)n_sizes, st));
   HIPCHK(h, h->d_bw.assign(bw, (size_t)n_sizes, st));
   if (edge_masks_packed && mask_offsets) {
@@ -345,6 +350,9 @@ extern "C" int gsm_set_factors(gsm_handle h, int32_t n_classes, const double* co
   if (!h) return GSM_E_ARG;
   if (!h->have_blocks) return fail(h, GSM_E_STATE, "gsm_set_factors: call gsm_set_blocks first");
   if (n_classes < 1 || !factors) return fail(h, GSM_E_ARG, "gsm_set_factors: bad argument");
+  if ((int64_t)h->B.n_sizes * n_classes > 4096)      // cz_bucket_kernel keeps its per-group counters in LDS
+    return fail(h, GSM_E_UNSUPPORTED, "gsm_set_factors: at most 4096 (block size, range class) groups, n_sizes * n_classes = " +
+                                      std::to_string((int64_t)h->B.n_sizes * n_classes));
   const int groups = h->B.n_sizes * n_classes;
   for (int g = 0; g < groups; ++g)
     if (!factors[g]) return fail(h, GSM_E_ARG, "gsm_set_factors: NULL factor");

@@ -305,3 +305,102 @@ def test_largeScaleChain_mp_starts_its_own_ranks(tmp_path, monkeypatch):
         for s in seeds:
             assert np.array_equal(np.load(tmp_path / f"one_{mode}" / "LargeScaleChain" / str(s) / "bed_0k.npy"),
                                   np.load(tmp_path / f"two_{mode}" / "LargeScaleChain" / str(s) / "bed_0k.npy"))
+
+
+# ---- C-ABI state and argument errors of the Cholesky generator's setup calls ---------------------------------------------------
+def _chol_engine(n_chains=2):
+    from gpu_common import make_engine
+    rfp = orc.standard_rf_params(model="Exponential")
+    eng, prob, cfg, pairs, masks, _ = make_engine(64, n_chains, rf_params=rfp)
+    rfp.resolution = prob["resolution"]
+    rfp.generator = "cholesky"
+    return eng, prob, rfp
+
+
+def _raises(code, match, fn, *args):
+    from mcmc_gpu_amd._lib import GsmError
+    with pytest.raises(GsmError, match=match) as ei:
+        fn(*args)
+    assert ei.value.code == code
+    return ei.value
+
+
+def test_cholesky_generator_needs_registered_factors():
+    eng, prob, rfp = _chol_engine()
+    _raises(-2, "gsm_propose_philox: call gsm_set_factors first", eng.propose_philox, 4, 0, [1, 2], rfp)
+    eng.set_state(np.stack([prob["bed"]] * 2))
+    _raises(-2, "gsm_run_philox: call gsm_set_factors first", eng.run_philox, 4, 0, [1, 2], rfp)
+    eng.close()
+
+
+def test_set_blocks_drops_the_registered_factors():
+    """The factor pointers are one per (size, class) of the table they were built for: a new table (here one with other sizes
+    and a larger largest block) must not meet them.  Built, replaced, refused, built again, used."""
+    import cholesky_cases as cc
+    import cholesky_oracle as co
+    from mcmc_gpu_amd import cholesky as chol
+    eng, prob, rfp = _chol_engine()
+    chol.build_factors(eng, rfp, n_classes=2)
+    eng.propose_philox(4, 0, [1, 2], rfp)
+    pairs, masks = cc.tile_pairs(), cc.tile_masks()
+    eng.set_blocks(pairs, masks)
+    _raises(-2, "call gsm_set_factors first", eng.propose_philox, 4, 0, [1, 2], rfp)
+    factors = chol.build_factors(eng, rfp, n_classes=1)
+    out = eng.propose_philox(4, 0, [1, 2], rfp)
+    _, cfg, *_ = orc.standard_setup(64)
+    centres = np.flatnonzero(cfg.region_mask.ravel() == 1)
+    for c, s in ((0, 0), (1, 3)):
+        e = co.proposal([1, 2][c], s, rfp, pairs, masks, centres, 64, rfp.resolution, chol.class_varios(rfp, 1))
+        assert int(out["size_idx"][c, s]) == e["size_idx"]
+        N = e["field"].size
+        U = factors[e["size_idx"]].cpu().numpy()[:N, :N]
+        exact = ((U.T @ e["z"]) * e["scale"]) * masks[e["size_idx"]].ravel()
+        np.testing.assert_allclose(out["fields"][c, s, :N].cpu().numpy(), exact, rtol=0, atol=1e-12 * e["scale"])
+    eng.close()
+
+
+def test_set_factors_argument_errors():
+    import ctypes as C
+    import torch
+    eng, prob, rfp = _chol_engine()
+    assert eng.n_sizes == 25
+    U = torch.eye(256, dtype=torch.float64, device=eng.dev)
+    ptrs = (C.c_void_p * 25)(*[U.data_ptr()] * 25)
+    _raises(-1, "gsm_set_factors: bad argument", eng.call, eng.lib.gsm_set_factors, 0, ptrs)
+    _raises(-1, "gsm_set_factors: bad argument", lambda: eng._check(eng.lib.gsm_set_factors(eng.h, 1, None, eng._stream())))
+    holed = (C.c_void_p * 25)(*[U.data_ptr()] * 25)
+    holed[17] = None
+    _raises(-1, "gsm_set_factors: NULL factor", eng.call, eng.lib.gsm_set_factors, 1, holed)
+    # 25 sizes x 164 classes = 4100 groups: more than cz_bucket_kernel's LDS counters hold
+    many = (C.c_void_p * (25 * 164))(*[U.data_ptr()] * (25 * 164))
+    _raises(-4, "at most 4096", eng.call, eng.lib.gsm_set_factors, 164, many)
+    _raises(-2, "call gsm_set_factors first", eng.propose_philox, 4, 0, [1, 2], rfp)      # none of the refused calls registered anything
+    eng.close()
+
+
+def test_cholesky_upper_and_cov_assemble_argument_errors():
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd import cholesky as chol
+    eng, prob, rfp = _chol_engine()
+    A = torch.eye(128, dtype=torch.float64, device=eng.dev)
+    for n, ld in ((0, 128), (96, 128), (128, 120)):
+        _raises(-1, "gsm_cholesky_upper: n must be a positive multiple of 64 and ld >= n", eng.call, eng.lib.gsm_cholesky_upper, A, n, ld, 0.0)
+    _raises(-1, "gsm_cholesky_upper", eng.call, eng.lib.gsm_cholesky_upper, None, 128, 128, 0.0)
+    assert torch.equal(A, torch.eye(128, dtype=torch.float64, device=eng.dev))
+    sigma = torch.zeros((30, 30), dtype=torch.float64, device=eng.dev)
+
+    def assemble(v, ld=30, table=None):
+        vs = chol.vario_struct(v)
+        eng.call(eng.lib.gsm_cov_assemble, 6, 5, 500.0, C.byref(vs), table, sigma, ld)
+
+    _raises(-1, "Matern model needs the host-computed lag table", assemble, chol.make_vario("Matern", 4000.0, 2500.0, s=0.9125))
+    _raises(-1, "ranges and resolution must be > 0", assemble, chol.make_vario("Exponential", 4000.0, 0.0))
+    _raises(-1, "gsm_cov_assemble: bad argument", assemble, chol.make_vario("Exponential", 4000.0, 2500.0), 29)
+    bad = chol.vario_struct(chol.make_vario("Exponential", 4000.0, 2500.0))
+    bad.vtype = 7
+    _raises(-1, "gsm_cov_assemble: unknown vtype", eng.call, eng.lib.gsm_cov_assemble, 6, 5, 500.0, C.byref(bad), None, sigma, 30)
+    assert not sigma.any()                                  # no refused call wrote
+    assemble(chol.make_vario("Exponential", 4000.0, 2500.0))
+    assert float(sigma[0, 0]) == 1.0
+    eng.close()
