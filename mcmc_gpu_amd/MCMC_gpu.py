@@ -809,10 +809,7 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
                 l_b = torch.empty((n_chains, n), dtype=torch.float64, device=dev)
                 a_b = torch.empty((n_chains, n), dtype=torch.uint8, device=dev)
                 if fused:
-                    eng._check(eng.lib.gsm_run_noise(eng.h, n, _ptr(eng.beds), _ptr(eng.energy), _ptr(eng.resampled), _ptr(eng.loss_sum),
-                                                     _ptr(d['size_idx']), _ptr(d['centre']), _ptr(d['u']), _ptr(d['rf_scalars']), C.byref(p),
-                                                     _ptr(d['noise_re']), _ptr(d['noise_im']), _ptr(d['nugget']), stride,
-                                                     _ptr(l_b), _ptr(a_b), eng._stream()))
+                    eng.run_noise(n, d, p, l_b, a_b)
                 else:
                     fl = fields if n == batch else torch.zeros((n_chains, n, stride), dtype=torch.float64, device=dev)
                     eng._check(eng.lib.gsm_spectral_from_noise(eng.h, n_chains * n, _ptr(d['size_idx']), _ptr(d['rf_scalars']), C.byref(p),

@@ -409,6 +409,18 @@ class GsmEngine:
                     u=b["u"].view(self.n_chains, n_steps), rf_scalars=b["rf_scalars"].view(self.n_chains, n_steps, 4),
                     noise_re=b["noise_re"], noise_im=b["noise_im"], nugget=b["nugget"])
 
+    def run_noise(self, n_steps, d, rf, loss, accept):
+        """n_steps Metropolis steps for every chain with synthesis and step in one kernel (gsm_run_noise; block tables on the strip
+        kernels only), on the device draws `d` of draw_pcg64.  loss [n_chains, n_steps] float64 and accept [n_chains, n_steps] uint8
+        are device tensors that receive the results.  Asynchronous on the current stream."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
+        self._check(self.lib.gsm_run_noise(self.h, int(n_steps), _ptr(self.beds), _ptr(self.energy), _ptr(self.resampled), _ptr(self.loss_sum),
+                                           _ptr(d['size_idx']), _ptr(d['centre']), _ptr(d['u']), _ptr(d['rf_scalars']), C.byref(p),
+                                           _ptr(d['noise_re']), _ptr(d['noise_im']), _ptr(d['nugget']), self.field_stride,
+                                           _ptr(loss), _ptr(accept), self._stream()))
+
     def enable_timing(self, on=True):
         self._check(self.lib.gsm_enable_timing(self.h, 1 if on else 0))
 

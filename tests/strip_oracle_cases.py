@@ -8,7 +8,11 @@ as g column groups x sr row strips of n = ceil(wh / sr) rows, n <= kNR = 16:
   125-248: 64 lanes, g 4, sr 2  (block widths stop at kT1S = 128, so g 8 / sr 1 is out of reach).
 Each table's widths lie in one interval; its heights are the tallest the 80 KiB LDS bound of strip_table_ok admits.  Windows
 clip (centres anywhere), so a table also runs the decompositions of narrower windows: every case derives the decomposition of
-each step from its recorded block and centre and asserts how many steps ran the table's own one."""
+each step from its recorded block and centre and asserts how many steps ran the table's own one.
+
+noise_table and noise_every_shape run the 'pcg64' draw mode's kernel -- gsm_run_noise, the NOISE instantiation of
+chain_strip_kernel with the TABMODE 2 / FOLD_CK forms of the DFT stages -- on every table: against the oracle's chains from device
+draws, and shape by shape against gsm_spectral_from_noise + gsm_run_replay (which tests/test_gpu_spectral_shapes.py pins)."""
 import functools
 
 import numpy as np
@@ -262,6 +266,212 @@ def philox_table(name, state, fields_vs_oracle=False):
                 f = p["fields"][c, s, : fbh * fbw].cpu().numpy().reshape(fbh, fbw)
                 np.testing.assert_allclose(f, e["field"], rtol=0, atol=po.field_atol(e))
     eng.close()
+
+
+# ---- 'pcg64' draw mode: gsm_draw_pcg64 + gsm_run_noise ------------------------------------------------------------------------
+
+NOISE_VARIANTS = {"standard": None, "aniso_nugget": ("Exponential", False, 4.0)}      # rf parameters: the table's own, or these
+NOISE_CASES = [(name, "standard") for name in TABLES] + [(name, "aniso_nugget") for name in ("strip_l16", "strip_g4")]
+# Seeds of chain 0 (chain c: + c).  7 as everywhere, but for the variant on strip_g4: with seeds 7 and 8 its deepest own-decomposition
+# strip is 15 rows, not the table's 16 (conditions); seeds 9 and 10 are the next pair that meets every condition.
+NOISE_SEED0 = {("strip_g4", "aniso_nugget"): 9}
+
+
+def noise_seed0(name, variant):
+    return NOISE_SEED0.get((name, variant), 7)
+
+
+@functools.lru_cache(maxsize=None)
+def noise_oracle_outs(name, variant):
+    """The oracle's chains of noise_table (seeds 7 and 8): those of replay_table, or the same with the variant's rf parameters."""
+    if NOISE_VARIANTS[variant] is None:
+        return oracle_outs(name, False)
+    H, W, own, deepest, prob, cfg, pairs, masks, _ = _setup(name)
+    model, iso, nug = NOISE_VARIANTS[variant]
+    rfp = orc.standard_rf_params(model, isotropic=iso, nugget_max=nug)
+    return oracle_chains(prob, cfg, pairs, masks, rfp, N_CHAINS, N_STEPS + 1, seed0=noise_seed0(name, variant))
+
+
+def decision_margin(name, variant):
+    """min |log u - (loss_prev - loss_next)| / loss_prev over the steps of the oracle's chains of noise_table: how far the closest
+    accept decision is from flipping, relative to the loss (the device's losses follow the oracle's within 1e-10 relative).  CPU
+    only: every step is redone with mh_step from the recorded draws, once to learn loss_next, once to decide."""
+    H, W, prob, cfg, pairs, masks, rfp = _noise_rfp(name, variant)
+    worst = np.inf
+    for c, o in enumerate(noise_oracle_outs(name, variant)):
+        bed = orc.chain_initial_bed(prob, c)
+        mc = orc.mc_residual(bed, cfg.surf, cfg.velx, cfg.vely, cfg.dhdt, cfg.smb, cfg.resolution)
+        lp = orc.gaussian_loss(mc, cfg.mc_region_mask, cfg.sigma_mc)[0]
+        tr = o[7]
+        for s, (f, (row, col), u) in enumerate(zip(tr.fields, tr.centre, tr.u)):
+            ln = orc.mh_step(cfg, bed, mc, lp, f, row, col, 0.0)[3]           # u = 0 accepts whatever the loss
+            if np.isfinite(ln):
+                worst = min(worst, abs(np.log(u) - (lp - ln)) / lp)
+            a, bed, mc, lp, _ = orc.mh_step(cfg, bed, mc, lp, f, row, col, u)
+            assert a == bool(o[4][s + 1]) and lp == o[3][s + 1]
+    return worst
+
+
+def _noise_rfp(name, variant):
+    H, W, own, deepest, prob, cfg, pairs, masks, rfp = _setup(name)
+    if NOISE_VARIANTS[variant] is not None:
+        model, iso, nug = NOISE_VARIANTS[variant]
+        rfp = orc.standard_rf_params(model, isotropic=iso, nugget_max=nug)
+    rfp.resolution = prob["resolution"]
+    return H, W, prob, cfg, pairs, masks, rfp
+
+
+def _state_now(eng):
+    return (eng.beds.cpu().numpy().copy(), eng.energy.cpu().numpy().copy(), eng.resampled.cpu().numpy().copy())
+
+
+def _two_calls(eng, p, d, n_steps):
+    """gsm_spectral_from_noise + gsm_run_replay on the device draws d: (loss, accept, the fields as a host array)."""
+    import ctypes as C
+    import torch
+    fl = torch.zeros((eng.n_chains, n_steps, eng.field_stride), dtype=torch.float64, device=eng.dev)
+    eng.call(eng.lib.gsm_spectral_from_noise, eng.n_chains * n_steps, d["size_idx"], d["rf_scalars"], C.byref(p), d["noise_re"], d["noise_im"],
+             d["nugget"], fl, eng.field_stride)
+    loss, acc = eng.run_replay(d["size_idx"].cpu().numpy(), d["centre"].cpu().numpy(), d["u"].cpu().numpy(), fl)
+    return loss, acc, fl.cpu().numpy()
+
+
+def _run_noise(eng, p, d, n_steps):
+    import torch
+    loss = torch.empty((eng.n_chains, n_steps), dtype=torch.float64, device=eng.dev)
+    acc = torch.empty((eng.n_chains, n_steps), dtype=torch.uint8, device=eng.dev)
+    eng.run_noise(n_steps, d, p, loss, acc)
+    torch.cuda.synchronize(eng.dev)
+    return loss.cpu().numpy(), acc.cpu().numpy()
+
+
+def noise_table(name, variant="standard"):
+    """The 'pcg64' draw mode on a table: the generators of the oracle's chains (default_rng(noise_seed0 + c) for the RandField stream
+    and for the chain stream) advanced on the device, gsm_run_noise on those buffers.  The draws equal the oracle's trace exactly; accept
+    masks, blocks and resampled counts are the oracle chain's, losses within 1e-10 relative, final beds within 1e-9 m (the bars of
+    test_gpu_pcg64.test_pcg64_mode_follows_the_reference_chain); gsm_spectral_from_noise + gsm_run_replay from the same initial
+    state give every output bit for bit.
+    Equal accept masks are a fair demand for these seeds: min |log u - (loss_prev - loss_next)| / loss over the 120 steps of a table,
+    recomputed on the CPU from the oracle's chains (decision_margin), is 8.2e-7 on strip_g4, >= 9.6e-6 on the other tables and
+    7.7e-6 / 2.5e-6 on the two variants, against a loss bar of 1e-10.  tests/test_strip_geometry.py keeps it above 1e-7."""
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    H, W, prob, cfg, pairs, masks, rfp = _noise_rfp(name, variant)
+    outs = noise_oracle_outs(name, variant)
+    eng = _engine(H, W, N_CHAINS, cfg, pairs, masks, "f64")
+    p = eng.rf_struct(rfp)
+    beds0 = np.stack([orc.chain_initial_bed(prob, c) for c in range(N_CHAINS)])
+    gens = [np.random.default_rng(seed=noise_seed0(name, variant) + c) for c in range(N_CHAINS)]
+    d_rf = torch.as_tensor(GsmEngine.pack_pcg64_states(gens).view(np.int64)).to(eng.dev)
+    d_ch = torch.as_tensor(GsmEngine.pack_pcg64_states(gens).view(np.int64)).to(eng.dev)
+    d = eng.draw_pcg64(N_STEPS, p, d_rf, d_ch, None)
+    torch.cuda.synchronize(eng.dev)
+    assert (d["nugget"] is not None) == (rfp.nugget_max > 0)
+    si, ce = d["size_idx"].cpu().numpy(), d["centre"].cpu().numpy()
+    for c, o in enumerate(outs):
+        tr = o[7]
+        assert np.array_equal(si[c], tr.size_idx) and np.array_equal(ce[c], np.array(tr.centre)), f"chain {c}: blocks of the device draws"
+        assert np.array_equal(d["u"][c].cpu().numpy(), np.array(tr.u)), f"chain {c}: accept uniforms"
+        assert np.array_equal(d["rf_scalars"][c].cpu().numpy(), np.array(tr.rf_scalars)), f"chain {c}: scale, nugget, ranges"
+
+    loss0 = eng.set_state(beds0)
+    loss, acc = _run_noise(eng, p, d, N_STEPS)
+    st_a = _state_now(eng)
+    blocks = np.concatenate([ce, pairs[1][si][..., None], pairs[0][si][..., None]], axis=-1)
+    worst_l = worst_b = 0.0
+    for c, o in enumerate(outs):
+        assert abs(loss0[c] - o[3][0]) <= 1e-10 * abs(o[3][0])
+        assert np.array_equal(acc[c], o[4][1:].astype(np.uint8)), f"accept mask differs from the oracle chain, chain {c}"
+        assert np.array_equal(blocks[c], o[6][1:]), f"blocks, chain {c}"
+        assert np.array_equal(st_a[2][c].astype(np.float64), o[5]), f"resampled counts, chain {c}"
+        worst_l = max(worst_l, float(np.abs(loss[c] / o[3][1:] - 1).max()))
+        worst_b = max(worst_b, float(np.abs(st_a[0][c] - o[0]).max()))
+    print(f"    {name} {variant}: worst loss deviation {worst_l:.2e} relative, worst bed deviation {worst_b:.2e} m", flush=True)
+    for c, o in enumerate(outs):
+        np.testing.assert_allclose(loss[c], o[3][1:], rtol=1e-10, atol=0)
+        np.testing.assert_allclose(st_a[0][c], o[0], rtol=0, atol=1e-9)
+    conditions(name, blocks, float(acc.mean()))
+
+    eng.set_state(beds0)
+    loss_r, acc_r, _ = _two_calls(eng, p, d, N_STEPS)
+    assert np.array_equal(loss, loss_r) and np.array_equal(acc, acc_r)
+    for x, y in zip(st_a, _state_now(eng)):
+        assert np.array_equal(x, y)
+    eng.close()
+
+
+def every_shape_inputs(name):
+    """noise_every_shape's steps: every size index twice -- a centre that keeps the window and its halo ring inside the grid, then
+    the window clipped against the bottom right corner (3 rows and 2 columns lost, as guard_windows) -- with host draws in the
+    reference's order (mcmc_oracle.spectral_draws).  Matern, anisotropic, the ranges tied to the block as in
+    spectral_shape_cases.draws (U(0.15, 0.6) x the shorter side, at least 1.5 cells): with the driver's ranges the 8-cell sides
+    of strip_g4 have an all-DC spectrum, where the flat bar proves nothing.  No nugget: beside a scale of 1e-3 the rounding of the
+    sum with a nugget plane of order 1 would exceed 1e-12 x scale in the reference itself (noise_table's variant has the nugget)."""
+    import spectral_shape_cases as ssc
+    H, W, own, deepest, prob, cfg, pairs, _, _ = _setup(name)
+    res = prob["resolution"]
+    n = pairs.shape[1]
+    rng = np.random.default_rng(4242)
+    si, ce, ds = [], [], []
+    for i in range(n):
+        bw, bh = int(pairs[0, i]), int(pairs[1, i])
+        lo, hi = (max(f * min(bh, bw) * res, 1.5 * res) for f in (0.15, 0.6))
+        rfp = orc.RFParams(lo, hi, lo, hi, 50, 150, 0.0, "Matern", False, ssc.NU)
+        for row, col, want_interior in ((H // 2, W // 2, True), (H - bh // 2 + 3, W - bw // 2 + 2, False)):
+            assert window(row, col, bh, bw, H, W)[4] == want_interior and 0 <= row < H and 0 <= col < W
+            d = orc.spectral_draws(rng, rfp, (bh, bw))
+            d["scale"] = 1e-3
+            si.append(i); ce.append((row, col)); ds.append(d)
+    masks = [ssc.mask1d(int(pairs[1, i]), int(pairs[0, i])) for i in range(n)]
+    rfp = orc.RFParams(0, 0, 0, 0, 0, 0, 0.0, "Matern", False, ssc.NU)
+    rfp.resolution = res
+    return H, W, prob, cfg, pairs, masks, rfp, np.array(si), np.array(ce), ds
+
+
+def noise_every_shape(name):
+    """Every shape of the table through the TABMODE 2 / FOLD_CK code of the chain kernel, with never-zero 1-D edge masks: one chain,
+    2 n_sizes steps, scale 1e-3 and u = 1e-300 so that every step is accepted and every field enters the bed.  gsm_run_noise ==
+    gsm_spectral_from_noise + gsm_run_replay bit for bit (beds, energy, losses, accepts, resampled), and the fields of the two-call
+    path lie within 1e-12 x scale of the oracle -- the bar of tests/test_gpu_spectral_shapes.py."""
+    import torch
+    import spectral_shape_cases as ssc
+    H, W, prob, cfg, pairs, masks, rfp, si, ce, ds = every_shape_inputs(name)
+    n = len(si)
+    eng = _engine(H, W, 1, cfg, pairs, masks, "f64")
+    p = eng.rf_struct(rfp)
+    stride = eng.field_stride
+
+    def pack(key):
+        out = np.zeros((1, n, stride))
+        for s, dd in enumerate(ds):
+            out[0, s, :dd[key].size] = dd[key].ravel()
+        return eng._f64(out)
+
+    d = dict(size_idx=torch.as_tensor(si.astype(np.int32)[None]).to(eng.dev), centre=torch.as_tensor(ce.astype(np.int32)[None]).to(eng.dev),
+             u=eng._f64(np.full((1, n), 1e-300)), rf_scalars=eng._f64(np.array([[[x["scale"], x["nug"], x["range_x"], x["range_y"]] for x in ds]])),
+             noise_re=pack("n_re"), noise_im=pack("n_im"), nugget=None)
+    bed0 = orc.chain_initial_bed(prob, 0)[None]
+    eng.set_state(bed0)
+    loss, acc = _run_noise(eng, p, d, n)
+    st_a = _state_now(eng)
+    assert acc.all(), f"steps not accepted: {np.flatnonzero(acc[0] == 0).tolist()}"
+    assert not np.array_equal(st_a[0], bed0)
+    eng.set_state(bed0)
+    loss_r, acc_r, fields = _two_calls(eng, p, d, n)
+    assert np.array_equal(loss, loss_r) and np.array_equal(acc, acc_r)
+    for x, y in zip(st_a, _state_now(eng)):
+        assert np.array_equal(x, y)
+    eng.close()
+    worst = (0.0, None)
+    for s, dd in enumerate(ds):
+        bh, bw = dd["n_re"].shape
+        exp = orc.spectral_from_draws(dict(dd, n_nug=np.zeros((bh, bw))), rfp, (bh, bw), rfp.resolution) * masks[si[s]]
+        err = np.abs(fields[0, s, :bh * bw].reshape(bh, bw) - exp).max() / dd["scale"]
+        if not err <= worst[0]:
+            worst = (err, (bh, bw))
+        assert err <= ssc.BAR, f"{name} step {s}, {bh} x {bw}: max error {err:.3e} x scale"
+        assert not fields[0, s, bh * bw:].any()
+    print(f"    {name}: {n} steps on {n // 2} shapes, all accepted; worst field error {worst[0]:.2e} x scale at {worst[1]}", flush=True)
 
 
 FIELDS_VS_ORACLE = ("strip_l32", "strip_g4")     # 15 stage-2 tiles of the 16 allowed; bh != bw by a factor of 4 to 16

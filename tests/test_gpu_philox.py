@@ -101,7 +101,8 @@ def test_tiny_and_odd_shaped_blocks_match_oracle():
             shapes.add((bh, bw))
             f = out["fields"][c, s, : bh * bw].cpu().numpy().reshape(bh, bw)
             np.testing.assert_allclose(f, e["field"], rtol=0, atol=po.field_atol(e))
-    assert len(shapes) >= 6 and (2, 2) in shapes or len(shapes) >= 6
+    # seeds 3 and 4 draw all nine shapes of the table (philox_oracle, no device needed): the smallest and the two most oblong among them
+    assert len(shapes) >= 6 and {(2, 2), (2, 12), (12, 2)} <= shapes, sorted(shapes)
     eng.close()
 
 

@@ -12,6 +12,10 @@ decomposition has a table whose widths lie in its interval and whose heights are
                     deeper than the 4-slot (wupd, surf) ring of phase A, with an interior and with a clipped window
   philox_table      Philox mode: fused chain kernel == propose + replay == two-kernel pipeline, fp64 and fp32 state; on two
                     tables the proposal fields against the Philox oracle
+  noise_table       'pcg64' mode: gsm_draw_pcg64 + gsm_run_noise against the oracle's chains, and against gsm_spectral_from_noise +
+                    gsm_run_replay bit for bit; on two tables also with an anisotropic Exponential model and a nugget
+  noise_every_shape every shape of the table through the chain kernel's own DFT forms, interior and clipped, never-zero edge masks:
+                    gsm_run_noise == the two calls bit for bit, the two-call fields within 1e-12 x scale of the oracle
 
 Every oracle case asserts what keeps it from passing vacuously (strip_oracle_cases.conditions) and prints the figures.  The
 integer geometry of the decompositions has a host test of its own: tests/test_strip_geometry.py.
@@ -46,3 +50,13 @@ def test_guard_table(name):
 @pytest.mark.parametrize("name", NAMES)
 def test_philox_table(name, state):
     cases.philox_table(name, state, fields_vs_oracle=(state == "f64" and name in cases.FIELDS_VS_ORACLE))
+
+
+@pytest.mark.parametrize("name,variant", cases.NOISE_CASES)
+def test_noise_table(name, variant):
+    cases.noise_table(name, variant)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_noise_every_shape(name):
+    cases.noise_every_shape(name)
