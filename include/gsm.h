@@ -552,7 +552,24 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
  * Errors: GSM_E_ARG for NULL pointers, n_per_seq < 2, n_seq_per_chain not 1 or 2, n_closed outside [0, n_seq_per_chain],
  * seq_stride < n_chains*H*W with two sequences.
  * Replaces: numpy statistics over bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
- * All five are asynchronous on `stream`. */
+ *
+ * gsm_posterior_histogram: one snapshot into per-cell counts over ALL chains, from which quantiles of the bed (to within one
+ * bin width) and probabilities of lying below fixed levels (exactly) follow; moments give neither where the posterior is skewed.
+ * counts [dev, (n_bins + 3 + n_levels)*H*W] int32, slot-major (slot s of a cell at s*H*W + cell), is ADDED to: zero it once,
+ * call once per snapshot; counts of several handles (ranks) add.  Per chain-cell value x = (double)bed, d = x - g[cell] with the
+ * common field g [dev, H*W] fp64, and kf = floor(d * inv_width) + n_bins/2 in double (a product, a floor and a sum: nothing to
+ * contract, so the slot is reproducible in any IEEE arithmetic), compared in double:
+ *   NaN -> slot n_bins + 2;  kf < 0 -> slot 0 (underflow, also -inf);  kf >= n_bins -> slot n_bins + 1 (overflow, also +inf);
+ *   otherwise slot (int)kf + 1: bin k = slot - 1 holds (k - n_bins/2) w <= d < (k + 1 - n_bins/2) w, w = 1 / inv_width (to the product's rounding).
+ * Slots 0 .. n_bins + 2 of a cell therefore sum to the number of values seen.  Slot n_bins + 3 + l counts x < levels[l] (strict;
+ * a NaN is below no level), levels [host, n_levels] absolute heights, read during the call.  n_bins even, 2 <= n_bins <= 128;
+ * 0 <= n_levels <= 8.  Reads the beds only (8 bytes per chain-cell with fp64 state, 4 with fp32) and adds each part's non-zero
+ * counters to `counts` (at most (n_bins + 3 + n_levels) * 4 bytes per cell and part of the chain axis).  Integer sums: the result
+ * does not depend on the order and is bit-reproducible.  The caller keeps a cell's total below 2^31.
+ * Errors: GSM_E_ARG for a NULL beds, g or counts, n_bins odd or outside [2, 128], n_levels outside [0, 8], NULL levels with
+ * n_levels > 0, an inv_width that is not finite and > 0.
+ * Replaces: np.quantile / (bed_cache < level).mean over bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
+ * All six are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -563,6 +580,8 @@ int gsm_posterior_close(gsm_handle h, const void* ref, const double* g, double* 
 int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const double* s1, const double* s2,
                            int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
                            void* stream);
+int gsm_posterior_histogram(gsm_handle h, const void* beds, const double* g, double inv_width, int32_t n_bins, const double* levels,
+                            int32_t n_levels, int32_t* counts, void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

@@ -571,7 +571,7 @@ def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
     g = opt['common_ref'] if opt['common_ref'] is not None else default_common_ref(chain.initial_bed)
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
-                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc)
+                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'])
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -594,7 +594,12 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     running moments on the device, and the call returns (results, PosteriorSummary): mean, sd and split-R-hat maps over all
     chains, and the thinned traces at chain.sample_loc if set_sample_points_locations was called.  `results` is what the call
     returns without `posterior`.  With return_device=True the PosteriorAccumulator is returned in place of the summary (its
-    partials() can be merged over ranks first)."""
+    partials() can be merged over ranks first).
+    posterior['hist']: None, or dict(bins=64, half_width=<metres, required>, levels=()): a per-cell histogram of the same values
+    about `common_ref`, `bins` (even, <= 128) equal bins over [-half_width, half_width) plus underflow, overflow and NaN counts,
+    and for up to 8 absolute `levels` the count of values below each, accumulated on the device at every snapshot that the
+    moments use.  The summary then answers quantile(q), interval(p) (to within one bin width, NaN where the rank leaves the
+    range) and prob_below(l) (exact).  The chains and the moments are bit-identical with and without it."""
     if not isinstance(RF, RandField):
         raise TypeError('The arugment "RF" has to be an object of the class RandField')
     beds = np.asarray(initial_beds, dtype=np.float64)
@@ -603,7 +608,7 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
         raise ValueError('need one seed per chain')
     if posterior is not None:
         from .posterior import check_options
-        posterior = check_options(posterior, n_iter)
+        posterior = check_options(posterior, n_iter, n_chains=n_chains)
     eng = chain._make_engine(RF, n_chains, device)
     accum = None
     try:

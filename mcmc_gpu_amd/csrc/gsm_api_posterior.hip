@@ -1,5 +1,6 @@
-// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip).
+// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip).
 #include "gsm_context.h"
+#include <cmath>
 
 using namespace gsm;
 
@@ -68,6 +69,21 @@ extern "C" int gsm_posterior_close(gsm_handle h, const void* ref, const double* 
   if (h->n_chains > 65535) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_close: more than 65535 chains");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, launch_posterior_close(ref, g, s1, s2, (int64_t)h->H * h->W, h->n_chains, n_per_seq, h->f32_state, (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_histogram(gsm_handle h, const void* beds, const double* g, double inv_width, int32_t n_bins, const double* levels,
+                                       int32_t n_levels, int32_t* counts, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !g || !counts) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: NULL pointer");
+  if (n_bins < 2 || n_bins > kHistMaxBins || n_bins % 2) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: n_bins must be even and in [2, 128]");
+  if (n_levels < 0 || n_levels > kHistMaxLevels) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: n_levels must be in [0, 8]");
+  if (n_levels > 0 && !levels) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: NULL levels with n_levels > 0");
+  if (!(inv_width > 0.0) || !std::isfinite(inv_width)) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: inv_width must be finite and > 0");
+  int rc = posterior_setup(h, 1, 0, nullptr);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_histogram(beds, g, inv_width, n_bins, levels, n_levels, counts, (int64_t)h->H * h->W, h->n_chains, h->f32_state, h->n_cu,
+                                       (hipStream_t)stream));
   return GSM_OK;
 }
 

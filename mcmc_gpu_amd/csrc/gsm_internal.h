@@ -355,6 +355,12 @@ hipError_t launch_posterior_close(const void* ref, const double* g, double* s1, 
                                   int f32_state, hipStream_t st);
 hipError_t launch_posterior_sample(const void* beds, const int32_t* cells, int n_samples, int n_chains, int64_t plane, int f32_state,
                                    double* out, hipStream_t st);
+// posterior_hist_kernel.hip
+constexpr int kHistMaxBins = 128;      // (bins + 4) / 2 KiB of LDS per workgroup
+constexpr int kHistMaxLevels = 8;
+int posterior_hist_parts(int64_t cell_blocks, int n_chains, int n_cu);
+hipError_t launch_posterior_histogram(const void* beds, const double* g, double inv_w, int n_bins, const double* levels, int n_levels,
+                                      int32_t* counts, int64_t plane, int n_chains, int f32_state, int n_cu, hipStream_t st);
 // variogram_kernel.hip
 constexpr int kVariogramMaxLag = 1 << 20;
 int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part

@@ -246,6 +246,21 @@ class GsmEngine:
                                                         int(n_closed), int(n_per_seq), _ptr(out), self._stream()))
         return out
 
+    def posterior_histogram(self, g, inv_width, n_bins, levels, counts):
+        """One snapshot of self.beds ADDED to the per-cell counts [(n_bins + 3 + L), H, W] int32: slot 0 underflow, 1 .. n_bins the
+        bins of floor((bed - g) * inv_width) + n_bins / 2, n_bins + 1 overflow, n_bins + 2 NaN, then one slot per level counting
+        bed < level.  g [H, W] float64 on the device, levels a host sequence of L <= 8 floats.  Asynchronous."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        self._check_sums(self.H * self.W, g=g)
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        n = (int(n_bins) + 3 + lv.size) * self.H * self.W
+        if counts.dtype != torch.int32 or counts.numel() != n or not counts.is_contiguous() or counts.device != self.dev:
+            raise ValueError(f"counts must be a contiguous int32 tensor of {n} elements on {self.dev}")
+        with torch.cuda.device(self.dev):
+            self._check(self.lib.gsm_posterior_histogram(self.h, _ptr(self.beds), _ptr(g), float(inv_width), int(n_bins),
+                                                         lv.ctypes.data if lv.size else None, int(lv.size), _ptr(counts), self._stream()))
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

@@ -105,6 +105,21 @@ def all_reduce_posterior(partials: torch.Tensor, n_local_sequences: int):
     return t, int(m.item())
 
 
+def all_reduce_counts(counts: torch.Tensor) -> torch.Tensor:
+    """Integer counts (the posterior histogram of this rank's chains, posterior.PosteriorAccumulator.hist_counts) summed over
+    ranks: one SUM all-reduce, int64 on the wire so that the total may pass what a rank's int32 holds.  Returns an int64 tensor
+    on the device of `counts`."""
+    t = counts.to(torch.int64)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        if _via_host(t) or not t.is_cuda:
+            h = t.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM)
+            t = h.to(t.device)
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
 def barrier():
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.barrier()

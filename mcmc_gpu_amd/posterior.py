@@ -14,6 +14,10 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               W == 0 (exactly the cells that are constant within every sequence).  A NaN bed value makes its cell NaN everywhere.
   rhat=False  mean and sd only, from sums pooled over the chains: no per-chain storage.
   sample_values[c, p, t]   bed of chain c at sample point p at snapshot t, for all T snapshots (also one that split drops).
+  hist        optional per-cell histogram of the same M*N values about the common field g (gsm_posterior_histogram): `bins` = B
+              equal bins of width w = 2 half_width / B over [g - half_width, g + half_width), an underflow, an overflow and a NaN
+              slot, and per level the count of values below it.  Integer counts, on the device, added over ranks: quantiles to
+              within w (PosteriorSummary.quantile, .interval) and P(bed < level) exactly (.prob_below).
 """
 from __future__ import annotations
 
@@ -63,6 +67,49 @@ class PosteriorSummary:
     split: bool
     sample_values: np.ndarray | None = None
     sample_loc: np.ndarray | None = None
+    # with hist=: counts [B + 3, H, W] int64 (slot 0 underflow, 1 .. B the bins, B + 1 overflow, B + 2 NaN) of the M*N values about
+    # hist_centre = g [H, W], bins of width 2 hist_half_width / B; level_counts [L, H, W] int64: values below level_values [L]
+    hist_counts: np.ndarray | None = None
+    hist_half_width: float | None = None
+    hist_centre: np.ndarray | None = None
+    level_values: np.ndarray | None = None
+    level_counts: np.ndarray | None = None
+
+    def _need_hist(self):
+        if self.hist_counts is None:
+            raise ValueError("this summary holds no histogram: run with posterior=dict(..., hist=dict(half_width=...))")
+        return int(self.hist_counts.shape[0]) - 3, self.n_sequences * self.n_per_sequence
+
+    def prob_below(self, l):
+        """[H, W] share of the M*N values of every cell that lie below level_values[l] (strictly; exact: a ratio of counts)."""
+        _, n = self._need_hist()
+        return np.asarray(self.level_counts)[l] / n
+
+    def quantile(self, q):
+        """[H, W] q-quantile of the M*N values of every cell, 0 < q <= 1, from the histogram: the bin s in which the cumulative
+        count reaches the rank ceil(q n) holds the order statistic of that rank (NumPy's method='inverted_cdf'), and the value
+        returned is placed inside that bin by the share of its count below q n, so it is within one bin width of that order
+        statistic.  NaN where the rank falls into the underflow or the overflow slot and where the cell saw a NaN."""
+        B, n = self._need_hist()
+        q = float(q)
+        if not 0.0 < q <= 1.0:
+            raise ValueError("q must be in (0, 1]")
+        cnt = np.asarray(self.hist_counts, dtype=np.int64)
+        w = 2.0 * float(self.hist_half_width) / B
+        cum = np.cumsum(cnt[:B + 2], axis=0)
+        s = np.argmax(cum >= np.ceil(q * n), axis=0)
+        here = np.take_along_axis(cnt, s[None], axis=0)[0]
+        before = np.take_along_axis(cum, s[None], axis=0)[0] - here
+        with np.errstate(invalid="ignore", divide="ignore"):
+            val = np.asarray(self.hist_centre, dtype=np.float64) + (s - 1 - B // 2) * w + (q * n - before) / here * w
+        return np.where((s == 0) | (s == B + 1) | (cnt[B + 2] != 0), np.nan, val)
+
+    def interval(self, p):
+        """(lower, upper) [H, W] maps of the central credible interval of probability p: quantile((1 - p) / 2), quantile((1 + p) / 2)."""
+        p = float(p)
+        if not 0.0 < p < 1.0:
+            raise ValueError("p must be in (0, 1)")
+        return self.quantile((1.0 - p) / 2.0), self.quantile((1.0 + p) / 2.0)
 
     def save(self, path):
         """One .npz; fields that are None are left out."""
@@ -76,6 +123,8 @@ class PosteriorSummary:
         for k in ("n_chains", "n_sequences", "n_per_sequence", "burn_in", "thin"):
             kw[k] = int(kw[k])
         kw["split"] = bool(kw["split"])
+        if kw["hist_half_width"] is not None:
+            kw["hist_half_width"] = float(kw["hist_half_width"])
         return cls(**kw)
 
 
@@ -111,6 +160,53 @@ def finalize(partials_sum, M, N, common_ref, rhat=True, **meta):
     return PosteriorSummary(mean=mean, sd=sd, rhat=r, within_var=W, between_var_over_n=B_over_N, n_sequences=M, n_per_sequence=N, **meta)
 
 
+HIST_KEYS = ("bins", "half_width", "levels")
+HIST_MAX_BINS, HIST_MAX_LEVELS = 128, 8
+HIST_MAX_COUNT = 2 ** 31 - 1
+
+
+def check_hist(hist):
+    """Validate the `hist` option: None, or dict(bins=64, half_width=<metres, required>, levels=()).  Returns None or the dict
+    with defaults filled in, bins an int, half_width a float and levels a tuple of floats."""
+    if hist is None:
+        return None
+    if not isinstance(hist, dict):
+        raise ValueError("hist must be None or a dict with the keys half_width and optionally bins, levels")
+    unknown = set(hist) - set(HIST_KEYS)
+    if unknown:
+        raise ValueError(f"unknown hist option(s) {sorted(unknown)}; the options are {HIST_KEYS}")
+    if "half_width" not in hist:
+        raise ValueError("hist needs half_width: the histogram spans [g - half_width, g + half_width) metres about the common field")
+    bins = hist.get("bins", 64)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 2 or bins > HIST_MAX_BINS or bins % 2:
+        raise ValueError(f"hist bins must be an even integer in [2, {HIST_MAX_BINS}], got {bins!r}")
+    try:
+        hw = float(hist["half_width"])
+    except (TypeError, ValueError):
+        raise ValueError(f"hist half_width must be a number > 0, got {hist['half_width']!r}") from None
+    if not (hw > 0.0 and np.isfinite(hw)):
+        raise ValueError(f"hist half_width must be finite and > 0, got {hw}")
+    try:
+        levels = tuple(float(v) for v in np.asarray(hist.get("levels", ()), dtype=np.float64).ravel())
+    except (TypeError, ValueError):
+        raise ValueError("hist levels must be a sequence of numbers") from None
+    if len(levels) > HIST_MAX_LEVELS:
+        raise ValueError(f"hist takes at most {HIST_MAX_LEVELS} levels, got {len(levels)}")
+    if not all(np.isfinite(v) for v in levels):
+        raise ValueError("hist levels must be finite")
+    return dict(bins=int(bins), half_width=hw, levels=levels)
+
+
+def check_hist_count(n_chains, n_iter, burn_in, thin, split=True):
+    """Refuse a histogram whose per-cell total, n_chains (of all ranks) x the snapshots that belong to a sequence, does not fit
+    the int32 counters."""
+    _, N, _ = sequence_plan(n_iter, burn_in, thin, split)
+    total = int(n_chains) * N * (2 if split else 1)
+    if total > HIST_MAX_COUNT:
+        raise ValueError(f"hist: {int(n_chains)} chains x {N * (2 if split else 1)} snapshots = {total} values per cell exceed the "
+                         f"int32 counters ({HIST_MAX_COUNT}): thin more or use fewer chains")
+
+
 def default_common_ref(initial_bed):
     """The template chain's initial bed with non-finite cells set to 0: the same on every rank because the template is."""
     g = np.array(initial_bed, dtype=np.float64)
@@ -122,9 +218,10 @@ class PosteriorAccumulator:
     """Running moments of eng.beds over the snapshot schedule of one run.  Owns the torch tensors: with rhat, `ref`
     [n_chains, H, W] in the state dtype (every chain's bed at the first snapshot of the sequence being filled) and 1 + split pairs of [n_chains, H, W] float64 sums (1 + 2 (1 + split) arrays of
     the beds' shape); without, one [H, W] pair.  Call add() when eng.beds holds the next snapshot of the schedule, then
-    partials() (sum it over ranks) and finalize()."""
+    partials() (sum it over ranks) and finalize().  hist (see check_hist): also one int32 tensor `hist_counts` [(B + 3 + L), H, W],
+    to which add() adds the histogram of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_counts)."""
 
-    def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None):
+    def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -132,6 +229,11 @@ class PosteriorAccumulator:
         self.T = int(self.snapshot_iterations.size)
         self.n_seq = 2 if self.split else 1
         H, W, n = eng.H, eng.W, eng.n_chains
+        self.hist = check_hist(hist)
+        if self.hist is not None:
+            check_hist_count(n, n_iter, burn_in, thin, self.split)
+            self.hist_inv_w = self.hist["bins"] / (2 * self.hist["half_width"])
+            self.hist_slots = self.hist["bins"] + 3 + len(self.hist["levels"])
         # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
         g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
         if g.shape != (H, W) or not np.isfinite(g).all():
@@ -147,6 +249,8 @@ class PosteriorAccumulator:
         state_bytes = 8 if eng.state_dtype == torch.float64 else 4
         need = (n * H * W * state_bytes + 2 * self.n_seq * self.seq_stride * 8) if self.rhat else 2 * H * W * 8
         need += self.T * n * self.n_samples * 8
+        if self.hist is not None:
+            need += self.hist_slots * H * W * 4
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
@@ -162,6 +266,7 @@ class PosteriorAccumulator:
             self.s2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
         self.d_cells = None if not self.n_samples else torch.as_tensor(cells).to(dev)
         self.d_samples = None if not self.n_samples else torch.empty((self.T, n, self.n_samples), dtype=torch.float64, device=dev)
+        self.hist_counts = None if self.hist is None else torch.zeros((self.hist_slots, H, W), dtype=torch.int32, device=dev)
         self.n_added = 0
         self._partials = None
 
@@ -189,6 +294,8 @@ class PosteriorAccumulator:
             eng.posterior_accumulate(self.ref, self.s1[k], self.s2[k], first, self.d_cells, smp)
         else:
             eng.posterior_accumulate_pooled(self.d_g, self.s1, self.s2, self.d_cells, smp)
+        if self.hist is not None and t >= self.dropped:      # the values that mean and sd describe, each counted once
+            eng.posterior_histogram(self.d_g, self.hist_inv_w, self.hist["bins"], self.hist["levels"], self.hist_counts)
         self.n_added += 1
         self._partials = None
 
@@ -211,27 +318,43 @@ class PosteriorAccumulator:
         """[n_chains, n_points, T] numpy array of the traces, or None."""
         return None if self.d_samples is None else np.ascontiguousarray(self.d_samples.permute(1, 2, 0).cpu().numpy())
 
-    def finalize(self, partials_sum=None, M=None, sample_values=None):
-        """PosteriorSummary from partials summed over ranks and their sequence count (default: this accumulator's own)."""
+    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None):
+        """PosteriorSummary from partials summed over ranks and their sequence count (default: this accumulator's own);
+        hist_counts: the histogram summed over ranks (all_reduce_counts; default: this accumulator's own)."""
         if partials_sum is None:
             partials_sum, M = self.partials(), self.n_sequences
         M = int(M)
+        meta = {}
+        if self.hist is not None:
+            if self.n_added != self.T:
+                raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
+            hc = self.hist_counts if hist_counts is None else hist_counts
+            hc = np.asarray(hc.detach().cpu().numpy() if hasattr(hc, "detach") else hc).astype(np.int64)
+            if hc.shape != (self.hist_slots,) + self.common_ref.shape:
+                raise ValueError(f"histogram counts of shape {hc.shape}, expected {(self.hist_slots,) + self.common_ref.shape}")
+            B = self.hist["bins"]
+            meta = dict(hist_counts=hc[:B + 3].copy(), hist_half_width=self.hist["half_width"], hist_centre=self.common_ref.copy(),
+                        level_values=np.asarray(self.hist["levels"], dtype=np.float64), level_counts=hc[B + 3:].copy())
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
-                        sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc)
+                        sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist")
 
 
-def check_options(posterior, n_iter):
-    """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in."""
+def check_options(posterior, n_iter, n_chains=None):
+    """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
+    n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None)
     opt.update(posterior)
     sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
+    opt["hist"] = check_hist(opt["hist"])
+    if opt["hist"] is not None and n_chains is not None:
+        check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])
     return opt

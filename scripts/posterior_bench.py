@@ -6,8 +6,12 @@
               after a warm-up; the median and the range are reported.  The bytes are what the algorithm needs, from the shapes.
   end to end  wall time of MCMC_gpu.run_many (Philox mode, results left on the device) without `posterior` and with it at
               several `thin`, rhat on and off: the overhead per snapshot.  The configurations alternate within each repeat.
+  --hist      only the histogram pass (gsm_posterior_histogram, 64 bins, 2 levels) at 1024 chains of 256 x 256, fp64 and fp32
+              state: time per snapshot beside the pooled form and the stream copy of the same bytes, timed in the same process,
+              and its ratio to the pooled form.  The beds are N(g, 1) and the histogram spans g +- 4, so that a part of 256
+              chains fills about fifty bins of every cell: nearly every counter is flushed.  Counted bytes: the beds alone.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick]
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist]
 """
 import argparse
 import json
@@ -88,6 +92,42 @@ def kernel_rows(n_chains, H, W, state, reps):
     return rows
 
 
+def hist_rows(n_chains, H, W, state, reps, bins=64, levels=(1000.0, 999.0)):
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    try:
+        dev, n, sb = eng.dev, n_chains * H * W, 8 if state == "f64" else 4
+        eng.beds = (1000.0 + torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        g = torch.full((H, W), 1000.0, dtype=torch.float64, device=dev)
+        p1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        counts = torch.zeros((bins + 3 + len(levels), H, W), dtype=torch.int32, device=dev)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        po = _rate(f"pooled accumulate {shape}", sb * n, _timed(lambda: eng.posterior_accumulate_pooled(g, p1, p2), reps))
+        m = sb * n // 16
+        src = torch.ones(m, dtype=torch.float64, device=dev)
+        dst = torch.empty(m, dtype=torch.float64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        cp = _rate(f"stream copy of the beds' bytes ({shape})", 16 * m,
+                   _timed(lambda: eng._check(eng.lib.gsm_debug_stream_copy(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st)), reps))
+        inv_w = bins / (2 * 4.0)
+        hi = _rate(f"histogram {bins} bins {len(levels)} levels {shape}", sb * n,
+                   _timed(lambda: eng.posterior_histogram(g, inv_w, bins, levels, counts), reps))
+        hi["ms_per_snapshot"] = hi["ms_median"]
+        hi["ratio_to_pooled"] = hi["ms_median"] / po["ms_median"]
+        hi["fraction_of_copy"] = hi["TB_per_s_median"] / cp["TB_per_s_median"]
+        calls = 3 + reps
+        hi["counts_check"] = bool((counts[:bins + 3].sum(dim=0) == calls * n_chains).all().item())
+        rows = [po, cp, hi]
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
 def end_to_end_rows(H, n_chains, n_iter, thins, repeats):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
@@ -138,11 +178,15 @@ def main():
     ap.add_argument("--quick", action="store_true", help="small shapes: a rehearsal of the script, not a measurement")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--hist", action="store_true", help="only the histogram pass beside the pooled pass and the stream copy")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
     rows = []
-    if args.quick:
+    if args.hist:
+        for state in ("f64", "f32"):
+            rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
+    elif args.quick:
         rows += kernel_rows(8, 64, 64, "f64", 3)
         rows += kernel_rows(8, 64, 64, "f32", 3)
         rows += end_to_end_rows(64, 8, 129, [64, 16], 1)
