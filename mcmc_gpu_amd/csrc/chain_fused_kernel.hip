@@ -23,6 +23,7 @@
 // (tests/test_gpu_philox.py: bit-identical losses, accepts and beds).
 #include "gsm_internal.h"
 #include "device_util.h"
+#include "step_common.h"
 #include "proposal_device.h"
 #include <math.h>
 #include <algorithm>
@@ -45,58 +46,16 @@ size_t fused_lds_doubles(const FusedArgs& a) {
 
 static_assert(sizeof(PropScalars) == 136, "PropScalars: 136-byte records, read field by field with scalar loads");
 
-// The per-step record (propose_scalars_kernel's output) is read through the constant address space: the address is uniform
-// and the memory is never written by this kernel, so every access is a scalar load.  Each phase re-reads the few fields it
-// needs through a laundered pointer instead of keeping the whole record (and everything derived from it) in SGPRs for the
-// whole step -- the kernel has far more uniform values than scalar registers, and a spilled SGPR comes back through
-// v_readlane, a VECTOR instruction (round 1: ~8 % of the vector instructions of a step were such reloads).
-typedef const __attribute__((address_space(4))) PropScalars* crec_t;
-
-// copy of a struct that lives in the constant address space (device pass only: the host pass never runs this code)
-template <class T>
-__device__ __forceinline__ T load_c(const __attribute__((address_space(4))) T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *p;
-#else
-  (void)p;
-  return T();
-#endif
-}
-
-// window of a step, clipped to the grid (MCMC.py:1266-1276), its halo (MCMC.py:1293-1297) and the matching sub-block of f
-struct Win {
-  int r0, r1, c0, c1;      // window rows / cols [r0, r1) x [c0, c1)
-  int mr0, mc0;            // first row / col of the block that lies inside the grid
-  int wh, ww;              // window size
-  int hr0, hc0, hr1, hc1;  // halo tile
-  int tw, ncell;           // tile width, tile cells
-  int dr, dc;              // window origin inside the tile (0 or 1)
-  uint32_t m_tw;           // magic reciprocal of tw
-};
-// m_tw: the magic reciprocal of the tile width, from the step's record (computing it here would be a uniform 32-bit
-// division: a float reciprocal on the vector unit, v_readfirstlane and ~20 dependent scalar instructions)
-__device__ __forceinline__ Win make_win(int H, int W, int row, int col, int bh, int bw, uint32_t m_tw) {
-  Win g;
-  g.r0 = max(0, row - bh / 2); g.r1 = min(H, row + bh / 2);
-  g.c0 = max(0, col - bw / 2); g.c1 = min(W, col + bw / 2);
-  g.mr0 = max(bh - g.r1, 0); g.mc0 = max(bw - g.c1, 0);
-  g.wh = g.r1 - g.r0; g.ww = g.c1 - g.c0;
-  g.hr0 = max(0, g.r0 - 1); g.hr1 = min(H, g.r1 + 1);
-  g.hc0 = max(0, g.c0 - 1); g.hc1 = min(W, g.c1 + 1);
-  g.tw = g.hc1 - g.hc0;
-  g.ncell = (g.hr1 - g.hr0) * g.tw;
-  g.m_tw = m_tw;
-  g.dr = g.r0 - g.hr0; g.dc = g.c0 - g.hc0;
-  return g;
-}
+using step::crec_t;
+using step::load_c;
 
 template <typename TS, int KT, bool FAST_DIV>
 __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa) {
   constexpr bool F32 = sizeof(TS) == 4;
   // The kernel arguments are re-read from the kernarg segment (scalar loads, scalar cache) in every phase through a
   // laundered pointer: read once, they would be loop invariants that the compiler keeps in -- and spills from -- SGPRs.
-  typedef const __attribute__((address_space(4))) FusedArgs* cargs_t;
-  auto kargs = [] { cargs_t p = (cargs_t)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p)); return p; };
+  typedef step::cptr_t<FusedArgs> cargs_t;
+  auto kargs = [] { return step::kargs<FusedArgs>(); };
   extern __shared__ double lds[];
   double* __restrict__ qx = lds;
   double* __restrict__ qy = lds + fa.T.tile_cap;
@@ -134,7 +93,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
   double loss_prev = (s_hi + s_lo) / two_sigma2;
   // window of the previous step if it was accepted (its stores may still be in flight), else empty.  Older stores
   // are complete: vmcnt counts in order and every thread has since waited for younger loads of its own.
-  int pr0 = 0, pr1 = 0, pc0 = 0, pc1 = 0;
+  step::Window prev = {};
 
   const NoiseIn no_noise{nullptr, nullptr, nullptr};
   // the fields of a record the proposal stages use
@@ -156,15 +115,17 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     // costs one v_readlane; re-reading them costs two dependent scalar-memory round trips at the head of every phase).
     const crec_t rec = rec0 + s;
     const int s_row = rec->row, s_col = rec->col, s_bh = rec->bh, s_bw = rec->bw;
+    // m_tw: the magic reciprocal of the tile width (step::halo_tile_width), from the step's record: computing it here would
+    // be a uniform 32-bit division (a float reciprocal on the vector unit, v_readfirstlane and ~20 dependent scalar instructions)
     const uint32_t s_mtw = rec->m_tw;
-    auto win_now = [&] { return make_win(gH, gW, s_row, s_col, s_bh, s_bw, s_mtw); };
-    auto cell = [&](const Win& G, int W, int k, int& i, int& lr, int& lc, uint32_t& g, bool& valid, bool& inwin) {
+    auto win_now = [&] { return step::clip_window(gH, gW, s_row, s_col, s_bh, s_bw); };
+    auto cell = [&](const step::Window& G, const step::HaloTile& T, int W, int k, int& i, int& lr, int& lc, uint32_t& g, bool& valid, bool& inwin) {
       i = ptid + k * kNT;
-      valid = i < G.ncell;
-      lr = (int)__umulhi((uint32_t)i, G.m_tw);
-      lc = i - lr * G.tw;
-      g = (uint32_t)((G.hr0 + lr) * W + G.hc0 + lc);
-      inwin = valid && (unsigned)(lr - G.dr) < (unsigned)G.wh && (unsigned)(lc - G.dc) < (unsigned)G.ww;
+      valid = i < T.ncell;
+      lr = (int)__umulhi((uint32_t)i, s_mtw);
+      lc = i - lr * T.tw;
+      g = (uint32_t)((T.hr0 + lr) * W + T.hc0 + lc);
+      inwin = valid && (unsigned)(lr - T.dr) < (unsigned)G.wh && (unsigned)(lc - T.dc) < (unsigned)G.ww;
     };
 
     // ---- P: DFT tables -> LDS by LDS-DMA (in flight during the coefficient phase), folded coefficients -> LDS planes -----
@@ -184,9 +145,10 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     {
       relaunder();
       const cargs_t K = kargs();
-      const Win G = win_now();
+      const step::Window G = win_now();
+      const step::HaloTile T = step::halo_tile(gH, gW, G);
       // stores of an earlier accepted step must have landed before this step reads an overlapping halo window
-      if ((G.hr0 < pr1) && (pr0 < G.hr1) && (G.hc0 < pc1) && (pc0 < G.hc1)) __syncthreads();
+      if (step::halo_touches(G, prev)) __syncthreads();
       const rsrc_t r_bed = rsrc_bed(K);
       const rsrc_t r_en = rsrc_en(K);
       const int W = gW;
@@ -194,9 +156,9 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       for (int k = 0; k < KT; ++k) {
         // a slot past the end of the tile for the whole wave: no geometry, but the two loads are still issued (out of
         // range, they return 0) so that the counted wait below holds for every wave
-        if (k * kNT + 64 * wave < G.ncell) {
+        if (k * kNT + 64 * wave < T.ncell) {
           int i, lr, lc; uint32_t g; bool valid, inwin;
-          cell(G, W, k, i, lr, lc, g, valid, inwin);
+          cell(G, T, W, k, i, lr, lc, g, valid, inwin);
           vb[k] = StateIO<TS>::load(r_bed, valid ? g * (uint32_t)sizeof(TS) : kOOB);
           ve[k] = StateIO<TS>::load(r_en, inwin ? g * (uint32_t)sizeof(TS) : kOOB);
           rq[k] = (uint32_t)lr | ((uint32_t)lc << 8) | (valid ? 1u << 16 : 0u) | (inwin ? 1u << 17 : 0u);
@@ -257,12 +219,12 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     double2 A2p[KBA], B2p[KBA];
     {
       const cargs_t K = kargs();
-      const Win G = win_now();
+      const step::HaloTile T = step::halo_tile(gH, gW, win_now());
       const rsrc_t r_st = rsrc_st(K);
       const uint32_t off_sB = n_cells(K) * 16u;
 #pragma unroll
       for (int j = 0; j < KBA; ++j) {
-        const uint32_t g = (uint32_t)((G.hr0 + (int)(rq[j] & 0xFFu)) * gW + G.hc0 + (int)((rq[j] >> 8) & 0xFFu));
+        const uint32_t g = (uint32_t)((T.hr0 + (int)(rq[j] & 0xFFu)) * gW + T.hc0 + (int)((rq[j] >> 8) & 0xFFu));
         const bool valid = (rq[j] >> 16) & 1u;
         A2p[j] = ld_f64x2(r_st, valid ? g * 16u : kOOB, 0u);
         B2p[j] = ld_f64x2(r_st, valid ? g * 16u : kOOB, off_sB);
@@ -295,13 +257,14 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     double acc_old = 0.0;
     {
       const cargs_t K = kargs();
-      const Win G = win_now();
+      const step::Window G = win_now();
+      const step::HaloTile T = step::halo_tile(gH, gW, G);
       const int bw = s_bw, W = gW;
       const uint32_t off_sB = n_cells(K) * 16u, off_sC = 2u * off_sB;
-      auto slot_on = [&](int k) { return k * kNT + 64 * wave < G.ncell; };
+      auto slot_on = [&](int k) { return k * kNT + 64 * wave < T.ncell; };
 #pragma unroll
       for (int k = 0; k < KT; ++k) {
-        gq[k] = (uint32_t)((G.hr0 + (int)(rq[k] & 0xFFu)) * W + G.hc0 + (int)((rq[k] >> 8) & 0xFFu));
+        gq[k] = (uint32_t)((T.hr0 + (int)(rq[k] & 0xFFu)) * W + T.hc0 + (int)((rq[k] >> 8) & 0xFFu));
       }
       const rsrc_t r_st = rsrc_st(K);
       constexpr int KB = KBA;                    // cells per sub-batch of phase A (2: +0.8 % over 4, same box)
@@ -321,7 +284,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
               A2[j] = ld_f64x2(r_st, valid ? g * 16u : kOOB, 0u);       // (wupd, surf)
               B2[j] = ld_f64x2(r_st, valid ? g * 16u : kOOB, off_sB);   // (velx, vely)
             }
-            vf[j] = inwin ? fld[(G.mr0 + lr - G.dr) * bw + G.mc0 + lc - G.dc] : 0.0;
+            vf[j] = inwin ? fld[step::field_index(G, T, lr, lc, bw)] : 0.0;
           }
         }
 #pragma unroll
@@ -330,20 +293,14 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
           if (k < KT) {
             int i, lr, lc; uint32_t g; bool valid, inwin;
             cellq(k, i, lr, lc, g, valid, inwin);
-            const bool upd = inwin && (__builtin_bit_cast(uint64_t, A2[j].x) != kNoUpdBits);
-            upd_bits |= upd ? (1u << k) : 0u;
-            double v = vb[k];
-            if (upd) {
-              v = v + vf[j] * A2[j].x;
-              if (F32) v = (double)(float)v;
-            }
-            const double thick = A2[j].y - v;
-            if (upd && thick <= 0.0) guard = 1;
-            v_new[k] = v;
+            const step::Candidate cb = step::candidate_bed<F32>(inwin, vb[k], vf[j], A2[j]);
+            upd_bits |= cb.upd ? (1u << k) : 0u;
+            if (cb.grounded) guard = 1;
+            v_new[k] = cb.v;
             acc_old += ve[k];
             if (valid) {
-              qx[i] = B2[j].x * thick;
-              qy[i] = B2[j].y * thick;
+              qx[i] = B2[j].x * cb.thick;
+              qy[i] = B2[j].y * cb.thick;
             }
           }
         }
@@ -368,16 +325,17 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     launderq();
     {
       const int H = gH, W = gW;
-      const Win G = win_now();
-      const int tw = G.tw, hr0 = G.hr0, hc0 = G.hc0;
-      auto slot_on = [&](int k) { return k * kNT + 64 * wave < G.ncell; };
+      const step::Window G = win_now();
+      const step::HaloTile T = step::halo_tile(gH, gW, G);
+      const int tw = T.tw, hr0 = T.hr0, hc0 = T.hc0;
+      auto slot_on = [&](int k) { return k * kNT + 64 * wave < T.ncell; };
       // interior step (a halo ring on all four sides, ~5 steps in 6): no window cell touches a grid border, every
       // difference is central.  The general form applies np.gradient's one-sided edge rules.
-      const bool interior = (G.hr0 < G.r0) && (G.hr1 > G.r1) && (G.hc0 < G.c0) && (G.hc1 > G.c1);
+      const bool interior = step::interior(H, W, G);
       auto phase_d = [&](auto interior_tag) {
         constexpr bool INTERIOR = decltype(interior_tag)::value;
-        double res = 0.0, rcp_res = 0.0;                                   // border windows only: read where they are needed
-        if (!INTERIOR) { const cargs_t K = kargs(); res = K->T.S.res; rcp_res = K->T.S.rcp_res; }
+        step::StepConsts SC{0.0, 0.0, two_res, rcp_two_res};              // res: border windows only, read where it is needed
+        if (!INTERIOR) { const cargs_t K = kargs(); SC.res = K->T.S.res; SC.rcp_res = K->T.S.rcp_res; }
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
           if (!slot_on(k)) { e_new[k] = 0.0; continue; }
@@ -385,29 +343,15 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
           cellq(k, i, lr, lc, g, valid, inwin);
           double e = 0.0;
           if (inwin) {
-            double dx, dy;
-            if (INTERIOR) {
-              const double ddx = qx[i + 1] - qx[i - 1];
-              const double ddy = qy[i + tw] - qy[i - tw];
-              if (FAST_DIV) { dx = exact_div(ddx, two_res, rcp_two_res); dy = exact_div(ddy, two_res, rcp_two_res); }
-              else { dx = ddx / two_res; dy = ddy / two_res; }
-            } else {
+            int il = i - 1, ir = i + 1, iu = i - tw, id = i + tw;
+            if (!INTERIOR) {
               const int r = hr0 + lr, c = hc0 + lc;
-              const int il = (c == 0) ? i : i - 1, ir = (c == W - 1) ? i : i + 1;
-              const int iu = (r == 0) ? i : i - tw, id = (r == H - 1) ? i : i + tw;
-              const double ddx = qx[ir] - qx[il];
-              const double ddy = qy[id] - qy[iu];
-              if (FAST_DIV) {
-                dx = (ir - il == 2) ? exact_div(ddx, two_res, rcp_two_res) : exact_div(ddx, res, rcp_res);
-                dy = (id - iu == 2 * tw) ? exact_div(ddy, two_res, rcp_two_res) : exact_div(ddy, res, rcp_res);
-              } else {
-                dx = ddx / ((ir - il == 2) ? two_res : res);
-                dy = ddy / ((id - iu == 2 * tw) ? two_res : res);
-              }
+              if (c == 0) il = i;
+              if (c == W - 1) ir = i;
+              if (r == 0) iu = i;
+              if (r == H - 1) id = i;
             }
-            const double v = ((dx + dy) + C2[k].x) - C2[k].y;
-            if (!isnan(v)) e = v * v;
-            if (F32) e = (double)(float)e;
+            e = step::flux_energy<FAST_DIV, F32, INTERIOR>(qx[ir] - qx[il], qy[id] - qy[iu], ir - il == 2, id - iu == 2 * tw, C2[k], SC);
           }
           e_new[k] = e;
           acc_new += e;
@@ -427,22 +371,16 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
     }
     __syncthreads();
     const double sd = row16_sum(red[lane & 15]);
-    double c_hi, c_err;
-    two_sum(s_hi, sd, c_hi, c_err);
-    const double c_lo = s_lo + c_err;
     const cargs_t Ke = kargs();
-    double loss_next = FAST_DIV ? exact_div(c_hi + c_lo, two_sigma2, rcp_two_sigma2) : (c_hi + c_lo) / two_sigma2;
-    if (sd == INFINITY) loss_next = INFINITY;
-    // every thread holds the same numbers: a scalar branch skips the exponential of a downhill step
-    double p_acc = 1.0;
-    if (!__builtin_amdgcn_readfirstlane((int)(loss_prev > loss_next))) p_acc = fmin(1.0, exp(loss_prev - loss_next));
-    const bool acc = (rec->u <= p_acc);
+    double c_hi, c_lo, loss_next;
+    const bool acc = step::decide<FAST_DIV>(sd, sd == INFINITY, s_hi, s_lo, two_sigma2, rcp_two_sigma2, loss_prev, rec->u, c_hi, c_lo, loss_next);
 
     // ---- E: commit -------------------------------------------------------------------------------------
     if (acc) {
       launderq();
-      const Win G = win_now();
-      auto slot_on = [&](int k) { return k * kNT + 64 * wave < G.ncell; };
+      const step::Window G = win_now();
+      const step::HaloTile T = step::halo_tile(gH, gW, G);
+      auto slot_on = [&](int k) { return k * kNT + 64 * wave < T.ncell; };
       const rsrc_t r_bed = rsrc_bed(Ke);
       const rsrc_t r_en = rsrc_en(Ke);
 #pragma unroll
@@ -456,16 +394,13 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       }
       two_sum(c_hi, c_lo, s_hi, s_lo);
       loss_prev = loss_next;
-      pr0 = G.r0; pr1 = G.r1; pc0 = G.c0; pc1 = G.c1;
+      prev = G;
     } else {
-      pr0 = pr1 = pc0 = pc1 = 0;
+      prev = step::Window{};
     }
     if (tid == 0) {
       const StepArgs a = load_c(&Ke->T);
-      const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
-      a.loss[rout] = loss_prev;
-      a.accept[rout] = acc ? 1 : 0;
-      if (a.blocks) { a.blocks[4 * rout] = s_row; a.blocks[4 * rout + 1] = s_col; a.blocks[4 * rout + 2] = s_bh; a.blocks[4 * rout + 3] = s_bw; }
+      step::write_record(a, step::record_index(a, chain, s), loss_prev, acc, s_row, s_col, s_bh, s_bw);
     }
   }
   if (tid == 0) {
@@ -476,20 +411,8 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
 
 template <typename TS, int KT>
 static hipError_t launch_fused_t(const FusedArgs& a, hipStream_t st) {
-  const size_t lds = fused_lds_doubles(a) * sizeof(double);
-  auto kfast = chain_fused_kernel<TS, KT, true>;
-  auto kslow = chain_fused_kernel<TS, KT, false>;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kslow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
-  if (a.T.S.fast_div) hipLaunchKernelGGL(kfast, dim3(a.T.n_chains), dim3(kNT), lds, st, a);
-  else hipLaunchKernelGGL(kslow, dim3(a.T.n_chains), dim3(kNT), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<chain_fused_kernel<TS, KT, true>, chain_fused_kernel<TS, KT, false>>(
+      a.T.S.fast_div, 160 * 1024, dim3(a.T.n_chains), dim3(kNT), fused_lds_doubles(a) * sizeof(double), st, a);
 }
 
 bool fused_supported(const FusedArgs& a) {
@@ -521,9 +444,9 @@ __global__ __launch_bounds__(kRsThreads) void resampled_from_records_kernel(cons
   const uint8_t* __restrict__ acc = fa.T.accept + (int64_t)chain * fa.T.rec_stride + fa.T.rec_offset;
   for (int s = tid; s < fa.T.n_steps; s += kRsThreads) {
     if (!acc[s]) continue;
-    const int row = recs[s].row, col = recs[s].col, bh = recs[s].bh, bw = recs[s].bw;
-    const int r0 = max(band0, max(0, row - bh / 2)), r1 = min(band1, min(H, row + bh / 2));   // window rows within the band
-    const int c0 = max(col0, max(0, col - bw / 2)), c1 = min(col1, min(W, col + bw / 2));
+    const step::Window G = step::clip_window(H, W, recs[s].row, recs[s].col, recs[s].bh, recs[s].bw);
+    const int r0 = max(band0, G.r0), r1 = min(band1, G.r1);   // window rows within the band
+    const int c0 = max(col0, G.c0), c1 = min(col1, G.c1);
     if (c0 >= c1) continue;
     for (int r = r0; r < r1; ++r) {
       atomicAdd(&cnt[(r - band0) * ld + (c0 - col0)], 1);

@@ -61,38 +61,15 @@ bool strip_table_ok(const StaticFields& S, const BlockTable& B, int lds_main, in
          B.max_bh <= kT1S && B.max_bw <= kT1S && (B.masks == nullptr || B.mask1d != nullptr) && lds <= 80 * 1024 && 2 * tiles1_max <= kSW * kSUPW && tiles2_max <= kSW * kSMAXT;
 }
 
-typedef const __attribute__((address_space(4))) PropScalars* srec_t;
-
-template <class T>
-__device__ __forceinline__ T load_cs(const __attribute__((address_space(4))) T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *p;
-#else
-  (void)p;
-  return T();
-#endif
-}
-
-// accept test of a step (MCMC.py:1331-1336) on the carried compensated sum: every thread evaluates the same numbers
-template <bool FAST_DIV>
-__device__ __forceinline__ bool decide(const double sd, const double s_hi, const double s_lo, const double two_sigma2, const double rcp_two_sigma2,
-                                       const double loss_prev, const double u, double& c_hi, double& c_lo, double& loss_next) {
-  double c_err;
-  two_sum(s_hi, sd, c_hi, c_err);
-  c_lo = s_lo + c_err;
-  loss_next = FAST_DIV ? exact_div(c_hi + c_lo, two_sigma2, rcp_two_sigma2) : (c_hi + c_lo) / two_sigma2;
-  if (sd == INFINITY) loss_next = INFINITY;
-  double p_acc = 1.0;
-  if (!__builtin_amdgcn_readfirstlane((int)(loss_prev > loss_next))) p_acc = fmin(1.0, exp(loss_prev - loss_next));
-  return u <= p_acc;
-}
+using step::crec_t;
+using step::load_c;
 
 // NOISE: the coefficients are formed from caller-supplied white-noise planes (the reference's own draws, advanced on the device
 // by gsm_draw_pcg64) instead of Philox draws: gsm_run_noise, the 'pcg64' draw mode with synthesis and step in one kernel.
 template <typename TS, bool FAST_DIV, bool NOISE>
 __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa) {
-  typedef const __attribute__((address_space(4))) FusedArgs* cargs_t;
-  auto kargs = [] { cargs_t p = (cargs_t)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p)); return p; };
+  typedef step::cptr_t<FusedArgs> cargs_t;
+  auto kargs = [] { return step::kargs<FusedArgs>(); };
   extern __shared__ double lds[];                                  // planes -> T^T -> field tile
   double* __restrict__ red = lds + fa.work_len;                    // [16] wave partials of the step (8 used, the rest 0)
   double* __restrict__ red2 = red + 16;                            // [32] proposal reductions, [16] carried sums: s_hi, s_lo, loss_prev
@@ -112,7 +89,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
   const double2* const p_st = fa.T.S.sA;
   const double two_sigma2 = fa.T.S.two_sigma2, rcp_two_sigma2 = fa.T.S.rcp_two_sigma2;
   const uint32_t n_cells = (uint32_t)gH * (uint32_t)gW;
-  const srec_t rec0 = (srec_t)(uintptr_t)(fa.P.scalars + (size_t)chain * fa.P.n_steps);
+  const crec_t rec0 = (crec_t)(uintptr_t)(fa.P.scalars + (size_t)chain * fa.P.n_steps);
   const uint64_t seed = NOISE ? 0ull : fa.P.seeds[chain];
   for (int i = tid; i < kMathTabDoubles; i += kST) mtab[i] = fa.P.mathtab[i];
   if (tid < 16) red[tid] = 0.0;
@@ -126,9 +103,9 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     carry[0] = h0; carry[1] = l0; carry[2] = (h0 + l0) / two_sigma2;
   }
   __syncthreads();
-  int pr0 = 0, pr1 = 0, pc0 = 0, pc1 = 0;      // window of the previous step if it was accepted, else empty
+  step::Window prev = {};                      // window of the previous step if it was accepted, else empty
   const int64_t noise0 = NOISE ? (int64_t)chain * fa.P.n_steps * fa.noise_stride : 0;     // this chain's first record's planes
-  auto prop_rec = [&](srec_t r) {
+  auto prop_rec = [&](crec_t r) {
     PropScalars q;
     q.scale = r->scale; q.nug = r->nug; q.aa = r->aa; q.m_const = r->m_const; q.m_kappa = r->m_kappa;
     q.bh = r->bh; q.bw = r->bw; q.fy_off = r->fy_off; q.g_off = r->g_off; q.pad = r->pad; q.mask_off = r->mask_off;
@@ -140,7 +117,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     int ptid = tid;
     asm volatile("" : "+v"(ptid));
     auto relaunder = [&] { asm volatile("" : "+v"(ptid)); };
-    const srec_t rec = rec0 + s;
+    const crec_t rec = rec0 + s;
     const int s_row = rec->row, s_col = rec->col, s_bh = rec->bh, s_bw = rec->bw;
 
     // ---- P: twiddle tables of this block shape and folded coefficients -> LDS ------------------------------------------------
@@ -157,13 +134,12 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     }
     {
       const cargs_t K = kargs();
-      const ProposeArgs pa = load_cs(&K->P);
+      const ProposeArgs pa = load_c(&K->P);
       const PropScalars q = prop_rec(rec);
       const PropGeom pg = prop_geom(pa, q.bh, q.bw);
       NoiseIn nz{nullptr, nullptr, nullptr};
       if (NOISE) {
-        typedef const __attribute__((address_space(4))) FusedArgs* cfa_t;
-        const cfa_t F = (cfa_t)K;
+        const cargs_t F = K;
         const int64_t o = noise0 + (int64_t)s * F->noise_stride;
         nz.re = F->noise_re + o; nz.im = F->noise_im + o;
       }
@@ -171,24 +147,21 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     }
     // Stores of an accepted step must have landed before a later step reads an overlapping window.  They were issued a
     // whole coefficient phase ago; the wait is free, and the barriers that follow order it across the waves.
-    {
-      const strip::Window G = strip::make_window(gH, gW, s_row, s_col, s_bh, s_bw);
-      if ((G.r0 - 1 < pr1) && (pr0 < G.r0 + G.wh + 1) && (G.c0 - 1 < pc1) && (pc0 < G.c0 + G.ww + 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (step::halo_touches(step::clip_window(gH, gW, s_row, s_col, s_bh, s_bw), prev)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const double dc0 = lds[0];                 // mean of the field = DC coefficient / n; read before T^T overlays the plane
     {
       v4f64 uc[kSUPW], us[kSUPW];
       {
         const cargs_t K = kargs();
-        const ProposeArgs pa = load_cs(&K->P);
+        const ProposeArgs pa = load_c(&K->P);
         const PropScalars q = prop_rec(rec);
         dft_stage1<kSW, kSUPW, 2>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, t1, uc, us);
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has finished reading the planes
       {
         const cargs_t K = kargs();
-        const ProposeArgs pa = load_cs(&K->P);
+        const ProposeArgs pa = load_c(&K->P);
         relaunder();
         dft_tt_write<kSW, kSUPW>(wave, ptid & 63, prop_geom(pa, s_bh, s_bw), lds, uc, us);
       }
@@ -198,7 +171,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     // barrier inside standardise() has been passed) -------------------------------------------------------------------------
     {
       const cargs_t K = kargs();
-      const ProposeArgs pa = load_cs(&K->P);
+      const ProposeArgs pa = load_c(&K->P);
       const PropScalars q = prop_rec(rec);
       const PropGeom pg = prop_geom(pa, q.bh, q.bw);
       const int bw = q.bw;
@@ -210,8 +183,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
       const double gain = standardise<kSW, kSMAXT>(wave, ln, q, pg, dc0, red2, fe, fo, (pa.parseval && !((q.bh | q.bw) & 1)) ? red2 + 16 : nullptr);     // contains a barrier; even shapes: variance from the spectrum
       NoiseIn nz{nullptr, nullptr, nullptr};
       if (NOISE) {
-        typedef const __attribute__((address_space(4))) FusedArgs* cfa_t;
-        const cfa_t F = (cfa_t)K;
+        const cargs_t F = K;
         const double* nb = F->noise_nug;
         if (nb) nz.nug = nb + noise0 + (int64_t)s * F->noise_stride;
       }
@@ -225,6 +197,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     }
     // ---- the step: strip geometry, chain state -> registers, pass, reduce, decide, commit -------------------------------------
     relaunder();
+    const step::Window Gw = step::clip_window(gH, gW, s_row, s_col, s_bh, s_bw);
     const strip::Window G = strip::make_window(gH, gW, s_row, s_col, s_bh, s_bw);
     const strip::Cfg cfg = strip::config(G.wh, G.ww);
     const strip::Lane L = strip::lane_setup(ptid & 63, wave, cfg, G, gH, gW);
@@ -250,7 +223,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     {
       double acc_new;
       const cargs_t K = kargs();
-      const strip::StepConsts SC{K->T.S.res, K->T.S.rcp_res, K->T.S.two_res, K->T.S.rcp_two_res};
+      const step::StepConsts SC{K->T.S.res, K->T.S.rcp_res, K->T.S.two_res, K->T.S.rcp_two_res};
       if (G.interior) strip::phase_d<TS, FAST_DIV, true>(L, cfg.n, gW, s_bw, r_st, n_cells * 16u, SC, lds, en, acc_new);
       else strip::phase_d<TS, FAST_DIV, false>(L, cfg.n, gW, s_bw, r_st, n_cells * 16u, SC, lds, en, acc_new);
       double delta = acc_new - acc_old;
@@ -264,7 +237,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const double sd = strip::waves_sum(red, lane);
     double c_hi, c_lo, loss_next;
-    const bool acc = decide<FAST_DIV>(sd, s_hi, s_lo, two_sigma2, rcp_two_sigma2, loss_prev, rec->u, c_hi, c_lo, loss_next);
+    const bool acc = step::decide<FAST_DIV>(sd, sd == INFINITY, s_hi, s_lo, two_sigma2, rcp_two_sigma2, loss_prev, rec->u, c_hi, c_lo, loss_next);
     if (acc) {
       if (G.interior) strip::commit<TS, true, false>(L, cfg.n, gW, r_bed, r_en, r_en, vn, en, upd_bits);
       else strip::commit<TS, false, false>(L, cfg.n, gW, r_bed, r_en, r_en, vn, en, upd_bits);
@@ -274,17 +247,14 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
         two_sum(c_hi, c_lo, n_hi, n_lo);
         carry[0] = n_hi; carry[1] = n_lo; carry[2] = loss_next;
       }
-      pr0 = G.r0; pr1 = G.r0 + G.wh; pc0 = G.c0; pc1 = G.c0 + G.ww;
+      prev = Gw;
     } else {
-      pr0 = pr1 = pc0 = pc1 = 0;
+      prev = step::Window{};
     }
     if (tid == 0) {
       const cargs_t Ke = kargs();
-      const StepArgs a = load_cs(&Ke->T);
-      const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
-      a.loss[rout] = loss_prev;
-      a.accept[rout] = acc ? 1 : 0;
-      if (a.blocks) { a.blocks[4 * rout] = s_row; a.blocks[4 * rout + 1] = s_col; a.blocks[4 * rout + 2] = s_bh; a.blocks[4 * rout + 3] = s_bw; }
+      const StepArgs a = load_c(&Ke->T);
+      step::write_record(a, step::record_index(a, chain, s), loss_prev, acc, s_row, s_col, s_bh, s_bw);
     }
   }
   if (tid == 0) {                      // thread 0 wrote the sums itself: program order, no barrier needed
@@ -311,38 +281,30 @@ __global__ __launch_bounds__(kST, 4) void step_strip_kernel(const StepArgs a) {
   const rsrc_t r_en = make_rsrc((const TS*)a.energy + (size_t)chain * plane, n_cells * (uint32_t)sizeof(TS));
   const rsrc_t r_rs = make_rsrc(a.resampled + (size_t)chain * plane, n_cells * 4u);
   const rsrc_t r_st = make_rsrc(S.sA, 3u * n_cells * 16u);
-  const strip::StepConsts SC{S.res, S.rcp_res, S.two_res, S.rcp_two_res};
+  const step::StepConsts SC{S.res, S.rcp_res, S.two_res, S.rcp_two_res};
 
   double s_hi = a.loss_sum[2 * chain], s_lo = a.loss_sum[2 * chain + 1];
   double loss_prev = (s_hi + s_lo) / S.two_sigma2;
   for (int i = tid; i < a.B.n_sizes; i += kST) { tab[2 * i] = a.B.bh[i]; tab[2 * i + 1] = a.B.bw[i]; }
   if (tid < 16) red[tid] = 0.0;
   const int64_t rin0 = (int64_t)chain * a.in_stride;
-  int n_si = a.size_idx[rin0], n_row = a.centre[2 * rin0], n_col = a.centre[2 * rin0 + 1];
-  double n_u = a.u[rin0];
+  step::ReplayRec nxt = step::read_replay(a, rin0);
   __syncthreads();
 
   for (int s = 0; s < a.n_steps; ++s) {
     const int64_t rin = rin0 + s;
-    const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
-    const int si = n_si, row = n_row, col = n_col;
-    const double uu = n_u;
+    const int64_t rout = step::record_index(a, chain, s);
+    const step::ReplayRec cur = nxt;
     const bool has_next = s + 1 < a.n_steps;
-    if (has_next) {
-      n_si = a.size_idx[rin + 1]; n_row = a.centre[2 * rin + 2]; n_col = a.centre[2 * rin + 3]; n_u = a.u[rin + 1];
-    }
-    if (si < 0 || si >= a.B.n_sizes || row < 0 || row >= H || col < 0 || col >= W) {
-      if (tid == 0) {
-        atomicExch(a.err_flag, 1);
-        a.loss[rout] = loss_prev;
-        a.accept[rout] = 0;
-        if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = 0; a.blocks[4 * rout + 3] = 0; }
-      }
+    if (has_next) nxt = step::read_replay(a, rin + 1);
+    if (!step::replay_valid(a, cur)) {
+      if (tid == 0) step::reject_record(a, rout, loss_prev, cur);
       continue;  // uniform across the workgroup
     }
-    const int bh = tab[2 * si], bw = tab[2 * si + 1];
+    const int bh = tab[2 * cur.si], bw = tab[2 * cur.si + 1];
     const rsrc_t r_f = make_rsrc(a.fields + rin * a.field_stride, (uint32_t)(bh * bw) * 8u);
-    const strip::Window G = strip::make_window(H, W, row, col, bh, bw);
+    const step::Window Gw = step::clip_window(H, W, cur.row, cur.col, bh, bw);
+    const strip::Window G = strip::make_window(H, W, cur.row, cur.col, bh, bw);
     const strip::Cfg cfg = strip::config(G.wh, G.ww);
     const strip::Lane L = strip::lane_setup(lane, wave, cfg, G, H, W);
     uint32_t upd_bits;
@@ -375,25 +337,18 @@ __global__ __launch_bounds__(kST, 4) void step_strip_kernel(const StepArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const double sd = strip::waves_sum(red, lane);
     double c_hi, c_lo, loss_next;
-    const bool acc = decide<FAST_DIV>(sd, s_hi, s_lo, S.two_sigma2, S.rcp_two_sigma2, loss_prev, uu, c_hi, c_lo, loss_next);
+    const bool acc = step::decide<FAST_DIV>(sd, sd == INFINITY, s_hi, s_lo, S.two_sigma2, S.rcp_two_sigma2, loss_prev, cur.u, c_hi, c_lo, loss_next);
     if (acc) {
       if (G.interior) strip::commit<TS, true, true>(L, cfg.n, W, r_bed, r_en, r_rs, vn, en, upd_bits);
       else strip::commit<TS, false, true>(L, cfg.n, W, r_bed, r_en, r_rs, vn, en, upd_bits);
       two_sum(c_hi, c_lo, s_hi, s_lo);
       loss_prev = loss_next;
     }
-    if (tid == 0) {
-      a.loss[rout] = loss_prev;
-      a.accept[rout] = acc ? 1 : 0;
-      if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = bh; a.blocks[4 * rout + 3] = bw; }
-    }
+    if (tid == 0) step::write_record(a, rout, loss_prev, acc, cur.row, cur.col, bh, bw);
     // End of step: one barrier, so that no wave writes its partial of the next step into `red` while another still reads this
     // step's; where the next halo window touches the window just written, each wave first waits for its own stores.
-    if (acc && has_next && (unsigned)n_si < (unsigned)a.B.n_sizes) {
-      const int nbh = tab[2 * n_si], nbw = tab[2 * n_si + 1];
-      const int nr0 = max(0, n_row - nbh / 2) - 1, nr1 = min(H, n_row + nbh / 2) + 1;
-      const int nc0 = max(0, n_col - nbw / 2) - 1, nc1 = min(W, n_col + nbw / 2) + 1;
-      if ((nr0 < G.r0 + G.wh) && (G.r0 < nr1) && (nc0 < G.c0 + G.ww) && (G.c0 < nc1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (acc && has_next && (unsigned)nxt.si < (unsigned)a.B.n_sizes) {
+      if (step::halo_touches(step::clip_window(H, W, nxt.row, nxt.col, tab[2 * nxt.si], tab[2 * nxt.si + 1]), Gw)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
@@ -405,20 +360,8 @@ __global__ __launch_bounds__(kST, 4) void step_strip_kernel(const StepArgs a) {
 
 template <typename TS>
 static hipError_t launch_step_strip_t(const StepArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)strip_tile_len(a.B) * sizeof(double);
-  auto kfast = step_strip_kernel<TS, true>;
-  auto kslow = step_strip_kernel<TS, false>;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kslow, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
-  if (a.S.fast_div) hipLaunchKernelGGL(kfast, dim3(a.n_chains), dim3(kST), lds, st, a);
-  else hipLaunchKernelGGL(kslow, dim3(a.n_chains), dim3(kST), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<step_strip_kernel<TS, true>, step_strip_kernel<TS, false>>(
+      a.S.fast_div, 80 * 1024, dim3(a.n_chains), dim3(kST), (size_t)strip_tile_len(a.B) * sizeof(double), st, a);
 }
 hipError_t launch_step_strip(const StepArgs& a, hipStream_t st) {
   if (!a.strip) return hipErrorInvalidValue;
@@ -427,20 +370,8 @@ hipError_t launch_step_strip(const StepArgs& a, hipStream_t st) {
 
 template <typename TS, bool NOISE>
 static hipError_t launch_fused_strip_t(const FusedArgs& a, hipStream_t st) {
-  const size_t lds = fused_strip_lds_doubles(a) * sizeof(double);
-  auto kfast = chain_strip_kernel<TS, true, NOISE>;
-  auto kslow = chain_strip_kernel<TS, false, NOISE>;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kslow, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
-  if (a.T.S.fast_div) hipLaunchKernelGGL(kfast, dim3(a.T.n_chains), dim3(kST), lds, st, a);
-  else hipLaunchKernelGGL(kslow, dim3(a.T.n_chains), dim3(kST), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<chain_strip_kernel<TS, true, NOISE>, chain_strip_kernel<TS, false, NOISE>>(
+      a.T.S.fast_div, 80 * 1024, dim3(a.T.n_chains), dim3(kST), fused_strip_lds_doubles(a) * sizeof(double), st, a);
 }
 
 // One launch: propose_scalars_kernel for all steps must have filled a.P.scalars (n_chains x a.P.n_steps records).  The

@@ -51,7 +51,9 @@ template <> struct StateIO<float> {
 
 __device__ __forceinline__ uint32_t magic_for(uint32_t d) { return (uint32_t)(0xFFFFFFFFu / d) + 1u; }
 
-// Correctly rounded x / d from y = RN(1/d) (Markstein); see step_kernel.hip and tests/test_gpu_api.py.
+// Correctly rounded x / d from y = RN(1/d): q0 = RN(x*y), r = x - q0*d (exact in an fma), q = RN(q0 + r*y)
+// (Markstein 1990).  Enabled by the host only when d's significand is not all ones and d is far from the
+// exponent limits; tests/test_host_api.py (test_exact_div_is_correctly_rounded) checks it against exact rational arithmetic.
 __device__ __forceinline__ double exact_div(double x, double d, double y) {
   const double q0 = x * y;
   const double r = __fma_rn(-q0, d, x);

@@ -15,6 +15,22 @@ inline bool attr_needed_on_this_device(bool (&flags)[kMaxDevices], int& dev) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { dev = -1; return true; }
   return !flags[dev];
 }
+// A pair of kernels with more dynamic LDS than the default limit: raise the limit of both to lds_cap once per device (the flags
+// are this instantiation's, i.e. one set per kernel pair), then launch K0 if `first`, else K1.
+template <auto K0, auto K1, class... Args>
+inline hipError_t launch_pair(bool first, int lds_cap, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static bool attr_set[kMaxDevices] = {};
+  int attr_dev;
+  if (attr_needed_on_this_device(attr_set, attr_dev)) {
+    hipError_t e = hipFuncSetAttribute((const void*)K0, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)K1, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);
+    if (e != hipSuccess) return e;
+    if (attr_dev >= 0) attr_set[attr_dev] = true;
+  }
+  if (first) hipLaunchKernelGGL(K0, grid, block, lds, st, args...);
+  else hipLaunchKernelGGL(K1, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
 
 // Static fields shared by every chain of a handle (device pointers, H*W each, row-major).
 struct StaticFields {

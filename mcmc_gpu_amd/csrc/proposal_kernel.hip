@@ -28,6 +28,7 @@
 #include "gsm_internal.h"
 #include "philox.h"
 #include "proposal_device.h"
+#include "step_common.h"
 #include <math.h>
 
 namespace gsm {
@@ -58,9 +59,7 @@ __device__ __forceinline__ void block_shape(PropScalars& r, const ProposeArgs& a
   const int ncol = r.bw / 2 + 1;
   r.m_nc = pmagic((uint32_t)ncol);
   r.m_m1 = pmagic((uint32_t)((ncol + 15) & ~15));
-  // halo tile of the clipped window (make_win in chain_fused_kernel.hip)
-  const int c0 = max(0, r.col - r.bw / 2), c1 = min(a.W, r.col + r.bw / 2);
-  r.m_tw = pmagic((uint32_t)max(1, min(a.W, c1 + 1) - max(0, c0 - 1)));
+  r.m_tw = pmagic((uint32_t)step::halo_tile_width(a.W, r.col, r.bw));   // chain_fused_kernel divides tile cells by it
   r.reserved = 0;
   r.m_bh = pmagic((uint32_t)r.bh); r.m_bw = pmagic((uint32_t)r.bw);
   r.t1h_off = a.t1_off ? a.t1_off[r.bh] : 0;
@@ -208,18 +207,9 @@ hipError_t launch_spectral_from_noise(const ProposeArgs& a, const int32_t* size_
                                       const double* noise_re, const double* noise_im, const double* nugget_field, hipStream_t st) {
   const size_t lds = ((size_t)a.lds_main + 32 + kMathTabDoubles) * sizeof(double);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)spectral_from_noise_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)spectral_from_noise_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
   hipLaunchKernelGGL(noise_scalars_kernel, dim3((unsigned)((a.n_steps + 255) / 256)), dim3(256), 0, st, a, size_idx, rf_scalars);
-  if (wide_table(a)) hipLaunchKernelGGL(spectral_from_noise_kernel<2>, dim3(a.n_steps), dim3(512), lds, st, a, noise_re, noise_im, nugget_field);
-  else hipLaunchKernelGGL(spectral_from_noise_kernel<1>, dim3(a.n_steps), dim3(512), lds, st, a, noise_re, noise_im, nugget_field);
-  return hipGetLastError();
+  return launch_pair<spectral_from_noise_kernel<2>, spectral_from_noise_kernel<1>>(wide_table(a), 160 * 1024, dim3(a.n_steps), dim3(512), lds, st, a,
+                                                                                  noise_re, noise_im, nugget_field);
 }
 
 // test hook (gsm_debug_normals): normals2 exactly as the coefficient phase calls it
@@ -242,20 +232,10 @@ hipError_t launch_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id,
 
 hipError_t launch_propose(const ProposeArgs& a, hipStream_t st) {
   const size_t lds = ((size_t)a.lds_main + 32 + kMathTabDoubles) * sizeof(double);
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)propose_kernel<512, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)propose_kernel<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   const int64_t nrec = (int64_t)a.n_chains * a.n_steps;
   hipLaunchKernelGGL(propose_scalars_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, a);
-  if (wide_table(a)) hipLaunchKernelGGL((propose_kernel<512, 2>), dim3(a.n_steps, a.n_chains), dim3(512), lds, st, a);
-  else hipLaunchKernelGGL((propose_kernel<512, 1>), dim3(a.n_steps, a.n_chains), dim3(512), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<propose_kernel<512, 2>, propose_kernel<512, 1>>(wide_table(a), 160 * 1024, dim3(a.n_steps, a.n_chains), dim3(512), lds, st, a);
 }
 
 hipError_t launch_propose_scalars(const ProposeArgs& a, hipStream_t st) {

@@ -25,6 +25,7 @@
 //           E  commit on accept; the stores are waited for only when the next window overlaps this one
 #include "gsm_internal.h"
 #include "device_util.h"
+#include "step_common.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -65,42 +66,26 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
 
   for (int i = tid; i < a.B.n_sizes; i += kNT) { tab[2 * i] = a.B.bh[i]; tab[2 * i + 1] = a.B.bw[i]; }
   const int64_t rin0 = (int64_t)chain * a.in_stride;
-  int n_si = a.size_idx[rin0], n_row = a.centre[2 * rin0], n_col = a.centre[2 * rin0 + 1];
-  double n_u = a.u[rin0];
+  step::ReplayRec nxt = step::read_replay(a, rin0);
   __syncthreads();
 
   for (int s = 0; s < a.n_steps; ++s) {
     const int64_t rin = rin0 + s;
-    const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
-    const int si = n_si, row = n_row, col = n_col;
-    const double uu = n_u;
+    const int64_t rout = step::record_index(a, chain, s);
+    const step::ReplayRec cur = nxt;
     const bool has_next = s + 1 < a.n_steps;
-    if (has_next) {
-      n_si = a.size_idx[rin + 1]; n_row = a.centre[2 * rin + 2]; n_col = a.centre[2 * rin + 3]; n_u = a.u[rin + 1];
-    }
-    if (si < 0 || si >= a.B.n_sizes || row < 0 || row >= H || col < 0 || col >= W) {
-      if (tid == 0) {
-        atomicExch(a.err_flag, 1);
-        a.loss[rout] = loss_prev;
-        a.accept[rout] = 0;
-        if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = 0; a.blocks[4 * rout + 3] = 0; }
-      }
+    if (has_next) nxt = step::read_replay(a, rin + 1);
+    if (!step::replay_valid(a, cur)) {
+      if (tid == 0) step::reject_record(a, rout, loss_prev, cur);
       continue;  // uniform across the workgroup
     }
-    const int bh = tab[2 * si], bw = tab[2 * si + 1];
+    const int bh = tab[2 * cur.si], bw = tab[2 * cur.si + 1];
     const rsrc_t r_f = make_rsrc(a.fields + rin * a.field_stride, (uint32_t)(bh * bw) * 8u);
 
-    // window, clipped to the grid, and the matching sub-block of f (MCMC.py:1266-1276); halo (MCMC.py:1293-1297)
-    const int r0 = max(0, row - bh / 2), r1 = min(H, row + bh / 2);
-    const int c0 = max(0, col - bw / 2), c1 = min(W, col + bw / 2);
-    const int mr0 = max(bh - r1, 0), mc0 = max(bw - c1, 0);
-    const int wh = r1 - r0, ww = c1 - c0;
-    const int hr0 = max(0, r0 - 1), hr1 = min(H, r1 + 1);
-    const int hc0 = max(0, c0 - 1), hc1 = min(W, c1 + 1);
-    const int th = hr1 - hr0, tw = hc1 - hc0;
-    const int ncell = th * tw;
+    const step::Window G = step::clip_window(H, W, cur.row, cur.col, bh, bw);
+    const step::HaloTile T = step::halo_tile(H, W, G);
+    const int tw = T.tw, ncell = T.ncell;
     const uint32_t m_tw = magic_for((uint32_t)tw);
-    const int dr = r0 - hr0, dc = c0 - hc0;  // window origin inside the tile (0 or 1)
 
     // geometry of the thread's k-th tile cell (recomputed per phase: cheaper than 2 registers per cell)
     int ptid = tid;   // re-laundered at each phase so that the geometry is recomputed, not kept live across phases
@@ -109,8 +94,8 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       valid = i < ncell;
       lr = (int)__umulhi((uint32_t)i, m_tw);
       lc = i - lr * tw;
-      g = (uint32_t)((hr0 + lr) * W + hc0 + lc);
-      inwin = valid && (unsigned)(lr - dr) < (unsigned)wh && (unsigned)(lc - dc) < (unsigned)ww;
+      g = (uint32_t)((T.hr0 + lr) * W + T.hc0 + lc);
+      inwin = valid && (unsigned)(lr - T.dr) < (unsigned)G.wh && (unsigned)(lc - T.dc) < (unsigned)G.ww;
     };
 
     // cell slot k of this wave is past the end of the tile for the later slots of smaller blocks: wave-uniform skip
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
           cell(k, i, lr, lc, g, valid, inwin);
           vb[j] = StateIO<TS>::load(r_bed, valid ? g * (uint32_t)sizeof(TS) : kOOB);
           ve[j] = StateIO<TS>::load(r_en, inwin ? g * (uint32_t)sizeof(TS) : kOOB);
-          vf[j] = ld_f64<2>(r_f, inwin ? (uint32_t)((mr0 + lr - dr) * bw + mc0 + lc - dc) * 8u : kOOB);
+          vf[j] = ld_f64<2>(r_f, inwin ? (uint32_t)step::field_index(G, T, lr, lc, bw) * 8u : kOOB);
           A2[j] = ld_f64x2(r_sA, valid ? g * 16u : kOOB);   // (wupd, surf)
           B2[j] = ld_f64x2(r_sB, valid ? g * 16u : kOOB);   // (velx, vely)
         }
@@ -147,20 +132,14 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
         if (k < KT) {
           int i, lr, lc; uint32_t g; bool valid, inwin;
           cell(k, i, lr, lc, g, valid, inwin);
-          const bool upd = inwin && (__builtin_bit_cast(uint64_t, A2[j].x) != kNoUpdBits);
-          upd_bits |= upd ? (1u << k) : 0u;
-          double v = vb[j];
-          if (upd) {
-            v = v + vf[j] * A2[j].x;
-            if (F32) v = (double)(float)v;
-          }
-          const double thick = A2[j].y - v;
-          if (upd && thick <= 0.0) guard = 1;
-          v_new[k] = v;
+          const step::Candidate cb = step::candidate_bed<F32>(inwin, vb[j], vf[j], A2[j]);
+          upd_bits |= cb.upd ? (1u << k) : 0u;
+          if (cb.grounded) guard = 1;
+          v_new[k] = cb.v;
           acc_old += ve[j];
           if (valid) {
-            qx[i] = B2[j].x * thick;
-            qy[i] = B2[j].y * thick;
+            qx[i] = B2[j].x * cb.thick;
+            qy[i] = B2[j].y * cb.thick;
           }
         }
       }
@@ -173,6 +152,7 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
     double e_new[KT];
     double acc_new = 0.0;
     asm volatile("" : "+v"(ptid));
+    const step::StepConsts SC{S.res, S.rcp_res, S.two_res, S.rcp_two_res};
     {
       double2 C2[KT];   // (dhdt_mc, smb) of the window cells
 #pragma unroll
@@ -186,25 +166,11 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
         if (!slot_on(k)) { e_new[k] = 0.0; continue; }
         int i, lr, lc; uint32_t g; bool valid, inwin;
         cell(k, i, lr, lc, g, valid, inwin);
-        const int r = hr0 + lr, c = hc0 + lc;
+        const int r = T.hr0 + lr, c = T.hc0 + lc;
         const int il = (c == 0) ? i : i - 1, ir = (c == W - 1) ? i : i + 1;
         const int iu = (r == 0) ? i : i - tw, id = (r == H - 1) ? i : i + tw;
         double e = 0.0;
-        if (inwin) {
-          const double ddx = qx[ir] - qx[il];
-          const double ddy = qy[id] - qy[iu];
-          double dx, dy;
-          if (FAST_DIV) {
-            dx = (ir - il == 2) ? exact_div(ddx, S.two_res, S.rcp_two_res) : exact_div(ddx, S.res, S.rcp_res);
-            dy = (id - iu == 2 * tw) ? exact_div(ddy, S.two_res, S.rcp_two_res) : exact_div(ddy, S.res, S.rcp_res);
-          } else {
-            dx = ddx / ((ir - il == 2) ? S.two_res : S.res);
-            dy = ddy / ((id - iu == 2 * tw) ? S.two_res : S.res);
-          }
-          const double v = ((dx + dy) + C2[k].x) - C2[k].y;
-          if (!isnan(v)) e = v * v;
-          if (F32) e = (double)(float)e;
-        }
+        if (inwin) e = step::flux_energy<FAST_DIV, F32, false>(qx[ir] - qx[il], qy[id] - qy[iu], ir - il == 2, id - iu == 2 * tw, C2[k], SC);
         e_new[k] = e;
         acc_new += e;
         if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);
@@ -222,13 +188,8 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
     }
     __syncthreads();
     const double sd = row16_sum(red[lane & 15]);
-    double c_hi, c_err;
-    two_sum(s_hi, sd, c_hi, c_err);
-    const double c_lo = s_lo + c_err;
-    double loss_next = (c_hi + c_lo) / S.two_sigma2;
-    if (sd == INFINITY) loss_next = INFINITY;
-    const double p_acc = (loss_prev > loss_next) ? 1.0 : fmin(1.0, exp(loss_prev - loss_next));
-    const bool acc = (uu <= p_acc);
+    double c_hi, c_lo, loss_next;          // this kernel divides plainly in both instantiations
+    const bool acc = step::decide<false>(sd, sd == INFINITY, s_hi, s_lo, S.two_sigma2, S.rcp_two_sigma2, loss_prev, cur.u, c_hi, c_lo, loss_next);
 
     // ---- E: commit -------------------------------------------------------------------------------------
     if (acc) {
@@ -246,19 +207,12 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
       two_sum(c_hi, c_lo, s_hi, s_lo);
       loss_prev = loss_next;
     }
-    if (tid == 0) {
-      a.loss[rout] = loss_prev;
-      a.accept[rout] = acc ? 1 : 0;
-      if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = bh; a.blocks[4 * rout + 3] = bw; }
-    }
+    if (tid == 0) step::write_record(a, rout, loss_prev, acc, cur.row, cur.col, bh, bw);
     // End of step.  LDS needs no barrier here: the tiles are rewritten only after every wave has passed the R barrier
     // (its stencil reads are done), and `red` only after the next A barrier.  The global stores of an accepted step must
     // be visible to the next step's loads only if the next halo window touches this window.
-    if (acc && has_next && (unsigned)n_si < (unsigned)a.B.n_sizes) {
-      const int nbh = tab[2 * n_si], nbw = tab[2 * n_si + 1];
-      const int nr0 = max(0, n_row - nbh / 2) - 1, nr1 = min(H, n_row + nbh / 2) + 1;
-      const int nc0 = max(0, n_col - nbw / 2) - 1, nc1 = min(W, n_col + nbw / 2) + 1;
-      if ((nr0 < r1) && (r0 < nr1) && (nc0 < c1) && (c0 < nc1)) __syncthreads();
+    if (acc && has_next && (unsigned)nxt.si < (unsigned)a.B.n_sizes) {
+      if (step::halo_touches(step::clip_window(H, W, nxt.row, nxt.col, tab[2 * nxt.si], tab[2 * nxt.si + 1]), G)) __syncthreads();
     }
   }
   if (tid == 0) {
@@ -269,20 +223,8 @@ __global__ __launch_bounds__(kNT, 4) void step_flux_kernel(const StepArgs a) {
 
 template <typename TS, int KT>
 static hipError_t launch_flux_t(const StepArgs& a, hipStream_t st) {
-  const size_t lds = step_flux_lds_bytes(a.tile_cap);
-  auto kfast = step_flux_kernel<TS, KT, true>;
-  auto kslow = step_flux_kernel<TS, KT, false>;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kslow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
-  if (a.S.fast_div) hipLaunchKernelGGL(kfast, dim3(a.n_chains), dim3(kNT), lds, st, a);
-  else hipLaunchKernelGGL(kslow, dim3(a.n_chains), dim3(kNT), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<step_flux_kernel<TS, KT, true>, step_flux_kernel<TS, KT, false>>(
+      a.S.fast_div, 160 * 1024, dim3(a.n_chains), dim3(kNT), step_flux_lds_bytes(a.tile_cap), st, a);
 }
 
 bool step_flux_supported(const StepArgs& a) {

@@ -30,39 +30,25 @@
 
 #include "gsm_internal.h"
 #include "residual_device.h"
+#include "step_common.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
 
 namespace gsm {
 
-__device__ __forceinline__ uint32_t magic_for(uint32_t d) {
-  // q = __umulhi(n, M) == n / d for n*d < 2^32 (here n < 2^16, 2 <= d < 2^8); d == 1 would need M = 2^32
-  return (uint32_t)(0xFFFFFFFFu / d) + 1u;
-}
+using dev::magic_for;
+using dev::two_sum;
+
+// q = __umulhi(n, M) == n / d with M = magic_for(d), for n*d < 2^32 (here n < 2^16, 2 <= d < 2^8); d == 1 would need M = 2^32
 __device__ __forceinline__ int div_magic(int n, uint32_t d, uint32_t M) {
   return (d == 1u) ? n : (int)__umulhi((uint32_t)n, M);   // a 2-wide block clipped at the grid edge is 1 cell wide
-}
-
-// Correctly rounded x / d from y = RN(1/d): q0 = RN(x*y), r = x - q0*d (exact in an fma), q = RN(q0 + r*y)
-// (Markstein 1990).  Enabled by the host only when d's significand is not all ones and d is far from the
-// exponent limits; tests/test_exact_div.py checks it against exact rational arithmetic.
-__device__ __forceinline__ double exact_div(double x, double d, double y) {
-  const double q0 = x * y;
-  const double r = __fma_rn(-q0, d, x);
-  return __fma_rn(r, y, q0);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return v;  // valid in lane 0
-}
-
-__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
-  s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -100,43 +86,28 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
   int* tab = (int*)(red + 3 * 16);
   for (int i = tid; i < a.B.n_sizes; i += NT) { tab[2 * i] = a.B.bh[i]; tab[2 * i + 1] = a.B.bw[i]; }
   const int64_t rin0 = (int64_t)chain * a.in_stride;
-  int n_si = a.size_idx[rin0], n_row = a.centre[2 * rin0], n_col = a.centre[2 * rin0 + 1];
-  double n_u = a.u[rin0];
+  step::ReplayRec nxt = step::read_replay(a, rin0);
+  const step::StepConsts SC{S.res, S.rcp_res, S.two_res, S.rcp_two_res};
   __syncthreads();
 
   for (int s = 0; s < a.n_steps; ++s) {
     const int64_t rin = rin0 + s;
-    const int64_t rout = (int64_t)chain * a.rec_stride + a.rec_offset + s;
-    const int si = n_si, row = n_row, col = n_col;
-    const double uu = n_u;
+    const int64_t rout = step::record_index(a, chain, s);
+    const step::ReplayRec cur = nxt;
     const bool has_next = s + 1 < a.n_steps;
-    if (has_next) {
-      n_si = a.size_idx[rin + 1]; n_row = a.centre[2 * rin + 2]; n_col = a.centre[2 * rin + 3]; n_u = a.u[rin + 1];
-    }
-    if (si < 0 || si >= a.B.n_sizes || row < 0 || row >= H || col < 0 || col >= W) {
-      if (tid == 0) {
-        atomicExch(a.err_flag, 1);
-        a.loss[rout] = loss_prev;
-        a.accept[rout] = 0;
-        if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = 0; a.blocks[4 * rout + 3] = 0; }
-      }
+    if (has_next) nxt = step::read_replay(a, rin + 1);
+    if (!step::replay_valid(a, cur)) {
+      if (tid == 0) step::reject_record(a, rout, loss_prev, cur);
       continue;  // uniform across the workgroup
     }
-    const int bh = tab[2 * si], bw = tab[2 * si + 1];
+    const int bh = tab[2 * cur.si], bw = tab[2 * cur.si + 1];
     const double* __restrict__ fld = a.fields + rin * a.field_stride;
 
-    // window, clipped to the grid, and the matching sub-block of f (MCMC.py:1266-1276)
-    const int r0 = max(0, row - bh / 2), r1 = min(H, row + bh / 2);
-    const int c0 = max(0, col - bw / 2), c1 = min(W, col + bw / 2);
-    const int mr0 = max(bh - r1, 0), mc0 = max(bw - c1, 0);
-    const int wh = r1 - r0, ww = c1 - c0;
-    // halo window (MCMC.py:1293-1297)
-    const int hr0 = max(0, r0 - 1), hr1 = min(H, r1 + 1);
-    const int hc0 = max(0, c0 - 1), hc1 = min(W, c1 + 1);
-    const int th = hr1 - hr0, tw = hc1 - hc0;
-    const int ncell = th * tw, nwin = wh * ww;
+    const step::Window G = step::clip_window(H, W, cur.row, cur.col, bh, bw);
+    const step::HaloTile T = step::halo_tile(H, W, G);
+    const int r0 = G.r0, c0 = G.c0, ww = G.ww, hr0 = T.hr0, hc0 = T.hc0, tw = T.tw;
+    const int ncell = T.ncell, nwin = G.wh * ww;
     const uint32_t m_tw = magic_for((uint32_t)tw), m_ww = magic_for((uint32_t)ww);
-    const int dr = r0 - hr0, dc = c0 - hc0;  // window origin inside the tile (0 or 1)
 
     // ---- A: candidate bed -> LDS, guard, sum of the carried energy of the window ------------------
     double acc_old = 0.0;
@@ -155,10 +126,9 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
           const int lc = i - lr * tw;
           const int g = (hr0 + lr) * W + hc0 + lc;
           vb[k] = (double)__builtin_nontemporal_load(&bed[g]);
-          const int wr = lr - dr, wc = lc - dc;
-          if ((unsigned)wr < (unsigned)wh && (unsigned)wc < (unsigned)ww) {
+          if (step::in_window(G, T, lr, lc)) {
             ve[k] = (double)__builtin_nontemporal_load(&energy[g]);
-            vf[k] = __builtin_nontemporal_load(&fld[(mr0 + wr) * bw + mc0 + wc]);
+            vf[k] = __builtin_nontemporal_load(&fld[step::field_index(G, T, lr, lc, bw)]);
           }
         }
       }
@@ -172,8 +142,7 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
           const int lc = i - lr * tw;
           const int g = (hr0 + lr) * W + hc0 + lc;
           double v = vb[k];
-          const int wr = lr - dr, wc = lc - dc;
-          if ((unsigned)wr < (unsigned)wh && (unsigned)wc < (unsigned)ww && S.upd[g]) {
+          if (step::in_window(G, T, lr, lc) && S.upd[g]) {
             const double pert = S.weight ? vf[k] * S.weight[g] : vf[k];
             v = v + pert;
             if (F32) v = (double)(float)v;
@@ -189,11 +158,10 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
       const int lc = i - lr * tw;
       const int g = (hr0 + lr) * W + hc0 + lc;
       double v = (double)__builtin_nontemporal_load(&bed[g]);
-      const int wr = lr - dr, wc = lc - dc;
-      if ((unsigned)wr < (unsigned)wh && (unsigned)wc < (unsigned)ww) {
+      if (step::in_window(G, T, lr, lc)) {
         acc_old += (double)__builtin_nontemporal_load(&energy[g]);
         if (S.upd[g]) {
-          const double f = __builtin_nontemporal_load(&fld[(mr0 + wr) * bw + mc0 + wc]);
+          const double f = __builtin_nontemporal_load(&fld[step::field_index(G, T, lr, lc, bw)]);
           const double pert = S.weight ? f * S.weight[g] : f;
           v = v + pert;
           if (F32) v = (double)(float)v;
@@ -228,17 +196,7 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
           const double qxl = xl.y * (xl.x - tile[trow + cl]);
           const double qyd = yd.y * (yd.x - tile[(rd - hr0) * tw + (c - hc0)]);
           const double qyu = yu.y * (yu.x - tile[(ru - hr0) * tw + (c - hc0)]);
-          double dx, dy;
-          if (FAST_DIV) {
-            dx = (cr - cl == 2) ? exact_div(qxr - qxl, S.two_res, S.rcp_two_res) : exact_div(qxr - qxl, S.res, S.rcp_res);
-            dy = (rd - ru == 2) ? exact_div(qyd - qyu, S.two_res, S.rcp_two_res) : exact_div(qyd - qyu, S.res, S.rcp_res);
-          } else {
-            dx = (qxr - qxl) / ((cr - cl == 2) ? S.two_res : S.res);
-            dy = (qyd - qyu) / ((rd - ru == 2) ? S.two_res : S.res);
-          }
-          const double v = ((dx + dy) + dd.x) - dd.y;
-          if (!isnan(v)) e = v * v;
-          if (F32) e = (double)(float)e;
+          e = step::flux_energy<FAST_DIV, F32, false>(qxr - qxl, qyd - qyu, cr - cl == 2, rd - ru == 2, dd, SC);   // dd = (dhdt, smb), mc_mask tested above
         }
       }
       e_new[k] = e;
@@ -258,13 +216,9 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
     double so = 0.0, sn = 0.0, gd = 0.0;
 #pragma unroll
     for (int w = 0; w < NW; ++w) { so += red[w * 3]; sn += red[w * 3 + 1]; gd += red[w * 3 + 2]; }
-    double c_hi, c_err;
-    two_sum(s_hi, sn - so, c_hi, c_err);
-    const double c_lo = s_lo + c_err;
-    double loss_next = (c_hi + c_lo) / S.two_sigma2;
-    if (gd > 0.0) loss_next = INFINITY;
-    const double p_acc = (loss_prev > loss_next) ? 1.0 : fmin(1.0, exp(loss_prev - loss_next));
-    const bool acc = (uu <= p_acc);
+    // the guard is counted apart from the (finite) sums; this kernel divides plainly in both instantiations
+    double c_hi, c_lo, loss_next;
+    const bool acc = step::decide<false>(sn - so, gd > 0.0, s_hi, s_lo, S.two_sigma2, S.rcp_two_sigma2, loss_prev, cur.u, c_hi, c_lo, loss_next);
 
     // ---- E: commit -------------------------------------------------------------------------------------
     if (acc) {
@@ -286,22 +240,14 @@ __global__ __launch_bounds__(NT, MINW) void step_kernel(const StepArgs a) {
       two_sum(c_hi, c_lo, s_hi, s_lo);
       loss_prev = loss_next;
     }
-    if (tid == 0) {
-      a.loss[rout] = loss_prev;
-      a.accept[rout] = acc ? 1 : 0;
-      if (a.blocks) { a.blocks[4 * rout] = row; a.blocks[4 * rout + 1] = col; a.blocks[4 * rout + 2] = bh; a.blocks[4 * rout + 3] = bw; }
-    }
+    if (tid == 0) step::write_record(a, rout, loss_prev, acc, cur.row, cur.col, bh, bw);
     // End of step.  The LDS tile / reduction scratch may be reused once every wave is here (raw barrier after the
     // wave's own LDS reads have returned).  The global stores of an accepted step must be visible to the next step's
     // loads only if the next halo window touches this window; otherwise the workgroup does not wait for them
     // (__syncthreads() would: its release fence drains vmcnt, one exposed HBM round trip per step).
     bool fence = acc;
-    if (fence && has_next && (unsigned)n_si < (unsigned)a.B.n_sizes) {
-      const int nbh = tab[2 * n_si], nbw = tab[2 * n_si + 1];
-      const int nr0 = max(0, n_row - nbh / 2) - 1, nr1 = min(H, n_row + nbh / 2) + 1;
-      const int nc0 = max(0, n_col - nbw / 2) - 1, nc1 = min(W, n_col + nbw / 2) + 1;
-      fence = (nr0 < r1) && (r0 < nr1) && (nc0 < c1) && (c0 < nc1);
-    }
+    if (fence && has_next && (unsigned)nxt.si < (unsigned)a.B.n_sizes)
+      fence = step::halo_touches(step::clip_window(H, W, nxt.row, nxt.col, tab[2 * nxt.si], tab[2 * nxt.si + 1]), G);
     if (fence) __syncthreads();
     else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
@@ -315,20 +261,8 @@ size_t step_lds_bytes(int tile_cap) { return ((size_t)tile_cap + 3 * 16 + 64) * 
 
 template <typename TS, int NT, int KMAX, int MINW>
 static hipError_t launch_step_t(const StepArgs& a, hipStream_t st) {
-  const size_t lds = step_lds_bytes(a.tile_cap);
-  auto kfast = step_kernel<TS, NT, KMAX, true, MINW>;
-  auto kslow = step_kernel<TS, NT, KMAX, false, MINW>;
-  static bool attr_set[kMaxDevices] = {};
-  int attr_dev;
-  if (attr_needed_on_this_device(attr_set, attr_dev)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kslow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (attr_dev >= 0) attr_set[attr_dev] = true;
-  }
-  if (a.S.fast_div) hipLaunchKernelGGL(kfast, dim3(a.n_chains), dim3(NT), lds, st, a);
-  else hipLaunchKernelGGL(kslow, dim3(a.n_chains), dim3(NT), lds, st, a);
-  return hipGetLastError();
+  return launch_pair<step_kernel<TS, NT, KMAX, true, MINW>, step_kernel<TS, NT, KMAX, false, MINW>>(
+      a.S.fast_div, 160 * 1024, dim3(a.n_chains), dim3(NT), step_lds_bytes(a.tile_cap), st, a);
 }
 
 hipError_t launch_step(const StepArgs& a, hipStream_t st) {

@@ -31,6 +31,7 @@
 #pragma once
 #include "gsm_internal.h"
 #include "device_util.h"
+#include "step_common.h"
 #include <math.h>
 
 namespace gsm {
@@ -81,7 +82,7 @@ __host__ __device__ __forceinline__ int small_div(int t, int d) {
   return (int)(((uint32_t)t * m) >> 15);
 }
 
-// geometry of a step's window (MCMC.py:1266-1276) -- uniform
+// what the strip pass keeps of a step's window (step::clip_window, step_common.h) -- uniform
 struct Window {
   int r0, c0, wh, ww;      // origin and size of the clipped window
   int mr0, mc0;            // first row / column of the block that lies inside the grid
@@ -89,14 +90,8 @@ struct Window {
   bool interior;           // a halo ring on all four sides lies inside the grid
 };
 __host__ __device__ __forceinline__ Window make_window(int H, int W, int row, int col, int bh, int bw) {
-  Window g;
-  const int r0 = max(0, row - bh / 2), r1 = min(H, row + bh / 2);
-  const int c0 = max(0, col - bw / 2), c1 = min(W, col + bw / 2);
-  g.r0 = r0; g.c0 = c0; g.wh = r1 - r0; g.ww = c1 - c0;
-  g.mr0 = max(bh - r1, 0); g.mc0 = max(bw - c1, 0);
-  g.bw = bw;
-  g.interior = (r0 > 0) && (r1 < H) && (c0 > 0) && (c1 < W);
-  return g;
+  const step::Window w = step::clip_window(H, W, row, col, bh, bw);
+  return Window{w.r0, w.c0, w.wh, w.ww, w.mr0, w.mc0, bw, step::interior(H, W, w)};
 }
 
 // what a lane does in a step: fixed for the step.  The yes / no facts are bits of one register; a phase turns the ones it
@@ -277,15 +272,10 @@ __device__ __forceinline__ void phase_a(const Lane& L_in, const int n, const int
           row_offsets<INTERIOR>(L, jj + kNA, W, 16u, off, soff);
           a2[(jj - 1) % kNA] = ld_f64x2(r_st, row_own(L, jj + kNA) ? (INTERIOR ? own16 : (colown ? off : oob)) : oob, soff);
         }
-        const double f = field(jj, own);
-        const bool upd = own && (__builtin_bit_cast(uint64_t, A2.x) != kNoUpdBits);
-        if (upd) {
-          v = v + f * A2.x;
-          if (F32) v = (double)(float)v;
-        }
-        const double thick = A2.y - v;
-        guard = guard || (upd && thick <= 0.0);
-        upd_bits |= upd ? (1u << jj) : 0u;
+        const step::Candidate cb = step::candidate_bed<F32>(own, v, field(jj, own), A2);
+        v = cb.v;
+        guard = guard || cb.grounded;
+        upd_bits |= cb.upd ? (1u << jj) : 0u;
       }
       if (cell_written<INTERIOR>(L, wm, jj)) tile[L.tidx + jj * ts] = v;
     }
@@ -307,7 +297,7 @@ __device__ __forceinline__ double wave_shift(double x) {
 constexpr int kWaveShr1 = 0x138;   // lane i <- lane i - 1
 constexpr int kWaveShl1 = 0x130;   // lane i <- lane i + 1
 
-struct StepConsts { double res, rcp_res, two_res, rcp_two_res; };
+using step::StepConsts;
 
 // ---- phase D: fluxes from the tile, residual stencil (Topography.py:592-600, np.gradient's one-sided differences at the
 // grid border), new energies -> en[R - 1] of the lane's own rows; acc_new = their sum.  Every lane of the wave must be here
@@ -353,32 +343,17 @@ struct PhaseD {
         constexpr int R = (JJ >= 2) ? JJ - 1 : 1;
         double qxl = wave_shift<kWaveShr1>(qx_m1), qxr = wave_shift<kWaveShl1>(qx_m1);
         double qya = qy_m2, qyb = qy;
-        double dx, dy;
-        if (INTERIOR) {
-          const double ddx = qxr - qxl, ddy = qyb - qya;
-          if (FAST_DIV) { dx = exact_div(ddx, K.two_res, K.rcp_two_res); dy = exact_div(ddy, K.two_res, K.rcp_two_res); }
-          else { dx = ddx / K.two_res; dy = ddy / K.two_res; }
-        } else {
+        bool xedge = false, yedge = false;
+        if (!INTERIOR) {
           const bool atleft = has(L, kFAtLeft), atright = has(L, kFAtRight);
-          const bool xedge = atleft || atright;
           const bool attop = (R == L.jtop), atbot = (R == L.jbot);
+          xedge = atleft || atright; yedge = attop || atbot;
           if (atleft) qxl = qx_m1;
           if (atright) qxr = qx_m1;
           if (attop) qya = qy_m1;
           if (atbot) qyb = qy_m1;
-          const double ddx = qxr - qxl, ddy = qyb - qya;
-          if (FAST_DIV) {
-            dx = xedge ? exact_div(ddx, K.res, K.rcp_res) : exact_div(ddx, K.two_res, K.rcp_two_res);
-            dy = (attop || atbot) ? exact_div(ddy, K.res, K.rcp_res) : exact_div(ddy, K.two_res, K.rcp_two_res);
-          } else {
-            dx = ddx / (xedge ? K.res : K.two_res);
-            dy = ddy / ((attop || atbot) ? K.res : K.two_res);
-          }
         }
-        const double r = ((dx + dy) + C_m1.x) - C_m1.y;
-        double e = 0.0;
-        if (own_m1 && !isnan(r)) e = r * r;
-        if (F32) e = (double)(float)e;
+        const double e = step::flux_energy<FAST_DIV, F32, INTERIOR>(qxr - qxl, qyb - qya, !xedge, !yedge, C_m1, K, own_m1);
         en[R - 1] = e;
         acc_new += e;
       }

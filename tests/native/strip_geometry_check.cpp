@@ -14,6 +14,14 @@
 //   divisions    rows_per_strip == ceil, small_div == t / d, config == the table of decompositions restated below,
 //                table_ok == "n <= kNR for every width up to bw, bw <= 496"
 // It prints, per decomposition and INTERIOR value, how many windows it checked and the deepest n, and fails if a count is 0.
+//
+// The geometry every step kernel shares (mcmc_gpu_amd/csrc/step_common.h), on every window above plus all centres of a 12 x 12
+// and a 9 x 14 grid with blocks 4 x 4, 6 x 10 and 12 x 12 (clipped on each edge, on two at once, as large as the grid):
+//   window       clip_window (r0, r1, c0, c1, mr0, mc0, wh, ww), interior and halo_tile equal the oracle's window_bounds and the
+//                halo slice of MCMC.py:1293-1297, restated below; dr, dc place the window inside the tile
+//   tile width   halo_tile_width(W, col, bw) == the tile's tw
+//   overlap      halo_touches(second, first) == "some cell of the second step's halo tile is a cell of the first step's window",
+//                by brute force over all ordered pairs of windows of the two small grids
 #include "strip_step.h"
 
 #include <algorithm>
@@ -58,7 +66,59 @@ static std::vector<uint8_t> g_cnt, g_tcnt;
 static std::vector<uint32_t> g_touched;
 static std::vector<int> g_ttouched;
 
+// the shared window and halo tile against the oracle's window_bounds (oracle/mcmc_oracle.py, MCMC.py:1266-1276; bh and bw
+// even) and the halo slice max(0, r0 - 1) : min(H, r1 + 1) of MCMC.py:1293-1297, restated here
+static gsm::step::Window check_step_window(int H, int W, int row, int col, int bh, int bw) {
+  namespace st = gsm::step;
+  const st::Window w = st::clip_window(H, W, row, col, bh, bw);
+  const st::HaloTile t = st::halo_tile(H, W, w);
+  const int r0 = std::max(0, row - bh / 2), r1 = std::min(H, row + bh / 2);
+  const int c0 = std::max(0, col - bw / 2), c1 = std::min(W, col + bw / 2);
+  const int mr0 = std::max(bh - r1, 0), mc0 = std::max(bw - c1, 0);
+  CHECK(w.r0 == r0 && w.r1 == r1 && w.c0 == c0 && w.c1 == c1 && w.mr0 == mr0 && w.mc0 == mc0 && w.wh == r1 - r0 && w.ww == c1 - c0,
+        "clip_window H %d W %d row %d col %d bh %d bw %d", H, W, row, col, bh, bw);
+  CHECK(st::interior(H, W, w) == (r0 > 0 && r1 < H && c0 > 0 && c1 < W), "interior H %d W %d row %d col %d bh %d bw %d", H, W, row, col, bh, bw);
+  const int hr0 = std::max(0, r0 - 1), hr1 = std::min(H, r1 + 1), hc0 = std::max(0, c0 - 1), hc1 = std::min(W, c1 + 1);
+  CHECK(t.hr0 == hr0 && t.hr1 == hr1 && t.hc0 == hc0 && t.hc1 == hc1 && t.tw == hc1 - hc0 && t.ncell == (hr1 - hr0) * (hc1 - hc0) &&
+            t.dr == r0 - hr0 && t.dc == c0 - hc0,
+        "halo_tile H %d W %d row %d col %d bh %d bw %d", H, W, row, col, bh, bw);
+  CHECK(st::halo_tile_width(W, col, bw) == t.tw, "halo_tile_width(%d, %d, %d) = %d, tile %d", W, col, bw, st::halo_tile_width(W, col, bw), t.tw);
+  // the window's cells inside the tile and inside the field, as the kernels address them
+  CHECK(st::in_window(w, t, t.dr, t.dc) && st::in_window(w, t, t.dr + w.wh - 1, t.dc + w.ww - 1) && !st::in_window(w, t, t.dr - 1, t.dc) &&
+            !st::in_window(w, t, t.dr, t.dc - 1) && !st::in_window(w, t, t.dr + w.wh, t.dc) && !st::in_window(w, t, t.dr, t.dc + w.ww),
+        "in_window H %d W %d row %d col %d bh %d bw %d", H, W, row, col, bh, bw);
+  CHECK(st::field_index(w, t, t.dr, t.dc, bw) == mr0 * bw + mc0, "field_index H %d W %d row %d col %d bh %d bw %d", H, W, row, col, bh, bw);
+  return w;
+}
+
+// every centre of a small grid with three block shapes; the overlap predicate over all ordered pairs of these windows
+static void check_small_grid(int H, int W) {
+  namespace st = gsm::step;
+  const int shapes[3][2] = {{4, 4}, {6, 10}, {12, 12}};
+  std::vector<st::Window> ws;
+  for (const auto& sh : shapes)
+    for (int row = 0; row < H; ++row)
+      for (int col = 0; col < W; ++col) ws.push_back(check_step_window(H, W, row, col, sh[0], sh[1]));
+  long touching = 0;
+  for (const st::Window& first : ws) {
+    for (const st::Window& second : ws) {
+      const st::HaloTile t = st::halo_tile(H, W, second);
+      bool brute = false;
+      for (int r = t.hr0; r < t.hr1 && !brute; ++r)
+        for (int c = t.hc0; c < t.hc1 && !brute; ++c) brute = r >= first.r0 && r < first.r1 && c >= first.c0 && c < first.c1;
+      touching += brute;
+      CHECK(st::halo_touches(second, first) == brute, "halo_touches: second [%d, %d) x [%d, %d), first [%d, %d) x [%d, %d) on %d x %d", second.r0,
+            second.r1, second.c0, second.c1, first.r0, first.r1, first.c0, first.c1, H, W);
+    }
+    CHECK(!st::halo_touches(first, st::Window{}) || (first.r0 == 0 && first.c0 == 0), "an empty window touches [%d, %d) x [%d, %d)", first.r0, first.r1,
+          first.c0, first.c1);
+  }
+  CHECK(touching > 0 && touching < (long)ws.size() * (long)ws.size(), "overlap pairs on %d x %d: %ld", H, W, touching);
+  printf("shared     grid %3d x %3d: %zu windows, %zu ordered pairs, %ld touching\n", H, W, ws.size(), ws.size() * ws.size(), touching);
+}
+
 static void check_window(int H, int W, int row, int col, int bh, int bw) {
+  check_step_window(H, W, row, col, bh, bw);
   const Window g = make_window(H, W, row, col, bh, bw);
   // the oracle's window_bounds (oracle/mcmc_oracle.py, MCMC.py:1266-1276), bh and bw even
   const int r0 = std::max(0, row - bh / 2), r1 = std::min(H, row + bh / 2);
@@ -185,6 +245,8 @@ int main() {
   // the grids of tests/test_gpu_parity.py with their block sizes
   check_table("parity_64", 64, 64, 8, 16, 8, 16, 2, 2);
   check_table("tiny_8x10", 8, 10, 2, 4, 2, 4, 1, 1);
+  check_small_grid(12, 12);
+  check_small_grid(9, 14);
 
   bool empty = false;
   for (int i = 0; i < 5; ++i) {                                // the sixth (g = 8) is out of reach: block widths stop at 128

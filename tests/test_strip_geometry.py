@@ -1,9 +1,13 @@
 """CPU: the integer geometry of the strip kernels (mcmc_gpu_amd/csrc/strip_step.h: config, rows_per_strip, small_div,
-make_window, lane_setup, write_masks, cell_written are __host__ __device__) run on the host for every (wave, lane) of the
+make_window on step_common.h's clip_window, lane_setup, write_masks, cell_written are __host__ __device__) run on the host for every (wave, lane) of the
 workgroup, over the windows of the five tables of tests/strip_oracle_cases.py and of the small grids of test_gpu_parity:
 own cells partition the window and stay inside the grid, phase A writes every window cell of the tile once, the ring cells
 that exist in the grid and nothing else, fidx / tidx agree with the oracle's window_bounds, and the divisions without a divide
-are exact.  tests/native/strip_geometry_check.cpp states each property; it needs no GPU and calls no HIP runtime function.
+are exact.  The same program checks the geometry all five step kernels share (mcmc_gpu_amd/csrc/step_common.h: clip_window,
+halo_tile, halo_tile_width, halo_touches, in_window, field_index) on those windows and on every centre of a 12 x 12 and a 9 x 14
+grid: window and halo tile against the oracle's window_bounds, the record's tile width against the tile, and the overlap predicate
+against a brute-force test over all ordered pairs of windows.  tests/native/strip_geometry_check.cpp states each property; it needs
+no GPU and calls no HIP runtime function.
 
 Also on the CPU: what makes the 'pcg64'-mode cases of tests/strip_oracle_cases.py (noise_table, noise_every_shape) fair."""
 import shutil
