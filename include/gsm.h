@@ -98,6 +98,8 @@ int gsm_set_static(gsm_handle h, const double* surf, const double* velx, const d
 /* Proposal block table: n_sizes (bh, bw) pairs [host] and their edge masks packed back to back [dev],
  * mask i starting at mask_offsets[i] doubles [host, n_sizes entries].  Masks are needed only by the
  * Philox proposal generator; replay mode receives fields that already carry the mask.
+ * Every bh and bw must be even and >= 2 (RandField.get_block_sizes makes them so, MCMC.py:576-579) and at most the grid's
+ * size, else GSM_E_ARG: the proposal kernels' DFT stages exist for even lengths only.
  * A new table drops the factors registered with gsm_set_factors (they belong to the old one): call it again.
  * Replaces: RandField.set_block_sizes / set_weight_param (MCMC.py:524-566, :568-623). */
 int gsm_set_blocks(gsm_handle h, int32_t n_sizes, const int32_t* bh, const int32_t* bw,

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       const PropGeom pg = prop_geom(pa, q.bh, q.bw);
       dma_to_lds<kNW, 0>(pa.tables + q.fy_off, lds + lds_xh4, 2 * pg.KR * pg.NR, wave, lane);
       dma_to_lds<kNW, 0>(pa.tables + q.g_off, fld, 2 * pg.Kc * pg.M1, wave, lane);
-      coef_items<kNT, false>(ptid, 0, pg.nrow * pg.ncol, true, pa, q, pg, seed, pa.step0 + s, lds, pa.lds_x_half, no_noise, mtab);
+      coef_items<kNT, false>(ptid, pa, q, pg, seed, pa.step0 + s, lds, no_noise, mtab);
     }
     // ---- P0: chain state of the window -> registers, in flight during the two MFMA stages ------------------------------
     double vb[KT], ve[KT];
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
         const cargs_t K = kargs();
         const ProposeArgs pa = load_c(&K->P);
         const PropScalars q = prop_rec(rec);
-        dft_stage1<kNW, kUPW, true>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, lds + lds_xh4, uc, us);
+        dft_stage1<kNW, kUPW, kTabLds2D>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, lds + lds_xh4, uc, us);
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has finished reading the planes
       {
@@ -202,11 +202,11 @@ __global__ __launch_bounds__(kNT, 4) void chain_fused_kernel(const FusedArgs fa)
       double mreg[1][8];
       relaunder();
       const int ln = ptid & 63;
-      dft_stage2<kNW, 1, true>(wave, ln, pa, q, pg, lds, fld, fe, fo);
+      dft_stage2<kNW, 1, kTabLds2D>(wave, ln, pa, q, pg, lds, fld, fe, fo);
       mask_prefetch<kNW, 1>(wave, ln, pa, q, pg, mreg);
       const double gain = standardise<kNW, 1>(wave, ln, q, pg, dc0, red2, fe, fo);     // contains a barrier
       const bool with_nugget = pa.rf.nugget_max > 0.0;
-      emit_field<kNW, 1, true>(wave, ln, pa, q, pg, fe, fo, mreg, gain, with_nugget, fld, [bw](int y, int x) { return y * bw + x; });
+      emit_field<kNW, 1, kMaskRegs>(wave, ln, pa, q, pg, fe, fo, mreg, gain, with_nugget, fld, [bw](int y, int x) { return y * bw + x; });
       if (with_nugget) {
         __syncthreads();
         relaunder();

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
         const int64_t o = noise0 + (int64_t)s * F->noise_stride;
         nz.re = F->noise_re + o; nz.im = F->noise_im + o;
       }
-      coef_items<kST, NOISE, true>(ptid, 0, pg.nrow * pg.ncol, true, pa, q, pg, seed, pa.step0 + s, lds, pa.lds_x_half, nz, mtab, (pa.parseval && !((q.bh | q.bw) & 1)) ? red2 + 16 : nullptr);
+      coef_items<kST, NOISE, true>(ptid, pa, q, pg, seed, pa.step0 + s, lds, nz, mtab, pa.parseval ? red2 + 16 : nullptr);
     }
     // Stores of an accepted step must have landed before a later step reads an overlapping window.  They were issued a
     // whole coefficient phase ago; the wait is free, and the barriers that follow order it across the waves.
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
         const cargs_t K = kargs();
         const ProposeArgs pa = load_c(&K->P);
         const PropScalars q = prop_rec(rec);
-        dft_stage1<kSW, kSUPW, 2>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, t1, uc, us);
+        dft_stage1<kSW, kSUPW, kTabLds1D>(wave, ptid & 63, pa, q, prop_geom(pa, q.bh, q.bw), lds, t1, uc, us);
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has finished reading the planes
       {
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
       const double mreg[kSMAXT][8] = {};        // not used: the edge mask comes from the 1-D table in LDS (m1)
       relaunder();
       const int ln = ptid & 63;
-      dft_stage2<kSW, kSMAXT, 2>(wave, ln, pa, q, pg, lds, t1 + 2 * kT1S, fe, fo);
-      const double gain = standardise<kSW, kSMAXT>(wave, ln, q, pg, dc0, red2, fe, fo, (pa.parseval && !((q.bh | q.bw) & 1)) ? red2 + 16 : nullptr);     // contains a barrier; even shapes: variance from the spectrum
+      dft_stage2<kSW, kSMAXT, kTabLds1D>(wave, ln, pa, q, pg, lds, t1 + 2 * kT1S, fe, fo);
+      const double gain = standardise<kSW, kSMAXT>(wave, ln, q, pg, dc0, red2, fe, fo, pa.parseval ? red2 + 16 : nullptr);     // contains a barrier; parseval: variance from the spectrum
       NoiseIn nz{nullptr, nullptr, nullptr};
       if (NOISE) {
         const cargs_t F = K;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
         if (nb) nz.nug = nb + noise0 + (int64_t)s * F->noise_stride;
       }
       const bool with_nugget = NOISE ? (nz.nug != nullptr) : (pa.rf.nugget_max > 0.0);
-      emit_field<kSW, kSMAXT, 2>(wave, ln, pa, q, pg, fe, fo, mreg, gain, with_nugget, lds, [bw](int y, int x) { return (y + 1) * (bw + 2) + x + 1; }, m1);
+      emit_field<kSW, kSMAXT, kMaskLds1D>(wave, ln, pa, q, pg, fe, fo, mreg, gain, with_nugget, lds, [bw](int y, int x) { return (y + 1) * (bw + 2) + x + 1; }, m1);
       if (with_nugget) {
         __syncthreads();
         relaunder();

@@ -177,11 +177,11 @@ struct PropGeom {
   int N1;   // stage-2 M  (y), multiple of 16
   int SX, ST;
   uint32_t q_mt, q_mt2;   // tile_magic of M1 / 16 (stage-1 tile columns) and N1 / 16 (stage-2 tile rows)
-  // even block heights (every table of the reference: MCMC.py:576-579 rounds the sizes to even): stage 1 is split by the parity of ky
+  // block sizes are even (gsm_set_blocks; every table of the reference: MCMC.py:576-579 rounds the sizes to even): stage 1 is split by the parity of ky
   int hq;   // hh / 2: the half-sums are evaluated for y in [0, hq]; hh - y mirrors them
   int NRh;  // ... padded to a multiple of 16
   int Ke;   // terms of a half-sum, padded to a multiple of 4
-  // stage 2 likewise by the parity of kx -- where the width is even, the handle allows it (ProposeArgs::split2) and the pairs of
+  // stage 2 likewise by the parity of kx -- where the handle allows it (ProposeArgs::split2) and the pairs of
   // (x, hw - x) tile slots fit the 16 slots of a workgroup: two slots j, j + 1 of a wave hold x0 = 16 nt + l15 <= hqx and its mirror hw - x0
   bool split2;
   int hqx, M1h, Kce;     // hw / 2, (hqx + 1) padded to 16, terms of a half-sum padded to 4
@@ -197,29 +197,28 @@ __device__ __forceinline__ PropGeom prop_geom(const ProposeArgs& a, int bh, int 
   g.q_mt = tile_magic(g.M1 >> 4); g.q_mt2 = tile_magic(g.N1 >> 4);
   g.hq = g.hh >> 1; g.NRh = (g.hq + 16) & ~15; g.Ke = (g.hq + 4) & ~3;
   g.hqx = g.hw >> 1; g.M1h = (g.hqx + 16) & ~15; g.Kce = (g.hqx + 4) & ~3;
-  g.split2 = a.split2 && !(bw & 1) && (g.N1 >> 4) * (g.M1h >> 4) <= 8;
+  g.split2 = a.split2 && (g.N1 >> 4) * (g.M1h >> 4) <= 8;
   return g;
 }
 
 // ---- folded Hermitian half-plane coefficients ------------------------------------------------------
 // One work item per (ky <= hh, kx <= hw): rows ky and bh-ky share the spectral amplitude, and on the two self-conjugate
-// columns they are a conjugate pair built from the same two draws.  Thread t of NTH handles items i_lo + t, + NTH, ... below
-// i_hi, and -- if `pad` -- the zero padding of the [KR][M1] operand grid.  The four planes may live in LDS or in global
-// memory (plane stride `plane`, row stride SX).
+// columns they are a conjugate pair built from the same two draws.  Thread t of NTH handles items t, t + NTH, ... and the zero
+// padding of the [KR][M1] operand grid.  The four planes lie in LDS from Pr on (plane stride a.lds_x_half, row stride SX).
 // FOLD_CK: the Hermitian-half factor c_kx (1 for kx in {0, bw / 2}, else 2) of the stage-2 operand table is applied here, to the
 // spectral amplitude -- one multiply per work item; stage 1 is linear, so T^T comes out scaled exactly as if its rows had been
-// doubled (powers of two commute with every rounding) and TABMODE 2 of dft_stage2 reads plain cos / sin.
+// doubled (powers of two commute with every rounding) and kTabLds1D of dft_stage2 reads plain cos / sin.
 template <int NTH, bool NOISE_IN, bool FOLD_CK = false>
-__device__ __forceinline__ void coef_items(const int t, const int i_lo, const int i_hi, const bool pad, const ProposeArgs& a,
-                                           const PropScalars& sc, const PropGeom& g, const uint64_t seed, const int64_t step,
-                                           double* __restrict__ Pr, const int plane, const NoiseIn noise, const double* mt,
-                                           double* pw_red = nullptr) {
+__device__ __forceinline__ void coef_items(const int t, const ProposeArgs& a, const PropScalars& sc, const PropGeom& g,
+                                           const uint64_t seed, const int64_t step, double* __restrict__ Pr, const NoiseIn noise,
+                                           const double* mt, double* pw_red = nullptr) {
   const gsm_rf_params& P = a.rf;
+  const int plane = a.lds_x_half;
   double* __restrict__ Pi = Pr + plane;
   double* __restrict__ Mr = Pi + plane;
   double* __restrict__ Mi = Mr + plane;
   const int SX = g.SX, bh = g.bh, bw = g.bw, hh = g.hh, hw = g.hw, ncol = g.ncol, nrow = g.nrow;
-  if (pad) {
+  {
     // zero padding of the [KR][M1] operand grid around the nrow x ncol coefficients: the (at most 3) rows below them, whole,
     // and the (at most 15) columns to their right -- 16 columns x NTH / 16 rows per pass, no division
     const int M1 = g.M1, KR = g.KR;
@@ -240,7 +239,7 @@ __device__ __forceinline__ void coef_items(const int t, const int i_lo, const in
   const uint32_t m_nc = sc.m_nc;
   double pw = 0.0;
   const double* __restrict__ k2tab = a.k2tab + sc.pad;          // this shape's [nrow][ncol] table (pad = its offset)
-  for (int i = i_lo + t; i < i_hi; i += NTH) {
+  for (int i = t; i < nrow * ncol; i += NTH) {
     const double k2 = k2tab[i];                                 // requested first: lands under the Box-Muller code
     const int ky = (int)__umulhi((uint32_t)i, m_nc);
     const int kx = i - ky * ncol;
@@ -282,7 +281,7 @@ __device__ __forceinline__ void coef_items(const int t, const int i_lo, const in
     // power of the item's entries of the full Hermitian spectrum, the DC term left out: columns 0 < kx < bw / 2 stand for kx and bw - kx
     // (with FOLD_CK they are stored doubled: |2 X|^2 / 2 = 2 |X|^2 exactly), rows ky and bh - ky are a and b
     if (pw_red && i != 0) {
-      const bool inner = (kx != 0) && (kx != hw);          // (callers pass pw_red for even shapes only)
+      const bool inner = (kx != 0) && (kx != hw);
       const double wc = FOLD_CK ? (inner ? 0.5 : 1.0) : (inner ? 2.0 : 1.0);
       pw += wc * ((ar * ar + ai * ai) + (br * br + bi * bi));
     }
@@ -303,18 +302,26 @@ __device__ __forceinline__ void dma_to_lds(const double* __restrict__ src, doubl
     __builtin_amdgcn_global_load_lds(src + c * 128 + 2 * lane, (__attribute__((address_space(3))) void*)(dst + c * 128), 16, 0, AUX);
 }
 
-// ---- stage 1 (MFMA): U = P^T C, V = M^T S on ky, y in [0, hh] -----------------------------------
-// Work unit = half an output tile: half 0 accumulates (Ur, Vi) = (Pr C, Mi S), which is all the real part of T^T
-// needs; half 1 accumulates (Ui, Vr) = (Pi C, Mr S) for the imaginary part.  Unit u goes to wave u mod NW.  Results wait
-// in registers until every wave has finished reading the planes, then overwrite them as T^T (tt_write).
-// TABMODE: 0 = the [K][N] operand tables from global memory (L2), 1 = the same tables staged in LDS (tabA),
-// 2 = 1-D twiddle tables in LDS (tabA: cos(2 pi m / n) at [m], sin at [kT1S + m], n = block height), the operand of
-// (k, j) read at m = (k * j) mod n, advanced from one K step to the next by an add and a conditional subtract -- the
-// same numbers at 1 / 30 of the LDS footprint (chain_strip_kernel: two workgroups per CU).
+// ---- stage 1 (MFMA): U = P^T C, V = M^T S on ky in [0, hh], split by the parity of ky (radix 2) ---------------------------------
+// Block heights are even, n = 2 h (gsm_set_blocks refuses any other: there is no code for odd lengths here):
+//   U[y] = Ue[y] + Uo[y], U[h - y] = Ue[y] - Uo[y];  V[y] = Ve[y] + Vo[y], V[h - y] = -Ve[y] + Vo[y]   (dft_tt_write)
+// with Ue / Ve over ky = 2 m and Uo / Vo over ky = 2 m + 1, each evaluated for y in [0, h / 2] only: half the products of the
+// direct sums.  An (output tile, re | im) pair accumulates (Ur, Vi) = (Pr C, Mi S), which is all the real part of T^T needs, or
+// (Ui, Vr) = (Pi C, Mr S) for the imaginary part.  A work unit is one parity of one pair; the two parities of a pair are units
+// j, j + 1 of the same wave and run through the K loop together (four independent MFMAs per K step); pair p goes to wave
+// p mod NW.  Row 2 (k0 + l4) (+ 1) of a plane may lie beyond its zero padding in the last K step only: that step reads a
+// clamped row and zeroes the operand.  Results wait in registers until every wave has finished reading the planes, then
+// overwrite them as T^T (dft_tt_write).
+// TabMode: where the MFMA loops of both stages read their DFT operand from.  The 2-D tables are the host-built [K][N] tables
+// (gsm_set_blocks), from global memory (L2) or staged in LDS (tabA / tabG); the 1-D tables hold cos(2 pi m / n) at [m] and
+// (-)sin at [kT1S + m], n = block length, in LDS: the operand of (k, j) is read at m = (k * j) mod n, advanced from one K step
+// to the next by an add and a conditional subtract -- the same numbers at 1 / 30 of the LDS footprint (chain_strip_kernel: two
+// workgroups per CU).
+enum TabMode : int { kTabGlobal2D, kTabLds2D, kTabLds1D };
 constexpr int kT1S = 128;    // doubles between the cos and the sin half of a 1-D table: block lengths up to 128
 __device__ __forceinline__ uint32_t mod_magic(uint32_t x, uint32_t n, uint32_t magic) { return x - __umulhi(x, magic) * n; }
 
-template <int NW, int UPW, int TABMODE>
+template <int NW, int UPW, TabMode TABMODE>
 __device__ __forceinline__ void dft_stage1(const int w, const int lane, const ProposeArgs& a, const PropScalars& sc, const PropGeom& g,
                                            const double* plds, const double* tabA, v4f64 (&uc)[UPW], v4f64 (&us)[UPW]) {
   const int SX = g.SX, KR = g.KR, NR = g.NR;
@@ -323,238 +330,98 @@ __device__ __forceinline__ void dft_stage1(const int w, const int lane, const Pr
   const double* Mr = Pi + a.lds_x_half;
   const double* Mi = Mr + a.lds_x_half;
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int n_mt = g.M1 >> 4, n_nt = NR >> 4;
-  const int n_t1 = n_mt * n_nt;
-  if (!(g.bh & 1)) {
-    // ---- even block height n = 2 h: the sums split by the parity of ky (radix 2) ----------------------------------------------
-    //   U[y] = Ue[y] + Uo[y], U[h - y] = Ue[y] - Uo[y];  V[y] = Ve[y] + Vo[y], V[h - y] = -Ve[y] + Vo[y]   (dft_tt_write)
-    // with Ue / Ve over ky = 2 m and Uo / Vo over ky = 2 m + 1, each evaluated for y in [0, h / 2] only: half the products of the
-    // direct sums.  A work unit is one parity of one (output tile, re | im) pair; the two parities of a pair are units j, j + 1
-    // of the same wave and run through the K loop together (four independent MFMAs per K step).  Row 2 (k0 + l4) (+ 1) of a
-    // plane may lie beyond its zero padding in the last K step only: that step reads a clamped row and zeroes the operand.
-    const int n_pairs = 2 * n_mt * (g.NRh >> 4);
-    const int Ke = g.Ke, bh = g.bh;
-    const uint32_t n8 = 8u * (uint32_t)bh;
-    const double* __restrict__ T2 = (TABMODE == 1) ? tabA : (TABMODE == 0 ? a.tables + sc.fy_off : nullptr);      // [cos: KR x NR][sin: KR x NR]
+  const int n_mt = g.M1 >> 4;
+  const int n_pairs = 2 * n_mt * (g.NRh >> 4);
+  const int Ke = g.Ke, bh = g.bh;
+  const uint32_t n8 = 8u * (uint32_t)bh;
+  const double* __restrict__ T2 = (TABMODE == kTabLds2D) ? tabA : (TABMODE == kTabGlobal2D ? a.tables + sc.fy_off : nullptr);      // [cos: KR x NR][sin: KR x NR]
 #pragma unroll
-    for (int j = 0; j < UPW; j += 2) {
-      const int pq = w + (j >> 1) * NW;
-      v4f64 cE = {0.0, 0.0, 0.0, 0.0}, sE = cE, cO = cE, sO = cE;
-      if ((j + 1 < UPW) && pq < n_pairs) {
-        const int t = pq >> 1;
-        const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
-        const double* __restrict__ Ac = (pq & 1) ? Pi : Pr;
-        const double* __restrict__ As = (pq & 1) ? Mr : Mi;
-        const int col = 16 * mt + l15, y = 16 * nt + l15;
-        uint32_t mE = 0u, mO = 0u, d8 = 0u;
-        if (TABMODE == 2) {
-          const uint32_t yy = mod_magic((uint32_t)y, (uint32_t)bh, sc.m_bh);
-          mE = 8u * mod_magic((uint32_t)(2 * l4) * yy, (uint32_t)bh, sc.m_bh);
-          mO = 8u * mod_magic((uint32_t)(2 * l4 + 1) * yy, (uint32_t)bh, sc.m_bh);
-          d8 = 8u * mod_magic(8u * yy, (uint32_t)bh, sc.m_bh);
-        }
-        auto kstep = [&](const int k0, const bool last) {
-          int rE = 2 * (k0 + l4), rO = rE + 1;
-          const bool vE = rE < KR, vO = rO < KR;
-          if (last) { rE = min(rE, KR - 1); rO = min(rO, KR - 1); }
-          double aEc = Ac[rE * SX + col], aEs = As[rE * SX + col], aOc = Ac[rO * SX + col], aOs = As[rO * SX + col];
-          if (last) {
-            if (!vE) { aEc = 0.0; aEs = 0.0; }
-            if (!vO) { aOc = 0.0; aOs = 0.0; }
-          }
-          double bEc, bEs, bOc, bOs;
-          if (TABMODE == 2) {
-            const char* tE = (const char*)tabA + mE;
-            const char* tO = (const char*)tabA + mO;
-            bEc = *(const double*)tE; bEs = *(const double*)(tE + 8 * kT1S);
-            bOc = *(const double*)tO; bOs = *(const double*)(tO + 8 * kT1S);
-            mE += d8; mE = min(mE, mE - n8);
-            mO += d8; mO = min(mO, mO - n8);
-          } else {
-            bEc = T2[rE * NR + y]; bEs = T2[KR * NR + rE * NR + y];
-            bOc = T2[rO * NR + y]; bOs = T2[KR * NR + rO * NR + y];
-          }
-          cE = __builtin_amdgcn_mfma_f64_16x16x4f64(aEc, bEc, cE, 0, 0, 0);
-          sE = __builtin_amdgcn_mfma_f64_16x16x4f64(aEs, bEs, sE, 0, 0, 0);
-          cO = __builtin_amdgcn_mfma_f64_16x16x4f64(aOc, bOc, cO, 0, 0, 0);
-          sO = __builtin_amdgcn_mfma_f64_16x16x4f64(aOs, bOs, sO, 0, 0, 0);
-        };
-        for (int k0 = 0; k0 < Ke - 4; k0 += 4) kstep(k0, false);
-        kstep(Ke - 4, true);
-      }
-      uc[j] = cE; us[j] = sE;
-      if (j + 1 < UPW) { uc[j + 1] = cO; us[j + 1] = sO; }
-    }
-    return;
-  }
-  if constexpr (TABMODE == 2) {
-    // Two units at a time: per K step the eight operands of both are requested together, then four independent MFMAs follow --
-    // one exposed LDS round trip per four MFMAs instead of per two (a lone unit, the odd one out, runs two K steps per turn).
-    struct Unit { int ao; uint32_t m8, d8; const double* Ac; const double* As; bool on; };
-    const uint32_t n8 = 8u * (uint32_t)g.bh;
-    auto setup = [&](const int j) {
-      Unit x{0, 0u, 0u, Pr, Mi, false};
-      const int u = w + j * NW, t = u >> 1;
-      x.on = (j < UPW) && (t < n_t1);
-      if (x.on) {
-        const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
-        x.ao = l4 * SX + 16 * mt + l15;
-        x.Ac = (u & 1) ? Pi : Pr; x.As = (u & 1) ? Mr : Mi;
-        const uint32_t yy = mod_magic((uint32_t)(16 * nt + l15), (uint32_t)g.bh, sc.m_bh);
-        x.m8 = 8u * mod_magic((uint32_t)l4 * yy, (uint32_t)g.bh, sc.m_bh);       // byte index of (k, y) = 8 * ((k * y) mod bh)
-        x.d8 = 8u * mod_magic(4u * yy, (uint32_t)g.bh, sc.m_bh);                 // ... stepping k by 4
-      }
-      return x;
-    };
-    auto fetch = [&](Unit& x, const int k0, double& a1, double& a2, double& b1, double& b2) {
-      const char* tb = (const char*)tabA + x.m8;
-      const int o = x.ao + k0 * SX;
-      a1 = x.Ac[o]; a2 = x.As[o]; b1 = *(const double*)tb; b2 = *(const double*)(tb + 8 * kT1S);
-      x.m8 += x.d8;
-      x.m8 = min(x.m8, x.m8 - n8);            // unsigned: m8 - n8 wraps to a huge value when m8 < n8
-    };
-#pragma unroll
-    for (int j = 0; j < UPW; j += 2) {
-      Unit A = setup(j), B = setup(j + 1);
-      v4f64 cA = {0.0, 0.0, 0.0, 0.0}, sA = cA, cB = cA, sB = cA;
-      if (A.on && B.on) {
-        {
-          const v4f64 Z = {0.0, 0.0, 0.0, 0.0};
-          double a1, a2, b1, b2, a3, a4, b3, b4;
-          fetch(A, 0, a1, a2, b1, b2);
-          fetch(B, 0, a3, a4, b3, b4);
-          cA = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, Z, 0, 0, 0);
-          sA = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, Z, 0, 0, 0);
-          cB = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, Z, 0, 0, 0);
-          sB = __builtin_amdgcn_mfma_f64_16x16x4f64(a4, b4, Z, 0, 0, 0);
-        }
-        for (int k0 = 4; k0 < KR; k0 += 4) {
-          double a1, a2, b1, b2, a3, a4, b3, b4;
-          fetch(A, k0, a1, a2, b1, b2);
-          fetch(B, k0, a3, a4, b3, b4);
-          cA = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, cA, 0, 0, 0);
-          sA = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, sA, 0, 0, 0);
-          cB = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, cB, 0, 0, 0);
-          sB = __builtin_amdgcn_mfma_f64_16x16x4f64(a4, b4, sB, 0, 0, 0);
-        }
-      } else if (A.on) {
-        int k0 = 0;
-        for (; k0 + 8 <= KR; k0 += 8) {
-          double a1, a2, b1, b2, a3, a4, b3, b4;
-          fetch(A, k0, a1, a2, b1, b2);
-          fetch(A, k0 + 4, a3, a4, b3, b4);
-          cA = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, cA, 0, 0, 0);
-          sA = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, sA, 0, 0, 0);
-          cA = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, cA, 0, 0, 0);
-          sA = __builtin_amdgcn_mfma_f64_16x16x4f64(a4, b4, sA, 0, 0, 0);
-        }
-        if (k0 < KR) {
-          double a1, a2, b1, b2;
-          fetch(A, k0, a1, a2, b1, b2);
-          cA = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, cA, 0, 0, 0);
-          sA = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, sA, 0, 0, 0);
-        }
-      }
-      uc[j] = cA; us[j] = sA;
-      if (j + 1 < UPW) { uc[j + 1] = cB; us[j + 1] = sB; }
-    }
-    return;
-  }
-  const double* __restrict__ FC = a.tables + sc.fy_off;      // [KR][NR]
-  const double* __restrict__ FS = FC + KR * NR;
-#pragma unroll
-  for (int j = 0; j < UPW; ++j) {
-    v4f64 ac = {0.0, 0.0, 0.0, 0.0}, as = ac;
-    const int u = w + j * NW;
-    const int t = u >> 1;
-    if (t < n_t1) {
+  for (int j = 0; j < UPW; j += 2) {
+    const int pq = w + (j >> 1) * NW;
+    v4f64 cE = {0.0, 0.0, 0.0, 0.0}, sE = cE, cO = cE, sO = cE;
+    if ((j + 1 < UPW) && pq < n_pairs) {
+      const int t = pq >> 1;
       const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
-      const int ao = l4 * SX + 16 * mt + l15;
-      const double* __restrict__ Ac = (u & 1) ? Pi : Pr;
-      const double* __restrict__ As = (u & 1) ? Mr : Mi;
-      const double* fc_p = FC + l4 * NR + 16 * nt + l15;
-      const double* fs_p = FS + l4 * NR + 16 * nt + l15;
-#pragma unroll 2
-      for (int k0 = 0; k0 < KR; k0 += 4) {
-        double bc, bs;
-        if (TABMODE == 1) {
-          const int bo = (l4 + k0) * NR + 16 * nt + l15;
-          bc = tabA[bo]; bs = tabA[KR * NR + bo];
-        } else {
-          bc = fc_p[k0 * NR]; bs = fs_p[k0 * NR];
-        }
-        const int o = ao + k0 * SX;
-        ac = __builtin_amdgcn_mfma_f64_16x16x4f64(Ac[o], bc, ac, 0, 0, 0);
-        as = __builtin_amdgcn_mfma_f64_16x16x4f64(As[o], bs, as, 0, 0, 0);
+      const double* __restrict__ Ac = (pq & 1) ? Pi : Pr;
+      const double* __restrict__ As = (pq & 1) ? Mr : Mi;
+      const int col = 16 * mt + l15, y = 16 * nt + l15;
+      uint32_t mE = 0u, mO = 0u, d8 = 0u;
+      if (TABMODE == kTabLds1D) {
+        const uint32_t yy = mod_magic((uint32_t)y, (uint32_t)bh, sc.m_bh);
+        mE = 8u * mod_magic((uint32_t)(2 * l4) * yy, (uint32_t)bh, sc.m_bh);
+        mO = 8u * mod_magic((uint32_t)(2 * l4 + 1) * yy, (uint32_t)bh, sc.m_bh);
+        d8 = 8u * mod_magic(8u * yy, (uint32_t)bh, sc.m_bh);
       }
+      auto kstep = [&](const int k0, const bool last) {
+        int rE = 2 * (k0 + l4), rO = rE + 1;
+        const bool vE = rE < KR, vO = rO < KR;
+        if (last) { rE = min(rE, KR - 1); rO = min(rO, KR - 1); }
+        double aEc = Ac[rE * SX + col], aEs = As[rE * SX + col], aOc = Ac[rO * SX + col], aOs = As[rO * SX + col];
+        if (last) {
+          if (!vE) { aEc = 0.0; aEs = 0.0; }
+          if (!vO) { aOc = 0.0; aOs = 0.0; }
+        }
+        double bEc, bEs, bOc, bOs;
+        if (TABMODE == kTabLds1D) {
+          const char* tE = (const char*)tabA + mE;
+          const char* tO = (const char*)tabA + mO;
+          bEc = *(const double*)tE; bEs = *(const double*)(tE + 8 * kT1S);
+          bOc = *(const double*)tO; bOs = *(const double*)(tO + 8 * kT1S);
+          mE += d8; mE = min(mE, mE - n8);            // unsigned: m - n8 wraps to a huge value when m < n8
+          mO += d8; mO = min(mO, mO - n8);
+        } else {
+          bEc = T2[rE * NR + y]; bEs = T2[KR * NR + rE * NR + y];
+          bOc = T2[rO * NR + y]; bOs = T2[KR * NR + rO * NR + y];
+        }
+        cE = __builtin_amdgcn_mfma_f64_16x16x4f64(aEc, bEc, cE, 0, 0, 0);
+        sE = __builtin_amdgcn_mfma_f64_16x16x4f64(aEs, bEs, sE, 0, 0, 0);
+        cO = __builtin_amdgcn_mfma_f64_16x16x4f64(aOc, bOc, cO, 0, 0, 0);
+        sO = __builtin_amdgcn_mfma_f64_16x16x4f64(aOs, bOs, sO, 0, 0, 0);
+      };
+      for (int k0 = 0; k0 < Ke - 4; k0 += 4) kstep(k0, false);
+      kstep(Ke - 4, true);
     }
-    uc[j] = ac; us[j] = as;
+    uc[j] = cE; us[j] = sE;
+    if (j + 1 < UPW) { uc[j + 1] = cO; us[j + 1] = sO; }
   }
 }
 
+// Units j, j + 1 hold the even- and odd-ky half-sums of pair w + (j / 2) NW (dft_stage1): rows y, bh - y, hh - y and hh + y of T^T.
 // FOLD_CK: the rows kx of T^T are scaled by the Hermitian-half factor c_kx (1 for kx in {0, bw / 2}, else 2) here instead of
-// in the stage-2 operand table (TABMODE 2 reads plain cos / sin): (2 a) b and a (2 b) are the same product, exactly.
+// in the stage-2 operand table (kTabLds1D reads plain cos / sin): (2 a) b and a (2 b) are the same product, exactly.
 template <int NW, int UPW, bool FOLD_CK = false>
 __device__ __forceinline__ void dft_tt_write(const int w, const int lane, const PropGeom& g, double* TT, const v4f64 (&uc)[UPW],
                                              const v4f64 (&us)[UPW]) {
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int n_mt = g.M1 >> 4, n_nt = g.NR >> 4;
-  const int n_t1 = n_mt * n_nt;
+  const int n_mt = g.M1 >> 4;
   const int ST = g.ST, Kc = g.Kc, hh = g.hh, bh = g.bh;
-  if (!(bh & 1)) {
-    // even block height: units j, j + 1 hold the even- and odd-ky half-sums of pair w + (j / 2) NW (dft_stage1); rows y and hh - y
-    const int n_pairs = 2 * n_mt * (g.NRh >> 4);
+  const int n_pairs = 2 * n_mt * (g.NRh >> 4);
 #pragma unroll
-    for (int j = 0; j + 1 < UPW; j += 2) {
-      const int pq = w + (j >> 1) * NW;
-      if (pq < n_pairs) {
-        const int t = pq >> 1;
-        const bool im = pq & 1;
-        const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
-        const int y = 16 * nt + l15;
-        if (y <= g.hq) {
-          const int ym = hh - y;
-          double* __restrict__ Th = TT + (im ? Kc * ST : 0);   // real rows, then imaginary rows
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int kx = 16 * mt + l4 + 4 * q;
-            if (kx < Kc) {
-              const double U = uc[j][q] + uc[j + 1][q], V = us[j][q] + us[j + 1][q];
-              const double Um = uc[j][q] - uc[j + 1][q], Vm = us[j + 1][q] - us[j][q];
-              double t1 = im ? U + V : U - V, t2 = im ? U - V : U + V;
-              double t3 = im ? Um + Vm : Um - Vm, t4 = im ? Um - Vm : Um + Vm;
-              if (FOLD_CK && kx != 0 && kx != g.hw) { t1 = 2.0 * t1; t2 = 2.0 * t2; t3 = 2.0 * t3; t4 = 2.0 * t4; }
-              Th[kx * ST + y] = t1;
-              if (y > 0 && y < hh) Th[kx * ST + (bh - y)] = t2;
-              if (ym != y) {
-                Th[kx * ST + ym] = t3;
-                if (ym > 0 && ym < hh) Th[kx * ST + (bh - ym)] = t4;
-              }
-            }
-          }
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < UPW; ++j) {
-    const int u = w + j * NW;
-    const int t = u >> 1;
-    if (t < n_t1) {
+  for (int j = 0; j + 1 < UPW; j += 2) {
+    const int pq = w + (j >> 1) * NW;
+    if (pq < n_pairs) {
+      const int t = pq >> 1;
+      const bool im = pq & 1;
       const int nt = tile_div(t, g.q_mt), mt = t - nt * n_mt;
       const int y = 16 * nt + l15;
-      if (y <= hh) {
-        double* __restrict__ Th = TT + ((u & 1) ? Kc * ST : 0);   // real rows, then imaginary rows
+      if (y <= g.hq) {
+        const int ym = hh - y;
+        double* __restrict__ Th = TT + (im ? Kc * ST : 0);   // real rows, then imaginary rows
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int kx = 16 * mt + l4 + 4 * q;
           if (kx < Kc) {
-            double t1 = (u & 1) ? uc[j][q] + us[j][q] : uc[j][q] - us[j][q];
-            double t2 = (u & 1) ? uc[j][q] - us[j][q] : uc[j][q] + us[j][q];
-            if (FOLD_CK && kx != 0 && kx != g.hw) { t1 = 2.0 * t1; t2 = 2.0 * t2; }
+            const double U = uc[j][q] + uc[j + 1][q], V = us[j][q] + us[j + 1][q];
+            const double Um = uc[j][q] - uc[j + 1][q], Vm = us[j + 1][q] - us[j][q];
+            double t1 = im ? U + V : U - V, t2 = im ? U - V : U + V;
+            double t3 = im ? Um + Vm : Um - Vm, t4 = im ? Um - Vm : Um + Vm;
+            if (FOLD_CK && kx != 0 && kx != g.hw) { t1 = 2.0 * t1; t2 = 2.0 * t2; t3 = 2.0 * t3; t4 = 2.0 * t4; }
             Th[kx * ST + y] = t1;
             if (y > 0 && y < hh) Th[kx * ST + (bh - y)] = t2;
+            if (ym != y) {
+              Th[kx * ST + ym] = t3;
+              if (ym > 0 && ym < hh) Th[kx * ST + (bh - ym)] = t4;
+            }
           }
         }
       }
@@ -588,8 +455,8 @@ __device__ __forceinline__ SlotX slot_x(const int w, const int j, const int NW, 
 
 // ---- stage 2 (MFMA): E = Tr^T Gc, O = Ti^T Gs on x in [0, hw]; results stay in registers -----------
 // tile t of the (N1/16) x (M1/16) output grid goes to wave t mod NW
-// TABMODE as in dft_stage1; 2: tabG = 1-D table of the block width, cos at [m], -sin at [kT1S + m]; T^T carries c_kx
-template <int NW, int MAXT, int TABMODE>
+// TabMode as for dft_stage1; kTabLds1D: tabG = 1-D table of the block width, cos at [m], -sin at [kT1S + m]; T^T carries c_kx
+template <int NW, int MAXT, TabMode TABMODE>
 __device__ __forceinline__ void dft_stage2(const int w, const int lane, const ProposeArgs& a, const PropScalars& sc, const PropGeom& g,
                                            const double* TT, const double* tabG, v4f64 (&fe)[MAXT], v4f64 (&fo)[MAXT]) {
   const int l15 = lane & 15, l4 = lane >> 4;
@@ -597,13 +464,13 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
   const int n_mt2 = g.N1 >> 4, n_nt2 = M1 >> 4;
   const int n_t2 = n_mt2 * n_nt2;
   if constexpr (MAXT >= 2) if (g.split2) {
-    // ---- even block width, split by the parity of kx (as dft_stage1 by the parity of ky): E[x] = Ee + Eo, E[hw - x] = Ee - Eo,
+    // ---- split by the parity of kx (as dft_stage1 by the parity of ky): E[x] = Ee + Eo, E[hw - x] = Ee - Eo,
     // O[x] = Oe + Oo, O[hw - x] = -Oe + Oo, the half-sums over kx = 2 m and kx = 2 m + 1 for x in [0, hw / 2] only.  Slot j of the wave
     // leaves with (E, O) of x0, slot j + 1 with (E, O) of hw - x0 (slot_x): standardise and emit_field treat them as two tiles.
     const int n_tp = n_mt2 * (g.M1h >> 4);
     const int Kce = g.Kce, bw = g.bw;
     const uint32_t n8 = 8u * (uint32_t)bw;
-    const double* __restrict__ G2 = (TABMODE == 1) ? tabG : (TABMODE == 0 ? a.tables + sc.g_off : nullptr);      // [cos: Kc x M1][-sin: Kc x M1]
+    const double* __restrict__ G2 = (TABMODE == kTabLds2D) ? tabG : (TABMODE == kTabGlobal2D ? a.tables + sc.g_off : nullptr);      // [cos: Kc x M1][-sin: Kc x M1]
 #pragma unroll
     for (int j = 0; j + 1 < MAXT; j += 2) {
       const int tp = w + (j >> 1) * NW;
@@ -612,7 +479,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
         const int nt = tile_div(tp, g.q_mt2), mt = tp - nt * n_mt2;
         const int ycol = 16 * mt + l15, x = 16 * nt + l15;
         uint32_t mE = 0u, mO = 0u, d8 = 0u;
-        if (TABMODE == 2) {
+        if (TABMODE == kTabLds1D) {
           const uint32_t xx = mod_magic((uint32_t)x, (uint32_t)bw, sc.m_bw);
           mE = 8u * mod_magic((uint32_t)(2 * l4) * xx, (uint32_t)bw, sc.m_bw);
           mO = 8u * mod_magic((uint32_t)(2 * l4 + 1) * xx, (uint32_t)bw, sc.m_bw);
@@ -628,7 +495,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
             if (!vO) { aOr = 0.0; aOi = 0.0; }
           }
           double bEc, bEs, bOc, bOs;
-          if (TABMODE == 2) {
+          if (TABMODE == kTabLds1D) {
             const char* tE = (const char*)tabG + mE;
             const char* tO = (const char*)tabG + mO;
             bEc = *(const double*)tE; bEs = *(const double*)(tE + 8 * kT1S);
@@ -652,8 +519,9 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
     }
     return;
   }
-  if constexpr (TABMODE == 2) {
-    // two tiles at a time, as in dft_stage1
+  if constexpr (TABMODE == kTabLds1D) {
+    // Two tiles at a time: per K step the eight operands of both are requested together, then four independent MFMAs follow --
+    // one exposed LDS round trip per four MFMAs instead of per two (a lone tile, the odd one out, runs two K steps per turn).
     struct Tile { const double* a_p; uint32_t m8, d8; bool on; };
     const uint32_t n8 = 8u * (uint32_t)g.bw;
     auto setup = [&](const int j) {
@@ -673,7 +541,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
       const char* tb = (const char*)tabG + x.m8;
       a1 = x.a_p[k0 * ST]; a2 = x.a_p[(Kc + k0) * ST]; b1 = *(const double*)tb; b2 = *(const double*)(tb + 8 * kT1S);
       x.m8 += x.d8;
-      x.m8 = min(x.m8, x.m8 - n8);
+      x.m8 = min(x.m8, x.m8 - n8);            // unsigned: m8 - n8 wraps to a huge value when m8 < n8
     };
 #pragma unroll
     for (int j = 0; j < MAXT; j += 2) {
@@ -736,7 +604,7 @@ __device__ __forceinline__ void dft_stage2(const int w, const int lane, const Pr
 #pragma unroll 2
       for (int k0 = 0; k0 < Kc; k0 += 4) {
         double gc, gs;
-        if (TABMODE == 1) {
+        if (TABMODE == kTabLds2D) {
           const int bo = (l4 + k0) * M1 + 16 * nt + l15;
           gc = tabG[bo]; gs = tabG[Kc * M1 + bo];
         } else {
@@ -860,9 +728,10 @@ __device__ __forceinline__ double standardise(const int w, const int lane, const
 // out = (t + n * sqrt(nug)) * mask with t = fe * gain, fe and gain as standardise leaves them.  Without a nugget the finished value is stored
 // directly; with one, t is stored first and nugget_pass adds the nugget normals and applies the mask -- the same
 // operations in the same order.  Cell (y, x) goes to out[omap(y, x)], or nowhere if omap returns a negative index.
-// MASKMODE: where the edge mask of a cell comes from -- 0 the packed table in global memory, 1 `mreg` (mask_prefetch), 2 a table
+// MaskMode: where the edge mask of a cell comes from -- the packed table in global memory, `mreg` (mask_prefetch), or a table
 // in LDS indexed by the cell's distance to the block border, m1d[min(y, bh - 1 - y, x, bw - 1 - x)] (BlockTable::mask1d).
-template <int NW, int MAXT, int MASKMODE, class OMap>
+enum MaskMode : int { kMaskGlobal, kMaskRegs, kMaskLds1D };
+template <int NW, int MAXT, MaskMode MASKMODE, class OMap>
 __device__ __forceinline__ void emit_field(const int w, const int lane, const ProposeArgs& a, const PropScalars& sc, const PropGeom& g,
                                            const v4f64 (&fe)[MAXT], const v4f64 (&fo)[MAXT], const double (&mreg)[MAXT][8],
                                            const double gain, const bool with_nugget,
@@ -888,8 +757,8 @@ __device__ __forceinline__ void emit_field(const int w, const int lane, const Pr
           const int oi = omap(y, xx);
           const double v = (half ? fo[j][q] : fe[j][q]) * gain;
           double mk;
-          if (MASKMODE == 2) mk = m1d[min(min(y, bh - 1 - y), min(xx, bw - 1 - xx))];
-          else mk = (MASKMODE == 1) ? mreg[j][2 * q + half] : mask[o];
+          if (MASKMODE == kMaskLds1D) mk = m1d[min(min(y, bh - 1 - y), min(xx, bw - 1 - xx))];
+          else mk = (MASKMODE == kMaskRegs) ? mreg[j][2 * q + half] : mask[o];
           if (oi >= 0) out[oi] = with_nugget ? v : v * mk;
         }
       }
@@ -935,25 +804,24 @@ __device__ __forceinline__ void propose_field(const int tid, const ProposeArgs& 
   double* mt = red + 32;                      // [kMathTabDoubles] math_tables.h
   for (int i = tid; i < kMathTabDoubles; i += NT) mt[i] = a.mathtab[i];
   __syncthreads();
-  // even shapes (every table of the reference) on handles of the strip family: red[16 .. 24) is free beside tiles_sum's 16 slots.  Odd sizes keep the
-  // pass over the field: the half-plane's last column / row is then no self-conjugate entry and the stages weight it by convention
-  double* pw_red = (a.parseval && NW == 8 && !((sc.bh | sc.bw) & 1)) ? red + 16 : nullptr;
-  coef_items<NT, NOISE_IN>(tid, 0, g.nrow * g.ncol, true, a, sc, g, seed, step, plds, a.lds_x_half, noise, mt, pw_red);
+  // handles of the strip family: red[16 .. 24) is free beside tiles_sum's 16 slots
+  double* pw_red = (a.parseval && NW == 8) ? red + 16 : nullptr;
+  coef_items<NT, NOISE_IN>(tid, a, sc, g, seed, step, plds, noise, mt, pw_red);
   __syncthreads();
   // Mean of the field (MCMC.py:248 subtracts it): every non-DC term of the inverse DFT sums to zero over the block, so
   // mean = X[0][0] / (bh bw) with X[0][0] = Pr[0] (real: its own conjugate partner).  Read before T^T overlays the plane.
   const double dc = plds[0];
   v4f64 uc[UPW], us[UPW];
-  dft_stage1<NW, UPW, false>(wave, lane, a, sc, g, plds, nullptr, uc, us);
+  dft_stage1<NW, UPW, kTabGlobal2D>(wave, lane, a, sc, g, plds, nullptr, uc, us);
   __syncthreads();
   dft_tt_write<NW, UPW>(wave, lane, g, plds, uc, us);
   __syncthreads();
   v4f64 fe[MAXT], fo[MAXT];
-  dft_stage2<NW, MAXT, false>(wave, lane, a, sc, g, plds, nullptr, fe, fo);
+  dft_stage2<NW, MAXT, kTabGlobal2D>(wave, lane, a, sc, g, plds, nullptr, fe, fo);
   double mreg[MAXT][8];
   const double gain = standardise<NW, MAXT>(wave, lane, sc, g, dc, red, fe, fo, pw_red);
   const bool with_nugget = NOISE_IN ? (noise.nug != nullptr) : (a.rf.nugget_max > 0.0);
-  emit_field<NW, MAXT, false>(wave, lane, a, sc, g, fe, fo, mreg, gain, with_nugget, out, omap);
+  emit_field<NW, MAXT, kMaskGlobal>(wave, lane, a, sc, g, fe, fo, mreg, gain, with_nugget, out, omap);
   if (with_nugget) {
     __syncthreads();
     nugget_pass<NT, NOISE_IN>(tid, a, sc, g, seed, step, noise, out, omap, mt);

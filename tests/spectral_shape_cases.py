@@ -125,7 +125,7 @@ def prop_geom(bh, bw, split2_allowed=False):
     g["N1"] = (bh + 15) & ~15
     g["hq"] = g["hh"] >> 1; g["NRh"] = (g["hq"] + 16) & ~15; g["Ke"] = (g["hq"] + 4) & ~3
     g["hqx"] = g["hw"] >> 1; g["M1h"] = (g["hqx"] + 16) & ~15; g["Kce"] = (g["hqx"] + 4) & ~3
-    g["split2"] = bool(split2_allowed) and not (bw & 1) and (g["N1"] >> 4) * (g["M1h"] >> 4) <= 8
+    g["split2"] = bool(split2_allowed) and (g["N1"] >> 4) * (g["M1h"] >> 4) <= 8
     return g
 
 

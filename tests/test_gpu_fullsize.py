@@ -102,6 +102,11 @@ def test_block_as_large_as_the_grid_and_single_chain():
         eng.set_blocks(np.array([[18], [16]]), None)
     with pytest.raises(GsmError):
         eng.set_blocks(np.array([[7], [8]]), None)
+    # ... in either direction: the proposal kernels' DFT stages exist for even heights and widths only, and this refusal is their gate
+    with pytest.raises(GsmError):
+        eng.set_blocks(np.array([[8], [7]]), None)
+    with pytest.raises(GsmError):
+        eng.set_blocks(np.array([[7], [7]]), None)
     eng.close()
 
 
