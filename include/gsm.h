@@ -474,6 +474,34 @@ int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32
                    int32_t hw, double radius, int32_t num_points, double sill,
                    double* est, double* var, int32_t* n_neighbours, void* stream);
 
+/* ---- a variogram per cell: non-stationary interpolate.sgs / interpolate.krige ------------------------------------------------
+ * The reference takes every variogram parameter as a number or as a map of the grid's shape and builds a local_vario for each
+ * visited cell (interpolate.py:56-62, :141-147, scalars broadcast by _preprocess :226-231): the kriging system of cell (i, j) is
+ * assembled from the parameters AT (i, j), whatever its neighbours' own parameters are.  gsm_sgs_grid_local / gsm_krige_grid_local
+ * are gsm_sgs_grid / gsm_krige_grid with `lag_cov, lag_mi, lag_mj, sill` replaced by
+ *   local    [dev, H*W*6]               per cell R00, R01, R10, R11, sill, nugget: R = make_rotation_matrix(azimuth, major_range,
+ *                                       minor_range) (_krige.py:83-103), computed by the caller.  Rows of cells that are never
+ *                                       visited may hold NaN
+ *   vtype                               GSM_VTYPE_EXPONENTIAL, GSM_VTYPE_GAUSSIAN or GSM_VTYPE_SPHERICAL (covariance.py:4-15);
+ *                                       anything else (GSM_VTYPE_MATERN: no Bessel K on the device) is GSM_E_UNSUPPORTED
+ * No covariance table exists when every cell has its own model: each covariance of a system is evaluated in the kernel from
+ * the two points' coordinates (x_axis, y_axis; either may descend), dx = x_a - x_b, dy = y_a - y_b, u = dx R00 + dy R10,
+ * v = dx R01 + dy R11, h = sqrt(u u + v v), C(h) the model with the cell's sill and nugget.  (The reference multiplies the
+ * absolute coordinates by R and subtracts afterwards, make_sigma / make_rho, _krige.py:105-144.)  The kriging variance is the
+ * cell's sill - sum w rho.  Every other argument, the search, the solve, the records, errors and limits are those of the table
+ * functions; the "lag covariance table" error cannot occur.
+ * Replaces: the local_vario of interpolate.krige and interpolate.sgs (gstatsim_custom/interpolate.py:56-62, :141-147),
+ * make_rotation_matrix's use, make_sigma, make_rho (gstatsim_custom/_krige.py:105-144), the covariance models
+ * (gstatsim_custom/covariance.py:4-15). */
+int gsm_sgs_grid_local(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                       const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                       const double* y_axis, const double* local, int32_t vtype, int32_t hw, double radius,
+                       int32_t num_points, int32_t seg_cells, double* trace, void* stream);
+int gsm_krige_grid_local(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells,
+                         const double* x_axis, const double* y_axis, const double* local, int32_t vtype,
+                         int32_t hw, double radius, int32_t num_points,
+                         double* est, double* var, int32_t* n_neighbours, void* stream);
+
 /* One batch of small-scale iterations in ONE call: for j < n_iters, in the order of chain_sgs.run's loop body
  * (MCMC.py:1741-1822) -- [gsm_qt_transform cur -> next] gsm_sgs_blocks_batch [gsm_sgs_finish | gsm_qt_transform next ->
  * proposed, gsm_sgs_loss, gsm_sgs_decide, gsm_sgs_commit(_map)] -- with iteration j's draws at windows + 4*n_chains*j,

@@ -205,6 +205,8 @@ def load() -> C.CDLL:
     lib.gsm_sgs_set_kriging.argtypes = [vp, i32, vp]
     lib.gsm_sgs_grid.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, i32, vp, vp]
     lib.gsm_krige_grid.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, vp, vp]
+    lib.gsm_sgs_grid_local.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, dbl, i32, i32, vp, vp]
+    lib.gsm_krige_grid_local.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, dbl, i32, vp, vp, vp, vp]
     lib.gsm_draw_pcg64.argtypes = [vp, i32, C.POINTER(RfParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.gsm_sgs_state_init.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.gsm_sgs_finish.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]

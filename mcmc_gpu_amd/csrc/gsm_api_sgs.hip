@@ -1,4 +1,4 @@
-// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid.
+// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid, each with its per-cell-variogram twin (gsm_*_local).
 #include "gsm_context.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -101,13 +101,19 @@ extern "C" int gsm_sgs_set_kriging(gsm_handle h, int32_t ktype, const double* gl
   return GSM_OK;
 }
 
-extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
-                            const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
-                            const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
-                            int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream) {
-  if (!h) return GSM_E_ARG;
-  const std::string w = "gsm_sgs_grid";
-  if (!grids || !path || !path_off || !draws || !x_axis || !y_axis || !lag_cov) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+// the model of a per-cell variogram table: the three the device evaluates (Matern needs Bessel K)
+static int local_vtype_check(gsm_handle h, const std::string& w, int32_t vtype) {
+  if (vtype != GSM_VTYPE_EXPONENTIAL && vtype != GSM_VTYPE_GAUSSIAN && vtype != GSM_VTYPE_SPHERICAL)
+    return fail(h, GSM_E_UNSUPPORTED, w + ": vtype must be GSM_VTYPE_EXPONENTIAL, GSM_VTYPE_GAUSSIAN or GSM_VTYPE_SPHERICAL");
+  return GSM_OK;
+}
+
+// gsm_sgs_grid (lag_cov, local NULL) and gsm_sgs_grid_local (local, lag_cov NULL; lag_mi, lag_mj, sill unused)
+static int sgs_grid_run(gsm_handle h, const std::string& w, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                        const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                        const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, const double* local, int32_t vtype,
+                        int32_t hw, double radius, int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream) {
+  if (!grids || !path || !path_off || !draws || !x_axis || !y_axis || (!lag_cov && !local)) return fail(h, GSM_E_ARG, w + ": NULL pointer");
   if (draw_kind != GSM_DRAW_NORMAL && draw_kind != GSM_DRAW_TRUNCATED) return fail(h, GSM_E_ARG, w + ": draw_kind must be GSM_DRAW_NORMAL or GSM_DRAW_TRUNCATED");
   if ((draw_kind == GSM_DRAW_TRUNCATED) != (lower != nullptr) || (lower != nullptr) != (upper != nullptr))
     return fail(h, GSM_E_ARG, w + ": bounds (lower and upper) go with GSM_DRAW_TRUNCATED and only with it");
@@ -141,7 +147,7 @@ extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, co
   e = launch_sgs_grid_ranks(a, max_path, st);
   for (int s0 = 0; e == hipSuccess && s0 < max_path; s0 += seg_cap) {
     a.seg0 = s0; a.seg_len = std::min(seg_cap, max_path - s0);
-    e = launch_sgs_grid_segment(a, st);
+    e = launch_sgs_grid_segment(a, st, local, vtype);
   }
   if (e != hipSuccess) return fail(h, GSM_E_HIP, w + ": " + hipGetErrorString(e));
   int32_t flag = 0;
@@ -158,14 +164,33 @@ extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, co
   return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
 }
 
-extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
-                              const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
-                              int32_t num_points, double sill, double* est, double* var, int32_t* n_neighbours, void* stream) {
+extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                            const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                            const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
+                            int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream) {
   if (!h) return GSM_E_ARG;
-  const std::string w = "gsm_krige_grid";
+  return sgs_grid_run(h, "gsm_sgs_grid", grids, path, path_off, max_path, draws, lower, upper, draw_kind, x_axis, y_axis, lag_cov, lag_mi,
+                      lag_mj, nullptr, 0, hw, radius, num_points, sill, seg_cells, trace, stream);
+}
+
+extern "C" int gsm_sgs_grid_local(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
+                                  const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
+                                  const double* y_axis, const double* local, int32_t vtype, int32_t hw, double radius,
+                                  int32_t num_points, int32_t seg_cells, double* trace, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (int rc = local_vtype_check(h, "gsm_sgs_grid_local", vtype)) return rc;
+  return sgs_grid_run(h, "gsm_sgs_grid_local", grids, path, path_off, max_path, draws, lower, upper, draw_kind, x_axis, y_axis, nullptr, 0,
+                      0, local, vtype, hw, radius, num_points, 0.0, seg_cells, trace, stream);
+}
+
+// gsm_krige_grid (lag_cov, local NULL) and gsm_krige_grid_local (local, lag_cov NULL; lag_mi, lag_mj, sill unused)
+static int krige_grid_run(gsm_handle h, const std::string& w, const double* grid, const int32_t* cells, int32_t n_cells,
+                          const double* x_axis, const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj,
+                          const double* local, int32_t vtype, int32_t hw, double radius, int32_t num_points, double sill, double* est,
+                          double* var, int32_t* n_neighbours, void* stream) {
   if (n_cells < 0 || (int64_t)n_cells > (int64_t)h->H * h->W) return fail(h, GSM_E_ARG, w + ": n_cells must be in [0, H * W]");
   if (n_cells == 0) return GSM_OK;
-  if (!grid || !cells || !x_axis || !y_axis || !lag_cov || !est || !var || !n_neighbours) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  if (!grid || !cells || !x_axis || !y_axis || (!lag_cov && !local) || !est || !var || !n_neighbours) return fail(h, GSM_E_ARG, w + ": NULL pointer");
   if (int rc = sgs_check_search(h, w, hw, num_points, radius, lag_mi, lag_mj)) return rc;
   if (h->H < 2 || h->W < 2 || h->H > 32767 || h->W > 32767) return fail(h, GSM_E_ARG, w + ": grid sides must be in [2, 32767]");
   if (h->n_chains != 1) return fail(h, GSM_E_ARG, w + ": one grid per handle (create it with n_chains = 1)");
@@ -177,7 +202,7 @@ extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* c
   a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov; a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points;
   a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.radius = radius; a.sill = sill;
   a.est = est; a.var = var; a.n = n_neighbours; a.err = h->d_err.get();
-  HIPCHK(h, launch_krige_grid(a, st));
+  HIPCHK(h, launch_krige_grid(a, st, local, vtype));
   int32_t flag = 0;
   if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
   if (!flag) return GSM_OK;
@@ -188,6 +213,23 @@ extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* c
   if (flag & 64) return fail(h, GSM_E_DEVICE_DATA, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
                                                     "(it must cover twice the widest search radius)");
   return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+}
+
+extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
+                              const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
+                              int32_t num_points, double sill, double* est, double* var, int32_t* n_neighbours, void* stream) {
+  if (!h) return GSM_E_ARG;
+  return krige_grid_run(h, "gsm_krige_grid", grid, cells, n_cells, x_axis, y_axis, lag_cov, lag_mi, lag_mj, nullptr, 0, hw, radius,
+                        num_points, sill, est, var, n_neighbours, stream);
+}
+
+extern "C" int gsm_krige_grid_local(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
+                                    const double* y_axis, const double* local, int32_t vtype, int32_t hw, double radius,
+                                    int32_t num_points, double* est, double* var, int32_t* n_neighbours, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (int rc = local_vtype_check(h, "gsm_krige_grid_local", vtype)) return rc;
+  return krige_grid_run(h, "gsm_krige_grid_local", grid, cells, n_cells, x_axis, y_axis, nullptr, 0, 0, local, vtype, hw, radius,
+                        num_points, 0.0, est, var, n_neighbours, stream);
 }
 
 extern "C" int gsm_sgs_check(gsm_handle h, void* stream) {

@@ -280,9 +280,10 @@ struct KrigeGridArgs {
   int32_t* n;              // [n_cells] neighbours; 0 where the cell raised an error
   int32_t* err;
 };
-hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st);
+// `local` non-null (and a.lag null): a variogram per cell, [H*W][6] = R00 R01 R10 R11 sill nugget, of model `vtype` (GSM_VTYPE_*)
+hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
-hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st);      // weights, then values of one segment
+hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);   // weights, then values of one segment
 hipError_t launch_sgs_blocks(const SgsArgs& a, int launch_cells, hipStream_t st);
 hipError_t launch_sgs_weights(const SgsArgs& a, int launch_cells, hipStream_t st);     // ranks + records
 hipError_t launch_sgs_sequence(const SgsArgs& a, hipStream_t st);                      // value pass

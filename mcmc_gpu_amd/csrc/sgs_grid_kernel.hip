@@ -18,6 +18,7 @@
 //   sgs_grid_weights_kernel  one wavefront per (realisation, path slot) of a segment, all side by side: the ring search with its
 //                        radius widening (a cell qualifies when its rank is below the slot), then the kriging system and its
 //                        Gauss-Jordan solve -- both sgs_search.h's, shared with the block kernel -> a record per cell.
+//                        sgs_grid_weights_local_kernel is the same pass with a variogram per cell (interpolate.py:141-147).
 //                        A neighbour is either a value (conditioning data, or a path cell whose bounds coincide) or an
 //                        earlier path cell, NaN-boxed (slot << 25 | cell); no simulated value is read, so a segment's
 //                        records do not wait for the values before it;
@@ -72,10 +73,11 @@ __global__ __launch_bounds__(256) void sgs_grid_slot_kernel(const SgsGridArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// sgs_grid_weights_kernel: one 64-lane workgroup per (slot of the segment, realisation)
+// sgs_grid_weights_kernel: one 64-lane workgroup per (slot of the segment, realisation).  kLocal: a variogram per cell
+// (sgs_grid_weights_local_kernel) -- `local` [H*W][6] and `vtype` as sgs_search.h's LocalCov takes them, a.lag and a.sill unused
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs a) {
-  __shared__ SgsSearchLds L;
+template <bool kLocal>
+__device__ __forceinline__ void sgs_grid_weights_cell(const SgsGridArgs& a, SgsSearchLds& L, const double* __restrict__ local, int vtype) {
   const int r = blockIdx.y, lane = threadIdx.x;
   const int slot = a.seg0 + blockIdx.x;
   const int64_t p0 = a.path_off[r];
@@ -106,8 +108,16 @@ __global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs 
   const bool lagr = a.ktype == 0;
   double w_l, rho_l;
   int my_i, my_j;                                                // the neighbour's (row, column): only the block kernel's record needs it
-  if (const int e = krige_solve<false>(L, n, i0, j0, H, W, a.lag, a.mi, a.mj, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
-  double var = a.sill - dev::wave64_sum(w_l * rho_l);
+  double sill;
+  if constexpr (kLocal) {
+    const LocalCov cov{local + 6 * (size_t)cell, a.xs, a.ys, vtype};
+    sill = cov.p[4];
+    if (const int e = krige_solve(L, n, i0, j0, H, W, cov, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
+  } else {
+    sill = a.sill;
+    if (const int e = krige_solve<false>(L, n, i0, j0, H, W, a.lag, a.mi, a.mj, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
+  }
+  double var = sill - dev::wave64_sum(w_l * rho_l);
   var = fabs(var);                                               // interpolate.py:168
   const double sw = dev::wave64_sum(w_l);
   if (lane < kSgsMaxPts) {
@@ -128,6 +138,14 @@ __global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs 
     hd.c1 = lagr ? (1.0 - sw) / (double)n : a.gmean[r] * (1.0 - sw);
     a.rec_hdr[rec] = hd;
   }
+}
+__global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs a) {
+  __shared__ SgsSearchLds L;
+  sgs_grid_weights_cell<false>(a, L, nullptr, 0);
+}
+__global__ __launch_bounds__(64) void sgs_grid_weights_local_kernel(const SgsGridArgs a, const double* __restrict__ local, int vtype) {
+  __shared__ SgsSearchLds L;
+  sgs_grid_weights_cell<true>(a, L, local, vtype);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -238,9 +256,10 @@ hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t
   if (max_path > 0) hipLaunchKernelGGL(sgs_grid_slot_kernel, dim3((max_path + 255) / 256, a.n_real), dim3(256), 0, st, a);
   return hipGetLastError();
 }
-hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st) {
-  if (!grid_args_ok(a)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sgs_grid_weights_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a);
+hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st, const double* local, int vtype) {
+  if (!grid_args_ok(a) || (a.lag == nullptr) == (local == nullptr)) return hipErrorInvalidValue;
+  if (local) hipLaunchKernelGGL(sgs_grid_weights_local_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a, local, vtype);
+  else hipLaunchKernelGGL(sgs_grid_weights_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a);
   hipLaunchKernelGGL(sgs_grid_values_kernel, dim3(a.n_real), dim3(64 * kGridSeqWaves), 0, st, a);
   return hipGetLastError();
 }

@@ -1,7 +1,9 @@
 // The per-cell work that the block SGS kernel (sgs_kernel.hip), the whole-grid SGS kernel (sgs_grid_kernel.hip) and the kriging
 // kernel (krige_grid_kernel.hip) share, one wavefront per cell: the octant ring search with the reference's radius widening
-// (octant_ring_search; a kernel says which cells qualify) and the kriging system from the lag table with its Gauss-Jordan solve in
-// registers (krige_solve).  sgs_kernel.hip's header comment describes the search and the solve.
+// (octant_ring_search; a kernel says which cells qualify) and the kriging system with its Gauss-Jordan solve in registers
+// (krige_solve), its covariances from the lag table of the call's one variogram (LagTableCov) or evaluated from the variogram of
+// the cell that is solved (LocalCov: the whole-grid kernels' non-stationary form).  sgs_kernel.hip's header comment describes the
+// search and the solve.
 #pragma once
 #include "device_util.h"
 #include <math.h>
@@ -231,64 +233,135 @@ struct GjStep<49> {
   static __device__ __forceinline__ void run(double (&)[50], int, int, bool, double, double, double&, bool&) {}
 };
 
+// ---- where krige_solve takes its covariances from -------------------------------------------------------------------------------
+// One variogram for the whole call: `lag`, (2 mi + 1) x (2 mj + 1) covariances indexed by the integer lag between two cells.
+// kWholeGridTable compiles the row loads of a table that spans every lag of the grid.
+template <bool kWholeGridTable>
+struct LagTableCov {
+  static constexpr bool kLocal = false, kWholeGrid = kWholeGridTable;
+  const double* __restrict__ lag;
+  int mi, mj;
+};
+// A variogram per cell (the reference's local_vario, interpolate.py:56-62, :141-147): `p` points at the six numbers of the cell
+// that is being solved -- R00, R01, R10, R11 of make_rotation_matrix (_krige.py:83-103, computed on the host), sill, nugget --
+// and every covariance is evaluated from the two points' coordinates.  vtype: GSM_VTYPE_EXPONENTIAL / _GAUSSIAN / _SPHERICAL.
+struct LocalCov {
+  static constexpr bool kLocal = true;
+  const double* __restrict__ p;
+  const double* __restrict__ xs;
+  const double* __restrict__ ys;
+  int vtype;
+};
+
+// covariance.py:4-15 on the squared normalised lag h2 (c0 = sill - nugget), the reference's oddities included: its "nugget" only
+// scales the model, and the spherical model is sill - 1 beyond the range.  Not inlined: krige_fill_local calls it from a loop that is
+// unrolled 48 times over a row held in registers, and 48 copies of exp's polynomial push that row into scratch.
+__device__ __noinline__ double local_cov_of(double h2, double c0, double sill, int vtype) {
+  const double h = sqrt(h2);
+  if (vtype == 0) return c0 * exp(-3.0 * h);
+  if (vtype == 1) return c0 * exp(-3.0 * (h * h));
+  const double c = c0 - 1.5 * h + 0.5 * (h * h * h);
+  return (h > 1.0) ? sill - 1.0 : c;
+}
+
+// This lane's row of [Sigma 1 | rho] (r[0..47], r[48], r[49]) from the cell's own variogram.  A pair's lag is taken from the
+// coordinates (either axis may descend, the cells need not be square), rotated and scaled by R: u = dx R00 + dy R10, v = dx R01 + dy R11, h2 = u u + v v.  The reference multiplies
+// the absolute coordinates by R and subtracts afterwards (make_sigma / make_rho, _krige.py:105-144); subtracting first loses
+// fewer digits.  L.list_d (free once the search is over) carries the neighbours' coordinates.
+__device__ __forceinline__ void krige_fill_local(SgsSearchLds& L, const LocalCov& cov, double (&r)[50], int n, int i0, int j0, bool lagr,
+                                                 int lane, int my_i, int my_j) {
+  const double R00 = cov.p[0], R01 = cov.p[1], R10 = cov.p[2], R11 = cov.p[3], sill = cov.p[4], c0 = cov.p[4] - cov.p[5];
+  const double my_x = cov.xs[my_j], my_y = cov.ys[my_i];        // lanes >= n: cell (0, 0), computed and dropped
+  if (lane < n) { L.list_d[0][lane] = my_x; L.list_d[1][lane] = my_y; }
+  __syncthreads();
+  auto pair = [&](double ddx, double ddy) {
+    const double u = ddx * R00 + ddy * R10, v = ddx * R01 + ddy * R11;
+    return local_cov_of(u * u + v * v, c0, sill, cov.vtype);
+  };
+#pragma unroll
+  for (int j = 0; j < 48; ++j) {
+    double v = 0.0;
+    if (j < n) {                                                 // wave-uniform
+      const double c = pair(my_x - L.list_d[0][j], my_y - L.list_d[1][j]);
+      v = (lane < n) ? c : ((lane == 48 && lagr) ? 1.0 : 0.0);
+    }
+    r[j] = v;
+  }
+  const double c = pair(my_x - cov.xs[j0], my_y - cov.ys[i0]);
+  r[48] = (lane < n && lagr) ? 1.0 : 0.0;
+  r[49] = (lane < n) ? c : ((lane == 48 && lagr) ? 1.0 : 0.0);
+}
+
 // The kriging system of cell (i0, j0) with the n > 0 neighbours that octant_ring_search left in L.nb_g, one row per lane in
 // registers, and its solve: ordinary kriging [Sigma 1; 1' 0] w = [rho; 1] (_krige.py:25-37) or, with lagr false, simple kriging
-// Sigma w = rho (_krige.py:66-73: no Lagrange row / column).  The covariances come from `lag`, (2 mi + 1) x (2 mj + 1) entries
-// indexed by the integer lag between two cells.  All 64 lanes call it.  Returns 0, 64 (a lag beyond the table) or 8 (singular);
-// with 0, lane < n holds its neighbour's weight w_l, its covariance with the cell rho_l and its (row, column) (my_i, my_j); w_l
-// is 0 in the other lanes.  L.nb_rc is scratch.  kWholeGridTable compiles the row loads of a table that spans every lag of the grid.
-template <bool kWholeGridTable>
-__device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j0, int H, int W, const double* __restrict__ lag, int mi,
-                                           int mj, bool lagr, int lane, double& w_l, double& rho_l, int& my_i, int& my_j) {
+// Sigma w = rho (_krige.py:66-73: no Lagrange row / column).  The covariances come from `cov`: a LagTableCov or a LocalCov.
+// All 64 lanes call it.  Returns 0, 64 (a lag beyond the table; never with a LocalCov) or 8 (singular); with 0, lane < n holds its
+// neighbour's weight w_l, its covariance with the cell rho_l and its (row, column) (my_i, my_j); w_l is 0 in the other lanes.
+// L.nb_rc is scratch.
+template <class Cov>
+__device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j0, int H, int W, const Cov& cov, bool lagr, int lane,
+                                           double& w_l, double& rho_l, int& my_i, int& my_j) {
   if (lane < n) { const int gg = L.nb_g[lane]; const int rr = gg / W; L.nb_rc[lane] = (rr << 16) | (gg - rr * W); }
   __syncthreads();
-  const int lag_w = 2 * mj + 1;
   double r[50];
-  const int my_rc = (lane < n) ? L.nb_rc[lane] : 0;
-  my_i = my_rc >> 16; my_j = my_rc & 0xFFFF;
-  bool lag_ok = true;
-  if (kWholeGridTable && mi >= H - 1 && mj >= W - 1) {
-    // the table spans every lag of the grid (lag_extents: grids up to 2048 x 2048 lags): no range test, and the index of the pair
-    // (this lane's neighbour, neighbour j) is one subtraction -- (my_i + mi) lag_w + my_j + mj minus neighbour j's i lag_w + j
-    const int my_base = (my_i + mi) * lag_w + my_j + mj;
-    __syncthreads();
-    if (lane < n) L.nb_rc[lane] = my_i * lag_w + my_j;           // the (row, col) pairs are in registers by now
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 48; ++j) {
-      double v = 0.0;
-      if (j < n) {                                               // wave-uniform
-        if (lane < n) v = lag[my_base - L.nb_rc[j]];
-        else if (lane == 48 && lagr) v = 1.0;
-      }
-      r[j] = v;
-    }
+  double c00;
+  if constexpr (Cov::kLocal) {
+    const int my_rc = (lane < n) ? L.nb_rc[lane] : 0;
+    my_i = my_rc >> 16; my_j = my_rc & 0xFFFF;
+    krige_fill_local(L, cov, r, n, i0, j0, lagr, lane, my_i, my_j);
+    rho_l = r[49];
+    c00 = cov.p[4] - cov.p[5];
   } else {
+    constexpr bool kWholeGridTable = Cov::kWholeGrid;
+    const double* __restrict__ lag = cov.lag;
+    const int mi = cov.mi, mj = cov.mj;
+    const int lag_w = 2 * mj + 1;
+    const int my_rc = (lane < n) ? L.nb_rc[lane] : 0;
+    my_i = my_rc >> 16; my_j = my_rc & 0xFFFF;
+    bool lag_ok = true;
+    if (kWholeGridTable && mi >= H - 1 && mj >= W - 1) {
+      // the table spans every lag of the grid (lag_extents: grids up to 2048 x 2048 lags): no range test, and the index of the pair
+      // (this lane's neighbour, neighbour j) is one subtraction -- (my_i + mi) lag_w + my_j + mj minus neighbour j's i lag_w + j
+      const int my_base = (my_i + mi) * lag_w + my_j + mj;
+      __syncthreads();
+      if (lane < n) L.nb_rc[lane] = my_i * lag_w + my_j;           // the (row, col) pairs are in registers by now
+      __syncthreads();
 #pragma unroll
-    for (int j = 0; j < 48; ++j) {
-      double v = 0.0;
-      if (j < n) {                                               // wave-uniform
-        if (lane < n) {
-          const int rc = L.nb_rc[j];
-          const int di = my_i - (rc >> 16), dj = my_j - (rc & 0xFFFF);
-          if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v = lag[(di + mi) * lag_w + dj + mj];
-        } else if (lane == 48 && lagr) v = 1.0;
+      for (int j = 0; j < 48; ++j) {
+        double v = 0.0;
+        if (j < n) {                                               // wave-uniform
+          if (lane < n) v = lag[my_base - L.nb_rc[j]];
+          else if (lane == 48 && lagr) v = 1.0;
+        }
+        r[j] = v;
       }
-      r[j] = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 48; ++j) {
+        double v = 0.0;
+        if (j < n) {                                               // wave-uniform
+          if (lane < n) {
+            const int rc = L.nb_rc[j];
+            const int di = my_i - (rc >> 16), dj = my_j - (rc & 0xFFFF);
+            if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v = lag[(di + mi) * lag_w + dj + mj];
+          } else if (lane == 48 && lagr) v = 1.0;
+        }
+        r[j] = v;
+      }
     }
+    {
+      double v48 = 0.0, v49 = 0.0;
+      if (lane < n) {
+        const int di = my_i - i0, dj = my_j - j0;
+        v48 = lagr ? 1.0 : 0.0;
+        if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v49 = lag[(di + mi) * lag_w + dj + mj];
+      } else if (lane == 48 && lagr) v49 = 1.0;
+      r[48] = v48; r[49] = v49;
+    }
+    if (__ballot(!lag_ok)) return 64;
+    rho_l = r[49];
+    c00 = lag[mi * lag_w + mj];
   }
-  {
-    double v48 = 0.0, v49 = 0.0;
-    if (lane < n) {
-      const int di = my_i - i0, dj = my_j - j0;
-      v48 = lagr ? 1.0 : 0.0;
-      if (abs(di) > mi || abs(dj) > mj) lag_ok = false; else v49 = lag[(di + mi) * lag_w + dj + mj];
-    } else if (lane == 48 && lagr) v49 = 1.0;
-    r[48] = v48; r[49] = v49;
-  }
-  if (__ballot(!lag_ok)) return 64;
-  rho_l = r[49];
-  const double c00 = lag[mi * lag_w + mj];
   // relative pivot test: eps * N * max|diag| for the covariance pivots (conditional variances), eps * N / max|diag| for the
   // Lagrange pivot -1' Sigma^-1 1
   const double tol = 2.220446049250313e-16 * (double)(n + 1) * fabs(c00), tol_l = 2.220446049250313e-16 * (double)(n + 1) / fabs(c00);
@@ -298,6 +371,12 @@ __device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j
   if (singular) return 8;
   w_l = (lane < n) ? r[49] / mypiv : 0.0;
   return 0;
+}
+// the lag-table form under its own name: what every kernel with one variogram per call uses
+template <bool kWholeGridTable>
+__device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j0, int H, int W, const double* __restrict__ lag, int mi,
+                                           int mj, bool lagr, int lane, double& w_l, double& rho_l, int& my_i, int& my_j) {
+  return krige_solve(L, n, i0, j0, H, W, LagTableCov<kWholeGridTable>{lag, mi, mj}, lagr, lane, w_l, rho_l, my_i, my_j);
 }
 
 }  // namespace gsm

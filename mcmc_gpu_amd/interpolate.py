@@ -20,6 +20,15 @@ truncated-normal ppf is a restatement of scipy's (csrc/truncnorm.h), so values a
 normal-score scale, not bit for bit.  Equidistant neighbour candidates are taken in ascending (row, col); the reference's
 argsort is unstable there.
 
+Variogram: every parameter (major_range, minor_range, azimuth, sill, nugget) is a number or a map of the grid's shape, in any
+mix, as in the reference (non-stationary SGS / kriging: the system of a cell is built from the parameters at that cell,
+interpolate.py:56-62, :141-147).  All numbers: one covariance table per call, made on the host, any of the four models.  As
+soon as one parameter is a map the call goes through gsm_sgs_grid_local / gsm_krige_grid_local: the host makes a six-number
+row per cell (_local_table: the rotation matrix in the reference's arithmetic, sill, nugget) and the kernels evaluate every
+covariance from the coordinates -- exponential, gaussian and spherical; Matern needs Bessel K, which the device does not have.
+The reference's gaussian model has no nugget on the diagonal (covariance.py:8-10: its "nugget" scales the model), so with
+ranges of many cells its systems are near singular, in the reference as here.
+
 Grids: axis-aligned with uniform spacing; either axis may ascend or descend (north-up rasters) and the cells need not be
 square (tests/test_gpu_interp_sgs_geometry.py: both signs of both axes, |dy| / |dx| from 0.5 to 2).
 """
@@ -97,8 +106,9 @@ class _Plan:
         if stencil is not None or rcond is not None:
             raise NotImplementedError("the device SGS searches the circular stencil and solves with lstsq's default cut-off "
                                       "(stencil=None, rcond=None)")
+        self.local = None
         if any(isinstance(v, np.ndarray) for k, v in variogram.items() if k != "vtype"):
-            raise NotImplementedError("the device SGS takes scalar variogram parameters (one covariance table per call)")
+            self.local = _local_table(variogram, grid.shape)
         if not 8 <= int(num_points) <= 48:
             raise NotImplementedError("the device SGS takes 8 <= num_points <= 48")
         grid = np.asarray(grid, dtype=np.float64)
@@ -117,7 +127,8 @@ class _Plan:
         ii, jj = np.meshgrid(np.arange(self.H), np.arange(self.W), indexing="ij")
         self.inds = np.array([ii[sim_mask].flatten(), jj[sim_mask].flatten()]).T
         self.xs, self.ys, self.dx, self.dy = _axes(np.asarray(xx, dtype=np.float64), np.asarray(yy, dtype=np.float64))
-        self.vario = {k: (v if k == "vtype" else float(v)) for k, v in variogram.items()}
+        self.vario = None if self.local is not None else {k: (v if k == "vtype" else float(v)) for k, v in variogram.items()}
+        self.vtype = variogram["vtype"].lower()
         self.radius, self.num_points, self.ktype = float(radius), int(num_points), ktype
 
     def _bounds(self, bounds, shape):
@@ -154,6 +165,39 @@ class _Plan:
             d = np.zeros(path.size)
             d[live] = rng.random(int(live.sum()))                                    # truncnorm.rvs: uniform(size=1), :185
         return np.ascontiguousarray(path, dtype=np.int32), d
+
+
+LOCAL_KEYS = ("major_range", "minor_range", "azimuth", "sill", "nugget")
+LOCAL_VTYPES = {"exponential": 0, "gaussian": 1, "spherical": 2}            # GSM_VTYPE_* (include/gsm.h)
+
+
+def _local_table(variogram, shape):
+    """The per-cell table of gsm_sgs_grid_local / gsm_krige_grid_local, [H * W, 6] = R00, R01, R10, R11, sill, nugget per cell,
+    for a variogram of which at least one parameter is a map.  interpolate._preprocess (interpolate.py:226-231) broadcasts the
+    numbers to the grid's shape and the cell loop picks every parameter at the visited cell (:141-147); R is
+    make_rotation_matrix(azimuth, major_range, minor_range) (_krige.py:83-103) in the reference's NumPy arithmetic -- theta =
+    (azimuth / 180.0) * pi, [[cos, -sin], [sin, cos]] . diag(1 / major, 1 / minor) -- so that the device takes no sine.  The
+    dot product's second terms are exact zeros: R00 = cos * (1 / major), R01 = -sin * (1 / minor), R10 = sin * (1 / major),
+    R11 = cos * (1 / minor), the bits of oracle/mcmc_oracle.rotation_matrix cell by cell (tests/test_nonstationary_host.py)."""
+    if variogram["vtype"].lower() == "matern":
+        raise NotImplementedError("the device has no Bessel K: with vtype 'matern' it takes scalar variogram parameters only (one "
+                                  "covariance table per call, made on the host); parameter maps take vtype exponential, gaussian "
+                                  "or spherical")
+    f = {}
+    for k in LOCAL_KEYS:
+        v = variogram[k]
+        if isinstance(v, np.ndarray):
+            if v.shape != tuple(shape):
+                raise ValueError(f"variogram parameter {k} has shape {v.shape}, the grid {tuple(shape)}")
+            f[k] = np.asarray(v, dtype=np.float64)
+        else:
+            f[k] = np.full(shape, v, dtype=np.float64)                                # interpolate.py:229-231
+    with np.errstate(all="ignore"):                                                  # cells outside sim_mask may hold NaN
+        th = (f["azimuth"] / 180.0) * np.pi
+        c, sn = np.cos(th), np.sin(th)
+        inv_major, inv_minor = 1 / f["major_range"], 1 / f["minor_range"]
+        out = np.stack([c * inv_major, -sn * inv_minor, sn * inv_major, c * inv_minor, f["sill"], f["nugget"]], axis=-1)
+    return np.ascontiguousarray(out.reshape(-1, 6))
 
 
 def _window_rows(ys, dx, dy):
@@ -215,12 +259,16 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False):
     eng = GsmEngine(H, W, R, device)
     try:
         dev, lib, h = eng.dev, eng.lib, eng.h
-        mi, mj = _lag_extents(plan, eng, torch)
-        if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
-            raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not fit "
-                              "the device; raise `radius` or add conditioning data")
         hw = int(math.ceil(plan.radius / abs(plan.dx)))
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        if plan.local is None:
+            mi, mj = _lag_extents(plan, eng, torch)
+            if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
+                raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not "
+                                  "fit the device; raise `radius` or add conditioning data")
+            d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        else:
+            d_local = f64(plan.local)                                                 # a variogram per cell: no table
         grids = f64(plan.grid_ns)[None].repeat(R, 1, 1).contiguous()
         d_path = torch.as_tensor(np.concatenate([p for p, _ in plans])).to(dev)
         d_off = torch.as_tensor(off).to(dev)
@@ -229,17 +277,20 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False):
         if plan.bounds is not None:
             d_lo, d_hi = f64(plan.bounds[0]), f64(plan.bounds[1])
         d_xs, d_ys = f64(plan.xs), f64(plan.ys)
-        d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
         d_gm = f64(np.full(R, plan.global_mean))
         d_tr = torch.zeros((int(off[-1]), 3), dtype=torch.float64, device=dev) if trace else None
         if segment_cells is None:
             segment_cells = _segment_cells(R, max_path, torch, dev, 0)
         with torch.cuda.device(dev):
             eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
-            eng._check(lib.gsm_sgs_grid(h, _ptr(grids), _ptr(d_path), _ptr(d_off), max_path, _ptr(d_draw), _ptr(d_lo), _ptr(d_hi),
-                                        1 if plan.bounds is not None else 0, _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), mi, mj, hw,
-                                        plan.radius, plan.num_points, float(plan.vario["sill"]), int(segment_cells), _ptr(d_tr),
-                                        eng._stream()))
+            head = (h, _ptr(grids), _ptr(d_path), _ptr(d_off), max_path, _ptr(d_draw), _ptr(d_lo), _ptr(d_hi),
+                    1 if plan.bounds is not None else 0, _ptr(d_xs), _ptr(d_ys))
+            if plan.local is None:
+                eng._check(lib.gsm_sgs_grid(*head, _ptr(d_lag), mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]),
+                                            int(segment_cells), _ptr(d_tr), eng._stream()))
+            else:
+                eng._check(lib.gsm_sgs_grid_local(*head, _ptr(d_local), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points,
+                                                  int(segment_cells), _ptr(d_tr), eng._stream()))
         ns = grids.cpu().numpy()
         extra = ([p for p, _ in plans], d_tr.cpu().numpy()) if trace else None
     finally:
@@ -256,8 +307,10 @@ def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_ma
     """Sequential Gaussian simulation with ordinary ('ok') or simple ('sk') kriging on the device -- interpolate.sgs
     (gstatsim_custom/interpolate.py:92-191): same arguments and return value (the simulated grid in data units), the generator
     consumed exactly as the reference consumes it.  `device`: CUDA/HIP device index (default: torch's current device).
-    Not supported (NotImplementedError): a custom stencil, rcond other than None, per-cell variogram arrays, num_points
-    outside [8, 48], a grid that is not axis-aligned with uniform spacing.  A grid without any conditioning value raises
+    Variogram parameters: numbers or maps of the grid's shape, in any mix (module docstring); a map of another shape raises
+    ValueError.
+    Not supported (NotImplementedError): a custom stencil, rcond other than None, vtype 'matern' with a parameter map,
+    num_points outside [8, 48], a grid that is not axis-aligned with uniform spacing.  A grid without any conditioning value raises
     ValueError (the reference never terminates there); so does a truncated draw scipy would not make (kriging variance 0,
     or bounds that leave no interval), raised from the device as GsmError."""
     return sgs_many(xx, yy, grid, variogram, [seed], radius=radius, num_points=num_points, ktype=ktype, sim_mask=sim_mask,
@@ -309,24 +362,31 @@ def _krige_run(plan, cells=None, device=None):
     eng = GsmEngine(H, W, 1, device)
     try:
         dev, lib, h = eng.dev, eng.lib, eng.h
-        mi, mj = _lag_extents(plan, eng, torch)
-        if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
-            raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not fit "
-                              "the device; raise `radius` or add conditioning data")
         hw = int(math.ceil(plan.radius / abs(plan.dx)))
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        if plan.local is None:
+            mi, mj = _lag_extents(plan, eng, torch)
+            if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
+                raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not "
+                                  "fit the device; raise `radius` or add conditioning data")
+            d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        else:
+            d_local = f64(plan.local)                                                 # a variogram per cell: no table
         d_grid, d_cells = f64(plan.grid_ns), torch.as_tensor(cells).to(dev)
         d_xs, d_ys = f64(plan.xs), f64(plan.ys)
-        d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
         d_gm = f64(np.full(1, plan.global_mean))
         d_est = torch.empty(cells.size, dtype=torch.float64, device=dev)
         d_var = torch.empty(cells.size, dtype=torch.float64, device=dev)
         d_n = torch.empty(cells.size, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
-            eng._check(lib.gsm_krige_grid(h, _ptr(d_grid), _ptr(d_cells), int(cells.size), _ptr(d_xs), _ptr(d_ys), _ptr(d_lag), mi, mj,
-                                          hw, plan.radius, plan.num_points, float(plan.vario["sill"]), _ptr(d_est), _ptr(d_var),
-                                          _ptr(d_n), eng._stream()))
+            head, tail = (h, _ptr(d_grid), _ptr(d_cells), int(cells.size), _ptr(d_xs), _ptr(d_ys)), (_ptr(d_est), _ptr(d_var), _ptr(d_n))
+            if plan.local is None:
+                eng._check(lib.gsm_krige_grid(*head, _ptr(d_lag), mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]),
+                                              *tail, eng._stream()))
+            else:
+                eng._check(lib.gsm_krige_grid_local(*head, _ptr(d_local), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points,
+                                                    *tail, eng._stream()))
         out = d_est.cpu().numpy(), d_var.cpu().numpy(), d_n.cpu().numpy()
     finally:
         eng.close()
@@ -377,8 +437,10 @@ def krige(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_
     normal score equals the kriging standard deviation -- the data median where sd = 0 (every conditioning cell), higher values
     where the data constrain less.  It is not a standard deviation in data units.  krige_scores returns the quantity that means
     something (the variance in normal-score space) and the neighbour counts.
-    Not supported (NotImplementedError): a custom stencil, per-cell variogram arrays, num_points outside [8, 48], a grid that
-    is not axis-aligned with uniform spacing.  A grid without any conditioning value raises ValueError (the reference never
+    Variogram parameters: numbers or maps of the grid's shape, in any mix (module docstring); a map of another shape raises
+    ValueError.
+    Not supported (NotImplementedError): a custom stencil, vtype 'matern' with a parameter map, num_points outside [8, 48], a
+    grid that is not axis-aligned with uniform spacing.  A grid without any conditioning value raises ValueError (the reference never
     terminates there)."""
     plan = _krige_plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil)
     est_ns, var_ns, _ = _scores(plan, device)

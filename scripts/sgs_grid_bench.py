@@ -2,7 +2,12 @@
 within 50 km, Matern, bounds on (T2_StatisticalAnalysis.ipynb's call), split into the host draw plan, the device call (weights
 and values; per-kernel times: run under rocprofv3 --kernel-trace --stats) and the inverse transform.
 
-    python scripts/sgs_grid_bench.py [--sizes 256,566] [--reals 10,64] [--out profiles/sgs_grid_bench.json]
+--local: the cost of a variogram per cell (gsm_sgs_grid_local: every covariance evaluated in the kernel) against the table path.
+The same problem is run twice in the same process, first with scalar parameters, then with every parameter a constant map of
+the grid's shape -- with the exponential model in both runs, because the device evaluates no Matern -- and a third line gives
+local_over_table, the ratio of the two cells_per_s_device.
+
+    python scripts/sgs_grid_bench.py [--sizes 256,566] [--reals 10,64] [--local] [--out profiles/sgs_grid_bench.json]
 """
 import argparse
 import json
@@ -30,37 +35,53 @@ def problem(n):
     return xx, yy, grid, vario, bounds
 
 
+def measure(interpolate, torch, n, R, xx, yy, grid, vario, bounds, label=None):
+    t0 = time.perf_counter()
+    plan = interpolate._Plan(xx, yy, grid, vario, 50e3, 48, "ok", None, None, None, bounds)
+    t1 = time.perf_counter()
+    gens = [np.random.default_rng(s) for s in range(R)]
+    draws = [plan.draws(np.random.default_rng(s)) for s in range(R)]
+    t2 = time.perf_counter()
+    ns, _ = interpolate._run(plan, gens)
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    out = interpolate._inverse(plan, ns)
+    t4 = time.perf_counter()
+    cells = int(sum(p.size for p, _ in draws))
+    dev_s = (t3 - t2) - (t2 - t1)                             # _run draws again on the host before its device call
+    row = {"grid": f"{n}x{n}", "realisations": R, "simulated_cells": cells, "fit_ms": 1e3 * (t1 - t0),
+           "draw_plan_ms": 1e3 * (t2 - t1), "device_ms": 1e3 * dev_s, "inverse_transform_ms": 1e3 * (t4 - t3),
+           "cells_per_s_device": cells / dev_s, "cells_per_s_total": cells / (t4 - t0 - (t2 - t1)),
+           "nan_cells": int(np.isnan(out).sum())}
+    if label:
+        row["variogram"] = label
+    print(json.dumps(row), flush=True)
+    return row
+
+
 def main():
     import torch
     from mcmc_gpu_amd import interpolate
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="256,566")
     ap.add_argument("--reals", default="10,64")
+    ap.add_argument("--local", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rows = []
     for n in [int(s) for s in args.sizes.split(",")]:
         xx, yy, grid, vario, bounds = problem(n)
         for R in [int(s) for s in args.reals.split(",")]:
-            t0 = time.perf_counter()
-            plan = interpolate._Plan(xx, yy, grid, vario, 50e3, 48, "ok", None, None, None, bounds)
-            t1 = time.perf_counter()
-            gens = [np.random.default_rng(s) for s in range(R)]
-            draws = [plan.draws(np.random.default_rng(s)) for s in range(R)]
-            t2 = time.perf_counter()
-            ns, _ = interpolate._run(plan, gens)
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
-            out = interpolate._inverse(plan, ns)
-            t4 = time.perf_counter()
-            cells = int(sum(p.size for p, _ in draws))
-            dev_s = (t3 - t2) - (t2 - t1)                     # _run draws again on the host before its device call
-            row = {"grid": f"{n}x{n}", "realisations": R, "simulated_cells": cells, "fit_ms": 1e3 * (t1 - t0),
-                   "draw_plan_ms": 1e3 * (t2 - t1), "device_ms": 1e3 * dev_s, "inverse_transform_ms": 1e3 * (t4 - t3),
-                   "cells_per_s_device": cells / dev_s, "cells_per_s_total": cells / (t4 - t0 - (t2 - t1)),
-                   "nan_cells": int(np.isnan(out).sum())}
-            rows.append(row)
-            print(json.dumps(row), flush=True)
+            if not args.local:
+                rows.append(measure(interpolate, torch, n, R, xx, yy, grid, vario, bounds))
+                continue
+            scalar = {k: v for k, v in dict(vario, vtype="Exponential").items() if k != "s"}
+            maps = {k: (v if k == "vtype" else np.full(grid.shape, v)) for k, v in scalar.items()}
+            table = measure(interpolate, torch, n, R, xx, yy, grid, scalar, bounds, "exponential, scalars (lag table)")
+            local = measure(interpolate, torch, n, R, xx, yy, grid, maps, bounds, "exponential, constant maps (per cell)")
+            ratio = {"grid": f"{n}x{n}", "realisations": R, "local_over_table": local["cells_per_s_device"] / table["cells_per_s_device"]}
+            print(json.dumps(ratio), flush=True)
+            rows += [table, local, ratio]
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps({"device": torch.cuda.get_device_name(0), "rows": rows}, indent=1))
