@@ -647,6 +647,35 @@ int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* strea
  * oracle/philox_oracle.normals2 (numpy log / sqrt / cos / sin). */
 int gsm_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int32_t n, double* out, void* stream);
 
+/* Test hook: the scalar special functions of the device, element by element -- out[i] = f(x0[i], x1[i], ...) for i < n, with the
+ * device compiler's code and the device's libm (exp, log, log1p, expm1, hypot, sqrt), through the very functions the whole-grid
+ * SGS and kriging kernels call.  Takes no handle.
+ *   which          GSM_SPECIAL_*: the function and the arguments it reads (x0, x1, ... in the order given below)
+ *   vtype          GSM_VTYPE_EXPONENTIAL / _GAUSSIAN / _SPHERICAL for GSM_SPECIAL_LOCAL_COV; ignored otherwise
+ *   x0 .. x4       [dev, n] each; the ones `which` does not read may be NULL
+ *   out            [dev, n]
+ *   flag           [dev, 1] int32: zeroed, then the error bits the function raises are OR-ed into it (only
+ *                  GSM_SPECIAL_TRUNCNORM_DRAW raises one: 128 for sd <= 0 or NaN, or lower >= upper after standardising -- that
+ *                  element is NaN, the others of the launch are unaffected)
+ * Returns after the stream has drained.  Errors: GSM_E_ARG for an unknown `which`, n < 1 or n >= 2^31 - 256, a NULL out / flag or
+ * a NULL argument that `which` reads, a vtype that GSM_SPECIAL_LOCAL_COV does not evaluate; GSM_E_HIP for a runtime failure.
+ * Checked against scipy 1.15 (scipy.special, scipy.stats.truncnorm) and mpmath by tests/test_gpu_special.py. */
+enum {
+  GSM_SPECIAL_NDTR = 0,           /* scipy.special.ndtr(x0) */
+  GSM_SPECIAL_NDTRI = 1,          /* scipy.special.ndtri(x0) */
+  GSM_SPECIAL_ERFC = 2,           /* scipy.special.erfc(x0) */
+  GSM_SPECIAL_LOG_NDTR = 3,       /* scipy.special.log_ndtr(x0) */
+  GSM_SPECIAL_NDTRI_EXP = 4,      /* scipy.special.ndtri_exp(x0) */
+  GSM_SPECIAL_ERFCX_POS = 5,      /* scipy.special.erfcx(x0), x0 >= 0 */
+  GSM_SPECIAL_LOG_GAUSS_MASS = 6, /* log of the standard normal mass in [x0, x1] */
+  GSM_SPECIAL_TRUNCNORM_PPF = 7,  /* scipy.stats.truncnorm.ppf(q = x0, a = x1, b = x2) */
+  GSM_SPECIAL_TRUNCNORM_DRAW = 8, /* the bounded draw of gsm_sgs_grid: (est, sd, lower, upper, u) = (x0 .. x4) */
+  GSM_SPECIAL_LOCAL_COV = 9,      /* the covariance of gsm_*_grid_local: (squared normalised lag, sill - nugget, sill) = (x0, x1, x2) */
+  GSM_SPECIAL_COUNT = 10
+};
+int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const double* x0, const double* x1, const double* x2, const double* x3,
+                      const double* x4, double* out, int32_t* flag, void* stream);
+
 /* Test hook: one Philox4x32-10 block on the host (ctr[4], key[2] -> out[4]); the device generator uses
  * the same inline function.  Checked against the Random123 known-answer vectors. */
 int gsm_philox_selftest(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);

@@ -232,6 +232,16 @@ extern "C" int gsm_krige_grid_local(gsm_handle h, const double* grid, const int3
                         num_points, 0.0, est, var, n_neighbours, stream);
 }
 
+extern "C" int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const double* x0, const double* x1, const double* x2,
+                                 const double* x3, const double* x4, double* out, int32_t* flag, void* stream) {
+  if (which == GSM_SPECIAL_LOCAL_COV && vtype != GSM_VTYPE_EXPONENTIAL && vtype != GSM_VTYPE_GAUSSIAN && vtype != GSM_VTYPE_SPHERICAL)
+    return GSM_E_ARG;
+  const hipError_t e = launch_debug_special(which, vtype, n, x0, x1, x2, x3, x4, out, flag, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return GSM_E_ARG;
+  if (e != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GSM_E_HIP;
+  return GSM_OK;
+}
+
 extern "C" int gsm_sgs_check(gsm_handle h, void* stream) {
   if (!h) return GSM_E_ARG;
   HIPCHK(h, hipSetDevice(h->device));

@@ -284,6 +284,9 @@ struct KrigeGridArgs {
 hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
 hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);   // weights, then values of one segment
+// gsm_debug_special: hipErrorInvalidValue for an unknown `which`, a NULL pointer it reads or n outside [1, 2^31 - 256)
+hipError_t launch_debug_special(int which, int vtype, int64_t n, const double* x0, const double* x1, const double* x2, const double* x3,
+                                const double* x4, double* out, int32_t* err, hipStream_t st);
 hipError_t launch_sgs_blocks(const SgsArgs& a, int launch_cells, hipStream_t st);
 hipError_t launch_sgs_weights(const SgsArgs& a, int launch_cells, hipStream_t st);     // ranks + records
 hipError_t launch_sgs_sequence(const SgsArgs& a, hipStream_t st);                      // value pass

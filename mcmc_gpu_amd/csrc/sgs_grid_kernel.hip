@@ -244,6 +244,43 @@ __global__ __launch_bounds__(64 * kGridSeqWaves) void sgs_grid_values_kernel(con
   }
 }
 
+// test hook (gsm_debug_special): the scalar functions behind the bounded draw, the normal-score transform and the per-cell
+// variogram, exactly as the kernels of this file and sgs_search.h call them -- one thread per element
+__global__ __launch_bounds__(256) void debug_special_kernel(int which, int vtype, int64_t n, const double* __restrict__ x0,
+                                                            const double* __restrict__ x1, const double* __restrict__ x2,
+                                                            const double* __restrict__ x3, const double* __restrict__ x4,
+                                                            double* __restrict__ out, int32_t* err) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double a = x0[i];
+  double r;
+  switch (which) {
+    case GSM_SPECIAL_NDTR: r = ns::ndtr(a); break;
+    case GSM_SPECIAL_NDTRI: r = ns::ndtri(a); break;
+    case GSM_SPECIAL_ERFC: r = ns::erfc_c(a); break;
+    case GSM_SPECIAL_LOG_NDTR: r = tn::log_ndtr(a); break;
+    case GSM_SPECIAL_NDTRI_EXP: r = tn::ndtri_exp(a); break;
+    case GSM_SPECIAL_ERFCX_POS: r = tn::erfcx_pos(a); break;
+    case GSM_SPECIAL_LOG_GAUSS_MASS: r = tn::log_gauss_mass(a, x1[i]); break;
+    case GSM_SPECIAL_TRUNCNORM_PPF: r = tn::ppf(a, x1[i], x2[i]); break;
+    case GSM_SPECIAL_TRUNCNORM_DRAW: r = grid_truncnorm_draw(a, x1[i], x2[i], x3[i], x4[i], err); break;
+    default: r = local_cov_of(a, x1[i], x2[i], vtype); break;     // GSM_SPECIAL_LOCAL_COV
+  }
+  out[i] = r;
+}
+hipError_t launch_debug_special(int which, int vtype, int64_t n, const double* x0, const double* x1, const double* x2, const double* x3,
+                                const double* x4, double* out, int32_t* err, hipStream_t st) {
+  static const int n_args[GSM_SPECIAL_COUNT] = {1, 1, 1, 1, 1, 1, 2, 3, 5, 3};
+  const double* x[5] = {x0, x1, x2, x3, x4};
+  if (which < 0 || which >= GSM_SPECIAL_COUNT || n < 1 || n >= ((int64_t)1 << 31) - 256 || !out || !err) return hipErrorInvalidValue;
+  for (int k = 0; k < n_args[which]; ++k)
+    if (!x[k]) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(err, 0, sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(debug_special_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, which, vtype, n, x0, x1, x2, x3, x4, out, err);
+  return hipGetLastError();
+}
+
 static bool grid_args_ok(const SgsGridArgs& a) {
   return !(a.hw < 1 || a.num_points < 8 || a.num_points > kSgsMaxPts || a.H < 2 || a.W < 2 || a.H > 32767 || a.W > 32767 ||
            (int64_t)a.H * a.W > (int64_t)kGridFieldMask + 1 || a.n_real < 1 || a.n_real > 65535 || a.seg_cap % 64 != 0 ||

@@ -32,6 +32,7 @@ GSM_NS_FN double erfcx_pos(double y) {
                       9.60896809063285878198E0, 3.36907645100081516050E0};
   if (y < 1.0) return ns::erfc_c(y) * std::exp(y * y);
   if (y < 8.0) return ns::polevl(y, P, 8) / ns::p1evl(y, Q, 8);
+  if (y > 1e50) return R[0] / y;          // the limit of the quotient below, before y^6 overflows there (y > 1.5e51: inf / inf)
   return ns::polevl(y, R, 5) / ns::p1evl(y, S, 6);
 }
 
@@ -71,6 +72,7 @@ GSM_NS_FN double ndtri_exp(double y) {
 
 // log(exp(p) + exp(q))
 GSM_NS_FN double log_sum(double p, double q) {
+  if (std::isnan(p) || std::isnan(q)) return p + q;                 // numpy.logaddexp gives NaN; fmax / fmin would drop it
   const double m = std::fmax(p, q), s = std::fmin(p, q);
   if (m == -INFINITY) return -INFINITY;
   return std::log1p(std::exp(s - m)) + m;
@@ -93,6 +95,7 @@ GSM_NS_FN double log_gauss_mass(double a, double b) {
 
 // scipy.stats.truncnorm.ppf(q, a, b) for a < b, 0 <= q <= 1
 GSM_NS_FN double ppf(double q, double a, double b) {
+  if (a < b && (q == 0.0 || q == 1.0)) return (q == 0.0) ? a : b;    // rv_continuous.ppf returns the bounds there without calling _ppf
   const double m = log_gauss_mass(a, b);
   if (a < 0.0) return ndtri_exp(log_sum(log_ndtr(a), std::log(q) + m));
   return -ndtri_exp(log_sum(log_ndtr(-b), std::log1p(-q) + m));

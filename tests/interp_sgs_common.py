@@ -127,3 +127,73 @@ def geometry():
                  dict(major_range=6000.0, minor_range=6000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Exponential"),
                  dict(radius=3000.0, num_points=16, ktype="ok"), [5, 6])
     return out
+
+
+def _oracle_run(xx, yy, grid_ns, vario, kw, seed, bounds):
+    """(normal scores, trace [cells, (i, j, n, est, var)], generator state) of the CPU helper with the device's tie rule."""
+    import warnings
+    import sgs_oracle as so
+    rng = np.random.default_rng(seed)
+    trace = []
+    so.STABLE_TIES = True
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out = so.sgs(xx, yy, grid_ns, dict(vario), kw["radius"], kw["num_points"], kw["ktype"], rng=rng, trace=trace, bounds=bounds)
+    finally:
+        so.STABLE_TIES = False
+    return out, np.array(trace), rng.bit_generator.state
+
+
+_REGIMES = None
+
+
+def regimes():
+    """A 24 x 24 whole-grid case whose bounded draws run through the regimes of truncnorm.h that F14 / F16 and geometry() leave
+    at moderate bounds: standardised a >= 6, b <= -6 and b - a <= 1e-3 (tests/test_interp_sgs_host.py counts them in the
+    helper's trace).  Tie-free spacing, 16 neighbours, conditioning lines every 6 rows and 8 columns.
+
+    The bounds are given in normal-score space (plan.bounds is set directly) and are built from the helper's own estimates.
+    The kriging variance of a cell depends on the path alone, so an unbounded run gives every sd.  A target T = that run's
+    estimate + k sd, k in +-[8, 30] for two thirds of the cells, is then pinned by intervals [T, T + 1e-6 sd], and the second
+    run's estimates say where T stands among them: cells with (T - est) / sd >= 7 get T as lower bound (no upper bound, or one
+    1e-8 .. 1e-4 sd above), cells with <= -7 the mirror image, the others intervals of 1e-8 .. 5e-4 sd.  Every interval keeps
+    its cell within a fraction of an sd of T, so the third run -- the case -- meets nearly the second one's estimates.
+    Returns dict(xx, yy, grid, vario, kw, seed, plan, out, trace, state): plan with the bounds, then the helper's run."""
+    global _REGIMES
+    if _REGIMES is not None:
+        return _REGIMES
+    from mcmc_gpu_amd import interpolate
+    H = W = 24
+    xx, yy = np.meshgrid(np.arange(W) * 500.0, np.arange(H) * TIE_FREE_DY)
+    grid = np.where(_lines(H, W, 6, 8), field(H, W, 31), np.nan)
+    vario = dict(major_range=6000.0, minor_range=6000.0, azimuth=0.0, sill=1.0, nugget=0.0, vtype="Exponential")
+    kw = dict(radius=3000.0, num_points=16, ktype="ok")
+    seed = 5
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                                 # 156 conditioning values: fewer than the transformer's 500 quantiles
+        plan = interpolate._Plan(xx, yy, grid, vario, kw["radius"], kw["num_points"], kw["ktype"], None, None, None, None)
+    _, tr, _ = _oracle_run(xx, yy, plan.grid_ns, vario, kw, seed, None)
+    ci, cj = tr[:, 0].astype(int), tr[:, 1].astype(int)
+    r = np.random.default_rng(32)
+    k = np.where(r.random(ci.size) < 2 / 3, np.where(r.random(ci.size) < 0.5, 1.0, -1.0) * r.uniform(8.0, 30.0, ci.size), r.uniform(-2.0, 2.0, ci.size))
+    sd = np.full((H, W), np.nan)
+    T = np.full((H, W), np.nan)
+    sd[ci, cj] = np.sqrt(tr[:, 4])
+    T[ci, cj] = tr[:, 3] + k * sd[ci, cj]
+    sim = ~np.isnan(T)
+    lo, hi = np.where(sim, T, 0.0), np.where(sim, T + 1e-6 * sd, 1.0)
+    _, tr, _ = _oracle_run(xx, yy, plan.grid_ns, vario, kw, seed, (lo, hi))
+    assert np.array_equal(tr[:, 0], ci) and np.array_equal(tr[:, 1], cj)                  # the path does not depend on the bounds
+    a2 = (T[ci, cj] - tr[:, 3]) / sd[ci, cj]
+    narrow = 10.0 ** r.uniform(-8.0, -4.0, ci.size) * sd[ci, cj]
+    open_end = r.random(ci.size) < 0.5
+    t = T[ci, cj]
+    lo_c = np.where(a2 <= -7.0, np.where(open_end, -np.inf, t - narrow), t)
+    hi_c = np.where(a2 <= -7.0, t, np.where(a2 >= 7.0, np.where(open_end, np.inf, t + narrow), t + 5.0 * narrow))
+    lo[ci, cj], hi[ci, cj] = lo_c, hi_c
+    plan.bounds = (np.ascontiguousarray(lo), np.ascontiguousarray(hi))
+    out, tr, state = _oracle_run(xx, yy, plan.grid_ns, vario, kw, seed, plan.bounds)
+    _REGIMES = dict(xx=xx, yy=yy, grid=grid, vario=vario, kw=kw, seed=seed, plan=plan, out=out, trace=tr, state=state)
+    return _REGIMES

@@ -6,4 +6,8 @@ void tn_ppf(const double* q, const double* a, const double* b, double* out, int 
 }
 void tn_log_ndtr(const double* x, double* out, int n) { for (int i = 0; i < n; ++i) out[i] = gsm::tn::log_ndtr(x[i]); }
 void tn_ndtri_exp(const double* x, double* out, int n) { for (int i = 0; i < n; ++i) out[i] = gsm::tn::ndtri_exp(x[i]); }
+void tn_erfcx_pos(const double* x, double* out, int n) { for (int i = 0; i < n; ++i) out[i] = gsm::tn::erfcx_pos(x[i]); }
+void tn_log_gauss_mass(const double* a, const double* b, double* out, int n) {
+  for (int i = 0; i < n; ++i) out[i] = gsm::tn::log_gauss_mass(a[i], b[i]);
+}
 }

@@ -74,8 +74,11 @@ def _assert_case_reaches_what_it_is_for(cid):
 
 def _compare(cid, plan, ns, path, t, rng, ref):
     """One realisation of the device (normal scores, path, trace, generator) against the oracle's."""
-    grid, vario = CASES[cid][2], CASES[cid][3]
-    out, tr, state, _ = ref
+    _compare_run(CASES[cid][2], CASES[cid][3], plan, ns, path, t, rng, ref[:3])
+
+
+def _compare_run(grid, vario, plan, ns, path, t, rng, ref):
+    out, tr, state = ref
     W = plan.W
     assert rng.bit_generator.state == state
     np.testing.assert_array_equal(path, tr[:, 0] * W + tr[:, 1])                                     # visiting order
@@ -106,6 +109,16 @@ def test_interpolate_sgs_equals_oracle_trace(cid):
     off = np.concatenate([[0], np.cumsum([p.size for p in paths])])
     for r, s in enumerate(seeds):
         _compare(cid, plan, ns[r], paths[r], tr[off[r]:off[r + 1]], rngs[r], ref[s])
+
+
+def test_interpolate_sgs_through_the_truncnorm_regimes():
+    """interp_sgs_common.regimes(): bounded draws far in both tails (standardised a >= 6, b <= -6) and from intervals of at most
+    1e-3 sd -- the branches of truncnorm.h that the other cases' moderate bounds leave alone -- at the same bounds."""
+    from mcmc_gpu_amd import interpolate
+    c = ic.regimes()
+    rng = np.random.default_rng(c["seed"])
+    ns, (paths, tr) = interpolate._run(c["plan"], [rng], trace=True)
+    _compare_run(c["grid"], c["vario"], c["plan"], ns[0], paths[0], tr, rng, (c["out"], c["trace"], c["state"]))
 
 
 def test_sgs_many_equals_oracle_maps_on_square_north_up_cells():

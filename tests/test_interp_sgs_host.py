@@ -174,6 +174,23 @@ def test_sgs_many_of_no_seed_is_empty():
     assert interpolate.sgs_many(xx, yy, grid, vario, [], radius=3000.0, num_points=16).shape == (0,) + grid.shape
 
 
+def test_regime_case_reaches_the_deep_tails_and_narrow_intervals():
+    """interp_sgs_common.regimes(): in the CPU helper's trace at least 20 simulated cells each draw from a standardised interval
+    with a >= 6, with b <= -6 and with b - a <= 1e-3 -- what tests/test_gpu_interp_sgs_geometry.py then runs on the device."""
+    c = ic.regimes()
+    tr = c["trace"]
+    lo, hi = c["plan"].bounds
+    i, j = tr[:, 0].astype(int), tr[:, 1].astype(int)
+    sd = np.sqrt(tr[:, 4])
+    a, b = (lo[i, j] - tr[:, 3]) / sd, (hi[i, j] - tr[:, 3]) / sd
+    assert tr.shape[0] == 420 and np.all(tr[:, 2] > 0) and np.all(a < b)
+    assert np.count_nonzero(a >= 6.0) >= 20 and np.count_nonzero(b <= -6.0) >= 20 and np.count_nonzero(b - a <= 1e-3) >= 20
+    # the tails in both forms: open-ended and a narrow interval far out
+    assert np.count_nonzero((a >= 6.0) & np.isinf(b)) >= 20 and np.count_nonzero((b <= -6.0) & np.isinf(a)) >= 20
+    assert np.count_nonzero((np.minimum(np.abs(a), np.abs(b)) >= 6.0) & (b - a <= 1e-3)) >= 20
+    assert np.all(np.isfinite(c["out"]))
+
+
 def _lag_case(cid):
     if cid.startswith("small"):
         xx, yy, grid, cases = ic.small()
