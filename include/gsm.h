@@ -502,6 +502,40 @@ int gsm_krige_grid_local(gsm_handle h, const double* grid, const int32_t* cells,
                          int32_t hw, double radius, int32_t num_points,
                          double* est, double* var, int32_t* n_neighbours, void* stream);
 
+/* ---- gsm_sgs_grid's path and draws from the callers' OWN NumPy generators ('pcg64' mode of interpolate.sgs) -----------------
+ * What interpolate.sgs takes from its numpy.random.Generator(PCG64), made on the device for all R = n_chains realisations side by
+ * side (one wavefront each), bit for bit what NumPy returns (mcmc_gpu_amd/csrc/pcg64_device.h):
+ *   states   [dev, R*6] in/out          per realisation state lo, hi, inc lo, hi, has_uint32, uinteger of bit_generator.state
+ *                                       (the layout of gsm_sgs_draw_pcg64); on return where NumPy would leave the generator
+ *   cells    [dev, n_cells]             flat indices (row * W + col) of the cells of sim_mask in C order: the rows of `inds`
+ *                                       before the shuffle, the same for every realisation
+ *   has_value [dev, H*W]                != 0 where the grid holds a conditioning value (the reference's cond_msk)
+ *   lower, upper [dev, H*W] or NULL     transformed bounds, read with GSM_DRAW_TRUNCATED only
+ *   work     [dev, R*n_cells]           scratch: each realisation's shuffled copy of `cells`
+ *   path     [dev, R*path_len]          out: realisation r's visiting order at r * path_len -- its shuffled cells without those that
+ *                                       hold a value (the cell loop skips them).  Every realisation filters the same
+ *                                       cells by the same mask, so all paths have path_len cells: gsm_sgs_grid's path_off[r] =
+ *                                       r * path_len, max_path = path_len
+ *   draws    [dev, R*path_len]          out: gsm_sgs_grid's `draws`, one number per path cell in path order
+ * In NumPy's order per realisation: rng.shuffle(inds) (interpolate.py:127; Generator.shuffle of a 2-D array: for i = n - 1 .. 1,
+ * j = random_interval(i) -- masked rejection on 32-bit words, the unused half of a 64-bit draw staying cached -- and rows i and j
+ * change places); then with GSM_DRAW_NORMAL one standard normal per path cell (the z of rng.normal(est, sqrt(var), 1),
+ * interpolate.py:174: the 256-layer ziggurat on 64-bit draws, wedge and tail paths included), with GSM_DRAW_TRUNCATED one
+ * rng.random() per path cell whose bounds differ (the uniform of truncnorm.rvs, interpolate.py:185; lower != upper as IEEE
+ * compares them, so a NaN bound draws) and 0.0 at the others (interpolate.py:181-182 draws nothing there).  The 64-bit draws
+ * leave the cached 32-bit word where the shuffle left it, as NumPy's next_uint64 does.  n_cells of 0 or 1 and path_len = 0 are
+ * valid and consume what NumPy consumes (nothing, or the shuffle alone).
+ * Errors: GSM_E_ARG, before anything is written, for a NULL pointer that is read, n_cells outside [0, H * W], path_len outside
+ * [0, n_cells], GSM_DRAW_TRUNCATED without both bounds, an unknown draw_kind.  GSM_E_DEVICE_DATA when the listed cells without a
+ * value are not path_len many ("path length": such a realisation makes no draw, its generator stays behind the shuffle) or a
+ * listed cell lies outside the grid.  Synchronises the stream.
+ * Replaces: rng.shuffle, the cond_msk filter and the per-cell draws of interpolate.sgs (gstatsim_custom/interpolate.py:127,
+ * :174, :185); numpy/random/_generator.pyx Generator.shuffle, src/distributions/distributions.c random_interval,
+ * random_standard_normal, next_double. */
+int gsm_sgs_grid_draw_pcg64(gsm_handle h, uint64_t* states, const int32_t* cells, int32_t n_cells, const uint8_t* has_value,
+                            const double* lower, const double* upper, int32_t draw_kind, int32_t* work, int32_t* path,
+                            double* draws, int32_t path_len, void* stream);
+
 /* One batch of small-scale iterations in ONE call: for j < n_iters, in the order of chain_sgs.run's loop body
  * (MCMC.py:1741-1822) -- [gsm_qt_transform cur -> next] gsm_sgs_blocks_batch [gsm_sgs_finish | gsm_qt_transform next ->
  * proposed, gsm_sgs_loss, gsm_sgs_decide, gsm_sgs_commit(_map)] -- with iteration j's draws at windows + 4*n_chains*j,

@@ -1,4 +1,4 @@
-// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid, each with its per-cell-variogram twin (gsm_*_local).
+// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid, each with its per-cell-variogram twin (gsm_*_local), and gsm_sgs_grid's draws from NumPy generators (gsm_sgs_grid_draw_pcg64).
 #include "gsm_context.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -296,6 +296,34 @@ extern "C" int gsm_sgs_draw_pcg64(gsm_handle h, uint64_t* chain_state, int32_t n
   a.win = windows; a.blk = blocks; a.cell_off = cell_off; a.cell_cnt = cell_cnt; a.cells = cells; a.z = z; a.u = u; a.err = h->d_err.get();
   HIPCHK(h, launch_sgs_draw_pcg64(a, chain_state, h->d_pcg_tab.get(), h->d_pcg_tab.get() + kPcgJumpWords, (hipStream_t)stream));
   return GSM_OK;
+}
+
+extern "C" int gsm_sgs_grid_draw_pcg64(gsm_handle h, uint64_t* states, const int32_t* cells, int32_t n_cells, const uint8_t* has_value,
+                                       const double* lower, const double* upper, int32_t draw_kind, int32_t* work, int32_t* path,
+                                       double* draws, int32_t path_len, void* stream) {
+  if (!h) return GSM_E_ARG;
+  const std::string w = "gsm_sgs_grid_draw_pcg64";
+  const int64_t n_grid = (int64_t)h->H * h->W;
+  if (n_grid > INT32_MAX) return fail(h, GSM_E_ARG, w + ": flat cell indices are 32-bit (H * W < 2^31)");
+  if (n_cells < 0 || (int64_t)n_cells > n_grid) return fail(h, GSM_E_ARG, w + ": n_cells must be in [0, H * W]");
+  if (path_len < 0 || path_len > n_cells) return fail(h, GSM_E_ARG, w + ": path_len must be in [0, n_cells]");
+  if (draw_kind != GSM_DRAW_NORMAL && draw_kind != GSM_DRAW_TRUNCATED) return fail(h, GSM_E_ARG, w + ": draw_kind must be GSM_DRAW_NORMAL or GSM_DRAW_TRUNCATED");
+  if (draw_kind == GSM_DRAW_TRUNCATED && (!lower || !upper)) return fail(h, GSM_E_ARG, w + ": GSM_DRAW_TRUNCATED needs both bounds (lower and upper)");
+  if (!states || (n_cells > 0 && (!cells || !has_value || !work)) || (path_len > 0 && (!path || !draws))) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  { int rc = ensure_pcg_tables(h); if (rc) return rc; }
+  hipStream_t st = (hipStream_t)stream;
+  SgsGridDrawArgs a{};
+  a.H = h->H; a.W = h->W; a.n_real = h->n_chains; a.states = states; a.cells = cells; a.n_cells = n_cells; a.has_value = has_value;
+  a.lo = lower; a.hi = upper; a.draw_kind = draw_kind; a.work = work; a.path = path; a.draws = draws; a.path_len = path_len;
+  a.jump = h->d_pcg_tab.get(); a.zig = h->d_pcg_tab.get() + kPcgJumpWords; a.err = h->d_err.get();
+  HIPCHK(h, launch_sgs_grid_draw_pcg64(a, st));
+  int32_t flag = 0;
+  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
+  if (!flag) return GSM_OK;
+  if (flag & kSgsGridDrawBadCell) return fail(h, GSM_E_DEVICE_DATA, w + ": an entry of `cells` outside the grid");
+  if (flag & kSgsGridDrawPathLen) return fail(h, GSM_E_DEVICE_DATA, w + ": path length: path_len is not the number of listed cells without a value");
+  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
 }
 
 // scratch of the loss kernels: a partial sum and bad-cell count per (chain, part), and per chain the ticket of sgs_loss_tail_kernel

@@ -265,6 +265,26 @@ struct SgsGridArgs {
   SgsGridHdr* rec_hdr;     // [n_real*seg_cap]
   double2* rec_vw;         // [n_real*seg_cap/64][48][64]: (value, or NaN-boxed (slot << 25 | cell) of a path cell; kriging weight)
 };
+// gsm_sgs_grid_draw_pcg64 (sgs_grid_draw_kernel.hip): path and draws of whole-grid SGS from NumPy's PCG64 streams, one wavefront per realisation
+struct SgsGridDrawArgs {
+  int H, W, n_real;
+  uint64_t* states;          // [n_real*6] state lo, hi, inc lo, hi, has_uint32, uinteger (in/out)
+  const int32_t* cells;      // [n_cells] flat indices of the cells of sim_mask in C order
+  int n_cells;
+  const uint8_t* has_value;  // [H*W] != 0 where the grid holds a conditioning value
+  const double* lo;          // [H*W] transformed bounds (draw_kind GSM_DRAW_TRUNCATED), else nullptr
+  const double* hi;
+  int draw_kind;
+  int32_t* work;             // [n_real][n_cells] the permutation of each realisation
+  int32_t* path;             // [n_real][path_len]
+  double* draws;             // [n_real][path_len]
+  int path_len;
+  const uint64_t* jump; const uint64_t* zig;     // device copies of the constant tables
+  int32_t* err;
+};
+constexpr int kSgsGridDrawPathLen = 256;   // device flag: the valueless cells of `cells` are not path_len many
+constexpr int kSgsGridDrawBadCell = 512;   // device flag: an entry of `cells` outside the grid
+hipError_t launch_sgs_grid_draw_pcg64(const SgsGridDrawArgs& a, hipStream_t st);
 // interpolate.krige: estimate and variance at listed cells of one grid (krige_grid_kernel.hip)
 struct KrigeGridArgs {
   int H, W, n_cells;

@@ -7,11 +7,14 @@ and its deterministic twin, the kriging estimate and spread on the whole grid (k
     krige         interpolate.krige's arguments and return value, plus `device`
     krige_scores  the same call in normal-score space: estimate, variance and neighbour count per cell
 
-The host does what the reference does with its generator, in its order -- one rng.shuffle of the cells of sim_mask, then one
+The generator is consumed as the reference consumes it, in its order -- one rng.shuffle of the cells of sim_mask, then one
 standard normal per simulated cell (rng.normal(est, sd, 1) = est + sd * z) or, with bounds, one uniform per simulated cell whose
 bounds differ (truncnorm.rvs = truncnorm.ppf(uniform, a, b) * scale + est) -- and the normal-score transform with
-scikit-learn (utilities.gaussian_transformation, the same call).  Neighbour search, kriging and the sequential value pass
-run on the device (gsm_sgs_grid, csrc/sgs_grid_kernel.hip); nothing is computed on the CPU in their place.  Kriging has no
+scikit-learn (utilities.gaussian_transformation, the same call) is made on the host.  The shuffle and the draws are NumPy's own
+on the host (mode='replay', the default) or the same PCG64 stream advanced on the device, all realisations side by side
+(mode='pcg64': gsm_sgs_grid_draw_pcg64, csrc/sgs_grid_draw_kernel.hip), bit for bit either way.  Neighbour search, kriging
+and the sequential value pass run on the device (gsm_sgs_grid, csrc/sgs_grid_kernel.hip); nothing is computed on the CPU in
+their place.  Kriging has no
 generator and no sequence -- every cell conditions on the measured values alone -- so all its cells are searched, solved and
 finished side by side in one kernel (gsm_krige_grid, csrc/krige_grid_kernel.hip).
 
@@ -246,21 +249,73 @@ def _segment_cells(R, max_path, torch, dev, extra_bytes):
     return max(64, min(s, (max_path + 63) // 64 * 64))
 
 
-def _run(plan, gens, segment_cells=None, device=None, trace=False):
-    """Draw for every generator in turn, simulate all realisations in one gsm_sgs_grid call.  Returns the normal-score grids
-    [R, H, W] and, with trace, (paths, traces [total, 3])."""
+MODES = ("replay", "pcg64")
+
+
+def _check_mode(mode, gens):
+    """The ValueErrors of the `mode` keyword, raised before any device work."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be 'replay' or 'pcg64', not {mode!r}")
+    if mode != "pcg64":
+        return
+    for g in gens:
+        if g.bit_generator.state.get("bit_generator") != "PCG64":
+            raise ValueError("mode 'pcg64' needs numpy.random.Generator(PCG64) generators (numpy.random.default_rng); "
+                             f"got {type(g.bit_generator).__name__}")
+    if len({id(g.bit_generator) for g in gens}) != len(gens):
+        raise ValueError("mode 'pcg64' advances the generators of `seeds` side by side on the device: the same Generator listed "
+                         "twice is one sequential stream (mode 'replay' consumes it row after row)")
+
+
+def _device_draws(plan, gens, eng, torch, d_lo, d_hi):
+    """mode 'pcg64': _Plan.draws of every generator on the device (gsm_sgs_grid_draw_pcg64), the generators left where NumPy would
+    leave them.  d_lo, d_hi: the transformed bounds on the device, or None.  Returns the device arrays gsm_sgs_grid takes -- path
+    [R * path_len], path_off [R + 1], draws [R * path_len] -- and path_len: every path filters the same cells by the same mask."""
+    from .engine import GsmEngine
+    dev, R = eng.dev, len(gens)
+    flat = np.ascontiguousarray(plan.inds[:, 0] * plan.W + plan.inds[:, 1], dtype=np.int32)
+    path_len = int(np.count_nonzero(~plan.cond.ravel()[flat]))
+    d_states = torch.as_tensor(GsmEngine.pack_pcg64_states(gens).view(np.int64)).to(dev)
+    d_cells = torch.as_tensor(flat).to(dev)
+    d_has = torch.as_tensor(plan.cond.astype(np.uint8).ravel()).to(dev)
+    d_work = torch.empty(max(1, R * flat.size), dtype=torch.int32, device=dev)
+    d_path = torch.empty(max(1, R * path_len), dtype=torch.int32, device=dev)
+    d_draw = torch.empty(max(1, R * path_len), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        eng._check(eng.lib.gsm_sgs_grid_draw_pcg64(eng.h, _ptr(d_states), _ptr(d_cells), int(flat.size), _ptr(d_has), _ptr(d_lo), _ptr(d_hi),
+                                                   1 if plan.bounds is not None else 0, _ptr(d_work), _ptr(d_path), _ptr(d_draw),
+                                                   path_len, eng._stream()))
+    for g, st in zip(gens, GsmEngine.unpack_pcg64_states(d_states.cpu().numpy().view(np.uint64))):
+        g.bit_generator.state = st
+    d_off = torch.arange(R + 1, dtype=torch.int64, device=dev) * path_len
+    return d_path, d_off, d_draw, path_len
+
+
+def _run(plan, gens, segment_cells=None, device=None, trace=False, mode="replay"):
+    """Draw for every generator -- mode 'replay': on the host, in turn; 'pcg64': on the device, side by side (_device_draws) --
+    and simulate all realisations in one gsm_sgs_grid call.  Returns the normal-score grids [R, H, W] and, with trace,
+    (paths, traces [total, 3])."""
     import torch
     from .engine import GsmEngine
-    plans = [plan.draws(g) for g in gens]
-    R, H, W = len(plans), plan.H, plan.W
-    lens = np.array([p.size for p, _ in plans], dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    max_path = int(lens.max()) if R else 0
+    _check_mode(mode, gens)
+    R, H, W = len(gens), plan.H, plan.W
+    if mode == "replay":
+        plans = [plan.draws(g) for g in gens]
+        lens = np.array([p.size for p, _ in plans], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        max_path = int(lens.max()) if R else 0
+        total = int(off[-1])
     eng = GsmEngine(H, W, R, device)
     try:
         dev, lib, h = eng.dev, eng.lib, eng.h
         hw = int(math.ceil(plan.radius / abs(plan.dx)))
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        d_lo = d_hi = None
+        if plan.bounds is not None:
+            d_lo, d_hi = f64(plan.bounds[0]), f64(plan.bounds[1])
+        if mode == "pcg64":
+            d_path, d_off, d_draw, max_path = _device_draws(plan, gens, eng, torch, d_lo, d_hi)
+            total = R * max_path
         if plan.local is None:
             mi, mj = _lag_extents(plan, eng, torch)
             if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
@@ -270,15 +325,13 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False):
         else:
             d_local = f64(plan.local)                                                 # a variogram per cell: no table
         grids = f64(plan.grid_ns)[None].repeat(R, 1, 1).contiguous()
-        d_path = torch.as_tensor(np.concatenate([p for p, _ in plans])).to(dev)
-        d_off = torch.as_tensor(off).to(dev)
-        d_draw = f64(np.concatenate([d for _, d in plans]))
-        d_lo = d_hi = None
-        if plan.bounds is not None:
-            d_lo, d_hi = f64(plan.bounds[0]), f64(plan.bounds[1])
+        if mode == "replay":
+            d_path = torch.as_tensor(np.concatenate([p for p, _ in plans])).to(dev)
+            d_off = torch.as_tensor(off).to(dev)
+            d_draw = f64(np.concatenate([d for _, d in plans]))
         d_xs, d_ys = f64(plan.xs), f64(plan.ys)
         d_gm = f64(np.full(R, plan.global_mean))
-        d_tr = torch.zeros((int(off[-1]), 3), dtype=torch.float64, device=dev) if trace else None
+        d_tr = torch.zeros((total, 3), dtype=torch.float64, device=dev) if trace else None
         if segment_cells is None:
             segment_cells = _segment_cells(R, max_path, torch, dev, 0)
         with torch.cuda.device(dev):
@@ -292,7 +345,9 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False):
                 eng._check(lib.gsm_sgs_grid_local(*head, _ptr(d_local), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points,
                                                   int(segment_cells), _ptr(d_tr), eng._stream()))
         ns = grids.cpu().numpy()
-        extra = ([p for p, _ in plans], d_tr.cpu().numpy()) if trace else None
+        if trace:
+            paths = [p for p, _ in plans] if mode == "replay" else list(d_path.cpu().numpy()[:total].reshape(R, max_path))
+        extra = (paths, d_tr.cpu().numpy()) if trace else None
     finally:
         eng.close()
     return ns, extra
@@ -303,10 +358,11 @@ def _inverse(plan, ns):
 
 
 def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None, rcond=None,
-        bounds=None, seed=None, device=None):
+        bounds=None, seed=None, device=None, mode='replay'):
     """Sequential Gaussian simulation with ordinary ('ok') or simple ('sk') kriging on the device -- interpolate.sgs
     (gstatsim_custom/interpolate.py:92-191): same arguments and return value (the simulated grid in data units), the generator
     consumed exactly as the reference consumes it.  `device`: CUDA/HIP device index (default: torch's current device).
+    `mode`: where the generator is consumed, 'replay' (host) or 'pcg64' (device), as in sgs_many; the result is the same.
     Variogram parameters: numbers or maps of the grid's shape, in any mix (module docstring); a map of another shape raises
     ValueError.
     Not supported (NotImplementedError): a custom stencil, rcond other than None, vtype 'matern' with a parameter map,
@@ -314,11 +370,11 @@ def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_ma
     ValueError (the reference never terminates there); so does a truncated draw scipy would not make (kriging variance 0,
     or bounds that leave no interval), raised from the device as GsmError."""
     return sgs_many(xx, yy, grid, variogram, [seed], radius=radius, num_points=num_points, ktype=ktype, sim_mask=sim_mask,
-                    quiet=quiet, stencil=stencil, rcond=rcond, bounds=bounds, device=device)[0]
+                    quiet=quiet, stencil=stencil, rcond=rcond, bounds=bounds, device=device, mode=mode)[0]
 
 
 def sgs_many(xx, yy, grid, variogram, seeds, *, radius=100e3, num_points=20, ktype='ok', sim_mask=None, quiet=False, stencil=None,
-             rcond=None, bounds=None, segment_cells=None, device=None):
+             rcond=None, bounds=None, segment_cells=None, device=None, mode='replay'):
     """len(seeds) realisations of interpolate.sgs in one device call: out[r] is bit for bit sgs(..., seed=seeds[r]) -- an int,
     a numpy Generator (advanced exactly as the reference advances it, in the order of `seeds`) or None.  Returns [R, H, W];
     list(out) is what largeScaleChain_mp takes as initial_beds.
@@ -326,14 +382,20 @@ def sgs_many(xx, yy, grid, variogram, seeds, *, radius=100e3, num_points=20, kty
     10 000 values: above that scikit-learn's QuantileTransformer fits on a random subsample (subsample=10_000, random_state=None),
     so the reference's own fit differs from call to call there.
     segment_cells: path slots whose records are resident at once (default: from the free device memory); it does not change
-    the result."""
+    the result.
+    mode: 'replay' (default) makes every row's shuffle and draws with NumPy on the host, one generator after the other; 'pcg64'
+    makes them on the device for all rows side by side (gsm_sgs_grid_draw_pcg64: the generators' own PCG64 streams, bit for
+    bit) -- the same result and the same final generator states, without the host's shuffle, which dominates a call of many
+    rows.  'pcg64' takes numpy.random.Generator(PCG64) generators (ints and None become such) and raises ValueError for another
+    bit generator or for the same Generator listed twice (one sequential stream in 'replay', rows side by side on the device)."""
     plan = _Plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil, rcond, bounds)
     if segment_cells is not None and int(segment_cells) < 1:
         raise ValueError("segment_cells must be >= 1")
     gens = [_generator(s) for s in seeds]
+    _check_mode(mode, gens)
     if not gens:
         return np.zeros((0,) + plan.grid_ns.shape)
-    ns, _ = _run(plan, gens, segment_cells, device)
+    ns, _ = _run(plan, gens, segment_cells, device, mode=mode)
     return _inverse(plan, ns)
 
 
