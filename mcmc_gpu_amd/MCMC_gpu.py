@@ -31,7 +31,7 @@ import numpy as np
 from . import Topography  # noqa: F401  (re-exported like the reference namespace does)
 
 __all__ = ["RandField", "chain_crf_gpu", "init_lsc_chain_by_instance", "initiate_RF_by_instance",
-           "spectral_synthesis_field", "run_many", "run_many_replay", "draw_chunk", "min_dist_from_mask"]
+           "spectral_synthesis_field", "run_many", "run_many_replay", "run_many_pcg64", "draw_chunk", "min_dist_from_mask"]
 
 
 def __getattr__(name):
@@ -440,21 +440,52 @@ class chain_crf_gpu:
             ij[k] = [int(i[0]), int(j[0])]
         return ij
 
-    # ---- the chain ----------------------------------------------------------------------------------
+    # ---- the chain: three sources of the next n steps' (loss, accept, blocks) as host arrays [n], [n], [n, 4], each with what has
+    # to happen once the run is over ----------------------------------------------------------------------------------------
+    def _replay_steps(self, eng, RF, chunk):
+        def step(n):
+            si, ce, u, fields = self._draw_chunk(RF, n)
+            loss, acc = eng.run_replay(si[None], ce[None], u[None], eng.pack_fields([fields]))
+            return loss[0], acc[0], eng.blocks_of(si, ce)
+        return step, lambda: None
+
+    def _philox_steps(self, eng, RF, chunk):
+        def step(n):
+            loss, acc, blk = eng.run_philox(n, self.philox_step, [self._philox_seed()], RF, batch=self.philox_batch)
+            self.philox_step += n
+            return loss[0], acc[0], blk[0]
+        return step, lambda: None
+
+    def _pcg64_steps(self, eng, RF, chunk):
+        import torch
+        if RF.rng is self.rng or RF.rng.bit_generator is self.rng.bit_generator:
+            # the device advances the two streams independently; one shared generator interleaves its draws between the
+            # proposal and the chain (set_random_generator's docstring) -- only the host-drawn replay mode follows that
+            raise ValueError("'pcg64' mode needs separate generators for the RandField and the chain (a shared generator "
+                             "interleaves the two draw sequences: use the 'replay' mode for that)")
+        gens = _Pcg64Streams(eng, self, RF, [RF.rng], [self.rng])
+        fields = torch.zeros((1, chunk, eng.field_stride), dtype=torch.float64, device=eng.dev)
+        loss = torch.empty((1, chunk), dtype=torch.float64, device=eng.dev)
+        acc = torch.empty((1, chunk), dtype=torch.uint8, device=eng.dev)
+
+        def step(n):                           # one chain: the first n steps of a buffer are a contiguous buffer of n steps
+            d = gens.draw(n)
+            eng.step_on_draws(n, d, gens.p, loss[:, :n], acc[:, :n], fields[:, :n])
+            return loss[0, :n].cpu().numpy(), acc[0, :n].cpu().numpy(), eng.blocks_of(d['size_idx'][0].cpu().numpy(), d['centre'][0].cpu().numpy())
+
+        def write_back():                      # the generators continue where the device left them, as after NumPy calls
+            rf_st, ch_st = gens.states()
+            RF.rng.bit_generator.state, self.rng.bit_generator.state = rf_st[0], ch_st[0]
+        return step, write_back
+
     def run(self, n_iter, RF, only_save_last_bed=False, info_per_iter=1000, plot=True, progress_bar=True):
         """n_iter-1 Metropolis proposals from self.initial_bed; returns the reference's tuple
         (bed or bed_cache, loss_mc_cache, loss_data_cache, loss_cache, step_cache, resampled_times,
         blocks_cache[, sample_values]) as NumPy arrays (MCMC.py:1137-1443)."""
-        if not isinstance(RF, RandField):
-            raise TypeError('The arugment "RF" has to be an object of the class RandField')
-        if not getattr(RF, 'spectral', False):
-            raise NotImplementedError('only the spectral-synthesis generator (set_generation_method(True)) is built')
+        n_iter = _check_args(RF, n_iter, spectral=True)
         if not hasattr(self, 'rng'):
             self.set_random_generator(getattr(self, 'rng_seed', None))
         H, W = self.xx.shape
-        n_iter = int(n_iter)
-        if n_iter < 1:
-            raise ValueError('n_iter must be >= 1')
         loss_cache = np.zeros(n_iter)
         step_cache = np.zeros(n_iter)
         blocks_cache = np.full((n_iter, 4), np.nan)
@@ -475,55 +506,17 @@ class chain_crf_gpu:
             if track:
                 sample_values[:, 0] = bed0[ij[:, 0], ij[:, 1]]
             per_step = keep_all or track
-            chunk = 1 if per_step else (self.replay_chunk if self.rng_mode in ('replay', 'pcg64') else max(n_iter - 1, 1))
-            if self.rng_mode == 'pcg64':
-                import ctypes as C
-                import torch
-                from .engine import GsmEngine, _ptr
-                if RF.rng is self.rng or RF.rng.bit_generator is self.rng.bit_generator:
-                    # the device advances the two streams independently; one shared generator interleaves its draws between the
-                    # proposal and the chain (set_random_generator's docstring) -- only the host-drawn replay mode follows that
-                    raise ValueError("'pcg64' mode needs separate generators for the RandField and the chain (a shared generator "
-                                     "interleaves the two draw sequences: use the 'replay' mode for that)")
-                p64 = eng.rf_struct(RF)
-                d_rf = torch.as_tensor(GsmEngine.pack_pcg64_states([RF.rng]).view(np.int64)).to(eng.dev)
-                d_ch = torch.as_tensor(GsmEngine.pack_pcg64_states([self.rng]).view(np.int64)).to(eng.dev)
-                d_reg = (torch.as_tensor(np.ascontiguousarray(np.asarray(self.region_mask) == 1, dtype=np.uint8)).to(eng.dev)
-                         if self.update_in_region else None)
+            # steps per call: 1 with per-step records, else replay_chunk for replay and pcg64 and the whole run for philox
+            chunk = 1 if per_step else (self.replay_chunk if self.rng_mode in ('replay', 'pcg64') else n_iter)
+            chunk = min(chunk, max(n_iter - 1, 1))
+            source = {'replay': self._replay_steps, 'pcg64': self._pcg64_steps}.get(self.rng_mode, self._philox_steps)
+            step, finish = source(eng, RF, chunk)
             t0 = time.time()
             done = 1
             next_info = info_per_iter
             while done < n_iter:
                 n = min(chunk, n_iter - done)
-                if self.rng_mode == 'pcg64':
-                    d = eng.draw_pcg64(n, p64, d_rf, d_ch, d_reg)
-                    fl = torch.zeros((1, n, eng.field_stride), dtype=torch.float64, device=eng.dev)
-                    l_b = torch.empty((1, n), dtype=torch.float64, device=eng.dev)
-                    a_b = torch.empty((1, n), dtype=torch.uint8, device=eng.dev)
-                    with torch.cuda.device(eng.dev):
-                        eng._check(eng.lib.gsm_spectral_from_noise(eng.h, n, _ptr(d['size_idx']), _ptr(d['rf_scalars']), C.byref(p64),
-                                                                   _ptr(d['noise_re']), _ptr(d['noise_im']), _ptr(d['nugget']), _ptr(fl),
-                                                                   eng.field_stride, eng._stream()))
-                        eng._check(eng.lib.gsm_run_replay(eng.h, n, _ptr(eng.beds), _ptr(eng.energy), _ptr(eng.resampled), _ptr(eng.loss_sum),
-                                                          _ptr(d['size_idx']), _ptr(d['centre']), _ptr(d['u']), _ptr(fl), eng.field_stride,
-                                                          _ptr(l_b), _ptr(a_b), eng._stream()))
-                    loss, acc = l_b.cpu().numpy(), a_b.cpu().numpy()
-                    si = d['size_idx'][0].cpu().numpy()
-                    blocks_cache[done:done + n, 0:2] = d['centre'][0].cpu().numpy()
-                    blocks_cache[done:done + n, 2] = eng.bh[si]
-                    blocks_cache[done:done + n, 3] = eng.bw[si]
-                elif self.rng_mode == 'replay':
-                    si, ce, u, fields = self._draw_chunk(RF, n)
-                    loss, acc = eng.run_replay(si[None], ce[None], u[None], eng.pack_fields([fields]))
-                    blocks_cache[done:done + n, 0:2] = ce
-                    blocks_cache[done:done + n, 2] = eng.bh[si]
-                    blocks_cache[done:done + n, 3] = eng.bw[si]
-                else:
-                    loss, acc, blk = eng.run_philox(n, self.philox_step, [self._philox_seed()], RF, batch=self.philox_batch)
-                    self.philox_step += n
-                    blocks_cache[done:done + n] = blk[0]
-                loss_cache[done:done + n] = loss[0]
-                step_cache[done:done + n] = acc[0]
+                loss_cache[done:done + n], step_cache[done:done + n], blocks_cache[done:done + n] = step(n)
                 if per_step:
                     b = eng.beds[0].double().cpu().numpy()
                     if keep_all:
@@ -540,9 +533,7 @@ class chain_crf_gpu:
                           file=sys.stdout, flush=True)
             bed_c = eng.beds[0].double().cpu().numpy()
             resampled = eng.resampled[0].cpu().numpy().astype(np.float64)
-            if self.rng_mode == 'pcg64':           # the generators continue where the device left them, as after NumPy calls
-                RF.rng.bit_generator.state = GsmEngine.unpack_pcg64_states(d_rf.cpu().numpy().view(np.uint64))[0]
-                self.rng.bit_generator.state = GsmEngine.unpack_pcg64_states(d_ch.cpu().numpy().view(np.uint64))[0]
+            finish()
         finally:
             eng.close()
         loss_mc_cache = loss_cache.copy()
@@ -551,8 +542,40 @@ class chain_crf_gpu:
         return out + (sample_values,) if track else out
 
 
+def _check_args(RF, n_iter, spectral, n_chains=0, per_chain=(), what='seed'):
+    """The argument checks of chain_crf_gpu.run and the run_many drivers; returns n_iter as an int."""
+    if not isinstance(RF, RandField):
+        raise TypeError('The arugment "RF" has to be an object of the class RandField')
+    if spectral and not getattr(RF, 'spectral', False):
+        raise NotImplementedError('only the spectral-synthesis generator (set_generation_method(True)) is built')
+    if any(len(x) != n_chains for x in per_chain):
+        raise ValueError(f'need one {what} per chain')
+    if int(n_iter) < 1:
+        raise ValueError('n_iter must be >= 1')
+    return int(n_iter)
+
+
+class _Pcg64Streams:
+    """What the 'pcg64' paths share: the RfParams, the chains' two sets of NumPy generator states on the device, where gsm_draw_pcg64
+    advances them in place, and the region mask."""
+
+    def __init__(self, eng, chain, RF, rf_gens, chain_gens):
+        self.eng = eng
+        self.p = eng.rf_struct(RF)
+        self.d_rf, self.d_ch = eng.pcg64_to_device(rf_gens), eng.pcg64_to_device(chain_gens)
+        self.d_reg = eng.mask_u8(chain.region_mask) if chain.update_in_region else None
+
+    def draw(self, n, buffers=None):
+        return self.eng.draw_pcg64(n, self.p, self.d_rf, self.d_ch, self.d_reg, buffers=buffers)
+
+    def states(self):
+        """(RandField states, chain states) as bit_generator.state dicts."""
+        return self.eng.pcg64_from_device(self.d_rf), self.eng.pcg64_from_device(self.d_ch)
+
+
 def _result_tuples(eng, loss0, loss, acc, blk, n_iter):
-    """Per-chain 7-tuples shaped like chain.run(..., only_save_last_bed=True) from a finished Philox-mode engine."""
+    """Per-chain 7-tuples shaped like chain.run(..., only_save_last_bed=True) from a finished engine (its beds and resampled counts), the
+    initial losses and the steps' host records: loss and acc [n_chains, n_steps], blk [n_chains, n_steps, 4]."""
     beds_out = eng.beds.double().cpu().numpy()
     res = eng.resampled.cpu().numpy().astype(np.float64)
     out = []
@@ -600,12 +623,9 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     and for up to 8 absolute `levels` the count of values below each, accumulated on the device at every snapshot that the
     moments use.  The summary then answers quantile(q), interval(p) (to within one bin width, NaN where the rank leaves the
     range) and prob_below(l) (exact).  The chains and the moments are bit-identical with and without it."""
-    if not isinstance(RF, RandField):
-        raise TypeError('The arugment "RF" has to be an object of the class RandField')
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
-    if len(seeds) != n_chains:
-        raise ValueError('need one seed per chain')
+    n_iter = _check_args(RF, n_iter, False, n_chains, (seeds,))
     if posterior is not None:
         from .posterior import check_options
         posterior = check_options(posterior, n_iter, n_chains=n_chains)
@@ -613,7 +633,7 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     accum = None
     try:
         loss0 = eng.set_state(beds)
-        n_steps = int(n_iter) - 1
+        n_steps = n_iter - 1
         seeds64 = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
         if posterior is not None:
             (loss, acc, blk), accum = _run_with_posterior(chain, eng, RF, seeds64, n_iter, batch, step0, posterior)
@@ -643,16 +663,10 @@ def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, ch
     final rf states, final chain states) -- results equal n independent chain_crf_gpu.run calls."""
     from multiprocessing import shared_memory
     import torch
-    if not isinstance(RF, RandField):
-        raise TypeError('The arugment "RF" has to be an object of the class RandField')
-    if not getattr(RF, 'spectral', False):
-        raise NotImplementedError('only the spectral-synthesis generator (set_generation_method(True)) is built')
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
-    if len(rf_states) != n_chains or len(chain_states) != n_chains:
-        raise ValueError('need one RandField and one chain generator state per chain')
+    n_iter = _check_args(RF, n_iter, True, n_chains, (rf_states, chain_states), 'RandField and one chain generator state')
     H, W = chain.xx.shape
-    n_iter = int(n_iter)
     n_steps = n_iter - 1
     eng = chain._make_engine(RF, n_chains, device)
     shms = []
@@ -697,9 +711,7 @@ def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, ch
                 tw = time.time()
                 loss[:, lo:lo + n], acc[:, lo:lo + n] = eng.run_replay(si, ce, u, fields.to(eng.dev))
                 t_dev += time.time() - tw
-                blocks[:, lo:lo + n, 0:2] = ce
-                blocks[:, lo:lo + n, 2] = eng.bh[si]
-                blocks[:, lo:lo + n, 3] = eng.bw[si]
+                blocks[:, lo:lo + n] = eng.blocks_of(si, ce)
                 if progress:
                     done = lo + n
                     print(f"{n_chains} chains: {100 * done / n_steps:3.0f}% | chain-it/s: {n_chains * done / max(time.time() - t0, 1e-9):9.1f} | "
@@ -710,8 +722,7 @@ def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, ch
             chain_states = [st[c][1] for c in range(n_chains)]
             pool.close()
             pool = None
-        beds_out = eng.beds.double().cpu().numpy()
-        res = eng.resampled.cpu().numpy().astype(np.float64)
+        out = _result_tuples(eng, loss0, loss, acc, blocks, n_iter)
     finally:
         eng.close()
         if pool is not None:
@@ -719,12 +730,6 @@ def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, ch
         for m in shms:
             m.close()
             m.unlink()
-    out = []
-    for c in range(n_chains):
-        lc = np.concatenate([[loss0[c]], loss[c]])
-        sc = np.concatenate([[0.0], acc[c].astype(np.float64)])
-        bc = np.vstack([np.full((1, 4), np.nan), blocks[c]])
-        out.append((beds_out[c], lc.copy(), np.zeros(n_iter), lc, sc, res[c], bc))
     return out, rf_states, chain_states
 
 
@@ -742,28 +747,16 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
     (gsm_run_noise: the field never leaves the CU) -- bit-identical to the two calls.
     timing: a dict that receives 'loop_seconds' -- the draw / synthesis / step batches alone, chain state resident in HBM
     (synchronised before and after) -- and 'fused'."""
-    import ctypes as C
     import torch
-    from .engine import GsmEngine, _ptr
-    if not isinstance(RF, RandField):
-        raise TypeError('The arugment "RF" has to be an object of the class RandField')
-    if not getattr(RF, 'spectral', False):
-        raise NotImplementedError('only the spectral-synthesis generator (set_generation_method(True)) is built')
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
-    if len(rf_states) != n_chains or len(chain_states) != n_chains:
-        raise ValueError('need one RandField and one chain generator state per chain')
-    n_iter = int(n_iter)
+    n_iter = _check_args(RF, n_iter, True, n_chains, (rf_states, chain_states), 'RandField and one chain generator state')
     n_steps = n_iter - 1
     eng = chain._make_engine(RF, n_chains, device)
     try:
         dev = eng.dev
         loss0 = eng.set_state(beds)
-        p = eng.rf_struct(RF)
-        d_rf = torch.as_tensor(GsmEngine.pack_pcg64_states(list(rf_states)).view(np.int64)).to(dev)
-        d_ch = torch.as_tensor(GsmEngine.pack_pcg64_states(list(chain_states)).view(np.int64)).to(dev)
-        d_reg = (torch.as_tensor(np.ascontiguousarray(np.asarray(chain.region_mask) == 1, dtype=np.uint8)).to(dev)
-                 if chain.update_in_region else None)
+        gens = _Pcg64Streams(eng, chain, RF, list(rf_states), list(chain_states))
         stride = eng.field_stride
         if fused is None:
             fused = eng.strip_active()
@@ -779,10 +772,9 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
         loss = torch.empty((n_chains, n_al), dtype=torch.float64, device=dev)
         acc = torch.empty((n_chains, n_al), dtype=torch.uint8, device=dev)
         si_all = torch.empty((n_chains, n_al), dtype=torch.int32, device=dev)
-        blocks = np.zeros((n_chains, n_steps, 4))
         ce_all = torch.empty((n_chains, n_al, 2), dtype=torch.int32, device=dev)
         fields = None if fused else torch.zeros((n_chains, batch, stride), dtype=torch.float64, device=dev)
-        nug = p.nugget_max > 0.0
+        nug = gens.p.nugget_max > 0.0
         bufs = [eng.alloc_pcg64_buffers(batch, nug), eng.alloc_pcg64_buffers(batch, nug)]
         # Two streams: the draws of batch k + 1 (one wavefront per chain: latency-bound, leaves most of the chip idle) run beside the
         # spectral synthesis and the steps of batch k.  Events order the reuse of the two draw buffers.
@@ -798,7 +790,7 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
                 if ev_free[k & 1] is not None:
                     s_draw.wait_event(ev_free[k & 1])
                 n = sizes[k]
-                d = eng.draw_pcg64(n, p, d_rf, d_ch, d_reg, buffers=bufs[k & 1] if n == batch else None)
+                d = gens.draw(n, buffers=bufs[k & 1] if n == batch else None)
                 ev_drawn[k & 1].record(s_draw)
             return d
 
@@ -813,16 +805,8 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
                 s_step.wait_event(ev_drawn[k & 1])
                 l_b = torch.empty((n_chains, n), dtype=torch.float64, device=dev)
                 a_b = torch.empty((n_chains, n), dtype=torch.uint8, device=dev)
-                if fused:
-                    eng.run_noise(n, d, p, l_b, a_b)
-                else:
-                    fl = fields if n == batch else torch.zeros((n_chains, n, stride), dtype=torch.float64, device=dev)
-                    eng._check(eng.lib.gsm_spectral_from_noise(eng.h, n_chains * n, _ptr(d['size_idx']), _ptr(d['rf_scalars']), C.byref(p),
-                                                               _ptr(d['noise_re']), _ptr(d['noise_im']), _ptr(d['nugget']), _ptr(fl), stride,
-                                                               eng._stream()))
-                    eng._check(eng.lib.gsm_run_replay(eng.h, n, _ptr(eng.beds), _ptr(eng.energy), _ptr(eng.resampled), _ptr(eng.loss_sum),
-                                                      _ptr(d['size_idx']), _ptr(d['centre']), _ptr(d['u']), _ptr(fl), stride,
-                                                      _ptr(l_b), _ptr(a_b), eng._stream()))
+                fl = fields if fused or n == batch else torch.zeros((n_chains, n, stride), dtype=torch.float64, device=dev)
+                eng.step_on_draws(n, d, gens.p, l_b, a_b, fl)
                 loss[:, done:done + n] = l_b
                 acc[:, done:done + n] = a_b
                 si_all[:, done:done + n] = d['size_idx']
@@ -840,24 +824,11 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
             timing['loop_seconds'] = time.time() - t0
             timing['fused'] = bool(fused)
             timing['batch'] = batch
-        si = si_all[:, :n_steps].cpu().numpy()
-        blocks[:, :, 0:2] = ce_all[:, :n_steps].cpu().numpy()
-        blocks[:, :, 2] = eng.bh[si]
-        blocks[:, :, 3] = eng.bw[si]
-        loss_h = loss[:, :n_steps].cpu().numpy()
-        acc_h = acc[:, :n_steps].cpu().numpy()
-        rf_out = GsmEngine.unpack_pcg64_states(d_rf.cpu().numpy().view(np.uint64))
-        ch_out = GsmEngine.unpack_pcg64_states(d_ch.cpu().numpy().view(np.uint64))
-        beds_out = eng.beds.double().cpu().numpy()
-        res = eng.resampled.cpu().numpy().astype(np.float64)
+        blocks = eng.blocks_of(si_all[:, :n_steps].cpu().numpy(), ce_all[:, :n_steps].cpu().numpy())
+        rf_out, ch_out = gens.states()
+        out = _result_tuples(eng, loss0, loss[:, :n_steps].cpu().numpy(), acc[:, :n_steps].cpu().numpy(), blocks, n_iter)
     finally:
         eng.close()
-    out = []
-    for c in range(n_chains):
-        lc = np.concatenate([[loss0[c]], loss_h[c]])
-        sc = np.concatenate([[0.0], acc_h[c].astype(np.float64)])
-        bc = np.vstack([np.full((1, 4), np.nan), blocks[c]])
-        out.append((beds_out[c], lc.copy(), np.zeros(n_iter), lc, sc, res[c], bc))
     return out, rf_out, ch_out
 
 

@@ -71,10 +71,14 @@ class GsmEngine:
     def _f64(self, a):
         return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
 
+    def mask_u8(self, mask):
+        """Device uint8 copy of a 0/1 mask: 1 where mask == 1."""
+        return torch.as_tensor(np.ascontiguousarray(np.asarray(mask) == 1, dtype=np.uint8)).to(self.dev)
+
     def call(self, fn, *args, stream=None):
-        """fn(handle, *args, stream) under the device guard, its return code checked.  Tensors and None become pointers; `stream`
-        is a torch stream (default: the current one)."""
-        args = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+        """fn(handle, *args, stream) under the device guard, its return code checked.  Tensors become pointers (None is ctypes'
+        NULL already); `stream` is a torch stream (default: the current one)."""
+        args = [_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
         st = self._stream() if stream is None else C.c_void_p(stream.cuda_stream)
         with torch.cuda.device(self.dev):
             self._check(fn(self.h, *args, st))
@@ -97,9 +101,7 @@ class GsmEngine:
         mm = torch.as_tensor(binary_mask(mc_mask, "mc_region_mask")).to(self.dev)
         if um.shape != shp or mm.shape != shp:
             raise ValueError("mask has the wrong shape")
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_set_static(self.h, *[_ptr(t) for t in arrs], _ptr(w), _ptr(um), _ptr(mm),
-                                                float(resolution), float(sigma_mc), self._stream()))
+        self.call(self.lib.gsm_set_static, *arrs, w, um, mm, float(resolution), float(sigma_mc))
 
     def set_blocks(self, pairs, edge_masks=None):
         """pairs: (2, n) int array, row 0 widths, row 1 heights (RandField.pairs, MCMC.py:576-579)."""
@@ -119,8 +121,7 @@ class GsmEngine:
                 tot += m.size
             packed = self._f64(np.concatenate(chunks))
             offs = (C.c_int64 * n)(*o)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_set_blocks(self.h, n, bh, bw, _ptr(packed), offs, self._stream()))
+        self.call(self.lib.gsm_set_blocks, n, bh, bw, packed, offs)
         self.bh = np.array(pairs[1], dtype=np.int64)
         self.bw = np.array(pairs[0], dtype=np.int64)
         self.n_sizes = n
@@ -131,8 +132,7 @@ class GsmEngine:
         if cells.size == 0:
             raise ValueError("region_mask has no cell equal to 1")
         t = torch.as_tensor(cells).to(self.dev)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_set_centres(self.h, _ptr(t), int(cells.size), self._stream()))
+        self.call(self.lib.gsm_set_centres, t, int(cells.size))
 
     def set_state(self, beds, resampled=None):
         """beds: (n_chains, H, W) array or cuda tensor.  Returns loss_cache[0] per chain (numpy)."""
@@ -152,9 +152,7 @@ class GsmEngine:
         self.loss_sum = torch.zeros((self.n_chains, 2), dtype=torch.float64, device=self.dev)
         self.energy = torch.empty((self.n_chains, self.H, self.W), dtype=self.state_dtype, device=self.dev)
         loss0 = torch.zeros(self.n_chains, dtype=torch.float64, device=self.dev)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_init_loss(self.h, _ptr(self.beds), _ptr(self.energy), _ptr(self.loss_sum), _ptr(loss0),
-                                               self._stream()))
+        self.call(self.lib.gsm_init_loss, self.beds, self.energy, self.loss_sum, loss0)
         return loss0.cpu().numpy()
 
     def min_dist_from_mask(self, xx, yy, mask):
@@ -164,8 +162,7 @@ class GsmEngine:
             raise ValueError("mask has the wrong shape")
         dx, dy, dm = self._f64(xx), self._f64(yy), torch.as_tensor(m).to(self.dev)
         out = torch.empty((self.H, self.W), dtype=torch.float64, device=self.dev)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_min_dist_from_mask(self.h, _ptr(dx), _ptr(dy), _ptr(dm), _ptr(out), self._stream()))
+        self.call(self.lib.gsm_min_dist_from_mask, dx, dy, dm, out)
         return out.cpu().numpy()
 
     def residual(self, beds):
@@ -173,18 +170,17 @@ class GsmEngine:
         if tuple(b.shape) != (self.n_chains, self.H, self.W):
             raise ValueError("beds has the wrong shape")
         out = torch.empty_like(b)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_residual(self.h, _ptr(b), _ptr(out), self._stream()))
+        self.call(self.lib.gsm_residual, b, out)
         return out
 
     # ---- posterior accumulator (gsm_posterior_*; mcmc_gpu_amd/posterior.py owns the tensors) ------------------------------
     def _sample_args(self, sample_cells, sample_out):
         if sample_out is None:
-            return _ptr(None), 0, _ptr(None)
+            return None, 0, None
         if sample_cells is None or sample_cells.dtype != torch.int32 or sample_out.dtype != torch.float64 or \
                 sample_out.numel() != self.n_chains * sample_cells.numel() or not sample_out.is_contiguous():
             raise ValueError("sample_cells must be an int32 device tensor and sample_out a contiguous float64 one of n_chains x n_samples")
-        return _ptr(sample_cells), int(sample_cells.numel()), _ptr(sample_out)
+        return sample_cells, int(sample_cells.numel()), sample_out
 
     def _check_sums(self, n, **tensors):
         for name, t in tensors.items():
@@ -200,25 +196,20 @@ class GsmEngine:
         if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
             raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
         self._check_sums(n, s1=s1, s2=s2)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_accumulate(self.h, _ptr(self.beds), _ptr(ref), _ptr(s1), _ptr(s2), 1 if first else 0,
-                                                          *self._sample_args(sample_cells, sample_out), self._stream()))
+        self.call(self.lib.gsm_posterior_accumulate, self.beds, ref, s1, s2, 1 if first else 0, *self._sample_args(sample_cells, sample_out))
 
     def posterior_accumulate_pooled(self, g, s1, s2, sample_cells=None, sample_out=None):
         """One snapshot of self.beds into sums over all chains: S1 += sum_c d, S2 += sum_c d * d, d = bed_c - g; g, s1, s2 [H, W] float64."""
         if self.beds is None:
             raise RuntimeError("set_state() first")
         self._check_sums(self.H * self.W, g=g, s1=s1, s2=s2)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_accumulate_pooled(self.h, _ptr(self.beds), _ptr(g), _ptr(s1), _ptr(s2),
-                                                                 *self._sample_args(sample_cells, sample_out), self._stream()))
+        self.call(self.lib.gsm_posterior_accumulate_pooled, self.beds, g, s1, s2, *self._sample_args(sample_cells, sample_out))
 
     def posterior_sample(self, sample_cells, sample_out):
         """sample_out[c, p] = self.beds[c] at flat cell sample_cells[p]."""
         if self.beds is None:
             raise RuntimeError("set_state() first")
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_sample(self.h, _ptr(self.beds), *self._sample_args(sample_cells, sample_out), self._stream()))
+        self.call(self.lib.gsm_posterior_sample, self.beds, *self._sample_args(sample_cells, sample_out))
 
     def posterior_close(self, ref, g, s1, s2, n_per_seq):
         """A finished sequence's sums become, in place, s1 = its mean minus g and s2 = its ddof=1 variance; `ref` is then free for
@@ -228,8 +219,7 @@ class GsmEngine:
         self._check_sums(n, s1=s1, s2=s2)
         if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
             raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_close(self.h, _ptr(ref), _ptr(g), _ptr(s1), _ptr(s2), int(n_per_seq), self._stream()))
+        self.call(self.lib.gsm_posterior_close, ref, g, s1, s2, int(n_per_seq))
 
     def posterior_partials(self, ref, g, s1, s2, n_seq_per_chain, seq_stride, n_closed, n_per_seq):
         """[3, H, W] device tensor (sum of sequence means minus g, of their squares, of sequence variances) over this handle's
@@ -241,9 +231,7 @@ class GsmEngine:
         if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
             raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
         out = torch.empty((3, self.H, self.W), dtype=torch.float64, device=self.dev)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_partials(self.h, _ptr(ref), _ptr(g), _ptr(s1), _ptr(s2), int(n_seq_per_chain), int(seq_stride),
-                                                        int(n_closed), int(n_per_seq), _ptr(out), self._stream()))
+        self.call(self.lib.gsm_posterior_partials, ref, g, s1, s2, int(n_seq_per_chain), int(seq_stride), int(n_closed), int(n_per_seq), out)
         return out
 
     def posterior_histogram(self, g, inv_width, n_bins, levels, counts):
@@ -257,9 +245,8 @@ class GsmEngine:
         n = (int(n_bins) + 3 + lv.size) * self.H * self.W
         if counts.dtype != torch.int32 or counts.numel() != n or not counts.is_contiguous() or counts.device != self.dev:
             raise ValueError(f"counts must be a contiguous int32 tensor of {n} elements on {self.dev}")
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_posterior_histogram(self.h, _ptr(self.beds), _ptr(g), float(inv_width), int(n_bins),
-                                                         lv.ctypes.data if lv.size else None, int(lv.size), _ptr(counts), self._stream()))
+        self.call(self.lib.gsm_posterior_histogram, self.beds, g, float(inv_width), int(n_bins), lv.ctypes.data if lv.size else None,
+                  int(lv.size), counts)
 
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
@@ -299,10 +286,8 @@ class GsmEngine:
         d_u = torch.as_tensor(u).to(self.dev)
         loss = torch.empty((self.n_chains, n_steps), dtype=torch.float64, device=self.dev)
         acc = torch.empty((self.n_chains, n_steps), dtype=torch.uint8, device=self.dev)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_run_replay(self.h, n_steps, _ptr(self.beds), _ptr(self.energy), _ptr(self.resampled), _ptr(self.loss_sum),
-                                                _ptr(d_si), _ptr(d_c), _ptr(d_u), _ptr(f), self.field_stride,
-                                                _ptr(loss), _ptr(acc), self._stream()))
+        self.call(self.lib.gsm_run_replay, n_steps, self.beds, self.energy, self.resampled, self.loss_sum, d_si, d_c, d_u, f, self.field_stride,
+                  loss, acc)
         return loss.cpu().numpy(), acc.cpu().numpy()
 
     # ------------------------------------------------------------------------------------------
@@ -336,11 +321,8 @@ class GsmEngine:
         fl = torch.zeros((self.n_chains, n_steps, self.field_stride), dtype=torch.float64, device=self.dev)
         sc = torch.empty(n * 4, dtype=torch.float64, device=self.dev) if want_scalars else None
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_propose_philox(self.h, int(n_steps), int(step0), _ptr(d_seeds), C.byref(p),
-                                                    _ptr(si), _ptr(ce), _ptr(u), _ptr(fl), self.field_stride,
-                                                    _ptr(sc), self._stream()))
-            torch.cuda.synchronize(self.dev)
+        self.call(self.lib.gsm_propose_philox, int(n_steps), int(step0), d_seeds, C.byref(p), si, ce, u, fl, self.field_stride, sc)
+        torch.cuda.synchronize(self.dev)
         return dict(size_idx=si.view(self.n_chains, n_steps), centre=ce.view(self.n_chains, n_steps, 2),
                     u=u.view(self.n_chains, n_steps), fields=fl,
                     rf_scalars=None if sc is None else sc.view(self.n_chains, n_steps, 4))
@@ -371,10 +353,8 @@ class GsmEngine:
         d_si, d_sc = torch.as_tensor(size_idx).to(self.dev), self._f64(sc)
         out = torch.zeros((n, self.field_stride), dtype=torch.float64, device=self.dev)
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_spectral_from_noise(self.h, n, _ptr(d_si), _ptr(d_sc), C.byref(p), _ptr(d_re), _ptr(d_im),
-                                                         _ptr(d_ng), _ptr(out), self.field_stride, self._stream()))
-            torch.cuda.synchronize(self.dev)
+        self.call(self.lib.gsm_spectral_from_noise, n, d_si, d_sc, C.byref(p), d_re, d_im, d_ng, out, self.field_stride)
+        torch.cuda.synchronize(self.dev)
         h = out.cpu().numpy()
         return [h[r, :int(self.bh[size_idx[r]] * self.bw[size_idx[r]])].reshape(int(self.bh[size_idx[r]]), int(self.bw[size_idx[r]]))
                 for r in range(n)]
@@ -399,6 +379,23 @@ class GsmEngine:
         return [{"bit_generator": "PCG64", "state": {"state": int(w[0]) | (int(w[1]) << 64), "inc": int(w[2]) | (int(w[3]) << 64)},
                  "has_uint32": int(w[4]), "uinteger": int(w[5])} for w in np.asarray(words, dtype=np.uint64)]
 
+    def pcg64_to_device(self, gens):
+        """int64 [n, 6] device tensor of pack_pcg64_states(gens): what gsm_draw_pcg64 and its kin advance in place."""
+        return torch.as_tensor(self.pack_pcg64_states(gens).view(np.int64)).to(self.dev)
+
+    @staticmethod
+    def pcg64_from_device(t):
+        """bit_generator.state dicts of such a tensor."""
+        return GsmEngine.unpack_pcg64_states(t.cpu().numpy().view(np.uint64))
+
+    def blocks_of(self, size_idx, centre):
+        """The reference's block records (row, col, bh, bw), float64 [..., n, 4], of host arrays size_idx [..., n] and centre [..., n, 2]."""
+        out = np.empty(size_idx.shape + (4,))
+        out[..., 0:2] = centre
+        out[..., 2] = self.bh[size_idx]
+        out[..., 3] = self.bw[size_idx]
+        return out
+
     def alloc_pcg64_buffers(self, n_steps, nugget):
         """Caller-owned outputs of draw_pcg64 for batches of n_steps (reused from batch to batch: only the bh * bw leading doubles of
         a record's planes are written and read)."""
@@ -416,10 +413,8 @@ class GsmEngine:
         [n, s, field_stride] and nugget (or None); `buffers` (alloc_pcg64_buffers of the same n_steps) are used if given."""
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
         b = buffers if (buffers is not None and buffers["n_steps"] == n_steps) else self.alloc_pcg64_buffers(n_steps, p.nugget_max > 0.0)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_draw_pcg64(self.h, int(n_steps), C.byref(p), _ptr(d_rf_state), _ptr(d_chain_state),
-                                                _ptr(d_region_mask), _ptr(b["size_idx"]), _ptr(b["centre"]), _ptr(b["u"]), _ptr(b["rf_scalars"]),
-                                                _ptr(b["noise_re"]), _ptr(b["noise_im"]), _ptr(b["nugget"]), self.field_stride, self._stream()))
+        self.call(self.lib.gsm_draw_pcg64, int(n_steps), C.byref(p), d_rf_state, d_chain_state, d_region_mask, b["size_idx"], b["centre"], b["u"],
+                  b["rf_scalars"], b["noise_re"], b["noise_im"], b["nugget"], self.field_stride)
         return dict(size_idx=b["size_idx"].view(self.n_chains, n_steps), centre=b["centre"].view(self.n_chains, n_steps, 2),
                     u=b["u"].view(self.n_chains, n_steps), rf_scalars=b["rf_scalars"].view(self.n_chains, n_steps, 4),
                     noise_re=b["noise_re"], noise_im=b["noise_im"], nugget=b["nugget"])
@@ -431,10 +426,19 @@ class GsmEngine:
         if self.beds is None:
             raise RuntimeError("set_state() first")
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
-        self._check(self.lib.gsm_run_noise(self.h, int(n_steps), _ptr(self.beds), _ptr(self.energy), _ptr(self.resampled), _ptr(self.loss_sum),
-                                           _ptr(d['size_idx']), _ptr(d['centre']), _ptr(d['u']), _ptr(d['rf_scalars']), C.byref(p),
-                                           _ptr(d['noise_re']), _ptr(d['noise_im']), _ptr(d['nugget']), self.field_stride,
-                                           _ptr(loss), _ptr(accept), self._stream()))
+        self.call(self.lib.gsm_run_noise, int(n_steps), self.beds, self.energy, self.resampled, self.loss_sum, d['size_idx'], d['centre'], d['u'],
+                  d['rf_scalars'], C.byref(p), d['noise_re'], d['noise_im'], d['nugget'], self.field_stride, loss, accept)
+
+    def step_on_draws(self, n_steps, d, p, loss, accept, fields=None):
+        """The device draws `d` of draw_pcg64 to losses and accepts: the fused kernel (run_noise), or with `fields`
+        [n_chains, n_steps, field_stride] the synthesis into it (gsm_spectral_from_noise) and the step from it (gsm_run_replay).
+        Asynchronous on the current stream; allocates nothing."""
+        if fields is None:
+            return self.run_noise(n_steps, d, p, loss, accept)
+        self.call(self.lib.gsm_spectral_from_noise, self.n_chains * n_steps, d['size_idx'], d['rf_scalars'], C.byref(p), d['noise_re'],
+                  d['noise_im'], d['nugget'], fields, self.field_stride)
+        self.call(self.lib.gsm_run_replay, n_steps, self.beds, self.energy, self.resampled, self.loss_sum, d['size_idx'], d['centre'], d['u'],
+                  fields, self.field_stride, loss, accept)
 
     def enable_timing(self, on=True):
         self._check(self.lib.gsm_enable_timing(self.h, 1 if on else 0))
@@ -472,10 +476,8 @@ class GsmEngine:
         else:
             loss, acc, blocks = out
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
-        with torch.cuda.device(self.dev):
-            self._check(self.lib.gsm_run_philox(self.h, int(n_steps), int(step0), int(batch), _ptr(d_seeds), C.byref(p),
-                                                _ptr(self.beds), _ptr(self.energy), _ptr(self.resampled), _ptr(self.loss_sum),
-                                                _ptr(loss), _ptr(acc), _ptr(blocks), self._stream()))
+        self.call(self.lib.gsm_run_philox, int(n_steps), int(step0), int(batch), d_seeds, C.byref(p), self.beds, self.energy, self.resampled,
+                  self.loss_sum, loss, acc, blocks)
         if to_host:
             return loss.cpu().numpy(), acc.cpu().numpy(), blocks.cpu().numpy()
         return loss, acc, blocks

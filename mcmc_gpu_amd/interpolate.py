@@ -43,7 +43,7 @@ import numbers
 
 import numpy as np
 
-from .sgs import _axes, _ptr, lag_cov_table
+from .sgs import _axes, lag_cov_table
 
 __all__ = ["sgs", "sgs_many", "krige", "krige_scores"]
 
@@ -235,8 +235,7 @@ def _lag_extents(plan, eng, torch):
     yy = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(ys[:, None], (H, W)))).to(dev)
     mask = torch.as_tensor(plan.cond.astype(np.uint8).ravel()).to(dev)
     dist = torch.empty(H * W, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        eng._check(eng.lib.gsm_min_dist_from_mask(eng.h, _ptr(xx), _ptr(yy), _ptr(mask), _ptr(dist), eng._stream()))
+    eng.call(eng.lib.gsm_min_dist_from_mask, xx, yy, mask, dist)
     return _lag_extents_from(dist.cpu().numpy()[~plan.cond.ravel()], plan.radius, plan.dx, H, W)
 
 
@@ -271,21 +270,18 @@ def _device_draws(plan, gens, eng, torch, d_lo, d_hi):
     """mode 'pcg64': _Plan.draws of every generator on the device (gsm_sgs_grid_draw_pcg64), the generators left where NumPy would
     leave them.  d_lo, d_hi: the transformed bounds on the device, or None.  Returns the device arrays gsm_sgs_grid takes -- path
     [R * path_len], path_off [R + 1], draws [R * path_len] -- and path_len: every path filters the same cells by the same mask."""
-    from .engine import GsmEngine
     dev, R = eng.dev, len(gens)
     flat = np.ascontiguousarray(plan.inds[:, 0] * plan.W + plan.inds[:, 1], dtype=np.int32)
     path_len = int(np.count_nonzero(~plan.cond.ravel()[flat]))
-    d_states = torch.as_tensor(GsmEngine.pack_pcg64_states(gens).view(np.int64)).to(dev)
+    d_states = eng.pcg64_to_device(gens)
     d_cells = torch.as_tensor(flat).to(dev)
     d_has = torch.as_tensor(plan.cond.astype(np.uint8).ravel()).to(dev)
     d_work = torch.empty(max(1, R * flat.size), dtype=torch.int32, device=dev)
     d_path = torch.empty(max(1, R * path_len), dtype=torch.int32, device=dev)
     d_draw = torch.empty(max(1, R * path_len), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        eng._check(eng.lib.gsm_sgs_grid_draw_pcg64(eng.h, _ptr(d_states), _ptr(d_cells), int(flat.size), _ptr(d_has), _ptr(d_lo), _ptr(d_hi),
-                                                   1 if plan.bounds is not None else 0, _ptr(d_work), _ptr(d_path), _ptr(d_draw),
-                                                   path_len, eng._stream()))
-    for g, st in zip(gens, GsmEngine.unpack_pcg64_states(d_states.cpu().numpy().view(np.uint64))):
+    eng.call(eng.lib.gsm_sgs_grid_draw_pcg64, d_states, d_cells, int(flat.size), d_has, d_lo, d_hi, 1 if plan.bounds is not None else 0,
+             d_work, d_path, d_draw, path_len)
+    for g, st in zip(gens, eng.pcg64_from_device(d_states)):
         g.bit_generator.state = st
     d_off = torch.arange(R + 1, dtype=torch.int64, device=dev) * path_len
     return d_path, d_off, d_draw, path_len
@@ -296,7 +292,7 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False, mode="replay"
     and simulate all realisations in one gsm_sgs_grid call.  Returns the normal-score grids [R, H, W] and, with trace,
     (paths, traces [total, 3])."""
     import torch
-    from .engine import GsmEngine
+    from .engine import GsmEngine, _ptr
     _check_mode(mode, gens)
     R, H, W = len(gens), plan.H, plan.W
     if mode == "replay":
@@ -414,7 +410,7 @@ def _krige_run(plan, cells=None, device=None):
     """One gsm_krige_grid call on `cells` (default: _krige_cells).  Returns per listed cell the estimate, the SIGNED variance
     (sill - sum w rho) and the neighbour count."""
     import torch
-    from .engine import GsmEngine
+    from .engine import GsmEngine, _ptr
     if cells is None:
         cells = _krige_cells(plan)
     cells = np.ascontiguousarray(cells, dtype=np.int32)

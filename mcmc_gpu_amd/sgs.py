@@ -105,7 +105,7 @@ def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_ma
     cells (the small-scale chain's blocks; MCMC.py:1762-1774), the circular search stencil and lstsq's default rcond,
     scalar variogram parameters, 8 <= num_points <= 48, an axis-aligned uniform grid."""
     import torch
-    from .engine import GsmEngine
+    from .engine import GsmEngine, _ptr
     for name, a in (("xx", xx), ("yy", yy), ("grid", grid)):
         if not isinstance(a, np.ndarray) or a.ndim != 2:
             raise ValueError(f"{name} must be a 2D NumPy array")                  # _sanity_checks, interpolate.py:282-298
@@ -336,10 +336,6 @@ class chain_sgs_gpu:
         return out[0]
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def host_draws(chain, rngs, cond_is_data, it0, kb, n):
     """The host draws of iterations it0 .. it0 + kb - 1 of n chains, packed for one gsm_sgs_iterate call.  Contract: chain c's
     generator rngs[c] is consumed for its kb iterations consecutively and the loop is chain-major -- what chain_sgs.run would
@@ -493,11 +489,11 @@ class _SgsRun:
         if self.source == 'replay':
             return
         if self.source == 'pcg64':
-            self.d_gen = torch.as_tensor(eng.pack_pcg64_states(list(self.rngs)).view(np.int64)).to(dev)
+            self.d_gen = eng.pcg64_to_device(list(self.rngs))
         else:
             self.d_seeds = torch.as_tensor(np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in philox_seeds], dtype=np.uint64).view(np.int64)).to(dev)
         if chain.update_in_region:
-            self.d_region = torch.as_tensor(np.ascontiguousarray(chain.region_mask == 1, dtype=np.uint8)).to(dev)
+            self.d_region = eng.mask_u8(chain.region_mask)
         self.d_isdata = torch.as_tensor(np.ascontiguousarray(self.cond_is_data, dtype=np.uint8)).to(dev)
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
         kn = min(self.batch, self.n_iter) * n
@@ -613,7 +609,7 @@ class _SgsRun:
         bed_c = self.beds_on_host()
         res = self.resampled.cpu().numpy().astype(np.float64)
         if self.source == 'pcg64':
-            for g, st in zip(self.rngs, self.eng.unpack_pcg64_states(self.d_gen.cpu().numpy().view(np.uint64))):
+            for g, st in zip(self.rngs, self.eng.pcg64_from_device(self.d_gen)):
                 g.bit_generator.state = st
         out = []
         for c in range(self.n):

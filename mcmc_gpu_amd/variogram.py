@@ -23,7 +23,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .sgs import _axes, _ptr, cov_norm
+from .sgs import _axes, cov_norm
 
 __all__ = ["VariogramMap", "variogram_map", "bin_map", "experimental", "fit", "variograms"]
 
@@ -73,7 +73,7 @@ def variogram_map(xx, yy, fields, maxlag, mask=None, device=None, _rows_per_part
     Sums are fp64 and bit-reproducible: the same call twice gives the same bits, and row r of a batched call gives the bits of
     the call on fields[r] alone.  A large batch is sent in slices sized from the free device memory; slicing changes nothing."""
     import torch
-    from .engine import GsmEngine
+    from .engine import GsmEngine, _ptr
     xx, yy = np.asarray(xx, dtype=np.float64), np.asarray(yy, dtype=np.float64)
     if xx.ndim != 2 or xx.shape != yy.shape:
         raise ValueError("xx and yy must be 2D arrays of the same shape")

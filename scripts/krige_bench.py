@@ -36,8 +36,8 @@ def device_call_ms(plan, repeats):
     """gsm_krige_grid alone, uploads outside the timed window: milliseconds of every repeat after one warm-up call."""
     import torch
     from mcmc_gpu_amd import interpolate
-    from mcmc_gpu_amd.engine import GsmEngine
-    from mcmc_gpu_amd.sgs import _ptr, lag_cov_table
+    from mcmc_gpu_amd.engine import GsmEngine, _ptr
+    from mcmc_gpu_amd.sgs import lag_cov_table
     cells = interpolate._krige_cells(plan)
     eng = GsmEngine(plan.H, plan.W, 1)
     try:

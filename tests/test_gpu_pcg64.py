@@ -110,6 +110,78 @@ def test_pcg64_mode_follows_the_reference_chain(golden_dir):
     assert c.rng.bit_generator.state == c2.rng.bit_generator.state and r.rng.bit_generator.state == r2.rng.bit_generator.state
 
 
+def test_pcg64_mode_with_per_step_records_equals_the_chunked_run():
+    """chain_crf_gpu.run in 'pcg64' mode with every bed and two sample points kept (one step per launch) against the same chain with
+    only the last bed kept (replay_chunk steps per launch): the kernels and their inputs are the same, only the launch boundaries
+    differ, so every record is equal bit for bit; and against the replay-mode run with every bed kept, to the tolerances of
+    test_pcg64_mode_follows_the_reference_chain."""
+    from mcmc_gpu_amd import synthetic
+    prob, ch, rf = synthetic.template(64)
+    loc = np.array([[prob["xx"][20, 30], prob["yy"][20, 30]], [prob["xx"][40, 12], prob["yy"][40, 12]]])
+    kw = dict(info_per_iter=10 ** 9, plot=False, progress_bar=None)
+    c, r = _rehydrate(ch, rf, 9, prob["bed"].copy())
+    c.set_rng_mode('pcg64')
+    c.set_sample_points_locations(loc)
+    out = c.run(25, r, only_save_last_bed=False, **kw)
+    assert len(out) == 8
+    bed_cache, _, _, loss, steps, resampled, blocks, sample_values = out
+    assert bed_cache.shape == (25, 64, 64) and sample_values.shape == (2, 25)
+    assert np.array_equal(bed_cache[0], prob["bed"])
+    assert np.array_equal(sample_values[0], bed_cache[:, 20, 30]) and np.array_equal(sample_values[1], bed_cache[:, 40, 12])
+    c2, r2 = _rehydrate(ch, rf, 9, prob["bed"].copy())
+    c2.set_rng_mode('pcg64')
+    last = c2.run(25, r2, only_save_last_bed=True, **kw)
+    assert len(last) == 7
+    assert np.array_equal(steps, last[4]) and np.array_equal(blocks, last[6], equal_nan=True)
+    assert np.array_equal(loss, last[3]) and np.array_equal(out[1], last[1]) and np.array_equal(resampled, last[5])
+    assert np.array_equal(bed_cache[-1], last[0])
+    assert c.rng.bit_generator.state == c2.rng.bit_generator.state and r.rng.bit_generator.state == r2.rng.bit_generator.state
+    c3, r3 = _rehydrate(ch, rf, 9, prob["bed"].copy())
+    rep = c3.run(25, r3, only_save_last_bed=False, **kw)
+    assert np.array_equal(steps, rep[4]) and np.array_equal(blocks, rep[6], equal_nan=True)
+    np.testing.assert_allclose(loss, rep[3], rtol=1e-10)
+    np.testing.assert_allclose(bed_cache, rep[0], rtol=0, atol=1e-9)
+
+
+def test_a_run_of_one_iteration_takes_no_step_through_any_entry_point():
+    """n_iter == 1 is the initial state alone: run in its three modes, run_many, run_many_replay and run_many_pcg64 return the
+    initial bed, its loss (run_many's value is the reference for the others), a zero accept entry, a NaN block row and zero
+    resampled counts, and leave every generator where it was."""
+    from mcmc_gpu_amd import MCMC_gpu, synthetic
+    prob, ch, rf = synthetic.template(64)
+    beds = np.stack(list(synthetic.initial_beds(prob, 2)))
+    st = [np.random.default_rng(seed=40 + i).bit_generator.state for i in range(2)]
+
+    def check(tup, c, loss0):
+        assert len(tup) == 7
+        bed, loss_mc, loss_data, loss, steps, resampled, blocks = tup
+        assert np.array_equal(bed, beds[c])
+        assert loss.shape == (1,) and loss[0] == loss0 and np.array_equal(loss_mc, loss)
+        assert loss_data.shape == (1,) and not loss_data.any()
+        assert steps.shape == (1,) and steps[0] == 0
+        assert blocks.shape == (1, 4) and np.isnan(blocks).all()
+        assert resampled.shape == (64, 64) and not resampled.any()
+
+    many = MCMC_gpu.run_many(ch, rf, beds, [5, 6], 1)
+    loss0 = [float(t[3][0]) for t in many]
+    assert all(np.isfinite(v) and v > 0 for v in loss0)
+    for c, t in enumerate(many):
+        check(t, c, loss0[c])
+    out, rf_st, ch_st = MCMC_gpu.run_many_replay(ch, rf, beds, st, st, 1)
+    assert rf_st == st and ch_st == st
+    for c, t in enumerate(out):
+        check(t, c, loss0[c])
+    out, rf_st, ch_st = MCMC_gpu.run_many_pcg64(ch, rf, beds, st, st, 1)
+    assert rf_st == st and ch_st == st
+    for c, t in enumerate(out):
+        check(t, c, loss0[c])
+    for mode in ('replay', 'pcg64', 'philox'):
+        c1, r1 = _rehydrate(ch, rf, 40, beds[0].copy())
+        c1.set_rng_mode(mode)
+        check(c1.run(1, r1, only_save_last_bed=True, info_per_iter=10 ** 9, plot=False, progress_bar=None), 0, loss0[0])
+        assert c1.rng.bit_generator.state == st[0] and r1.rng.bit_generator.state == st[0] and c1.philox_step == 0, mode
+
+
 def test_pcg64_batches_equal_host_replay_at_headline_geometry():
     """run_many_pcg64 against run_many_replay (host NumPy draws + NumPy FFT, the bit-exact parity mode): 24 chains x 120 steps at
     256 x 256 with blocks 50-80 -- identical accept masks, blocks and generator states, beds within 1e-9 m."""
