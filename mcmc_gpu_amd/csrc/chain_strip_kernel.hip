@@ -198,7 +198,13 @@ __global__ __launch_bounds__(kST, 4) void chain_strip_kernel(const FusedArgs fa)
     // ---- the step: strip geometry, chain state -> registers, pass, reduce, decide, commit -------------------------------------
     relaunder();
     const step::Window Gw = step::clip_window(gH, gW, s_row, s_col, s_bh, s_bw);
-    const strip::Window G = strip::make_window(gH, gW, s_row, s_col, s_bh, s_bw);
+    // the window cut down to the cells an update can reach (the static rectangle, re-read per step like the other uniforms); the
+    // fences keep the whole window Gw -- a superset of what is loaded and stored, so they wait never too little
+    strip::Window G;
+    {
+      const cargs_t K = kargs();
+      G = strip::make_window(gH, gW, s_row, s_col, s_bh, s_bw, K->T.S.tr0, K->T.S.tr1, K->T.S.tc0, K->T.S.tc1);
+    }
     const strip::Cfg cfg = strip::config(G.wh, G.ww);
     const strip::Lane L = strip::lane_setup(ptid & 63, wave, cfg, G, gH, gW);
     const rsrc_t r_bed = make_rsrc(p_bed, n_cells * (uint32_t)sizeof(TS));
@@ -303,8 +309,11 @@ __global__ __launch_bounds__(kST, 4) void step_strip_kernel(const StepArgs a) {
     }
     const int bh = tab[2 * cur.si], bw = tab[2 * cur.si + 1];
     const rsrc_t r_f = make_rsrc(a.fields + rin * a.field_stride, (uint32_t)(bh * bw) * 8u);
-    const step::Window Gw = step::clip_window(H, W, cur.row, cur.col, bh, bw);
-    const strip::Window G = strip::make_window(H, W, cur.row, cur.col, bh, bw);
+    strip::Window G;                            // trimmed to the static rectangle, re-read per step; the fences keep Gw
+    {
+      const step::cptr_t<StepArgs> K = step::kargs<StepArgs>();
+      G = strip::uniform(strip::make_window(H, W, cur.row, cur.col, bh, bw, K->S.tr0, K->S.tr1, K->S.tc0, K->S.tc1));
+    }
     const strip::Cfg cfg = strip::config(G.wh, G.ww);
     const strip::Lane L = strip::lane_setup(lane, wave, cfg, G, H, W);
     uint32_t upd_bits;
@@ -348,6 +357,9 @@ __global__ __launch_bounds__(kST, 4) void step_strip_kernel(const StepArgs a) {
     // End of step: one barrier, so that no wave writes its partial of the next step into `red` while another still reads this
     // step's; where the next halo window touches the window just written, each wave first waits for its own stores.
     if (acc && has_next && (unsigned)nxt.si < (unsigned)a.B.n_sizes) {
+      int w_row = cur.row;                      // the whole window, formed here from a value the compiler cannot trace: its bounds are not held from the step's head
+      asm volatile("" : "+s"(w_row));
+      const step::Window Gw = step::clip_window(H, W, w_row, cur.col, bh, bw);
       if (step::halo_touches(step::clip_window(H, W, nxt.row, nxt.col, tab[2 * nxt.si], tab[2 * nxt.si + 1]), Gw)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -70,6 +70,25 @@ extern "C" int gsm_set_static(gsm_handle h, const double* surf, const double* ve
   S.dhdt = h->d_static[3].get(); S.smb = h->d_static[4].get(); S.weight = h->d_static[5].get();
   S.upd = h->d_upd.get(); S.mc = h->d_mc.get();
   S.H = h->H; S.W = h->W;
+  {
+    // The rectangle the strip kernels cut every window down to (StaticFields::tr0 ..): bounding box of the set cells, grown by the
+    // stencil's reach and clipped to the grid.  One pass over a host copy of the mask (the caller's array may live on the device);
+    // gsm_set_static is the only place a handle's update mask is set.
+    std::vector<uint8_t> um(n);
+    HIPCHK(h, hipMemcpyAsync(um.data(), update_mask, n, hipMemcpyDefault, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    int r_lo = h->H, r_hi = -1, c_lo = h->W, c_hi = -1;
+    for (int r = 0; r < h->H; ++r) {
+      const uint8_t* m = um.data() + (size_t)r * h->W;
+      for (int c = 0; c < h->W; ++c)
+        if (m[c]) { r_lo = std::min(r_lo, r); r_hi = r; c_lo = std::min(c_lo, c); c_hi = std::max(c_hi, c); }
+    }
+    if (r_hi < 0) S.tr0 = S.tr1 = S.tc0 = S.tc1 = 0;
+    else {
+      S.tr0 = std::max(r_lo - 1, 0); S.tr1 = std::min(r_hi + 2, h->H);
+      S.tc0 = std::max(c_lo - 1, 0); S.tc1 = std::min(c_hi + 2, h->W);
+    }
+  }
   S.res = resolution;
   S.two_res = 2.0 * resolution;
   S.rcp_res = 1.0 / S.res;

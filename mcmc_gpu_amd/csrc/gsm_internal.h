@@ -51,6 +51,10 @@ struct StaticFields {
   const double2* sB;      // (velx, vely)
   const double2* sC;      // (dhdt where mc_mask == 1 else NaN, smb)
   int H, W;
+  // Rows [tr0, tr1) x columns [tc0, tc1): the bounding box of the set cells of `upd`, grown by one cell (the reach of the 5-point
+  // stencil) and clipped to the grid; tr0 == tr1 and tc0 == tc1 when no cell is set.  No cell outside it changes its bed or its
+  // energy in any step: the strip kernels cut every window down to it (strip_step.h: make_window).  Host-computed with the mask.
+  int32_t tr0, tr1, tc0, tc1;
   double res;             // grid spacing h
   double two_res;         // 2.0 * h  (np.gradient interior denominator)
   double rcp_res;         // RN(1/h), RN(1/(2h)): used when fast_div

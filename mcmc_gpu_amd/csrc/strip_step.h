@@ -93,6 +93,31 @@ __host__ __device__ __forceinline__ Window make_window(int H, int W, int row, in
   const step::Window w = step::clip_window(H, W, row, col, bh, bw);
   return Window{w.r0, w.c0, w.wh, w.ww, w.mr0, w.mc0, bw, step::interior(H, W, w)};
 }
+// The same window cut down to the static rectangle [tr0, tr1) x [tc0, tc1) (StaticFields: the bounding box of the update mask
+// grown by the stencil's reach, one cell).  No cell outside the rectangle takes an update, and none has an updatable cell in its
+// 5-point stencil: its bed and its energy are after the step what they were before it, so the strip pass leaves it out.  mr0 and
+// mc0 move on by the rows and columns cut at the top and left: a grid cell keeps its place in the proposal field and in the
+// tile.  The ring around the trimmed window is bed nobody updates, as the ring around the whole window is.  No common cell:
+// wh = ww = 0 at the untrimmed origin -- config gives n = 0, no lane is valid, the step is a zero change with nothing
+// committed.  A rectangle that holds the whole grid gives make_window(H, W, row, col, bh, bw) field for field.
+__host__ __device__ __forceinline__ Window make_window(int H, int W, int row, int col, int bh, int bw, int tr0, int tr1, int tc0, int tc1) {
+  const step::Window w = step::clip_window(H, W, row, col, bh, bw);
+  step::Window t = w;
+  t.r0 = max(w.r0, tr0); t.r1 = min(w.r1, tr1);
+  t.c0 = max(w.c0, tc0); t.c1 = min(w.c1, tc1);
+  if (t.r1 <= t.r0 || t.c1 <= t.c0) return Window{w.r0, w.c0, 0, 0, w.mr0, w.mc0, bw, false};
+  return Window{t.r0, t.c0, t.r1 - t.r0, t.c1 - t.c0, w.mr0 + (t.r0 - w.r0), w.mc0 + (t.c0 - w.c0), bw, step::interior(H, W, t)};
+}
+
+// The replay kernel's records come through vector loads: its window is the same in every lane, but held in vector registers, and
+// the trimmed one then costs the kernel its register budget (scratch spills).  This pins it to scalar registers.
+__device__ __forceinline__ Window uniform(Window g) {
+  g.r0 = __builtin_amdgcn_readfirstlane(g.r0); g.c0 = __builtin_amdgcn_readfirstlane(g.c0);
+  g.wh = __builtin_amdgcn_readfirstlane(g.wh); g.ww = __builtin_amdgcn_readfirstlane(g.ww);
+  g.mr0 = __builtin_amdgcn_readfirstlane(g.mr0); g.mc0 = __builtin_amdgcn_readfirstlane(g.mc0);
+  g.interior = __builtin_amdgcn_readfirstlane((int)g.interior) != 0;
+  return g;
+}
 
 // what a lane does in a step: fixed for the step.  The yes / no facts are bits of one register; a phase turns the ones it
 // needs into lane masks (scalar registers) for its own duration.
