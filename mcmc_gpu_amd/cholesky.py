@@ -16,6 +16,7 @@ import torch
 
 from ._lib import VTYPE_IDS, Vario
 from .engine import _ptr
+from .sgs import cov_norm, rotation_matrix
 
 MODEL_TO_VTYPE = {"Exponential": "exponential", "Gaussian": "gaussian", "Matern": "matern", "Spherical": "spherical"}
 
@@ -37,28 +38,16 @@ def vario_struct(v: dict) -> Vario:
     return out
 
 
-def rotation_matrix(v: dict) -> np.ndarray:
-    th = (v["azimuth"] / 180.0) * np.pi
-    return np.dot(np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]),
-                  np.array([[1 / v["major_range"], 0], [0, 1 / v["minor_range"]]]))
-
-
 def matern_lag_table(bh, bw, res, v: dict) -> np.ndarray:
     """Matern covariance at every distinct lag (di, dj) of a bh x bw block: (2bh-1, 2bw-1) values with
     scipy.special.kv -- the function covariance.py:17-22 evaluates on all N^2 pairs (19 s at N = 6400, SURVEY a14);
     a regular grid has only (2bh-1)(2bw-1) distinct lags."""
-    from scipy.special import gamma, kv
     R = rotation_matrix(v)
     di = np.arange(-(bh - 1), bh)[:, None] * res
     dj = np.arange(-(bw - 1), bw)[None, :] * res
     m0 = dj * R[0, 0] + di * R[1, 0]
     m1 = dj * R[0, 1] + di * R[1, 1]
-    h = np.sqrt(m0 * m0 + m1 * m1)
-    s = v["s"]
-    sc = 0.45246434 * np.exp(-0.70449189 * s) + 1.7863836
-    hh = np.where(h == 0.0, 1e-8, h)
-    c = (v["sill"] - v["nugget"]) * 2 / gamma(s) * np.power(sc * hh * np.sqrt(s), s) * kv(s, 2 * sc * hh * np.sqrt(s))
-    return np.where(np.isnan(c), v["sill"] - v["nugget"], c)
+    return cov_norm(np.sqrt(m0 * m0 + m1 * m1), "matern", v["sill"], v["nugget"], v["s"])
 
 
 def cov_assemble(eng, bh, bw, res, v: dict, ld=None) -> torch.Tensor:

@@ -5,21 +5,73 @@
 
 using namespace gsm;
 
-// the search parameters that gsm_sgs_blocks*, gsm_sgs_iterate and gsm_sgs_grid share
-static int sgs_check_search(gsm_handle h, const std::string& w, int32_t hw, int32_t num_points, double radius, int32_t lag_mi, int32_t lag_mj) {
+// The grid, variogram and search of a call from the arguments of its entry point `w` and the handle, with the checks that
+// gsm_sgs_blocks*, gsm_sgs_iterate, gsm_sgs_grid* and gsm_krige_grid* share: the search parameters, and a lag table (lag_cov; local
+// NULL, vtype 0) or a variogram per cell (local; lag_cov NULL, lag_mi, lag_mj, sill unused), never both.  Each entry has checked its
+// own pointers and keeps its own limits on the grid.
+static int krige_search_fill(gsm_handle h, const std::string& w, KrigeSearch& K, const double* x_axis, const double* y_axis,
+                             const double* lag_cov, int32_t lag_mi, int32_t lag_mj, const double* local, int32_t vtype, int32_t hw,
+                             double radius, int32_t num_points, double sill) {
   if (hw < 1) return fail(h, GSM_E_ARG, w + ": search half-width (ceil(radius / grid spacing)) must be >= 1 cell");
-  if (num_points < 8 || num_points > 48) return fail(h, GSM_E_UNSUPPORTED, w + ": num_points must be in [8, 48]");
+  if (num_points < 8 || num_points > kSgsMaxPts) return fail(h, GSM_E_UNSUPPORTED, w + ": num_points must be in [8, 48]");
   if (!(radius > 0.0)) return fail(h, GSM_E_ARG, w + ": radius must be > 0");
   if (lag_mi < 0 || lag_mj < 0) return fail(h, GSM_E_ARG, w + ": lag table extents must be >= 0");
+  if ((lag_cov == nullptr) == (local == nullptr)) return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  K.H = h->H; K.W = h->W; K.xs = x_axis; K.ys = y_axis; K.lag = lag_cov; K.mi = lag_mi; K.mj = lag_mj; K.local = local; K.vtype = vtype;
+  K.hw = hw; K.num_points = num_points; K.ktype = h->sgs_ktype; K.gmean = h->sgs_gmean; K.radius = radius; K.sill = sill;
+  K.err = h->d_err.get();
   return GSM_OK;
 }
+
+// One row of an entry point's table of device flags (gsm_internal.h: SgsFlag): the code and the text (after the entry's name) of the
+// error that the flag means there.  sgs_report_flags reads and clears the handle's flag once `st` has drained and reports the first
+// row whose bit is set; a flag of no row is `rest` (after the entry's name), or "device flag N" without one.
+struct SgsFlagRow { int32_t bit; int code; const char* text; };
+template <size_t N>
+static int sgs_report_flags(gsm_handle h, hipStream_t st, const std::string& w, const SgsFlagRow (&rows)[N], const char* rest = nullptr) {
+  int32_t flag = 0;
+  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
+  if (!flag) return GSM_OK;
+  for (const SgsFlagRow& r : rows)
+    if (flag & r.bit) return fail(h, r.code, w + r.text);
+  return fail(h, GSM_E_DEVICE_DATA, w + (rest ? std::string(rest) : ": device flag " + std::to_string(flag)));
+}
+// kSgsFlagLagTable is GSM_E_ARG from the block and whole-grid SGS entries and GSM_E_DEVICE_DATA from gsm_krige_grid*: kept as it was
+static const SgsFlagRow kBlockFlags[] = {
+  {kSgsFlagNoValue, GSM_E_DEVICE_DATA, ": a cell to simulate has no conditioning value anywhere on the grid (the reference "
+                                       "would widen its search radius for ever, MCMC.py:150-156)"},
+  {kSgsFlagSingular, GSM_E_DEVICE_DATA, ": singular kriging system (a pivot below eps * N * max|diag|: numpy.linalg.lstsq "
+                                        "would truncate singular values there, _krige.py:37)"},
+  {kSgsFlagNoCentre, GSM_E_DEVICE_DATA, ": no block centre inside the region mask after 64 attempts"},
+  {kSgsFlagLagTable, GSM_E_ARG, ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                "(lag_mi / lag_mj must cover 2 * hw, or the whole grid when the search radius is widened)"}};
+static const char kBlockFlagsRest[] = ": window outside the grid / larger than 1024 cells, more cells than max_cells, or a listed cell outside its window";
+static const SgsFlagRow kGridFlags[] = {
+  {kSgsFlagCell, GSM_E_DEVICE_DATA, ": a path cell outside the grid, holding a value, or listed twice"},
+  {kSgsFlagNoValue, GSM_E_DEVICE_DATA, ": a cell to simulate has no value anywhere on the grid (the reference would widen "
+                                       "its search radius for ever, interpolate.py:150-157)"},
+  {kSgsFlagSingular, GSM_E_DEVICE_DATA, ": singular kriging system (a pivot below eps * N * max|diag|)"},
+  {kSgsFlagLagTable, GSM_E_ARG, ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                "(it must cover twice the widest search radius)"},
+  {kSgsFlagTruncnorm, GSM_E_DEVICE_DATA, ": truncated-normal draw outside scipy's domain (kriging variance 0, or "
+                                         "lower >= upper after standardising)"}};
+static const SgsFlagRow kKrigeFlags[] = {
+  {kSgsFlagCell, GSM_E_DEVICE_DATA, ": a listed cell outside the grid or holding a value"},
+  {kSgsFlagNoValue, GSM_E_DEVICE_DATA, ": a cell to estimate has no value anywhere on the grid (the reference would widen "
+                                       "its search radius for ever, interpolate.py:65-71)"},
+  {kSgsFlagSingular, GSM_E_DEVICE_DATA, ": singular kriging system (a pivot below eps * N * max|diag|)"},
+  {kSgsFlagLagTable, GSM_E_DEVICE_DATA, ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                        "(it must cover twice the widest search radius)"}};
+static const SgsFlagRow kGridDrawFlags[] = {
+  {kSgsFlagDrawBadCell, GSM_E_DEVICE_DATA, ": an entry of `cells` outside the grid"},
+  {kSgsFlagDrawPathLen, GSM_E_DEVICE_DATA, ": path length: path_len is not the number of listed cells without a value"}};
 
 static int sgs_fill(gsm_handle h, SgsArgs& a, double* grids, const double* zcond, const int32_t* windows, const double* x_axis,
                     const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                     int32_t num_points, double sill, const int32_t* cell_off, const int32_t* cells, const double* z,
                     int32_t max_cells, const char* who, int parity = 0) {
   if (!grids || !windows || !x_axis || !y_axis || !lag_cov || !cell_off || !cells || !z) return fail(h, GSM_E_ARG, std::string(who) + ": NULL pointer");
-  if (int rc = sgs_check_search(h, who, hw, num_points, radius, lag_mi, lag_mj)) return rc;
+  if (int rc = krige_search_fill(h, who, a.K, x_axis, y_axis, lag_cov, lag_mi, lag_mj, nullptr, 0, hw, radius, num_points, sill)) return rc;
   if (max_cells < 1 || max_cells > 1024) return fail(h, GSM_E_ARG, std::string(who) + ": max_cells must be in [1, 1024]");
   // cells travel packed as (row << 16 | col) in an int32 and are unpacked with an arithmetic shift: rows up to 32767
   if (h->H < 2 || h->W < 2 || h->H > 32767 || h->W > 32767) return fail(h, GSM_E_UNSUPPORTED, std::string(who) + ": grid sides must be in [2, 32767]");
@@ -39,27 +91,9 @@ static int sgs_fill(gsm_handle h, SgsArgs& a, double* grids, const double* zcond
   a.rec_hdr = (SgsCellHdr*)p; p += cap * sizeof(SgsCellHdr);
   a.rank = (int32_t*)p; p += n * 1024 * 4;
   a.rank_ok = (int32_t*)p;
-  a.H = h->H; a.W = h->W; a.n_chains = h->n_chains;
-  a.grid = grids; a.zcond = zcond; a.win = windows; a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov;
-  a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points; a.radius = radius; a.sill = sill;
-  a.cell_off = cell_off; a.cells = cells; a.z = z; a.err = h->d_err.get(); a.max_cells = max_cells;
-  a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.defer = 0;
+  a.n_chains = h->n_chains; a.grid = grids; a.zcond = zcond; a.win = windows;
+  a.cell_off = cell_off; a.cells = cells; a.z = z; a.max_cells = max_cells; a.defer = 0;
   return GSM_OK;
-}
-
-static int sgs_report(gsm_handle h, hipStream_t st, const char* who) {
-  int32_t flag = 0;
-  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
-  if (!flag) return GSM_OK;
-  const std::string w(who);
-  if (flag & 4) return fail(h, GSM_E_DEVICE_DATA, w + ": a cell to simulate has no conditioning value anywhere on the grid (the reference "
-                                                   "would widen its search radius for ever, MCMC.py:150-156)");
-  if (flag & 8) return fail(h, GSM_E_DEVICE_DATA, w + ": singular kriging system (a pivot below eps * N * max|diag|: numpy.linalg.lstsq "
-                                                   "would truncate singular values there, _krige.py:37)");
-  if (flag & 16) return fail(h, GSM_E_DEVICE_DATA, w + ": no block centre inside the region mask after 64 attempts");
-  if (flag & 64) return fail(h, GSM_E_ARG, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
-                                            "(lag_mi / lag_mj must cover 2 * hw, or the whole grid when the search radius is widened)");
-  return fail(h, GSM_E_DEVICE_DATA, w + ": window outside the grid / larger than 1024 cells, more cells than max_cells, or a listed cell outside its window");
 }
 
 extern "C" int gsm_sgs_blocks(gsm_handle h, double* grids, const double* zcond, const int32_t* windows, const double* x_axis,
@@ -75,7 +109,7 @@ extern "C" int gsm_sgs_blocks(gsm_handle h, double* grids, const double* zcond, 
   a.cell_cnt = nullptr; a.trace = trace; a.nbr_trace = nbr_trace;
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(h, launch_sgs_blocks(a, a.max_cells, st));
-  return sgs_report(h, st, "gsm_sgs_blocks");
+  return sgs_report_flags(h, st, "gsm_sgs_blocks", kBlockFlags, kBlockFlagsRest);
 }
 
 extern "C" int gsm_sgs_blocks_batch(gsm_handle h, double* grids, const double* zcond, const int32_t* windows, const double* x_axis,
@@ -117,7 +151,8 @@ static int sgs_grid_run(gsm_handle h, const std::string& w, double* grids, const
   if (draw_kind != GSM_DRAW_NORMAL && draw_kind != GSM_DRAW_TRUNCATED) return fail(h, GSM_E_ARG, w + ": draw_kind must be GSM_DRAW_NORMAL or GSM_DRAW_TRUNCATED");
   if ((draw_kind == GSM_DRAW_TRUNCATED) != (lower != nullptr) || (lower != nullptr) != (upper != nullptr))
     return fail(h, GSM_E_ARG, w + ": bounds (lower and upper) go with GSM_DRAW_TRUNCATED and only with it");
-  if (int rc = sgs_check_search(h, w, hw, num_points, radius, lag_mi, lag_mj)) return rc;
+  SgsGridArgs a{};
+  if (int rc = krige_search_fill(h, w, a.K, x_axis, y_axis, lag_cov, lag_mi, lag_mj, local, vtype, hw, radius, num_points, sill)) return rc;
   if (h->H > 32767 || h->W > 32767 || (int64_t)h->H * h->W > (1LL << 25))
     return fail(h, GSM_E_ARG, w + ": at most 2^25 cells and 32767 per side (25-bit slot and cell fields in the records)");
   if (h->n_chains > 65535) return fail(h, GSM_E_ARG, w + ": at most 65535 realisations per handle");
@@ -128,12 +163,8 @@ static int sgs_grid_run(gsm_handle h, const std::string& w, double* grids, const
   hipStream_t st = (hipStream_t)stream;
   const size_t R = (size_t)h->n_chains, HW = (size_t)h->H * h->W;
   const int seg_cap = (int)std::min<int64_t>(((int64_t)seg_cells + 63) / 64 * 64, std::max<int64_t>(64, ((int64_t)max_path + 63) / 64 * 64));
-  SgsGridArgs a{};
-  a.H = h->H; a.W = h->W; a.n_real = (int)R;
-  a.grid = grids; a.path = path; a.path_off = path_off; a.draw = draws; a.lo = lower; a.hi = upper; a.draw_kind = draw_kind;
-  a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov; a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points;
-  a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.radius = radius; a.sill = sill; a.trace = trace; a.err = h->d_err.get();
-  a.seg_cap = seg_cap; a.seg_len = seg_cap;
+  a.n_real = (int)R; a.grid = grids; a.path = path; a.path_off = path_off; a.draw = draws; a.lo = lower; a.hi = upper;
+  a.draw_kind = draw_kind; a.trace = trace; a.seg_cap = seg_cap; a.seg_len = seg_cap;
   // scratch of the call: ranks [R][H*W], then per realisation seg_cap records (headers + 48 (value, weight) entries)
   const size_t bytes = R * HW * sizeof(int32_t) + 256 + R * (size_t)seg_cap * (sizeof(SgsGridHdr) + 48 * sizeof(double2));
   DevBuf<char> scratch;
@@ -147,21 +178,10 @@ static int sgs_grid_run(gsm_handle h, const std::string& w, double* grids, const
   e = launch_sgs_grid_ranks(a, max_path, st);
   for (int s0 = 0; e == hipSuccess && s0 < max_path; s0 += seg_cap) {
     a.seg0 = s0; a.seg_len = std::min(seg_cap, max_path - s0);
-    e = launch_sgs_grid_segment(a, st, local, vtype);
+    e = launch_sgs_grid_segment(a, st);
   }
   if (e != hipSuccess) return fail(h, GSM_E_HIP, w + ": " + hipGetErrorString(e));
-  int32_t flag = 0;
-  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;      // the scratch lives until the stream has drained
-  if (!flag) return GSM_OK;
-  if (flag & 2) return fail(h, GSM_E_DEVICE_DATA, w + ": a path cell outside the grid, holding a value, or listed twice");
-  if (flag & 4) return fail(h, GSM_E_DEVICE_DATA, w + ": a cell to simulate has no value anywhere on the grid (the reference would widen "
-                                                   "its search radius for ever, interpolate.py:150-157)");
-  if (flag & 8) return fail(h, GSM_E_DEVICE_DATA, w + ": singular kriging system (a pivot below eps * N * max|diag|)");
-  if (flag & 64) return fail(h, GSM_E_ARG, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
-                                            "(it must cover twice the widest search radius)");
-  if (flag & 128) return fail(h, GSM_E_DEVICE_DATA, w + ": truncated-normal draw outside scipy's domain (kriging variance 0, or "
-                                                     "lower >= upper after standardising)");
-  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+  return sgs_report_flags(h, st, w, kGridFlags);                  // the scratch lives until the stream has drained
 }
 
 extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, const int64_t* path_off, int32_t max_path,
@@ -191,28 +211,16 @@ static int krige_grid_run(gsm_handle h, const std::string& w, const double* grid
   if (n_cells < 0 || (int64_t)n_cells > (int64_t)h->H * h->W) return fail(h, GSM_E_ARG, w + ": n_cells must be in [0, H * W]");
   if (n_cells == 0) return GSM_OK;
   if (!grid || !cells || !x_axis || !y_axis || (!lag_cov && !local) || !est || !var || !n_neighbours) return fail(h, GSM_E_ARG, w + ": NULL pointer");
-  if (int rc = sgs_check_search(h, w, hw, num_points, radius, lag_mi, lag_mj)) return rc;
+  KrigeGridArgs a{};
+  if (int rc = krige_search_fill(h, w, a.K, x_axis, y_axis, lag_cov, lag_mi, lag_mj, local, vtype, hw, radius, num_points, sill)) return rc;
   if (h->H < 2 || h->W < 2 || h->H > 32767 || h->W > 32767) return fail(h, GSM_E_ARG, w + ": grid sides must be in [2, 32767]");
   if (h->n_chains != 1) return fail(h, GSM_E_ARG, w + ": one grid per handle (create it with n_chains = 1)");
   if (h->sgs_ktype == GSM_KRIGING_SIMPLE && !h->sgs_gmean) return fail(h, GSM_E_STATE, w + ": simple kriging without a global mean");
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  KrigeGridArgs a{};
-  a.H = h->H; a.W = h->W; a.n_cells = n_cells; a.grid = grid; a.cells = cells;
-  a.xs = x_axis; a.ys = y_axis; a.lag = lag_cov; a.hw = hw; a.mi = lag_mi; a.mj = lag_mj; a.num_points = num_points;
-  a.ktype = h->sgs_ktype; a.gmean = h->sgs_gmean; a.radius = radius; a.sill = sill;
-  a.est = est; a.var = var; a.n = n_neighbours; a.err = h->d_err.get();
-  HIPCHK(h, launch_krige_grid(a, st, local, vtype));
-  int32_t flag = 0;
-  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
-  if (!flag) return GSM_OK;
-  if (flag & 2) return fail(h, GSM_E_DEVICE_DATA, w + ": a listed cell outside the grid or holding a value");
-  if (flag & 4) return fail(h, GSM_E_DEVICE_DATA, w + ": a cell to estimate has no value anywhere on the grid (the reference would widen "
-                                                   "its search radius for ever, interpolate.py:65-71)");
-  if (flag & 8) return fail(h, GSM_E_DEVICE_DATA, w + ": singular kriging system (a pivot below eps * N * max|diag|)");
-  if (flag & 64) return fail(h, GSM_E_DEVICE_DATA, w + ": the lag covariance table does not reach the lag between two chosen neighbours "
-                                                    "(it must cover twice the widest search radius)");
-  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+  a.n_cells = n_cells; a.grid = grid; a.cells = cells; a.est = est; a.var = var; a.n = n_neighbours;
+  HIPCHK(h, launch_krige_grid(a, st));
+  return sgs_report_flags(h, st, w, kKrigeFlags);
 }
 
 extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
@@ -245,7 +253,7 @@ extern "C" int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const 
 extern "C" int gsm_sgs_check(gsm_handle h, void* stream) {
   if (!h) return GSM_E_ARG;
   HIPCHK(h, hipSetDevice(h->device));
-  return sgs_report(h, (hipStream_t)stream, "gsm_sgs_check");
+  return sgs_report_flags(h, (hipStream_t)stream, "gsm_sgs_check", kBlockFlags, kBlockFlagsRest);
 }
 
 // the block size ranges and cell capacity that both gsm_sgs_draw_* entry points take
@@ -318,12 +326,7 @@ extern "C" int gsm_sgs_grid_draw_pcg64(gsm_handle h, uint64_t* states, const int
   a.lo = lower; a.hi = upper; a.draw_kind = draw_kind; a.work = work; a.path = path; a.draws = draws; a.path_len = path_len;
   a.jump = h->d_pcg_tab.get(); a.zig = h->d_pcg_tab.get() + kPcgJumpWords; a.err = h->d_err.get();
   HIPCHK(h, launch_sgs_grid_draw_pcg64(a, st));
-  int32_t flag = 0;
-  if (int rc = read_and_clear_flag(h, st, &flag)) return rc;
-  if (!flag) return GSM_OK;
-  if (flag & kSgsGridDrawBadCell) return fail(h, GSM_E_DEVICE_DATA, w + ": an entry of `cells` outside the grid");
-  if (flag & kSgsGridDrawPathLen) return fail(h, GSM_E_DEVICE_DATA, w + ": path length: path_len is not the number of listed cells without a value");
-  return fail(h, GSM_E_DEVICE_DATA, w + ": device flag " + std::to_string(flag));
+  return sgs_report_flags(h, st, w, kGridDrawFlags);
 }
 
 // scratch of the loss kernels: a partial sum and bad-cell count per (chain, part), and per chain the ticket of sgs_loss_tail_kernel
@@ -502,10 +505,14 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
     if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_sgs_iterate: call gsm_set_static first");
     if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_iterate: fp64 beds only");
     if ((rc = sgs_parts_ensure(h))) return rc;
-    HIPCHK(h, launch_sgs_loss_tail(h->S, h->n_chains, b->trend, h->sgs_parts.sum.get(), h->sgs_parts.bad.get(), h->sgs_parts.ticket.get(), b->loss, b->bad, u,
-                                   b->loss_prev, b->accept, b->loss_rec ? b->loss_rec + j : nullptr, b->acc_rec ? b->acc_rec + j : nullptr,
-                                   n_iters, qt ? 1 : 2, b->cur, qt ? b->proposed : b->next, b->resampled, win, main_st,
-                                   tail_qt ? b->qt_quantiles : nullptr, b->qt_references, b->qt_n, qt_clip_min, qt_clip_max, b->next, h->d_sgs_next_acc.get()));
+    SgsTailArgs t{};
+    t.trend = b->trend; t.part_sum = h->sgs_parts.sum.get(); t.part_bad = h->sgs_parts.bad.get(); t.ticket = h->sgs_parts.ticket.get();
+    t.loss = b->loss; t.bad = b->bad; t.u = u; t.loss_prev = b->loss_prev; t.accept = b->accept;
+    t.loss_rec = b->loss_rec ? b->loss_rec + j : nullptr; t.acc_rec = b->acc_rec ? b->acc_rec + j : nullptr; t.rec_stride = n_iters;
+    t.mode = qt ? 1 : 2; t.cur = b->cur; t.beds = qt ? b->proposed : b->next; t.resampled = b->resampled; t.win = win;
+    t.qt_q = tail_qt ? b->qt_quantiles : nullptr; t.qt_ref = b->qt_references; t.qt_n = b->qt_n; t.clip_min = qt_clip_min; t.clip_max = qt_clip_max;
+    t.next = b->next; t.next_acc = h->d_sgs_next_acc.get();
+    HIPCHK(h, launch_sgs_loss_tail(h->S, h->n_chains, t, main_st));
   }
   return GSM_OK;
 }

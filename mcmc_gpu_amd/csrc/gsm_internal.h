@@ -203,6 +203,43 @@ void pcg64_host_tables(uint64_t* jump_out, const uint64_t** zig_out);
 struct SgsDrawArgs;
 hipError_t launch_sgs_draw_pcg64(const SgsDrawArgs& a, uint64_t* states, const uint64_t* jump, const uint64_t* zig, hipStream_t st);
 
+// Device flags of the SGS and kriging kernels, OR-ed into the handle's error word (KrigeSearch::err, SgsDrawArgs::err,
+// SgsGridDrawArgs::err) and decoded per entry point by gsm_api_sgs.hip's tables.  gsm_draw_pcg64's flags are another set.
+enum SgsFlag : int32_t {
+  kSgsFlagWindow = 1,        // a block window outside the grid or larger than 1024 cells, or more cells than max_cells
+  kSgsFlagCell = 2,          // a listed cell outside its window / the grid, holding a value, or listed twice
+  kSgsFlagNoValue = 4,       // no value anywhere on the grid for a cell's search
+  kSgsFlagSingular = 8,      // a pivot of the kriging system below its tolerance
+  kSgsFlagNoCentre = 16,     // no block centre inside the region mask
+  kSgsFlagLagTable = 64,     // a lag between two chosen neighbours beyond the lag table
+  kSgsFlagTruncnorm = 128,   // a truncated-normal draw outside scipy's domain
+  kSgsFlagDrawPathLen = 256, // gsm_sgs_grid_draw_pcg64: the valueless cells of `cells` are not path_len many
+  kSgsFlagDrawBadCell = 512, // gsm_sgs_grid_draw_pcg64: an entry of `cells` outside the grid
+};
+constexpr int kSgsMaxPts = 48;      // neighbours of a kriging system
+constexpr int kSgsMaxWin = 1024;    // cells of a block window of the small-scale chain
+// The grid, the variogram and the search of one SGS / kriging call: what sgs_search.h's octant_ring_search and krige_solve_at take
+// (first member of SgsArgs, SgsGridArgs and KrigeGridArgs; filled by gsm_api_sgs.hip's krige_search_fill).
+struct KrigeSearch {
+  int H, W;
+  const double* xs;        // [W] x coordinate of every column
+  const double* ys;        // [H] y coordinate of every row
+  const double* lag;       // [(2 mi + 1) * (2 mj + 1)] covariance at integer lag (di, dj), |di| <= mi, |dj| <= mj; or nullptr with `local`
+  int mi, mj;
+  const double* local;     // a variogram per cell, [H*W][6] = R00 R01 R10 R11 sill nugget, of model `vtype` (GSM_VTYPE_*); nullptr and 0 with `lag`
+  int vtype;
+  int hw, num_points;
+  int ktype;               // 0 ordinary kriging (ok_solve), 1 simple kriging (sk_solve) with gmean
+  const double* gmean;     // [n_chains] global mean of each chain's / realisation's conditioning values (simple kriging only)
+  double radius, sill;
+  int32_t* err;
+};
+// what every launcher of a kernel that searches checks again (the entry points have refused these with their own texts)
+inline bool krige_search_ok(const KrigeSearch& K) {
+  return K.hw >= 1 && K.num_points >= 8 && K.num_points <= kSgsMaxPts && K.H >= 2 && K.W >= 2 && K.H <= 32767 && K.W <= 32767 &&
+         (K.lag == nullptr) != (K.local == nullptr);
+}
+
 // small-scale chain: sequential Gaussian simulation of one block per chain (sgs_kernel.hip)
 struct SgsCellHdr {          // one per (chain, cell slot), written by sgs_weights_kernel
   int32_t n;                 // neighbours; -1: the cell holds conditioning data; -2: cell outside its window; 0: error
@@ -212,26 +249,19 @@ struct SgsCellHdr {          // one per (chain, cell slot), written by sgs_weigh
   double c1;                 // (1 - sum of the kriging weights) / n
 };
 struct SgsArgs {
-  int H, W, n_chains;
+  KrigeSearch K;
+  int n_chains;
   double* grid;            // [n_chains][H*W] in/out: the conditioning grid; the window's cells are rewritten
   const double* zcond;     // [H*W] or nullptr: initial content of the window cells (conditioning data, NaN elsewhere)
   const int32_t* win;      // [n_chains*4] r0, r1, c0, c1 of the simulated block
-  const double* xs;        // [W] x coordinate of every column
-  const double* ys;        // [H] y coordinate of every row
-  const double* lag;       // [(2 mi + 1) * (2 mj + 1)] covariance at integer lag (di, dj), |di| <= mi, |dj| <= mj
-  int hw, mi, mj, num_points;
-  int ktype;               // 0 ordinary kriging (ok_solve), 1 simple kriging (sk_solve) with gmean
   int defer;               // 1: every cell outside the blocks holds a value (the caller's promise); sgs_weights_kernel then reads no grid value
                            //    -- the records name the cells -- and can run while the grid of the iteration before is still being written
-  const double* gmean;     // [n_chains] global mean of each chain's conditioning values (simple kriging only)
-  double radius, sill;
   const int32_t* cell_off; // [n_chains+1] (or [n_chains] with cell_cnt)
   const int32_t* cell_cnt; // optional [n_chains]: number of cells of each chain
   const int32_t* cells;    // [total*2] (i, j) in simulation order
   const double* z;         // [total] standard normals
   double* trace;           // optional [total*3]: (neighbours, estimate, variance)
   int32_t* nbr_trace;      // optional [total*48]: the chosen neighbours (flat cell index, -1 padded) of every simulated cell
-  int32_t* err;
   // scratch of the handle: visiting ranks of the block cells and one record per (chain, cell slot)
   int max_cells;           // record stride per chain (>= the largest cell count of the call)
   int32_t* rank;           // [n_chains][1024]
@@ -250,7 +280,8 @@ struct SgsGridHdr {          // one per (realisation, path slot of the segment),
   double c1;                 // ordinary: (1 - sum of the kriging weights) / n; simple: global mean * (1 - sum of the weights)
 };
 struct SgsGridArgs {
-  int H, W, n_real;
+  KrigeSearch K;           // gmean [n_real]
+  int n_real;
   double* grid;            // [n_real][H*W] normal scores, NaN where a value is to be simulated; the path cells are rewritten
   const int32_t* path;     // flat cell indices in visiting order, realisation r's at [path_off[r], path_off[r + 1])
   const int64_t* path_off; // [n_real + 1]
@@ -258,12 +289,7 @@ struct SgsGridArgs {
   const double* lo;        // [H*W] transformed lower / upper bounds, or nullptr (draw_kind 0)
   const double* hi;
   int draw_kind;
-  const double* xs; const double* ys; const double* lag;
-  int hw, mi, mj, num_points, ktype;
-  const double* gmean;     // [n_real] (simple kriging)
-  double radius, sill;
   double* trace;           // optional [total*3]: (neighbours, estimate, variance) per path cell
-  int32_t* err;
   int32_t* rank;           // [n_real][H*W]: -1 conditioning value, slot of a path cell, INT32_MAX never filled
   int seg0, seg_len, seg_cap;   // this segment: slots [seg0, seg0 + seg_len); records per realisation (a multiple of 64)
   SgsGridHdr* rec_hdr;     // [n_real*seg_cap]
@@ -286,28 +312,23 @@ struct SgsGridDrawArgs {
   const uint64_t* jump; const uint64_t* zig;     // device copies of the constant tables
   int32_t* err;
 };
-constexpr int kSgsGridDrawPathLen = 256;   // device flag: the valueless cells of `cells` are not path_len many
-constexpr int kSgsGridDrawBadCell = 512;   // device flag: an entry of `cells` outside the grid
 hipError_t launch_sgs_grid_draw_pcg64(const SgsGridDrawArgs& a, hipStream_t st);
 // interpolate.krige: estimate and variance at listed cells of one grid (krige_grid_kernel.hip)
 struct KrigeGridArgs {
-  int H, W, n_cells;
+  KrigeSearch K;           // gmean [1]
+  int n_cells;
   int cell0;               // first entry of `cells` of this launch (set by launch_krige_grid)
-  const double* grid;      // [H*W] normal scores, NaN where there is no datum
-  const int32_t* cells;    // [n_cells] flat indices of the cells to estimate (each NaN in grid)
-  const double* xs; const double* ys; const double* lag;
-  int hw, mi, mj, num_points, ktype;
-  const double* gmean;     // [1] (simple kriging)
-  double radius, sill;
+  // The outputs stand before the inputs on purpose.  krige_grid_kernel uses every SGPR, and how the argument loads group decides
+  // which spill slots the compiler can drop: with grid and cells first it keeps 36 bytes of (unused) private segment per lane.
   double* est;             // [n_cells] kriging estimate, in the order of `cells`; NaN where the cell raised an error
   double* var;             // [n_cells] sill - sum w rho, signed
   int32_t* n;              // [n_cells] neighbours; 0 where the cell raised an error
-  int32_t* err;
+  const double* grid;      // [H*W] normal scores, NaN where there is no datum
+  const int32_t* cells;    // [n_cells] flat indices of the cells to estimate (each NaN in grid)
 };
-// `local` non-null (and a.lag null): a variogram per cell, [H*W][6] = R00 R01 R10 R11 sill nugget, of model `vtype` (GSM_VTYPE_*)
-hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);
+hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st);
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
-hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st, const double* local = nullptr, int vtype = 0);   // weights, then values of one segment
+hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st);   // weights, then values of one segment
 // gsm_debug_special: hipErrorInvalidValue for an unknown `which`, a NULL pointer it reads or n outside [1, 2^31 - 256)
 hipError_t launch_debug_special(int which, int vtype, int64_t n, const double* x0, const double* x1, const double* x2, const double* x3,
                                 const double* x4, double* out, int32_t* err, hipStream_t st);
@@ -329,11 +350,15 @@ hipError_t launch_sgs_draw(const SgsDrawArgs& a, hipStream_t st);
 int sgs_loss_parts(const StaticFields& S);      // workgroups per chain of the loss kernel; scratch = n_chains * parts doubles + ints
 hipError_t launch_sgs_loss(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* loss, int32_t* bad,
                            double* part_sum, int32_t* part_bad, hipStream_t st);
-hipError_t launch_sgs_loss_tail(const StaticFields& S, int n_chains, const double* trend, double* part_sum, int32_t* part_bad, int32_t* ticket,
-                                double* loss, int32_t* bad, const double* u, double* loss_prev, uint8_t* accept, double* loss_rec,
-                                uint8_t* acc_rec, int64_t rec_stride, int mode, double* cur, double* beds, uint32_t* resampled,
-                                const int32_t* win, hipStream_t st, const double* qt_q = nullptr, const double* qt_ref = nullptr, int qt_n = 0,
-                                double clip_min = 0.0, double clip_max = 0.0, double* next = nullptr, double* next_acc = nullptr);
+// the operands of sgs_loss_tail_kernel (sgs_iter_kernel.hip), filled by gsm_sgs_iterate; `parts` is the launcher's
+struct SgsTailArgs {
+  const double* trend; int parts; double* part_sum; int32_t* part_bad; int32_t* ticket;
+  double* loss; int32_t* bad; const double* u; double* loss_prev; uint8_t* accept; double* loss_rec; uint8_t* acc_rec; int64_t rec_stride;
+  int mode; double* cur; double* beds; uint32_t* resampled; const int32_t* win;
+  // QT (qt_q non-null): the two normal-score transforms of an iteration in this launch as well (see the kernel)
+  const double* qt_q; const double* qt_ref; int qt_n; double clip_min, clip_max; double* next; double* next_acc;
+};
+hipError_t launch_sgs_loss_tail(const StaticFields& S, int n_chains, const SgsTailArgs& args, hipStream_t st);
 bool sgs_tail_takes_qt(const StaticFields& S, int nq);
 hipError_t launch_sgs_state_init(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* energy, double* state,
                                  hipStream_t st);

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64) void sgs_draw_pcg64_kernel(const SgsDrawArgs a,
     for (int tries = 0;; ++tries) {
       row = G.integers(0, a.H); col = G.integers(0, a.W);
       if (!a.region_mask || a.region_mask[row * a.W + col] == 1) break;
-      if (tries > (1 << 20)) { if (lane == 0) atomicOr(a.err, 16); break; }
+      if (tries > (1 << 20)) { if (lane == 0) atomicOr(a.err, kSgsFlagNoCentre); break; }
     }
     const int bsx = G.integers(a.min_x, a.max_x), bsy = G.integers(a.min_y, a.max_y);
     // int(ix -/+ bs / 2) of MCMC.py:1758-1761 (truncation towards zero of a half-integer)
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void sgs_draw_pcg64_kernel(const SgsDrawArgs a,
       a.blk[4 * rec] = row; a.blk[4 * rec + 1] = col; a.blk[4 * rec + 2] = bsx; a.blk[4 * rec + 3] = bsy;
       a.cell_off[rec] = (int32_t)(rec * a.max_cells); a.cell_cnt[rec] = (n <= a.max_cells && n <= 1024) ? n : 0;
     }
-    if ((n > a.max_cells || n > 1024) && lane == 0) atomicOr(a.err, 1);
+    if ((n > a.max_cells || n > 1024) && lane == 0) atomicOr(a.err, kSgsFlagWindow);
     const int nn = (n > a.max_cells || n > 1024) ? 0 : n;
     for (int p = lane; p < nn; p += 64) order[p] = ((r0 + p / ww) << 16) | (c0 + p % ww);
     __syncthreads();

@@ -67,11 +67,11 @@ __global__ __launch_bounds__(64) void sgs_grid_draw_pcg64_kernel(const SgsGridDr
     if (free_cell && pos < a.path_len) path[pos] = cell;
     count += __popcll(m);
   }
-  if (__ballot(bad_cell) != 0ull && lane == 0) atomicOr(a.err, kSgsGridDrawBadCell);
+  if (__ballot(bad_cell) != 0ull && lane == 0) atomicOr(a.err, kSgsFlagDrawBadCell);
   if (count != a.path_len) {
     // the caller's path_len is not the number of valueless cells: no draw is made, the generator stays behind the shuffle
     if (lane == 0) {
-      atomicOr(a.err, kSgsGridDrawPathLen);
+      atomicOr(a.err, kSgsFlagDrawPathLen);
       gs[0] = G.s.lo; gs[1] = G.s.hi; gs[4] = G.has32; gs[5] = G.cached;
     }
     return;

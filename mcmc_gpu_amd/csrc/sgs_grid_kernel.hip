@@ -55,35 +55,35 @@ __device__ __forceinline__ double load_l2(const double* p) {
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sgs_grid_rank_kernel(const SgsGridArgs a) {
   const int r = blockIdx.y;
-  const int HW = a.H * a.W;
+  const int HW = a.K.H * a.K.W;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= HW) return;
   a.rank[(size_t)r * HW + c] = isnan(a.grid[(size_t)r * HW + c]) ? kGridNever : -1;
 }
 __global__ __launch_bounds__(256) void sgs_grid_slot_kernel(const SgsGridArgs a) {
   const int r = blockIdx.y;
-  const int HW = a.H * a.W;
+  const int HW = a.K.H * a.K.W;
   const int64_t p0 = a.path_off[r];
   const int cnt = (int)(a.path_off[r + 1] - p0);
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= cnt) return;
   const int cell = a.path[p0 + k];
-  if (cell < 0 || cell >= HW) { atomicOr(a.err, 2); return; }
-  if (atomicCAS(&a.rank[(size_t)r * HW + cell], kGridNever, k) != kGridNever) atomicOr(a.err, 2);   // not NaN, or listed twice
+  if (cell < 0 || cell >= HW) { atomicOr(a.K.err, kSgsFlagCell); return; }
+  if (atomicCAS(&a.rank[(size_t)r * HW + cell], kGridNever, k) != kGridNever) atomicOr(a.K.err, kSgsFlagCell);   // not NaN, or listed twice
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // sgs_grid_weights_kernel: one 64-lane workgroup per (slot of the segment, realisation).  kLocal: a variogram per cell
-// (sgs_grid_weights_local_kernel) -- `local` [H*W][6] and `vtype` as sgs_search.h's LocalCov takes them, a.lag and a.sill unused
+// (sgs_grid_weights_local_kernel) -- a.K.local [H*W][6] and a.K.vtype as sgs_search.h's LocalCov takes them, a.K.lag and a.K.sill unused
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool kLocal>
-__device__ __forceinline__ void sgs_grid_weights_cell(const SgsGridArgs& a, SgsSearchLds& L, const double* __restrict__ local, int vtype) {
+__device__ __forceinline__ void sgs_grid_weights_cell(const SgsGridArgs& a, SgsSearchLds& L) {
   const int r = blockIdx.y, lane = threadIdx.x;
   const int slot = a.seg0 + blockIdx.x;
   const int64_t p0 = a.path_off[r];
   const int cnt = (int)(a.path_off[r + 1] - p0);
   if (slot >= cnt) return;
-  const int H = a.H, W = a.W, HW = H * W;
+  const int H = a.K.H, W = a.K.W, HW = H * W;
   const size_t rec = (size_t)r * a.seg_cap + blockIdx.x;
   const int cell = a.path[p0 + slot];
   const int32_t* rank = a.rank + (size_t)r * HW;
@@ -98,25 +98,17 @@ __device__ __forceinline__ void sgs_grid_weights_cell(const SgsGridArgs& a, SgsS
   const double* __restrict__ g = a.grid + (size_t)r * HW;
   const int i0 = cell / W, j0 = cell - i0 * W;
   // rank: -1 = conditioning data, < slot = filled before this cell
-  const int n = octant_ring_search(L, [rank, slot, W](int ic, int jc) { return rank[ic * W + jc] < slot; }, i0, j0, H, W, a.xs, a.ys,
-                                   a.radius, a.hw, a.num_points / 8, lane);
+  const int n = octant_ring_search(L, [rank, slot, W](int ic, int jc) { return rank[ic * W + jc] < slot; }, i0, j0, H, W, a.K.xs, a.K.ys,
+                                   a.K.radius, a.K.hw, a.K.num_points / 8, lane);
   // a cell that fails gets no value: n = 0 in its record
   auto give_up = [&](int32_t flag) {
-    if (lane == 0) { atomicOr(a.err, flag); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; }
+    if (lane == 0) { atomicOr(a.K.err, flag); a.rec_hdr[rec].n = 0; a.rec_hdr[rec].cell = cell; }
   };
-  if (n == 0) { give_up(4); return; }                            // no value anywhere on the grid: the reference would loop forever
-  const bool lagr = a.ktype == 0;
-  double w_l, rho_l;
+  if (n == 0) { give_up(kSgsFlagNoValue); return; }                            // no value anywhere on the grid: the reference would loop forever
+  const bool lagr = a.K.ktype == 0;
+  double w_l, rho_l, sill;
   int my_i, my_j;                                                // the neighbour's (row, column): only the block kernel's record needs it
-  double sill;
-  if constexpr (kLocal) {
-    const LocalCov cov{local + 6 * (size_t)cell, a.xs, a.ys, vtype};
-    sill = cov.p[4];
-    if (const int e = krige_solve(L, n, i0, j0, H, W, cov, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
-  } else {
-    sill = a.sill;
-    if (const int e = krige_solve<false>(L, n, i0, j0, H, W, a.lag, a.mi, a.mj, lagr, lane, w_l, rho_l, my_i, my_j)) { give_up(e); return; }
-  }
+  if (const int e = krige_solve_at<kLocal, false>(L, a.K, cell, n, i0, j0, lagr, lane, w_l, rho_l, my_i, my_j, sill)) { give_up(e); return; }
   double var = sill - dev::wave64_sum(w_l * rho_l);
   var = fabs(var);                                               // interpolate.py:168
   const double sw = dev::wave64_sum(w_l);
@@ -135,17 +127,17 @@ __device__ __forceinline__ void sgs_grid_weights_cell(const SgsGridArgs& a, SgsS
   if (lane == 0) {
     SgsGridHdr hd;
     hd.n = n; hd.cell = cell; hd.sd = sqrt(var); hd.var = var;
-    hd.c1 = lagr ? (1.0 - sw) / (double)n : a.gmean[r] * (1.0 - sw);
+    hd.c1 = lagr ? (1.0 - sw) / (double)n : a.K.gmean[r] * (1.0 - sw);
     a.rec_hdr[rec] = hd;
   }
 }
 __global__ __launch_bounds__(64) void sgs_grid_weights_kernel(const SgsGridArgs a) {
   __shared__ SgsSearchLds L;
-  sgs_grid_weights_cell<false>(a, L, nullptr, 0);
+  sgs_grid_weights_cell<false>(a, L);
 }
-__global__ __launch_bounds__(64) void sgs_grid_weights_local_kernel(const SgsGridArgs a, const double* __restrict__ local, int vtype) {
+__global__ __launch_bounds__(64) void sgs_grid_weights_local_kernel(const SgsGridArgs a) {
   __shared__ SgsSearchLds L;
-  sgs_grid_weights_cell<true>(a, L, local, vtype);
+  sgs_grid_weights_cell<true>(a, L);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -155,9 +147,9 @@ constexpr int kGridSeqWaves = 4;
 // the bounded draw of interpolate.py:183-187 for one cell: truncnorm.rvs(a, b, loc=est, scale=sd) = ppf(u, a, b) * sd + est;
 // scale == 0 (scipy returns est without drawing) and a >= b (scipy raises) are domain errors
 __device__ __noinline__ double grid_truncnorm_draw(double est, double sd, double lo, double hi, double u, int32_t* err) {
-  if (!(sd > 0.0)) { atomicOr(err, 128); return NAN; }
+  if (!(sd > 0.0)) { atomicOr(err, kSgsFlagTruncnorm); return NAN; }
   const double ta = (lo - est) / sd, tb = (hi - est) / sd;
-  if (!(ta < tb)) { atomicOr(err, 128); return NAN; }
+  if (!(ta < tb)) { atomicOr(err, kSgsFlagTruncnorm); return NAN; }
   return tn::ppf(u, ta, tb) * sd + est;
 }
 
@@ -167,11 +159,11 @@ __global__ __launch_bounds__(64 * kGridSeqWaves) void sgs_grid_values_kernel(con
   __shared__ uint64_t mpart[kGridSeqWaves][64];
   const int r = blockIdx.x, lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int HW = a.H * a.W;
+  const int HW = a.K.H * a.K.W;
   double* __restrict__ g = a.grid + (size_t)r * HW;
   const int64_t p0 = a.path_off[r];
   const int k_end = min((int)(a.path_off[r + 1] - p0), a.seg0 + a.seg_len);
-  const bool ok_k = a.ktype == 0, bounded = a.draw_kind == 1;
+  const bool ok_k = a.K.ktype == 0, bounded = a.draw_kind == 1;
   for (int kc = a.seg0; kc < k_end; kc += 64) {
     __syncthreads();                                             // wave 0's values of the chunks before have been stored
     const int j = kc + lane;
@@ -225,7 +217,7 @@ __global__ __launch_bounds__(64 * kGridSeqWaves) void sgs_grid_values_kernel(con
       double vk = 0.0;
       if (nk > 0) {                                              // cell k's estimate is complete: every cell it lists came before
         const double ek = dev::readlane_f64(est, k), sk = dev::readlane_f64(hd.sd, k), dk = dev::readlane_f64(dr, k);
-        if (bounded) vk = grid_truncnorm_draw(ek, sk, dev::readlane_f64(lo_c, k), dev::readlane_f64(hi_c, k), dk, a.err);
+        if (bounded) vk = grid_truncnorm_draw(ek, sk, dev::readlane_f64(lo_c, k), dev::readlane_f64(hi_c, k), dk, a.K.err);
         else vk = ek + sk * dk;                                  // rng.normal(est, sqrt(var), 1), interpolate.py:174
       } else if (nk == -3) {
         vk = dev::readlane_f64(lo_c, k);
@@ -282,20 +274,19 @@ hipError_t launch_debug_special(int which, int vtype, int64_t n, const double* x
 }
 
 static bool grid_args_ok(const SgsGridArgs& a) {
-  return !(a.hw < 1 || a.num_points < 8 || a.num_points > kSgsMaxPts || a.H < 2 || a.W < 2 || a.H > 32767 || a.W > 32767 ||
-           (int64_t)a.H * a.W > (int64_t)kGridFieldMask + 1 || a.n_real < 1 || a.n_real > 65535 || a.seg_cap % 64 != 0 ||
-           a.seg_len < 1 || a.seg_len > a.seg_cap);
+  return krige_search_ok(a.K) && !((int64_t)a.K.H * a.K.W > (int64_t)kGridFieldMask + 1 || a.n_real < 1 || a.n_real > 65535 ||
+                                   a.seg_cap % 64 != 0 || a.seg_len < 1 || a.seg_len > a.seg_cap);
 }
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st) {
   if (!grid_args_ok(a)) return hipErrorInvalidValue;
-  const int HW = a.H * a.W;
+  const int HW = a.K.H * a.K.W;
   hipLaunchKernelGGL(sgs_grid_rank_kernel, dim3((HW + 255) / 256, a.n_real), dim3(256), 0, st, a);
   if (max_path > 0) hipLaunchKernelGGL(sgs_grid_slot_kernel, dim3((max_path + 255) / 256, a.n_real), dim3(256), 0, st, a);
   return hipGetLastError();
 }
-hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st, const double* local, int vtype) {
-  if (!grid_args_ok(a) || (a.lag == nullptr) == (local == nullptr)) return hipErrorInvalidValue;
-  if (local) hipLaunchKernelGGL(sgs_grid_weights_local_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a, local, vtype);
+hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st) {
+  if (!grid_args_ok(a)) return hipErrorInvalidValue;
+  if (a.K.local) hipLaunchKernelGGL(sgs_grid_weights_local_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a);
   else hipLaunchKernelGGL(sgs_grid_weights_kernel, dim3(a.seg_len, a.n_real), dim3(64), 0, st, a);
   hipLaunchKernelGGL(sgs_grid_values_kernel, dim3(a.n_real), dim3(64 * kGridSeqWaves), 0, st, a);
   return hipGetLastError();

@@ -5,12 +5,12 @@
 // the cell that is solved (LocalCov: the whole-grid kernels' non-stationary form).  sgs_kernel.hip's header comment describes the
 // search and the solve.
 #pragma once
+#include "gsm_internal.h"
 #include "device_util.h"
 #include <math.h>
 
 namespace gsm {
 
-constexpr int kSgsMaxPts = 48;
 // candidates kept per sector between prunings (a scan pass appends at most 64; a list is pruned to its k8 nearest when it holds more than
 // kSgsListCap - 64 = 16).  The search structure's LDS bounds the kernel's occupancy: 128 -> 80 entries, 64 rings of 16-bit certification
 // counters instead of 128 of 32 bits took it from 17 KiB to 9.7 KiB per workgroup = 9 -> 16 wavefronts per CU (the register budget's
@@ -247,7 +247,11 @@ struct LagTableCov {
 // and every covariance is evaluated from the two points' coordinates.  vtype: GSM_VTYPE_EXPONENTIAL / _GAUSSIAN / _SPHERICAL.
 struct LocalCov {
   static constexpr bool kLocal = true;
-  const double* __restrict__ p;
+  // The row is read through the constant address space (step_common.h does the same with its records): no kernel writes the table and
+  // the cell is the wavefront's, so the six numbers are scalar loads into SGPRs.  As a plain pointer out of the kernel's argument
+  // struct they are vector loads (the compiler cannot rule out the kernel's own stores): 12 VGPRs, 122 -> 134 in the per-cell kernels.
+  typedef const __attribute__((address_space(4))) double* row_t;
+  row_t p;
   const double* __restrict__ xs;
   const double* __restrict__ ys;
   int vtype;
@@ -295,7 +299,7 @@ __device__ __forceinline__ void krige_fill_local(SgsSearchLds& L, const LocalCov
 // The kriging system of cell (i0, j0) with the n > 0 neighbours that octant_ring_search left in L.nb_g, one row per lane in
 // registers, and its solve: ordinary kriging [Sigma 1; 1' 0] w = [rho; 1] (_krige.py:25-37) or, with lagr false, simple kriging
 // Sigma w = rho (_krige.py:66-73: no Lagrange row / column).  The covariances come from `cov`: a LagTableCov or a LocalCov.
-// All 64 lanes call it.  Returns 0, 64 (a lag beyond the table; never with a LocalCov) or 8 (singular); with 0, lane < n holds its
+// All 64 lanes call it.  Returns 0, kSgsFlagLagTable (a lag beyond the table; never with a LocalCov) or kSgsFlagSingular; with 0, lane < n holds its
 // neighbour's weight w_l, its covariance with the cell rho_l and its (row, column) (my_i, my_j); w_l is 0 in the other lanes.
 // L.nb_rc is scratch.
 template <class Cov>
@@ -358,7 +362,7 @@ __device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j
       } else if (lane == 48 && lagr) v49 = 1.0;
       r[48] = v48; r[49] = v49;
     }
-    if (__ballot(!lag_ok)) return 64;
+    if (__ballot(!lag_ok)) return kSgsFlagLagTable;
     rho_l = r[49];
     c00 = lag[mi * lag_w + mj];
   }
@@ -368,15 +372,23 @@ __device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j
   double mypiv = 1.0;
   bool singular = false;
   GjStep<0>::run(r, lane, n, lagr, tol, tol_l, mypiv, singular);
-  if (singular) return 8;
+  if (singular) return kSgsFlagSingular;
   w_l = (lane < n) ? r[49] / mypiv : 0.0;
   return 0;
 }
-// the lag-table form under its own name: what every kernel with one variogram per call uses
-template <bool kWholeGridTable>
-__device__ __forceinline__ int krige_solve(SgsSearchLds& L, int n, int i0, int j0, int H, int W, const double* __restrict__ lag, int mi,
-                                           int mj, bool lagr, int lane, double& w_l, double& rho_l, int& my_i, int& my_j) {
-  return krige_solve(L, n, i0, j0, H, W, LagTableCov<kWholeGridTable>{lag, mi, mj}, lagr, lane, w_l, rho_l, my_i, my_j);
+// krige_solve for cell `cell` = (i0, j0) of the call K, what every kernel calls: the covariances from K.local's row of the cell
+// (kLocal) or from K's lag table, and in `sill` the sill that the cell's kriging variance is taken from
+template <bool kLocal, bool kWholeGridTable>
+__device__ __forceinline__ int krige_solve_at(SgsSearchLds& L, const KrigeSearch& K, int cell, int n, int i0, int j0, bool lagr, int lane,
+                                              double& w_l, double& rho_l, int& my_i, int& my_j, double& sill) {
+  if constexpr (kLocal) {
+    const LocalCov cov{(LocalCov::row_t)(K.local + 6 * (size_t)cell), K.xs, K.ys, K.vtype};
+    sill = cov.p[4];
+    return krige_solve(L, n, i0, j0, K.H, K.W, cov, lagr, lane, w_l, rho_l, my_i, my_j);
+  } else {
+    sill = K.sill;
+    return krige_solve(L, n, i0, j0, K.H, K.W, LagTableCov<kWholeGridTable>{K.lag, K.mi, K.mj}, lagr, lane, w_l, rho_l, my_i, my_j);
+  }
 }
 
 }  // namespace gsm

@@ -43,7 +43,7 @@ import numbers
 
 import numpy as np
 
-from .sgs import _axes, lag_cov_table
+from .sgs import _axes, _generator, lag_cov_table
 
 __all__ = ["sgs", "sgs_many", "krige", "krige_scores"]
 
@@ -86,17 +86,6 @@ def _sanity_checks(xx, yy, grid, vario, radius, num_points, ktype, sim_mask):
         raise ValueError("num_points must be a number")
     if ktype not in ("ok", "sk"):
         raise ValueError("ktype must be 'ok' or 'sk'")
-
-
-def _generator(seed):
-    """utilities.get_random_generator (utilities.py:50-70)."""
-    if seed is None:
-        return np.random.default_rng()
-    if isinstance(seed, int):
-        return np.random.default_rng(seed=seed)
-    if isinstance(seed, np.random.Generator):
-        return seed
-    raise ValueError("Seed should be an integer, a NumPy random Generator, or None")
 
 
 class _Plan:
@@ -248,6 +237,31 @@ def _segment_cells(R, max_path, torch, dev, extra_bytes):
     return max(64, min(s, (max_path + 63) // 64 * 64))
 
 
+def _kriging_operands(plan, eng, torch, n_grids):
+    """What gsm_sgs_grid* and gsm_krige_grid* take alike, uploaded to the device of `eng`: the axes, the variogram -- one lag
+    covariance table that the radius widening never runs off (_lag_extents), or the plan's per-cell table -- and the global mean
+    of each of the handle's n_grids grids, handed to gsm_sgs_set_kriging with the plan's kriging type.  Returns (axes, suffix,
+    operands, keep): lib.gsm_sgs_grid + suffix (or gsm_krige_grid + suffix) is called with (..., *axes, *operands, ...); `keep`
+    holds the device arrays until the call is over."""
+    from .engine import _ptr
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(eng.dev)
+    hw = int(math.ceil(plan.radius / abs(plan.dx)))
+    if plan.local is None:
+        mi, mj = _lag_extents(plan, eng, torch)
+        if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(eng.dev)[0] // 4:
+            raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not "
+                              "fit the device; raise `radius` or add conditioning data")
+        d_vario = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
+        suffix, operands = "", (_ptr(d_vario), mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]))
+    else:
+        d_vario = f64(plan.local)                                                     # a variogram per cell: no table
+        suffix, operands = "_local", (_ptr(d_vario), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points)
+    d_xs, d_ys, d_gm = f64(plan.xs), f64(plan.ys), f64(np.full(n_grids, plan.global_mean))
+    with torch.cuda.device(eng.dev):
+        eng._check(eng.lib.gsm_sgs_set_kriging(eng.h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
+    return (_ptr(d_xs), _ptr(d_ys)), suffix, operands, (d_xs, d_ys, d_vario, d_gm)
+
+
 MODES = ("replay", "pcg64")
 
 
@@ -304,7 +318,6 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False, mode="replay"
     eng = GsmEngine(H, W, R, device)
     try:
         dev, lib, h = eng.dev, eng.lib, eng.h
-        hw = int(math.ceil(plan.radius / abs(plan.dx)))
         f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
         d_lo = d_hi = None
         if plan.bounds is not None:
@@ -312,34 +325,19 @@ def _run(plan, gens, segment_cells=None, device=None, trace=False, mode="replay"
         if mode == "pcg64":
             d_path, d_off, d_draw, max_path = _device_draws(plan, gens, eng, torch, d_lo, d_hi)
             total = R * max_path
-        if plan.local is None:
-            mi, mj = _lag_extents(plan, eng, torch)
-            if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
-                raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not "
-                                  "fit the device; raise `radius` or add conditioning data")
-            d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
-        else:
-            d_local = f64(plan.local)                                                 # a variogram per cell: no table
+        axes, suffix, operands, keep = _kriging_operands(plan, eng, torch, R)
         grids = f64(plan.grid_ns)[None].repeat(R, 1, 1).contiguous()
         if mode == "replay":
             d_path = torch.as_tensor(np.concatenate([p for p, _ in plans])).to(dev)
             d_off = torch.as_tensor(off).to(dev)
             d_draw = f64(np.concatenate([d for _, d in plans]))
-        d_xs, d_ys = f64(plan.xs), f64(plan.ys)
-        d_gm = f64(np.full(R, plan.global_mean))
         d_tr = torch.zeros((total, 3), dtype=torch.float64, device=dev) if trace else None
         if segment_cells is None:
             segment_cells = _segment_cells(R, max_path, torch, dev, 0)
         with torch.cuda.device(dev):
-            eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
-            head = (h, _ptr(grids), _ptr(d_path), _ptr(d_off), max_path, _ptr(d_draw), _ptr(d_lo), _ptr(d_hi),
-                    1 if plan.bounds is not None else 0, _ptr(d_xs), _ptr(d_ys))
-            if plan.local is None:
-                eng._check(lib.gsm_sgs_grid(*head, _ptr(d_lag), mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]),
-                                            int(segment_cells), _ptr(d_tr), eng._stream()))
-            else:
-                eng._check(lib.gsm_sgs_grid_local(*head, _ptr(d_local), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points,
-                                                  int(segment_cells), _ptr(d_tr), eng._stream()))
+            eng._check(getattr(lib, "gsm_sgs_grid" + suffix)(
+                h, _ptr(grids), _ptr(d_path), _ptr(d_off), max_path, _ptr(d_draw), _ptr(d_lo), _ptr(d_hi),
+                1 if plan.bounds is not None else 0, *axes, *operands, int(segment_cells), _ptr(d_tr), eng._stream()))
         ns = grids.cpu().numpy()
         if trace:
             paths = [p for p, _ in plans] if mode == "replay" else list(d_path.cpu().numpy()[:total].reshape(R, max_path))
@@ -420,31 +418,15 @@ def _krige_run(plan, cells=None, device=None):
     eng = GsmEngine(H, W, 1, device)
     try:
         dev, lib, h = eng.dev, eng.lib, eng.h
-        hw = int(math.ceil(plan.radius / abs(plan.dx)))
-        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        if plan.local is None:
-            mi, mj = _lag_extents(plan, eng, torch)
-            if (2 * mi + 1) * (2 * mj + 1) * 8 > torch.cuda.mem_get_info(dev)[0] // 4:
-                raise MemoryError(f"the lag covariance table for the widest search radius ({2 * mi + 1} x {2 * mj + 1} lags) does not "
-                                  "fit the device; raise `radius` or add conditioning data")
-            d_lag = f64(lag_cov_table(plan.vario, hw, plan.dx, plan.dy, mi, mj))
-        else:
-            d_local = f64(plan.local)                                                 # a variogram per cell: no table
-        d_grid, d_cells = f64(plan.grid_ns), torch.as_tensor(cells).to(dev)
-        d_xs, d_ys = f64(plan.xs), f64(plan.ys)
-        d_gm = f64(np.full(1, plan.global_mean))
+        axes, suffix, operands, keep = _kriging_operands(plan, eng, torch, 1)
+        d_grid = torch.as_tensor(np.ascontiguousarray(plan.grid_ns, dtype=np.float64)).to(dev)
+        d_cells = torch.as_tensor(cells).to(dev)
         d_est = torch.empty(cells.size, dtype=torch.float64, device=dev)
         d_var = torch.empty(cells.size, dtype=torch.float64, device=dev)
         d_n = torch.empty(cells.size, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
-            head, tail = (h, _ptr(d_grid), _ptr(d_cells), int(cells.size), _ptr(d_xs), _ptr(d_ys)), (_ptr(d_est), _ptr(d_var), _ptr(d_n))
-            if plan.local is None:
-                eng._check(lib.gsm_krige_grid(*head, _ptr(d_lag), mi, mj, hw, plan.radius, plan.num_points, float(plan.vario["sill"]),
-                                              *tail, eng._stream()))
-            else:
-                eng._check(lib.gsm_krige_grid_local(*head, _ptr(d_local), LOCAL_VTYPES[plan.vtype], hw, plan.radius, plan.num_points,
-                                                    *tail, eng._stream()))
+            eng._check(getattr(lib, "gsm_krige_grid" + suffix)(h, _ptr(d_grid), _ptr(d_cells), int(cells.size), *axes, *operands,
+                                                               _ptr(d_est), _ptr(d_var), _ptr(d_n), eng._stream()))
         out = d_est.cpu().numpy(), d_var.cpu().numpy(), d_n.cpu().numpy()
     finally:
         eng.close()

@@ -78,6 +78,17 @@ def lag_cov_table(vario: dict, hw: int, dx: float, dy: float, mi: int | None = N
     return np.ascontiguousarray(cov_norm(h, vario["vtype"], vario["sill"], vario["nugget"], vario.get("s")))
 
 
+def _generator(seed):
+    """utilities.get_random_generator (utilities.py:50-70)."""
+    if seed is None:
+        return np.random.default_rng()
+    if isinstance(seed, int):
+        return np.random.default_rng(seed=seed)
+    if isinstance(seed, np.random.Generator):
+        return seed
+    raise ValueError("Seed should be an integer, a NumPy random Generator, or None")
+
+
 def lag_extents(hw: int, H: int, W: int) -> tuple[int, int]:
     """Extents of the lag table handed to gsm_sgs_blocks: the whole grid while that stays small (4 M lags = 32 MiB), so that
     the radius-widening fallback (MCMC.py:150-156) finds every lag; else what a search window needs."""
@@ -124,14 +135,7 @@ def sgs(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_ma
         raise NotImplementedError("the device SGS takes scalar variogram parameters (one covariance table per call)")
     if not 8 <= int(num_points) <= 48:
         raise NotImplementedError("the device SGS takes 8 <= num_points <= 48")
-    if seed is None:                                                                  # utilities.get_random_generator, :50-70
-        rng = np.random.default_rng()
-    elif isinstance(seed, int):
-        rng = np.random.default_rng(seed=seed)
-    elif isinstance(seed, np.random.Generator):
-        rng = seed
-    else:
-        raise ValueError("Seed should be an integer, a NumPy random Generator, or None")
+    rng = _generator(seed)
     grid = np.asarray(grid, dtype=np.float64)
     H, W = grid.shape
     cond_msk = ~np.isnan(grid)
