@@ -633,7 +633,25 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
  * Errors: GSM_E_ARG for a NULL beds, g or counts, n_bins odd or outside [2, 128], n_levels outside [0, 8], NULL levels with
  * n_levels > 0, an inv_width that is not finite and > 0.
  * Replaces: np.quantile / (bed_cache < level).mean over bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
- * All six are asynchronous on `stream`. */
+ *
+ * gsm_posterior_lagged: one snapshot into per-cell sums of squared differences at the lags 1 .. n_lags, over ALL chains:
+ *   lag_sqdiff[(t - 1)*H*W + cell] += sum_c (x_c - y_{c,t})^2   for t = 1 .. n_valid,
+ * x_c = (double)bed of chain c, y_{c,t} = (double)bed of chain c at the snapshot t calls earlier.  These are the sums S_t of the
+ * variogram form of the autocorrelation rho_t = 1 - S_t / (M (N - t)) / (2 var+) (Gelman et al., BDA3 section 11.5), which needs no
+ * per-chain mean; the effective sample size follows on the host.  ring [dev, n_lags*n_chains*H*W], state dtype, slot-major
+ * (slot s of chain c at (s*n_chains + c)*H*W), holds the last snapshots of every chain and belongs to the caller, who also keeps
+ * its two counters: the call reads slot (head - t) mod n_lags for t = 1 .. n_valid (the other slots are not read: the ring needs
+ * no initialisation), then writes the beds to slot `head`; after it the caller sets head = (head + 1) mod n_lags and
+ * n_valid = min(n_valid + 1, n_lags).  n_valid = 0 starts a sequence: the call only stores the beds, so no pair straddles two
+ * sequences.  lag_sqdiff [dev, n_lags*H*W] fp64 is ADDED to: zero it once; sums of several handles (ranks) add.  A NaN bed makes
+ * the sums of its cell NaN at the lags that pair it.  Differences, squares and sums are fp64 with either state type.  Chains are
+ * summed in index order within a part of the chain axis and the parts in part order (a second kernel; no atomics):
+ * bit-reproducible from run to run.  (n_valid + 2) state values per chain-cell are moved (n_valid + 1 read, 1 written): 72 bytes
+ * at n_lags = 7 with fp64 state and a full ring, 36 with fp32.
+ * Errors: GSM_E_ARG for a NULL beds, ring or lag_sqdiff, n_lags outside [1, 15], head outside [0, n_lags), n_valid outside
+ * [0, n_lags], beds or ring not 16-byte aligned; nothing is written then.
+ * Replaces: autocorrelations of bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
+ * All seven are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -646,6 +664,8 @@ int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const
                            void* stream);
 int gsm_posterior_histogram(gsm_handle h, const void* beds, const double* g, double inv_width, int32_t n_bins, const double* levels,
                             int32_t n_levels, int32_t* counts, void* stream);
+int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, int32_t n_lags, int32_t head, int32_t n_valid,
+                         double* lag_sqdiff, void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

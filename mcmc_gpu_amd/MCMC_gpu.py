@@ -594,7 +594,8 @@ def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
     g = opt['common_ref'] if opt['common_ref'] is not None else default_common_ref(chain.initial_bed)
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
-                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'])
+                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
+                                 ess=opt['ess'])
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -622,7 +623,13 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     about `common_ref`, `bins` (even, <= 128) equal bins over [-half_width, half_width) plus underflow, overflow and NaN counts,
     and for up to 8 absolute `levels` the count of values below each, accumulated on the device at every snapshot that the
     moments use.  The summary then answers quantile(q), interval(p) (to within one bin width, NaN where the rank leaves the
-    range) and prob_below(l) (exact).  The chains and the moments are bit-identical with and without it."""
+    range) and prob_below(l) (exact).  The chains and the moments are bit-identical with and without it.
+    posterior['ess']: None, True or dict(max_lag=7) (odd, <= 15, at most the snapshots per sequence minus one; needs rhat): the
+    last max_lag snapshots of every chain stay on the device (max_lag more arrays of the beds' shape) and every snapshot adds
+    the squared differences at the lags 1 .. max_lag to per-cell sums (summary.lag_sqdiff).  The summary then answers
+    autocorrelation(), ess() -> (effective sample size of the M N values per cell, `truncated`: no negative Geyer pair up to
+    max_lag, so ess is an upper bound: raise max_lag or thin) and mcse() = sd / sqrt(ess), the error bar of `mean`.  The chains
+    and every other map are bit-identical with and without it."""
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     n_iter = _check_args(RF, n_iter, False, n_chains, (seeds,))

@@ -87,6 +87,24 @@ extern "C" int gsm_posterior_histogram(gsm_handle h, const void* beds, const dou
   return GSM_OK;
 }
 
+extern "C" int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, int32_t n_lags, int32_t head, int32_t n_valid,
+                                    double* lag_sqdiff, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !ring || !lag_sqdiff) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: NULL pointer");
+  if (n_lags < 1 || n_lags > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: n_lags must be in [1, 15]");
+  if (head < 0 || head >= n_lags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: head must be in [0, n_lags)");
+  if (n_valid < 0 || n_valid > n_lags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: n_valid must be in [0, n_lags]");
+  if (!aligned16(beds) || !aligned16(ring)) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: beds and ring must be 16-byte aligned");
+  const int64_t plane = (int64_t)h->H * h->W;
+  const int vec = posterior_lag_vec(plane, h->f32_state);
+  int parts = 1;
+  int rc = posterior_setup(h, (plane / vec + 255) / 256, n_lags, &parts);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_lagged(beds, ring, h->d_post_slab.get(), lag_sqdiff, plane, h->n_chains, parts, n_lags, head, n_valid, h->f32_state,
+                                    h->n_cu, (hipStream_t)stream));
+  return GSM_OK;
+}
+
 extern "C" int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const double* s1, const double* s2,
                                       int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
                                       void* stream) {

@@ -430,6 +430,11 @@ constexpr int kHistMaxLevels = 8;
 int posterior_hist_parts(int64_t cell_blocks, int n_chains, int n_cu);
 hipError_t launch_posterior_histogram(const void* beds, const double* g, double inv_w, int n_bins, const double* levels, int n_levels,
                                       int32_t* counts, int64_t plane, int n_chains, int f32_state, int n_cu, hipStream_t st);
+// posterior_lag_kernel.hip
+constexpr int kLagMaxLags = 15;        // K x V fp64 accumulators and K loads per lane stay in registers
+int posterior_lag_vec(int64_t plane, int f32_state);
+hipError_t launch_posterior_lagged(const void* beds, void* ring, double* slab, double* lag_sqdiff, int64_t plane, int n_chains, int parts,
+                                   int n_lags, int head, int n_valid, int f32_state, int n_cu, hipStream_t st);
 // variogram_kernel.hip
 constexpr int kVariogramMaxLag = 1 << 20;
 int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part

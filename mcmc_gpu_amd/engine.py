@@ -248,6 +248,22 @@ class GsmEngine:
         self.call(self.lib.gsm_posterior_histogram, self.beds, g, float(inv_width), int(n_bins), lv.ctypes.data if lv.size else None,
                   int(lv.size), counts)
 
+    def posterior_lagged(self, ring, n_lags, head, n_valid, lag_sqdiff):
+        """One snapshot of self.beds into the per-cell sums of squared differences at the lags 1 .. n_lags over all chains:
+        lag_sqdiff[t - 1] += sum_c (bed_c - ring[(head - t) % n_lags, c]) ** 2 for t = 1 .. n_valid, then ring[head] = beds.  ring
+        [n_lags, n_chains, H * W] in the state dtype, lag_sqdiff [n_lags, H, W] float64; the caller advances head and n_valid
+        (n_valid = 0 starts a sequence).  Asynchronous."""
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+        n_lags = int(n_lags)
+        n = self.n_chains * self.H * self.W
+        if ring.dtype != self.state_dtype or ring.numel() != n_lags * n or not ring.is_contiguous() or ring.device != self.dev:
+            raise ValueError(f"ring must be a contiguous tensor of n_lags x the beds' shape and dtype on {self.dev}")
+        if lag_sqdiff.numel() != n_lags * self.H * self.W:
+            raise ValueError(f"lag_sqdiff must hold n_lags x H x W = {n_lags * self.H * self.W} elements")
+        self._check_sums(n_lags * self.H * self.W, lag_sqdiff=lag_sqdiff)
+        self.call(self.lib.gsm_posterior_lagged, self.beds, ring, n_lags, int(head), int(n_valid), lag_sqdiff)
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

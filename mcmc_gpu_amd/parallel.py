@@ -120,6 +120,20 @@ def all_reduce_counts(counts: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def all_reduce_sum(sums: torch.Tensor) -> torch.Tensor:
+    """Per-cell sums that add over chains (the posterior's lagged squared differences of this rank's chains, posterior.
+    PosteriorAccumulator.lag_sqdiff) summed over ranks: one fp64 SUM all-reduce.  Returns a new tensor on the device of `sums`."""
+    t = sums.clone()
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        if _via_host(t) or not t.is_cuda:
+            h = t.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM)
+            t = h.to(t.device)
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
 def barrier():
     if dist.is_initialized() and dist.get_world_size() > 1:
         dist.barrier()

@@ -18,6 +18,14 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               equal bins of width w = 2 half_width / B over [g - half_width, g + half_width), an underflow, an overflow and a NaN
               slot, and per level the count of values below it.  Integer counts, on the device, added over ranks: quantiles to
               within w (PosteriorSummary.quantile, .interval) and P(bed < level) exactly (.prob_below).
+  ess         optional effective sample size of the same M*N values (needs rhat: it uses W and B_over_N), BDA3 section 11.5 in
+              variogram form.  Per cell and lag t = 1 .. K (`max_lag`, odd, <= 15): S_t = sum over the M sequences and n = 0 ..
+              N - 1 - t of (x[n + t, m] - x[n, m])^2 -- both members of a pair in the same sequence --, accumulated on the device
+              from a ring of every chain's last K snapshots (gsm_posterior_lagged) and added over ranks.  On the host V_t = S_t /
+              (M (N - t)), var+ = (N - 1)/N W + B_over_N, rho_t = 1 - V_t / (2 var+), rho_0 = 1; Geyer pairs P_k = rho_2k +
+              rho_(2k+1), k = 0 .. (K - 1)/2; tau = -1 + 2 sum of the pairs before the first negative one, floored at
+              1 / log10(M N); ess = M N / tau and mcse = sd / sqrt(ess).  A cell without a negative pair sums them all and is
+              flagged `truncated`: its ess is an upper bound (raise max_lag or thin).  NaN where W == 0 and where the cell saw a NaN.
 """
 from __future__ import annotations
 
@@ -74,6 +82,8 @@ class PosteriorSummary:
     hist_centre: np.ndarray | None = None
     level_values: np.ndarray | None = None
     level_counts: np.ndarray | None = None
+    # with ess=: lag_sqdiff [K, H, W] float64, S_t of the lags t = 1 .. K over all M sequences
+    lag_sqdiff: np.ndarray | None = None
 
     def _need_hist(self):
         if self.hist_counts is None:
@@ -110,6 +120,43 @@ class PosteriorSummary:
         if not 0.0 < p < 1.0:
             raise ValueError("p must be in (0, 1)")
         return self.quantile((1.0 - p) / 2.0), self.quantile((1.0 + p) / 2.0)
+
+    def autocorrelation(self):
+        """[K, H, W] rho_t of the lags t = 1 .. K: 1 - S_t / (M (N - t)) / (2 var+).  NaN where W == 0 and where the cell saw a NaN."""
+        if self.lag_sqdiff is None or self.within_var is None:
+            raise ValueError("this summary holds no lagged sums: run with posterior=dict(..., ess=dict(max_lag=...))")
+        S = np.asarray(self.lag_sqdiff, dtype=np.float64)
+        M, N = self.n_sequences, self.n_per_sequence
+        W = np.asarray(self.within_var, dtype=np.float64)
+        rho = np.empty_like(S)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var_plus = (N - 1) / N * W + np.asarray(self.between_var_over_n, dtype=np.float64)
+            for t in range(1, S.shape[0] + 1):
+                rho[t - 1] = 1.0 - S[t - 1] / (M * (N - t)) / (2.0 * var_plus)
+        rho[:, (W == 0) | np.isnan(self.mean)] = np.nan
+        return rho
+
+    def ess(self):
+        """(ess, truncated): [H, W] effective sample size of the M*N values of every cell, M N / tau with tau from Geyer's pairs of
+        autocorrelation(), and the bool map of the cells in which no pair up to max_lag was negative (ess is an upper bound there)."""
+        rho = self.autocorrelation()
+        K, n = rho.shape[0], self.n_sequences * self.n_per_sequence
+        if K % 2 == 0:
+            raise ValueError(f"lag_sqdiff holds {K} lags; Geyer's pairs need an odd number")
+        tau = np.full(rho.shape[1:], -1.0)
+        alive = ~np.isnan(rho).any(axis=0)                   # no negative pair so far
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for k in range((K + 1) // 2):
+                pair = (1.0 if k == 0 else rho[2 * k - 1]) + rho[2 * k]
+                alive &= ~(pair < 0)
+                tau = np.where(alive, tau + 2.0 * pair, tau)
+            tau = np.where(np.isnan(rho).any(axis=0), np.nan, np.maximum(tau, 1.0 / np.log10(n)))
+            return n / tau, alive
+
+    def mcse(self):
+        """[H, W] Monte-Carlo standard error of `mean`: sd / sqrt(ess)."""
+        with np.errstate(invalid="ignore"):
+            return np.asarray(self.sd, dtype=np.float64) / np.sqrt(self.ess()[0])
 
     def save(self, path):
         """One .npz; fields that are None are left out."""
@@ -158,6 +205,33 @@ def finalize(partials_sum, M, N, common_ref, rhat=True, **meta):
             W = B_over_N = r = None
         sd = np.sqrt(var)
     return PosteriorSummary(mean=mean, sd=sd, rhat=r, within_var=W, between_var_over_n=B_over_N, n_sequences=M, n_per_sequence=N, **meta)
+
+
+ESS_KEYS = ("max_lag",)
+ESS_MAX_LAG = 15
+
+
+def check_ess(ess, N=None, rhat=True):
+    """Validate the `ess` option: None (also False), True (the default) or dict(max_lag=7).  Returns None or dict(max_lag=K), K an
+    odd int in [1, 15] and, when the snapshots per sequence N are given, at most N - 1 (lag t needs N - t >= 1 pairs)."""
+    if ess is None or ess is False:
+        return None
+    if ess is True:
+        ess = {}
+    if not isinstance(ess, dict):
+        raise ValueError("ess must be None, True or a dict with the key max_lag")
+    unknown = set(ess) - set(ESS_KEYS)
+    if unknown:
+        raise ValueError(f"unknown ess option(s) {sorted(unknown)}; the options are {ESS_KEYS}")
+    K = ess.get("max_lag", 7)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1 or K > ESS_MAX_LAG or K % 2 == 0:
+        raise ValueError(f"ess max_lag must be an odd integer in [1, {ESS_MAX_LAG}], got {K!r}")
+    if not rhat:
+        raise ValueError("ess needs rhat=True: the autocorrelation uses the within- and between-sequence variances")
+    if N is not None and K > int(N) - 1:
+        raise ValueError(f"ess max_lag={int(K)} needs at least {int(K) + 1} snapshots per sequence, the schedule gives {int(N)}: "
+                         f"lower max_lag or thin less")
+    return dict(max_lag=int(K))
 
 
 HIST_KEYS = ("bins", "half_width", "levels")
@@ -219,9 +293,13 @@ class PosteriorAccumulator:
     [n_chains, H, W] in the state dtype (every chain's bed at the first snapshot of the sequence being filled) and 1 + split pairs of [n_chains, H, W] float64 sums (1 + 2 (1 + split) arrays of
     the beds' shape); without, one [H, W] pair.  Call add() when eng.beds holds the next snapshot of the schedule, then
     partials() (sum it over ranks) and finalize().  hist (see check_hist): also one int32 tensor `hist_counts` [(B + 3 + L), H, W],
-    to which add() adds the histogram of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_counts)."""
+    to which add() adds the histogram of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_counts).
+    ess (see check_ess): also `ring` [K, n_chains, H * W] in the state dtype, every chain's last K snapshots of the sequence being
+    filled, and `lag_sqdiff` [K, H, W] float64, to which add() adds the squared differences at the lags 1 .. K (sum it over ranks
+    with all_reduce_sum).  The ring is released with the last snapshot."""
 
-    def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None):
+    def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None,
+                 ess=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -234,6 +312,8 @@ class PosteriorAccumulator:
             check_hist_count(n, n_iter, burn_in, thin, self.split)
             self.hist_inv_w = self.hist["bins"] / (2 * self.hist["half_width"])
             self.hist_slots = self.hist["bins"] + 3 + len(self.hist["levels"])
+        self.ess = check_ess(ess, self.N, self.rhat)
+        self.n_lags = 0 if self.ess is None else self.ess["max_lag"]
         # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
         g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
         if g.shape != (H, W) or not np.isfinite(g).all():
@@ -251,6 +331,7 @@ class PosteriorAccumulator:
         need += self.T * n * self.n_samples * 8
         if self.hist is not None:
             need += self.hist_slots * H * W * 4
+        need += self.n_lags * (n * H * W * state_bytes + H * W * 8)          # the ring and lag_sqdiff
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
@@ -267,6 +348,9 @@ class PosteriorAccumulator:
         self.d_cells = None if not self.n_samples else torch.as_tensor(cells).to(dev)
         self.d_samples = None if not self.n_samples else torch.empty((self.T, n, self.n_samples), dtype=torch.float64, device=dev)
         self.hist_counts = None if self.hist is None else torch.zeros((self.hist_slots, H, W), dtype=torch.int32, device=dev)
+        self.ring = None if not self.n_lags else torch.empty((self.n_lags, n, H * W), dtype=eng.state_dtype, device=dev)
+        self.lag_sqdiff = None if not self.n_lags else torch.zeros((self.n_lags, H, W), dtype=torch.float64, device=dev)
+        self.ring_head = self.ring_valid = 0
         self.n_added = 0
         self._partials = None
 
@@ -292,6 +376,14 @@ class PosteriorAccumulator:
             if first and k > 0:            # the finished half becomes (mean - g, variance); ref then serves this half
                 eng.posterior_close(self.ref, self.d_g, self.s1[k - 1], self.s2[k - 1], self.N)
             eng.posterior_accumulate(self.ref, self.s1[k], self.s2[k], first, self.d_cells, smp)
+            if self.n_lags:
+                if first:                  # no pair straddles two sequences
+                    self.ring_valid = 0
+                eng.posterior_lagged(self.ring, self.n_lags, self.ring_head, self.ring_valid, self.lag_sqdiff)
+                self.ring_head = (self.ring_head + 1) % self.n_lags
+                self.ring_valid = min(self.ring_valid + 1, self.n_lags)
+                if t == self.T - 1:        # stream-ordered: the allocator reuses the block only behind the last call
+                    self.ring = None
         else:
             eng.posterior_accumulate_pooled(self.d_g, self.s1, self.s2, self.d_cells, smp)
         if self.hist is not None and t >= self.dropped:      # the values that mean and sd describe, each counted once
@@ -318,9 +410,10 @@ class PosteriorAccumulator:
         """[n_chains, n_points, T] numpy array of the traces, or None."""
         return None if self.d_samples is None else np.ascontiguousarray(self.d_samples.permute(1, 2, 0).cpu().numpy())
 
-    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None):
+    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None):
         """PosteriorSummary from partials summed over ranks and their sequence count (default: this accumulator's own);
-        hist_counts: the histogram summed over ranks (all_reduce_counts; default: this accumulator's own)."""
+        hist_counts: the histogram summed over ranks (all_reduce_counts; default: this accumulator's own); lag_sqdiff: the
+        lagged sums summed over ranks (all_reduce_sum; default: this accumulator's own)."""
         if partials_sum is None:
             partials_sum, M = self.partials(), self.n_sequences
         M = int(M)
@@ -335,25 +428,34 @@ class PosteriorAccumulator:
             B = self.hist["bins"]
             meta = dict(hist_counts=hc[:B + 3].copy(), hist_half_width=self.hist["half_width"], hist_centre=self.common_ref.copy(),
                         level_values=np.asarray(self.hist["levels"], dtype=np.float64), level_counts=hc[B + 3:].copy())
+        if self.n_lags:
+            if self.n_added != self.T:
+                raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
+            ls = self.lag_sqdiff if lag_sqdiff is None else lag_sqdiff
+            ls = np.array(ls.detach().cpu().numpy() if hasattr(ls, "detach") else ls, dtype=np.float64)
+            if ls.shape != (self.n_lags,) + self.common_ref.shape:
+                raise ValueError(f"lagged sums of shape {ls.shape}, expected {(self.n_lags,) + self.common_ref.shape}")
+            meta["lag_sqdiff"] = ls
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess")
 
 
 def check_options(posterior, n_iter, n_chains=None):
     """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
     n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None)
     opt.update(posterior)
-    sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
+    _, N, _ = sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
+    opt["ess"] = check_ess(opt["ess"], N, opt["rhat"])
     opt["hist"] = check_hist(opt["hist"])
     if opt["hist"] is not None and n_chains is not None:
         check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])

@@ -10,8 +10,12 @@
               state: time per snapshot beside the pooled form and the stream copy of the same bytes, timed in the same process,
               and its ratio to the pooled form.  The beds are N(g, 1) and the histogram spans g +- 4, so that a part of 256
               chains fills about fifty bins of every cell: nearly every counter is flushed.  Counted bytes: the beds alone.
+  --ess       only the lagged pass (gsm_posterior_lagged) at 1024 chains of 256 x 256, 7 and 15 lags, fp64 and fp32 state, ring
+              full: time per snapshot beside gsm_debug_stream_copy moving the same bytes, (K + 2) state values per chain-cell
+              (K + 1 read, 1 written), and beside the pooled pass and ITS stream copy, all timed in the same process; then the
+              wall time of MCMC_gpu.run_many without `posterior`, with it, and with `ess` (7 and 15 lags) at thin=100.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist]
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess]
 """
 import argparse
 import json
@@ -128,13 +132,74 @@ def hist_rows(n_chains, H, W, state, reps, bins=64, levels=(1000.0, 999.0)):
     return rows
 
 
-def end_to_end_rows(H, n_chains, n_iter, thins, repeats):
+def ess_rows(n_chains, H, W, state, lags, reps):
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        dev, n, sb = eng.dev, n_chains * H * W, 8 if state == "f64" else 4
+        eng.beds = (1000.0 + torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def copy_row(nbytes, label):
+            m = nbytes // 16                                   # doubles: 8 B read + 8 B written each
+            src = torch.ones(m, dtype=torch.float64, device=dev)
+            dst = torch.empty(m, dtype=torch.float64, device=dev)
+            r = _rate(label, 16 * m, _timed(lambda: eng._check(eng.lib.gsm_debug_stream_copy(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st)), reps))
+            del src, dst
+            return r
+
+        g = torch.full((H, W), 1000.0, dtype=torch.float64, device=dev)
+        p1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        po = _rate(f"pooled accumulate {shape}", sb * n, _timed(lambda: eng.posterior_accumulate_pooled(g, p1, p2), reps))
+        cp = copy_row(sb * n, f"stream copy of the pooled form's bytes ({shape})")
+        po["fraction_of_copy"] = po["TB_per_s_median"] / cp["TB_per_s_median"]
+        po["fraction_of_copy_range"] = [po["TB_per_s_range"][0] / cp["TB_per_s_median"], po["TB_per_s_range"][1] / cp["TB_per_s_median"]]
+        rows += [po, cp]
+        for K in lags:
+            ring = torch.empty((K, n_chains, H * W), dtype=eng.state_dtype, device=dev)
+            out = torch.zeros((K, H, W), dtype=torch.float64, device=dev)
+            state_ = {"head": 0, "valid": 0}
+
+            def call():
+                eng.posterior_lagged(ring, K, state_["head"], state_["valid"], out)
+                state_["head"] = (state_["head"] + 1) % K
+                state_["valid"] = min(state_["valid"] + 1, K)
+
+            for _ in range(K):                                 # fill the ring: the timed calls move the full (K + 2) values
+                call()
+            nbytes = (K + 2) * sb * n
+            la = _rate(f"lagged pass {K} lags {shape}", nbytes, _timed(call, reps))
+            cl = copy_row(nbytes, f"stream copy of the lagged pass's bytes ({K} lags, {shape})")
+            la["ms_per_snapshot"] = la["ms_median"]
+            la["fraction_of_copy"] = la["TB_per_s_median"] / cl["TB_per_s_median"]
+            la["fraction_of_copy_range"] = [la["TB_per_s_range"][0] / cl["TB_per_s_median"], la["TB_per_s_range"][1] / cl["TB_per_s_median"]]
+            la["ring_GiB"] = K * sb * n / 2 ** 30
+            la["sums_check"] = bool((out == 0).all().item())   # the beds never change: every difference is 0
+            rows += [la, cl]
+            del ring, out
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
     prob, ch, rf = synthetic.template(H)
     beds = synthetic.initial_beds(prob, n_chains)
     seeds = list(range(1000, 1000 + n_chains))
-    configs = [("no posterior", None)] + [(f"thin={t} rhat={r}", dict(burn_in=0, thin=t, rhat=r)) for t in thins for r in (True, False)]
+    if ess_lags is None:
+        configs = [("no posterior", None)] + [(f"thin={t} rhat={r}", dict(burn_in=0, thin=t, rhat=r)) for t in thins for r in (True, False)]
+    else:
+        configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
+                  [(f"thin={t} rhat=True ess max_lag={K}", dict(burn_in=0, thin=t, ess=dict(max_lag=K))) for t in thins for K in ess_lags]
 
     def run(opt):
         torch.cuda.synchronize()
@@ -179,6 +244,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--hist", action="store_true", help="only the histogram pass beside the pooled pass and the stream copy")
+    ap.add_argument("--ess", action="store_true", help="only the lagged pass beside its stream copy, and run_many with and without ess")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
@@ -186,6 +252,11 @@ def main():
     if args.hist:
         for state in ("f64", "f32"):
             rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
+    elif args.ess:
+        for state in ("f64", "f32"):
+            rows += ess_rows(8, 64, 64, state, (7, 15), 3) if args.quick else ess_rows(1024, 256, 256, state, (7, 15), max(args.reps, 20))
+        rows += end_to_end_rows(64, 8, 1701, [100], 1, ess_lags=(7,)) if args.quick else \
+            end_to_end_rows(256, 1024, 20001, [100], args.repeats, ess_lags=(7, 15))
     elif args.quick:
         rows += kernel_rows(8, 64, 64, "f64", 3)
         rows += kernel_rows(8, 64, 64, "f32", 3)
