@@ -1,19 +1,28 @@
-// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip).
+// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip).  Every
+// argument is validated here, once, where the error text is; the launchers take what they are given.
 #include "gsm_context.h"
+#include "posterior_device.h"
 #include <cmath>
 
 using namespace gsm;
 
-static int posterior_setup(gsm_handle h, int64_t cell_blocks, int n_fields, int* parts) {
+// selects the device and makes sure h->n_cu is known (grid sizing, the cut of the chain axis)
+static int posterior_device(gsm_handle h) {
   HIPCHK(h, hipSetDevice(h->device));
   if (!h->n_cu) {
     HIPCHK(h, hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
     if (h->n_cu < 1) h->n_cu = 1;
   }
-  if (!parts) return GSM_OK;
-  *parts = posterior_parts(cell_blocks, h->n_chains, h->n_cu);
-  const size_t need = (size_t)*parts * n_fields * h->H * h->W;
-  HIPCHK(h, h->d_post_slab.ensure(need));
+  return GSM_OK;
+}
+
+// *parts of the chain axis for a pass of plane / vec cells per chain, and the slab of *parts x n_fields planes
+static int posterior_slab(gsm_handle h, int vec, int n_fields, int* parts) {
+  int rc = posterior_device(h);
+  if (rc != GSM_OK) return rc;
+  const int64_t plane = (int64_t)h->H * h->W;
+  *parts = posterior_parts(posterior_cell_blocks(plane, vec), h->n_chains, h->n_cu);
+  HIPCHK(h, h->d_post_slab.ensure((size_t)*parts * n_fields * plane));
   return GSM_OK;
 }
 
@@ -33,7 +42,7 @@ extern "C" int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* re
   if (!beds || !ref || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: NULL pointer");
   if (!aligned16(beds) || !aligned16(ref) || !aligned16(s1) || !aligned16(s2))
     return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: beds, ref, s1 and s2 must be 16-byte aligned");
-  int rc = posterior_setup(h, 1, 0, nullptr);
+  int rc = posterior_device(h);
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_accumulate(beds, ref, s1, s2, (int64_t)h->n_chains * h->H * h->W, h->f32_state, first != 0, h->n_cu,
                                         (hipStream_t)stream));
@@ -46,9 +55,8 @@ extern "C" int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, c
   if (!beds || !g || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: NULL pointer");
   if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: beds must be 16-byte aligned");
   const int64_t plane = (int64_t)h->H * h->W;
-  const int vec = h->f32_state ? (plane % 4 == 0 ? 4 : plane % 2 == 0 ? 2 : 1) : (plane % 2 == 0 ? 2 : 1);
   int parts = 1;
-  int rc = posterior_setup(h, (plane / vec + 255) / 256, 2, &parts);
+  int rc = posterior_slab(h, posterior_vec(plane, h->f32_state), 2, &parts);
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_pooled(beds, g, s1, s2, h->d_post_slab.get(), plane, h->n_chains, parts, h->f32_state, h->n_cu, (hipStream_t)stream));
   return posterior_sample(h, "gsm_posterior_accumulate_pooled", beds, sample_cells, n_samples, sample_out, (hipStream_t)stream);
@@ -80,7 +88,7 @@ extern "C" int gsm_posterior_histogram(gsm_handle h, const void* beds, const dou
   if (n_levels < 0 || n_levels > kHistMaxLevels) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: n_levels must be in [0, 8]");
   if (n_levels > 0 && !levels) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: NULL levels with n_levels > 0");
   if (!(inv_width > 0.0) || !std::isfinite(inv_width)) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: inv_width must be finite and > 0");
-  int rc = posterior_setup(h, 1, 0, nullptr);
+  int rc = posterior_device(h);
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_histogram(beds, g, inv_width, n_bins, levels, n_levels, counts, (int64_t)h->H * h->W, h->n_chains, h->f32_state, h->n_cu,
                                        (hipStream_t)stream));
@@ -96,9 +104,8 @@ extern "C" int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, 
   if (n_valid < 0 || n_valid > n_lags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: n_valid must be in [0, n_lags]");
   if (!aligned16(beds) || !aligned16(ring)) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: beds and ring must be 16-byte aligned");
   const int64_t plane = (int64_t)h->H * h->W;
-  const int vec = posterior_lag_vec(plane, h->f32_state);
   int parts = 1;
-  int rc = posterior_setup(h, (plane / vec + 255) / 256, n_lags, &parts);
+  int rc = posterior_slab(h, posterior_vec(plane, h->f32_state), n_lags, &parts);
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_lagged(beds, ring, h->d_post_slab.get(), lag_sqdiff, plane, h->n_chains, parts, n_lags, head, n_valid, h->f32_state,
                                     h->n_cu, (hipStream_t)stream));
@@ -117,7 +124,7 @@ extern "C" int gsm_posterior_partials(gsm_handle h, const void* ref, const doubl
   if (n_seq_per_chain == 2 && seq_stride < (int64_t)h->n_chains * plane)
     return fail(h, GSM_E_ARG, "gsm_posterior_partials: seq_stride smaller than n_chains * H * W");
   int parts = 1;
-  int rc = posterior_setup(h, (plane + 255) / 256, 3, &parts);
+  int rc = posterior_slab(h, 1, 3, &parts);
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_partials(ref, g, s1, s2, h->d_post_slab.get(), partials, plane, h->n_chains, n_seq_per_chain, seq_stride, n_closed, n_per_seq,
                                       parts, h->f32_state, h->n_cu, (hipStream_t)stream));

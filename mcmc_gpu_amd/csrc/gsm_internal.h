@@ -411,30 +411,6 @@ size_t step_lds_bytes(int tile_cap);
 hipError_t launch_min_dist(const double* xx, const double* yy, const uint8_t* mask, int n, double2* pts, int* count,
                            double* dist, hipStream_t st);
 hipError_t launch_stream_copy(const double* src, double* dst, int64_t n, hipStream_t st);
-// posterior_kernel.hip
-int posterior_parts(int64_t cell_blocks, int n_chains, int n_cu);
-hipError_t launch_posterior_accumulate(const void* beds, void* ref, double* s1, double* s2, int64_t n, int f32_state, int first, int n_cu,
-                                       hipStream_t st);
-hipError_t launch_posterior_pooled(const void* beds, const double* g, double* s1, double* s2, double* slab, int64_t plane, int n_chains,
-                                   int parts, int f32_state, int n_cu, hipStream_t st);
-hipError_t launch_posterior_partials(const void* ref, const double* g, const double* s1, const double* s2, double* slab, double* partials,
-                                     int64_t plane, int n_chains, int n_seq, int64_t seq_stride, int n_closed, int n_per_seq, int parts, int f32_state,
-                                     int n_cu, hipStream_t st);
-hipError_t launch_posterior_close(const void* ref, const double* g, double* s1, double* s2, int64_t plane, int n_chains, int n_per_seq,
-                                  int f32_state, hipStream_t st);
-hipError_t launch_posterior_sample(const void* beds, const int32_t* cells, int n_samples, int n_chains, int64_t plane, int f32_state,
-                                   double* out, hipStream_t st);
-// posterior_hist_kernel.hip
-constexpr int kHistMaxBins = 128;      // (bins + 4) / 2 KiB of LDS per workgroup
-constexpr int kHistMaxLevels = 8;
-int posterior_hist_parts(int64_t cell_blocks, int n_chains, int n_cu);
-hipError_t launch_posterior_histogram(const void* beds, const double* g, double inv_w, int n_bins, const double* levels, int n_levels,
-                                      int32_t* counts, int64_t plane, int n_chains, int f32_state, int n_cu, hipStream_t st);
-// posterior_lag_kernel.hip
-constexpr int kLagMaxLags = 15;        // K x V fp64 accumulators and K loads per lane stay in registers
-int posterior_lag_vec(int64_t plane, int f32_state);
-hipError_t launch_posterior_lagged(const void* beds, void* ring, double* slab, double* lag_sqdiff, int64_t plane, int n_chains, int parts,
-                                   int n_lags, int head, int n_valid, int f32_state, int n_cu, hipStream_t st);
 // variogram_kernel.hip
 constexpr int kVariogramMaxLag = 1 << 20;
 int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part

@@ -27,13 +27,11 @@
 // exact in any order -- the result is bit-reproducible either way -- and because the slabs would be parts * (B + 3 + L) *
 // H * W ints written and read again per snapshot (72 MiB at 256 x 256, 4 parts, B = 64, L = 2) where most counters of a
 // part are zero and are skipped here.  The call adds to `counts`, so accumulation over snapshots needs nothing else.
-#include "gsm_internal.h"
-#include <algorithm>
+#include "posterior_device.h"
 
 namespace gsm {
 namespace {
 
-constexpr int kHistBlock = 256;
 constexpr int kHistChains = 8;          // chains whose loads are in flight together
 constexpr int kHistMaxCpp = 65535;      // chains per part that a 16-bit counter holds
 
@@ -50,16 +48,16 @@ __device__ __forceinline__ int hist_slot(double d, double inv_w, double half, do
 }
 
 template <typename T, int kRows, int kLev>
-__global__ __launch_bounds__(kHistBlock) void post_hist_kernel(const T* __restrict__ beds, const double* __restrict__ g, double inv_w, int B,
+__global__ __launch_bounds__(kPostBlock) void post_hist_kernel(const T* __restrict__ beds, const double* __restrict__ g, double inv_w, int B,
                                                                HistLevels lev, int n_levels, int32_t* __restrict__ counts, int64_t plane,
                                                                int n_chains, int cpp) {
-  __shared__ uint32_t lds[kRows * kHistBlock];
-  const int64_t cell = (int64_t)blockIdx.x * kHistBlock + threadIdx.x;
-  const int c0 = blockIdx.y * cpp, c1 = min(n_chains, c0 + cpp);
+  __shared__ uint32_t lds[kRows * kPostBlock];
+  const int64_t cell = (int64_t)blockIdx.x * kPostBlock + threadIdx.x;
+  const auto [c0, c1] = chain_range(cpp, n_chains);
   if (cell >= plane || c0 >= c1) return;
   const int rows = (B + 4) / 2;                          // B + 3 slots, two to a dword
   uint32_t* col = lds + threadIdx.x;
-  for (int r = 0; r < rows; ++r) col[r * kHistBlock] = 0u;
+  for (int r = 0; r < rows; ++r) col[r * kPostBlock] = 0u;
   const double gv = g[cell], half = (double)(B / 2), bins = (double)B;
   int below[kLev];
 #pragma unroll
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(kHistBlock) void post_hist_kernel(const T* __restri
   auto count = [&](T b) {
     const double x = (double)b;
     const int s = hist_slot(x - gv, inv_w, half, bins, B);
-    atomicAdd(&col[(s >> 1) * kHistBlock], 1u << ((s & 1) * 16));
+    atomicAdd(&col[(s >> 1) * kPostBlock], 1u << ((s & 1) * 16));
 #pragma unroll
     for (int l = 0; l < kLev; ++l) below[l] += x < lev.v[l] ? 1 : 0;
   };
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(kHistBlock) void post_hist_kernel(const T* __restri
   for (; c < c1; ++c) count(p[(int64_t)c * plane]);
   int32_t* out = counts + cell;
   for (int r = 0; r < rows; ++r) {
-    const uint32_t v = col[r * kHistBlock];
+    const uint32_t v = col[r * kPostBlock];
     const int lo = (int)(v & 0xffffu), hi = (int)(v >> 16);      // slot 2r + 1 == B + 3 does not exist and is never counted
     if (lo) atomicAdd(out + (int64_t)(2 * r) * plane, lo);
     if (hi) atomicAdd(out + (int64_t)(2 * r + 1) * plane, hi);
@@ -96,36 +94,33 @@ __global__ __launch_bounds__(kHistBlock) void post_hist_kernel(const T* __restri
 template <typename T, int kLev>
 void hist_t(const void* beds, const double* g, double inv_w, int B, const HistLevels& lev, int n_levels, int32_t* counts, int64_t plane,
             int n_chains, int parts, int cpp, hipStream_t st) {
-  const dim3 grid((unsigned)((plane + kHistBlock - 1) / kHistBlock), (unsigned)parts);
+  const dim3 grid((unsigned)posterior_cell_blocks(plane, 1), (unsigned)parts);
   if (B <= 32)
-    hipLaunchKernelGGL((post_hist_kernel<T, 18, kLev>), grid, dim3(kHistBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
+    hipLaunchKernelGGL((post_hist_kernel<T, 18, kLev>), grid, dim3(kPostBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
   else if (B <= 64)
-    hipLaunchKernelGGL((post_hist_kernel<T, 34, kLev>), grid, dim3(kHistBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
+    hipLaunchKernelGGL((post_hist_kernel<T, 34, kLev>), grid, dim3(kPostBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
   else
-    hipLaunchKernelGGL((post_hist_kernel<T, 66, kLev>), grid, dim3(kHistBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
+    hipLaunchKernelGGL((post_hist_kernel<T, 66, kLev>), grid, dim3(kPostBlock), 0, st, (const T*)beds, g, inv_w, B, lev, n_levels, counts, plane, n_chains, cpp);
 }
-
-}  // namespace
 
 // parts of the chain axis for the histogram: posterior_parts, raised where a part would hold more chains than a 16-bit counter counts
 int posterior_hist_parts(int64_t cell_blocks, int n_chains, int n_cu) {
   return std::max(posterior_parts(cell_blocks, n_chains, n_cu), (n_chains + kHistMaxCpp - 1) / kHistMaxCpp);
 }
 
+}  // namespace
+
 hipError_t launch_posterior_histogram(const void* beds, const double* g, double inv_w, int n_bins, const double* levels, int n_levels,
                                       int32_t* counts, int64_t plane, int n_chains, int f32_state, int n_cu, hipStream_t st) {
-  if (n_bins < 2 || n_bins > kHistMaxBins || n_bins % 2 || n_levels < 0 || n_levels > kHistMaxLevels) return hipErrorInvalidValue;
   HistLevels lev;
   for (int l = 0; l < kHistMaxLevels; ++l) lev.v[l] = l < n_levels ? levels[l] : -__builtin_inf();
-  const int parts = posterior_hist_parts((plane + kHistBlock - 1) / kHistBlock, n_chains, n_cu);
-  const int cpp = (n_chains + parts - 1) / parts;
-  if (f32_state) {
-    if (n_levels <= 2) hist_t<float, 2>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
-    else hist_t<float, kHistMaxLevels>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
-  } else {
-    if (n_levels <= 2) hist_t<double, 2>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
-    else hist_t<double, kHistMaxLevels>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
-  }
+  const int parts = posterior_hist_parts(posterior_cell_blocks(plane, 1), n_chains, n_cu);
+  const int cpp = chains_per_part(n_chains, parts);
+  dispatch_state(f32_state, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    if (n_levels <= 2) hist_t<T, 2>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
+    else hist_t<T, kHistMaxLevels>(beds, g, inv_w, n_bins, lev, n_levels, counts, plane, n_chains, parts, cpp, st);
+  });
   return hipGetLastError();
 }
 

@@ -6,18 +6,13 @@
 // consecutive lanes on consecutive addresses, every load of a loop trip issued before the first use.  Sums over chains are
 // taken in index order; where the chain axis is split over workgroups to fill the machine, each part writes its own slab
 // and a second kernel adds the slabs in part order, so results do not depend on scheduling.
-#include "gsm_internal.h"
-#include <algorithm>
+#include "posterior_device.h"
 
 namespace gsm {
 namespace {
 
-constexpr int kPostBlock = 256;
 constexpr int kPostUnroll = 2;     // 16-byte groups per lane and loop trip of the per-chain accumulate
 constexpr int kPostChains = 4;     // chains whose loads are in flight together in the pooled form
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack { T v[V]; };
 
 // ---- per-chain form --------------------------------------------------------------------------------------------------
 // d = bed - ref; s1 += d; s2 += d * d over the flat [n_chains * H * W] arrays.  kFirst: ref = bed is written instead of
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(kPostBlock) void post_pooled_kernel(const T* __rest
   using PT = Pack<T, V>;
   const int64_t cell = ((int64_t)blockIdx.x * kPostBlock + threadIdx.x) * V;
   if (cell >= plane) return;
-  const int c0 = blockIdx.y * cpp, c1 = min(n_chains, c0 + cpp);
+  const auto [c0, c1] = chain_range(cpp, n_chains);
   double gv[V], a1[V], a2[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) { gv[k] = g[cell + k]; a1[k] = 0.0; a2[k] = 0.0; }
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(kPostBlock) void post_partials_kernel(const T* __re
                                                                    int64_t seq_stride, int n_closed, double N, int cpp) {
   const int64_t cell = (int64_t)blockIdx.x * kPostBlock + threadIdx.x;
   if (cell >= plane) return;
-  const int c0 = blockIdx.y * cpp, c1 = min(n_chains, c0 + cpp);
+  const auto [c0, c1] = chain_range(cpp, n_chains);
   const double gv = g[cell], nm1 = N - 1.0;
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;
 #pragma unroll 2
@@ -162,8 +157,7 @@ __global__ __launch_bounds__(kPostBlock) void post_close_kernel(const T* __restr
   s2[i] = (x2 - x1 * x1 / N) / (N - 1.0);
 }
 
-// out_f[cell] (+)= sum over parts, in part order, of slab[(p * n_fields + f) * plane + cell]
-struct PostOut { double* f[3]; };
+// out.f[i][cell] (+)= sum over parts, in part order, of slab[(p * n_fields + i) * plane + cell]
 __global__ __launch_bounds__(kPostBlock) void post_combine_kernel(const double* __restrict__ slab, int parts, int n_fields, int64_t plane,
                                                                   PostOut out, int add) {
   for (int64_t cell = (int64_t)blockIdx.x * kPostBlock + threadIdx.x; cell < plane; cell += (int64_t)gridDim.x * kPostBlock)
@@ -185,92 +179,71 @@ __global__ __launch_bounds__(kPostBlock) void post_sample_kernel(const T* __rest
   out[i] = (cell >= 0 && cell < plane) ? (double)beds[(int64_t)c * plane + cell] : __builtin_nan("");
 }
 
-int grid_for(int64_t work_items, int per_block, int n_cu) {
-  const int64_t want = (work_items + per_block - 1) / per_block;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)n_cu * 8));
-}
-
-template <typename T, int V>
-void accumulate_t(const void* beds, void* ref, double* s1, double* s2, int64_t n, int first, int n_cu, hipStream_t st) {
-  const int grid = grid_for(n / V, kPostBlock * kPostUnroll, n_cu);
-  if (first) hipLaunchKernelGGL((post_accumulate_kernel<T, V, true>), dim3(grid), dim3(kPostBlock), 0, st, (const T*)beds, (T*)ref, s1, s2, n);
-  else hipLaunchKernelGGL((post_accumulate_kernel<T, V, false>), dim3(grid), dim3(kPostBlock), 0, st, (const T*)beds, (T*)ref, s1, s2, n);
-}
-
-template <typename T, int V>
-void pooled_t(const void* beds, const double* g, double* slab, int64_t plane, int n_chains, int parts, int cpp, hipStream_t st) {
-  const int gx = (int)((plane / V + kPostBlock - 1) / kPostBlock);
-  hipLaunchKernelGGL((post_pooled_kernel<T, V>), dim3(gx, parts), dim3(kPostBlock), 0, st, (const T*)beds, g, slab, plane, n_chains, cpp);
-}
-
 }  // namespace
 
-// how many parts the chain axis is cut into so that cell_blocks * parts workgroups fill the CUs about four times over
-int posterior_parts(int64_t cell_blocks, int n_chains, int n_cu) {
-  const int64_t want = ((int64_t)n_cu * 4 + cell_blocks - 1) / cell_blocks;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, n_chains));
+hipError_t launch_posterior_combine(const double* slab, int parts, int n_fields, int64_t plane, const PostOut& out, int add, int n_cu,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(post_combine_kernel, dim3(grid_for(plane, kPostBlock, n_cu)), dim3(kPostBlock), 0, st, slab, parts, n_fields, plane, out, add);
+  return hipGetLastError();
 }
 
 hipError_t launch_posterior_accumulate(const void* beds, void* ref, double* s1, double* s2, int64_t n, int f32_state, int first, int n_cu,
                                        hipStream_t st) {
-  if (f32_state) accumulate_t<float, 4>(beds, ref, s1, s2, n, first, n_cu, st);
-  else accumulate_t<double, 2>(beds, ref, s1, s2, n, first, n_cu, st);
+  dispatch_state(f32_state, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    const dim3 grid(grid_for(n / V, kPostBlock * kPostUnroll, n_cu));
+    if (first) hipLaunchKernelGGL((post_accumulate_kernel<T, V, true>), grid, dim3(kPostBlock), 0, st, (const T*)beds, (T*)ref, s1, s2, n);
+    else hipLaunchKernelGGL((post_accumulate_kernel<T, V, false>), grid, dim3(kPostBlock), 0, st, (const T*)beds, (T*)ref, s1, s2, n);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_posterior_pooled(const void* beds, const double* g, double* s1, double* s2, double* slab, int64_t plane, int n_chains,
                                    int parts, int f32_state, int n_cu, hipStream_t st) {
-  const int cpp = (n_chains + parts - 1) / parts;
-  if (f32_state) {
-    if (plane % 4 == 0) pooled_t<float, 4>(beds, g, slab, plane, n_chains, parts, cpp, st);
-    else if (plane % 2 == 0) pooled_t<float, 2>(beds, g, slab, plane, n_chains, parts, cpp, st);
-    else pooled_t<float, 1>(beds, g, slab, plane, n_chains, parts, cpp, st);
-  } else {
-    if (plane % 2 == 0) pooled_t<double, 2>(beds, g, slab, plane, n_chains, parts, cpp, st);
-    else pooled_t<double, 1>(beds, g, slab, plane, n_chains, parts, cpp, st);
-  }
+  const int vec = posterior_vec(plane, f32_state);
+  const dim3 grid((unsigned)posterior_cell_blocks(plane, vec), (unsigned)parts);
+  dispatch_state_vec(f32_state, vec, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((post_pooled_kernel<T, decltype(tag)::V>), grid, dim3(kPostBlock), 0, st, (const T*)beds, g, slab, plane, n_chains,
+                       chains_per_part(n_chains, parts));
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  PostOut out{{s1, s2, nullptr}};
-  hipLaunchKernelGGL(post_combine_kernel, dim3(grid_for(plane, kPostBlock, n_cu)), dim3(kPostBlock), 0, st, slab, parts, 2, plane, out, 1);
-  return hipGetLastError();
+  return launch_posterior_combine(slab, parts, 2, plane, PostOut{{s1, s2}}, 1, n_cu, st);
 }
 
 hipError_t launch_posterior_partials(const void* ref, const double* g, const double* s1, const double* s2, double* slab, double* partials,
                                      int64_t plane, int n_chains, int n_seq, int64_t seq_stride, int n_closed, int n_per_seq, int parts, int f32_state,
                                      int n_cu, hipStream_t st) {
-  const int cpp = (n_chains + parts - 1) / parts;
-  const int gx = (int)((plane + kPostBlock - 1) / kPostBlock);
-  if (f32_state)
-    hipLaunchKernelGGL((post_partials_kernel<float>), dim3(gx, parts), dim3(kPostBlock), 0, st, (const float*)ref, g, s1, s2, slab, plane, n_chains,
-                       n_seq, seq_stride, n_closed, (double)n_per_seq, cpp);
-  else
-    hipLaunchKernelGGL((post_partials_kernel<double>), dim3(gx, parts), dim3(kPostBlock), 0, st, (const double*)ref, g, s1, s2, slab, plane,
-                       n_chains, n_seq, seq_stride, n_closed, (double)n_per_seq, cpp);
+  const dim3 grid((unsigned)posterior_cell_blocks(plane, 1), (unsigned)parts);
+  dispatch_state(f32_state, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((post_partials_kernel<T>), grid, dim3(kPostBlock), 0, st, (const T*)ref, g, s1, s2, slab, plane, n_chains, n_seq, seq_stride,
+                       n_closed, (double)n_per_seq, chains_per_part(n_chains, parts));
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  PostOut out{{partials, partials + plane, partials + 2 * plane}};
-  hipLaunchKernelGGL(post_combine_kernel, dim3(grid_for(plane, kPostBlock, n_cu)), dim3(kPostBlock), 0, st, slab, parts, 3, plane, out, 0);
-  return hipGetLastError();
+  return launch_posterior_combine(slab, parts, 3, plane, PostOut{{partials, partials + plane, partials + 2 * plane}}, 0, n_cu, st);
 }
 
 hipError_t launch_posterior_close(const void* ref, const double* g, double* s1, double* s2, int64_t plane, int n_chains, int n_per_seq,
                                   int f32_state, hipStream_t st) {
-  const dim3 grid((unsigned)((plane + kPostBlock - 1) / kPostBlock), (unsigned)n_chains);
-  if (f32_state)
-    hipLaunchKernelGGL((post_close_kernel<float>), grid, dim3(kPostBlock), 0, st, (const float*)ref, g, s1, s2, plane, (double)n_per_seq);
-  else
-    hipLaunchKernelGGL((post_close_kernel<double>), grid, dim3(kPostBlock), 0, st, (const double*)ref, g, s1, s2, plane, (double)n_per_seq);
+  const dim3 grid((unsigned)posterior_cell_blocks(plane, 1), (unsigned)n_chains);
+  dispatch_state(f32_state, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((post_close_kernel<T>), grid, dim3(kPostBlock), 0, st, (const T*)ref, g, s1, s2, plane, (double)n_per_seq);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_posterior_sample(const void* beds, const int32_t* cells, int n_samples, int n_chains, int64_t plane, int f32_state,
                                    double* out, hipStream_t st) {
-  const int grid = (int)(((int64_t)n_chains * n_samples + kPostBlock - 1) / kPostBlock);
-  if (f32_state)
-    hipLaunchKernelGGL((post_sample_kernel<float>), dim3(grid), dim3(kPostBlock), 0, st, (const float*)beds, cells, n_samples, n_chains, plane, out);
-  else
-    hipLaunchKernelGGL((post_sample_kernel<double>), dim3(grid), dim3(kPostBlock), 0, st, (const double*)beds, cells, n_samples, n_chains, plane, out);
+  const dim3 grid((unsigned)(((int64_t)n_chains * n_samples + kPostBlock - 1) / kPostBlock));
+  dispatch_state(f32_state, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((post_sample_kernel<T>), grid, dim3(kPostBlock), 0, st, (const T*)beds, cells, n_samples, n_chains, plane, out);
+  });
   return hipGetLastError();
 }
 

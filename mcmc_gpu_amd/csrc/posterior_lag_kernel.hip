@@ -14,26 +14,20 @@
 // does not carry the registers of 15.
 //
 // Sums.  Differences, squares and sums are fp64 whatever the state type.  Each part writes [n_valid, plane] sums to its slab
-// and post_lag_combine_kernel adds the slabs in part order onto lag_sqdiff: nothing depends on scheduling, the same calls
+// and post_combine_kernel (posterior_kernel.hip) adds the slabs in part order onto lag_sqdiff: nothing depends on scheduling, the same calls
 // give the same bits.  A part without chains writes zeros.
-#include "gsm_internal.h"
-#include <algorithm>
+#include "posterior_device.h"
 
 namespace gsm {
 namespace {
 
-constexpr int kLagBlock = 256;
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) LagPack { T v[V]; };
-
 template <typename T, int V, int kMax>
-__global__ __launch_bounds__(kLagBlock) void post_lag_kernel(const T* __restrict__ beds, T* ring, double* __restrict__ slab, int64_t plane,
+__global__ __launch_bounds__(kPostBlock) void post_lag_kernel(const T* __restrict__ beds, T* ring, double* __restrict__ slab, int64_t plane,
                                                              int n_chains, int cpp, int n_lags, int head, int n_valid) {
-  using PT = LagPack<T, V>;
-  const int64_t cell = ((int64_t)blockIdx.x * kLagBlock + threadIdx.x) * V;
+  using PT = Pack<T, V>;
+  const int64_t cell = ((int64_t)blockIdx.x * kPostBlock + threadIdx.x) * V;
   if (cell >= plane) return;
-  const int c0 = blockIdx.y * cpp, c1 = min(n_chains, c0 + cpp);
+  const auto [c0, c1] = chain_range(cpp, n_chains);
   // where lag t + 1 lies: slot (head - (t + 1)) mod n_lags
   int slot[kMax];
 #pragma unroll
@@ -72,55 +66,31 @@ __global__ __launch_bounds__(kLagBlock) void post_lag_kernel(const T* __restrict
     }
 }
 
-// out[f * plane + cell] += sum over parts, in part order, of slab[(p * n_fields + f) * plane + cell]
-__global__ __launch_bounds__(kLagBlock) void post_lag_combine_kernel(const double* __restrict__ slab, int parts, int n_fields, int64_t plane,
-                                                                     double* __restrict__ out) {
-  for (int64_t cell = (int64_t)blockIdx.x * kLagBlock + threadIdx.x; cell < plane; cell += (int64_t)gridDim.x * kLagBlock)
-    for (int f = 0; f < n_fields; ++f) {
-      double s = 0.0;
-      for (int p = 0; p < parts; ++p) s += slab[((int64_t)p * n_fields + f) * plane + cell];
-      out[(int64_t)f * plane + cell] += s;
-    }
-}
-
 template <typename T, int V>
 void lag_t(const void* beds, void* ring, double* slab, int64_t plane, int n_chains, int parts, int cpp, int n_lags, int head, int n_valid,
            hipStream_t st) {
-  const dim3 grid((unsigned)((plane / V + kLagBlock - 1) / kLagBlock), (unsigned)parts);
+  const dim3 grid((unsigned)posterior_cell_blocks(plane, V), (unsigned)parts);
   if (n_lags <= 3)
-    hipLaunchKernelGGL((post_lag_kernel<T, V, 3>), grid, dim3(kLagBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
+    hipLaunchKernelGGL((post_lag_kernel<T, V, 3>), grid, dim3(kPostBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
   else if (n_lags <= 7)
-    hipLaunchKernelGGL((post_lag_kernel<T, V, 7>), grid, dim3(kLagBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
+    hipLaunchKernelGGL((post_lag_kernel<T, V, 7>), grid, dim3(kPostBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
   else
-    hipLaunchKernelGGL((post_lag_kernel<T, V, kLagMaxLags>), grid, dim3(kLagBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
+    hipLaunchKernelGGL((post_lag_kernel<T, V, kLagMaxLags>), grid, dim3(kPostBlock), 0, st, (const T*)beds, (T*)ring, slab, plane, n_chains, cpp, n_lags, head, n_valid);
 }
 
 }  // namespace
 
-// cells per lane: 16 bytes where the plane allows it, so that every chain's row of a lane starts on its own vector boundary
-int posterior_lag_vec(int64_t plane, int f32_state) {
-  if (f32_state) return plane % 4 == 0 ? 4 : plane % 2 == 0 ? 2 : 1;
-  return plane % 2 == 0 ? 2 : 1;
-}
-
 hipError_t launch_posterior_lagged(const void* beds, void* ring, double* slab, double* lag_sqdiff, int64_t plane, int n_chains, int parts,
                                    int n_lags, int head, int n_valid, int f32_state, int n_cu, hipStream_t st) {
-  if (n_lags < 1 || n_lags > kLagMaxLags || head < 0 || head >= n_lags || n_valid < 0 || n_valid > n_lags) return hipErrorInvalidValue;
-  const int cpp = (n_chains + parts - 1) / parts;
-  const int vec = posterior_lag_vec(plane, f32_state);
-  if (f32_state) {
-    if (vec == 4) lag_t<float, 4>(beds, ring, slab, plane, n_chains, parts, cpp, n_lags, head, n_valid, st);
-    else if (vec == 2) lag_t<float, 2>(beds, ring, slab, plane, n_chains, parts, cpp, n_lags, head, n_valid, st);
-    else lag_t<float, 1>(beds, ring, slab, plane, n_chains, parts, cpp, n_lags, head, n_valid, st);
-  } else {
-    if (vec == 2) lag_t<double, 2>(beds, ring, slab, plane, n_chains, parts, cpp, n_lags, head, n_valid, st);
-    else lag_t<double, 1>(beds, ring, slab, plane, n_chains, parts, cpp, n_lags, head, n_valid, st);
-  }
+  dispatch_state_vec(f32_state, posterior_vec(plane, f32_state), [&](auto tag) {
+    lag_t<typename decltype(tag)::T, decltype(tag)::V>(beds, ring, slab, plane, n_chains, parts, chains_per_part(n_chains, parts), n_lags, head,
+                                                       n_valid, st);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || n_valid == 0) return e;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((plane + kLagBlock - 1) / kLagBlock, (int64_t)n_cu * 8));
-  hipLaunchKernelGGL(post_lag_combine_kernel, dim3(grid), dim3(kLagBlock), 0, st, slab, parts, n_valid, plane, lag_sqdiff);
-  return hipGetLastError();
+  PostOut out{};
+  for (int t = 0; t < n_valid; ++t) out.f[t] = lag_sqdiff + (int64_t)t * plane;
+  return launch_posterior_combine(slab, parts, n_valid, plane, out, 1, n_cu, st);
 }
 
 }  // namespace gsm

@@ -138,19 +138,17 @@ def _segment_label(prev, n_iter):
     return f'{(label_count + n_iter) // 1000}k'
 
 
-def _merge_posterior(accum, part, n_chains, base, label):
-    """Sum this rank's posterior partials (and histogram counts, and lagged sums) with the other ranks', gather the sample traces,
-    and let rank 0 write the summary."""
+def _merge_posterior(accum, local_sums, n_chains, base, label):
+    """Sum this rank's additive posterior quantities (PosteriorAccumulator.local_sums) with the other ranks', integers as int64,
+    gather the sample traces, and let rank 0 write the summary."""
     import torch.distributed as dist
-    total, M = parallel.all_reduce_posterior(part, accum.n_sequences)
-    hc = None if accum.hist_counts is None else parallel.all_reduce_counts(accum.hist_counts)
-    ls = None if accum.lag_sqdiff is None else parallel.all_reduce_sum(accum.lag_sqdiff)
+    sums = {k: (parallel.all_reduce_sum if v.is_floating_point() else parallel.all_reduce_counts)(v) for k, v in local_sums.items()}
     sv = None
     if accum.d_samples is not None:                # [T, local chains, points] on the device -> [n_chains, points, T]
         sv = parallel.all_gather_chains(accum.d_samples.permute(1, 2, 0).contiguous(), n_chains).cpu().numpy()
     if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
         base.mkdir(parents=True, exist_ok=True)
-        accum.finalize(total, M, sample_values=sv, hist_counts=hc, lag_sqdiff=ls).save(base / f'posterior_{label}.npz')
+        accum.finalize(sample_values=sv, **sums).save(base / f'posterior_{label}.npz')
 
 
 def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, n_workers,
@@ -180,7 +178,7 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
                                            return_device=True, posterior=posterior)
             try:
                 local = MCMC_gpu._result_tuples(*dev, n_iter)
-                part = accum.partials()
+                local_sums = accum.local_sums()
             finally:
                 dev[0].close()
             steps1 = [steps0[0] + n_iter - 1] * len(idx)
@@ -202,7 +200,7 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
                               {'key': seeds[k] & 0xFFFFFFFFFFFFFFFF, 'step': steps1[k]})
             if accum is not None:
                 # only rank 0 writes, and its first chain is chain 0: the label is that of chain 0's files
-                _merge_posterior(accum, part, n_chains if n_chains is not None else len(idx), base, _segment_label(prevs[0], n_iter))
+                _merge_posterior(accum, local_sums, n_chains if n_chains is not None else len(idx), base, _segment_label(prevs[0], n_iter))
             return local
     local = []
     for i in idx:

@@ -182,6 +182,14 @@ class GsmEngine:
             raise ValueError("sample_cells must be an int32 device tensor and sample_out a contiguous float64 one of n_chains x n_samples")
         return sample_cells, int(sample_cells.numel()), sample_out
 
+    def _need_beds(self):
+        if self.beds is None:
+            raise RuntimeError("set_state() first")
+
+    def _check_state(self, name, t, k=1):
+        if t.dtype != self.state_dtype or t.numel() != k * self.n_chains * self.H * self.W or not t.is_contiguous() or t.device != self.dev:
+            raise ValueError(f"{name} must be a contiguous tensor of {k} x the beds' shape and dtype on {self.dev}")
+
     def _check_sums(self, n, **tensors):
         for name, t in tensors.items():
             if t.dtype != torch.float64 or t.numel() < n or not t.is_contiguous() or t.device != self.dev:
@@ -190,35 +198,28 @@ class GsmEngine:
     def posterior_accumulate(self, ref, s1, s2, first, sample_cells=None, sample_out=None):
         """One snapshot of self.beds into the per-chain sums of one sequence: d = bed - ref, s1 += d, s2 += d * d (first: ref = bed is
         written and the sums are set).  ref [n_chains, H, W] in the state dtype, s1 / s2 float64 of the same size.  Asynchronous."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
-        n = self.n_chains * self.H * self.W
-        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
-            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
-        self._check_sums(n, s1=s1, s2=s2)
+        self._need_beds()
+        self._check_state("ref", ref)
+        self._check_sums(self.n_chains * self.H * self.W, s1=s1, s2=s2)
         self.call(self.lib.gsm_posterior_accumulate, self.beds, ref, s1, s2, 1 if first else 0, *self._sample_args(sample_cells, sample_out))
 
     def posterior_accumulate_pooled(self, g, s1, s2, sample_cells=None, sample_out=None):
         """One snapshot of self.beds into sums over all chains: S1 += sum_c d, S2 += sum_c d * d, d = bed_c - g; g, s1, s2 [H, W] float64."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         self._check_sums(self.H * self.W, g=g, s1=s1, s2=s2)
         self.call(self.lib.gsm_posterior_accumulate_pooled, self.beds, g, s1, s2, *self._sample_args(sample_cells, sample_out))
 
     def posterior_sample(self, sample_cells, sample_out):
         """sample_out[c, p] = self.beds[c] at flat cell sample_cells[p]."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         self.call(self.lib.gsm_posterior_sample, self.beds, *self._sample_args(sample_cells, sample_out))
 
     def posterior_close(self, ref, g, s1, s2, n_per_seq):
         """A finished sequence's sums become, in place, s1 = its mean minus g and s2 = its ddof=1 variance; `ref` is then free for
         the chains' next sequence (posterior_accumulate with first=True)."""
-        n = self.n_chains * self.H * self.W
         self._check_sums(self.H * self.W, g=g)
-        self._check_sums(n, s1=s1, s2=s2)
-        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
-            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
+        self._check_sums(self.n_chains * self.H * self.W, s1=s1, s2=s2)
+        self._check_state("ref", ref)
         self.call(self.lib.gsm_posterior_close, ref, g, s1, s2, int(n_per_seq))
 
     def posterior_partials(self, ref, g, s1, s2, n_seq_per_chain, seq_stride, n_closed, n_per_seq):
@@ -228,8 +229,7 @@ class GsmEngine:
         n = self.n_chains * self.H * self.W
         self._check_sums(self.H * self.W, g=g)
         self._check_sums((int(n_seq_per_chain) - 1) * int(seq_stride) + n if n_seq_per_chain in (1, 2) else n, s1=s1, s2=s2)
-        if ref.dtype != self.state_dtype or ref.numel() != n or not ref.is_contiguous():
-            raise ValueError("ref must be a contiguous tensor of the beds' shape and dtype")
+        self._check_state("ref", ref)
         out = torch.empty((3, self.H, self.W), dtype=torch.float64, device=self.dev)
         self.call(self.lib.gsm_posterior_partials, ref, g, s1, s2, int(n_seq_per_chain), int(seq_stride), int(n_closed), int(n_per_seq), out)
         return out
@@ -238,8 +238,7 @@ class GsmEngine:
         """One snapshot of self.beds ADDED to the per-cell counts [(n_bins + 3 + L), H, W] int32: slot 0 underflow, 1 .. n_bins the
         bins of floor((bed - g) * inv_width) + n_bins / 2, n_bins + 1 overflow, n_bins + 2 NaN, then one slot per level counting
         bed < level.  g [H, W] float64 on the device, levels a host sequence of L <= 8 floats.  Asynchronous."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         self._check_sums(self.H * self.W, g=g)
         lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
         n = (int(n_bins) + 3 + lv.size) * self.H * self.W
@@ -253,12 +252,9 @@ class GsmEngine:
         lag_sqdiff[t - 1] += sum_c (bed_c - ring[(head - t) % n_lags, c]) ** 2 for t = 1 .. n_valid, then ring[head] = beds.  ring
         [n_lags, n_chains, H * W] in the state dtype, lag_sqdiff [n_lags, H, W] float64; the caller advances head and n_valid
         (n_valid = 0 starts a sequence).  Asynchronous."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         n_lags = int(n_lags)
-        n = self.n_chains * self.H * self.W
-        if ring.dtype != self.state_dtype or ring.numel() != n_lags * n or not ring.is_contiguous() or ring.device != self.dev:
-            raise ValueError(f"ring must be a contiguous tensor of n_lags x the beds' shape and dtype on {self.dev}")
+        self._check_state("ring", ring, n_lags)
         if lag_sqdiff.numel() != n_lags * self.H * self.W:
             raise ValueError(f"lag_sqdiff must hold n_lags x H x W = {n_lags * self.H * self.W} elements")
         self._check_sums(n_lags * self.H * self.W, lag_sqdiff=lag_sqdiff)
@@ -295,8 +291,7 @@ class GsmEngine:
             f = self._f64(fields_packed)
         if tuple(f.shape) != (self.n_chains, n_steps, self.field_stride):
             raise ValueError("fields_packed has the wrong shape")
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         d_si = torch.as_tensor(size_idx).to(self.dev)
         d_c = torch.as_tensor(centre).to(self.dev)
         d_u = torch.as_tensor(u).to(self.dev)
@@ -439,8 +434,7 @@ class GsmEngine:
         """n_steps Metropolis steps for every chain with synthesis and step in one kernel (gsm_run_noise; block tables on the strip
         kernels only), on the device draws `d` of draw_pcg64.  loss [n_chains, n_steps] float64 and accept [n_chains, n_steps] uint8
         are device tensors that receive the results.  Asynchronous on the current stream."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         p = rf if isinstance(rf, RfParams) else self.rf_struct(rf)
         self.call(self.lib.gsm_run_noise, int(n_steps), self.beds, self.energy, self.resampled, self.loss_sum, d['size_idx'], d['centre'], d['u'],
                   d['rf_scalars'], C.byref(p), d['noise_re'], d['noise_im'], d['nugget'], self.field_stride, loss, accept)
@@ -482,8 +476,7 @@ class GsmEngine:
     def run_philox(self, n_steps, step0, seeds, rf, batch=8, out=None, to_host=True):
         """n_steps Metropolis steps for every chain with on-device proposals.
         Returns (loss, accept, blocks): (n_chains, n_steps), (n_chains, n_steps), (n_chains, n_steps, 4)."""
-        if self.beds is None:
-            raise RuntimeError("set_state() first")
+        self._need_beds()
         d_seeds = self._seeds(seeds)
         if out is None:
             loss = torch.empty((self.n_chains, n_steps), dtype=torch.float64, device=self.dev)

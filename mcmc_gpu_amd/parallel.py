@@ -74,64 +74,41 @@ def all_gather_chains(local: torch.Tensor, n_chains: int) -> torch.Tensor:
     return torch.cat([p[:s] for p, s in zip(parts, sizes)], dim=0)
 
 
-def all_reduce_mean_field(local_sum: torch.Tensor, n_chains: int) -> torch.Tensor:
-    """Posterior-mean field from per-rank sums over local chains: one all-reduce of an (H, W) tensor."""
-    t = local_sum.clone()
+def _sum_over_ranks(t: torch.Tensor) -> torch.Tensor:
+    """SUM all-reduce of `t`, which must be the caller's own copy: in place where the backend reaches the tensor, through a host copy
+    under gloo.  Returns the tensor that holds the sum, on the device of `t`; `t` itself without a process group."""
     if dist.is_initialized() and dist.get_world_size() > 1:
         if _via_host(t):
             h = t.cpu()
             dist.all_reduce(h, op=dist.ReduceOp.SUM)
-            t = h.to(t.device)
-        else:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t / float(n_chains)
+            return h.to(t.device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+def all_reduce_mean_field(local_sum: torch.Tensor, n_chains: int) -> torch.Tensor:
+    """Posterior-mean field from per-rank sums over local chains: one all-reduce of an (H, W) tensor."""
+    return _sum_over_ranks(local_sum.clone()) / float(n_chains)
 
 
 def all_reduce_posterior(partials: torch.Tensor, n_local_sequences: int):
     """Posterior partials ([3, H, W] sums over this rank's sequences, posterior.PosteriorAccumulator.partials) and the sequence
     count summed over ranks: one SUM all-reduce each.  Returns (partials_sum, M)."""
-    t = partials.clone()
-    m = torch.tensor([int(n_local_sequences)], dtype=torch.int64)
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        if _via_host(t) or not t.is_cuda:
-            h = t.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM)
-            dist.all_reduce(m, op=dist.ReduceOp.SUM)
-            t = h.to(t.device)
-        else:
-            m = m.to(t.device)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            dist.all_reduce(m, op=dist.ReduceOp.SUM)
-    return t, int(m.item())
+    m = torch.tensor([int(n_local_sequences)], dtype=torch.int64, device=partials.device)
+    return _sum_over_ranks(partials.clone()), int(_sum_over_ranks(m).item())
 
 
 def all_reduce_counts(counts: torch.Tensor) -> torch.Tensor:
     """Integer counts (the posterior histogram of this rank's chains, posterior.PosteriorAccumulator.hist_counts) summed over
-    ranks: one SUM all-reduce, int64 on the wire so that the total may pass what a rank's int32 holds.  Returns an int64 tensor
+    ranks: one SUM all-reduce, int64 on the wire so that the total may pass what a rank's int32 holds.  Returns a new int64 tensor
     on the device of `counts`."""
-    t = counts.to(torch.int64)
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        if _via_host(t) or not t.is_cuda:
-            h = t.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM)
-            t = h.to(t.device)
-        else:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t
+    return _sum_over_ranks(counts.to(torch.int64, copy=True))
 
 
 def all_reduce_sum(sums: torch.Tensor) -> torch.Tensor:
     """Per-cell sums that add over chains (the posterior's lagged squared differences of this rank's chains, posterior.
     PosteriorAccumulator.lag_sqdiff) summed over ranks: one fp64 SUM all-reduce.  Returns a new tensor on the device of `sums`."""
-    t = sums.clone()
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        if _via_host(t) or not t.is_cuda:
-            h = t.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM)
-            t = h.to(t.device)
-        else:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t
+    return _sum_over_ranks(sums.clone())
 
 
 def barrier():

@@ -29,6 +29,7 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, fields
 
 import numpy as np
@@ -175,16 +176,22 @@ class PosteriorSummary:
         return cls(**kw)
 
 
+def _host_array(x, shape, dtype, what):
+    """A device tensor or an array as a new numpy array of `dtype`; ValueError unless it has `shape`."""
+    a = np.array(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=dtype)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} of shape {a.shape}, expected {tuple(shape)}")
+    return a
+
+
 def finalize(partials_sum, M, N, common_ref, rhat=True, **meta):
     """PosteriorSummary from the partials summed over all handles / ranks (gsm_posterior_partials), the number of sequences
     M behind them, the snapshots per sequence N and the common field g.  partials_sum [3, H, W]: with rhat, P0 = sum_m a_m,
     P1 = sum_m a_m^2, P2 = sum_m v_m (a_m: sequence mean minus g, v_m: sequence variance); without, P0 = sum d, P1 = sum d^2
     over all M*N values, d = bed - g.  meta: the remaining PosteriorSummary fields."""
-    P = np.asarray(partials_sum.detach().cpu().numpy() if hasattr(partials_sum, "detach") else partials_sum, dtype=np.float64)
     g = np.asarray(common_ref, dtype=np.float64)
+    P = _host_array(partials_sum, (3,) + g.shape, np.float64, "partials")
     M, N = int(M), int(N)
-    if P.ndim != 3 or P.shape[0] != 3 or P.shape[1:] != g.shape:
-        raise ValueError(f"partials of shape {P.shape} do not match a common field of shape {g.shape}")
     if N < 2 or M < 1:
         raise ValueError("need at least one sequence of at least two snapshots")
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -326,30 +333,29 @@ class PosteriorAccumulator:
         self.n_samples = 0 if cells is None else int(cells.size)
         # the second sequence's sums start on a 16-byte boundary whatever n_chains * H * W is
         self.seq_stride = (n * H * W + 31) // 32 * 32
-        state_bytes = 8 if eng.state_dtype == torch.float64 else 4
-        need = (n * H * W * state_bytes + 2 * self.n_seq * self.seq_stride * 8) if self.rhat else 2 * H * W * 8
-        need += self.T * n * self.n_samples * 8
+        # every device tensor this accumulator owns, (attribute, shape, dtype, zeroed): counted, then allocated, from this one list
+        sd, f64 = eng.state_dtype, torch.float64
+        sums = (self.n_seq, self.seq_stride) if self.rhat else (H, W)
+        table = [("d_g", (H, W), f64, False), ("s1", sums, f64, True), ("s2", sums, f64, True)]
+        if self.rhat:
+            table += [("ref", (n, H, W), sd, False)]
+        if self.n_samples:
+            table += [("d_cells", (self.n_samples,), torch.int32, False), ("d_samples", (self.T, n, self.n_samples), f64, False)]
         if self.hist is not None:
-            need += self.hist_slots * H * W * 4
-        need += self.n_lags * (n * H * W * state_bytes + H * W * 8)          # the ring and lag_sqdiff
+            table += [("hist_counts", (self.hist_slots, H, W), torch.int32, True)]
+        if self.n_lags:
+            table += [("ring", (self.n_lags, n, H * W), sd, False), ("lag_sqdiff", (self.n_lags, H, W), f64, True)]
+        self.device_bytes = need = sum(math.prod(shape) * dtype.itemsize for _, shape, dtype, _ in table)
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
                               f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
-        dev = eng.dev
-        self.d_g = torch.as_tensor(g).to(dev)
-        if self.rhat:
-            self.ref = torch.empty((n, H, W), dtype=eng.state_dtype, device=dev)
-            self.s1 = torch.zeros((self.n_seq, self.seq_stride), dtype=torch.float64, device=dev)
-            self.s2 = torch.zeros((self.n_seq, self.seq_stride), dtype=torch.float64, device=dev)
-        else:
-            self.s1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
-            self.s2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
-        self.d_cells = None if not self.n_samples else torch.as_tensor(cells).to(dev)
-        self.d_samples = None if not self.n_samples else torch.empty((self.T, n, self.n_samples), dtype=torch.float64, device=dev)
-        self.hist_counts = None if self.hist is None else torch.zeros((self.hist_slots, H, W), dtype=torch.int32, device=dev)
-        self.ring = None if not self.n_lags else torch.empty((self.n_lags, n, H * W), dtype=eng.state_dtype, device=dev)
-        self.lag_sqdiff = None if not self.n_lags else torch.zeros((self.n_lags, H, W), dtype=torch.float64, device=dev)
+        self.ref = self.d_cells = self.d_samples = self.hist_counts = self.ring = self.lag_sqdiff = None
+        for name, shape, dtype, zeroed in table:
+            setattr(self, name, (torch.zeros if zeroed else torch.empty)(shape, dtype=dtype, device=eng.dev))
+        self.d_g.copy_(torch.as_tensor(g))
+        if self.n_samples:
+            self.d_cells.copy_(torch.as_tensor(cells))
         self.ring_head = self.ring_valid = 0
         self.n_added = 0
         self._partials = None
@@ -391,51 +397,54 @@ class PosteriorAccumulator:
         self.n_added += 1
         self._partials = None
 
+    def _require_complete(self):
+        if self.n_added != self.T:
+            raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
+
     def partials(self):
         """[3, H, W] float64 device tensor of this handle's chains (see finalize); sums over ranks with all_reduce_posterior.
         Kept, so that it can be read after the engine is closed."""
         import torch
-        if self.n_added != self.T:
-            raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
+        self._require_complete()
         if self._partials is None:
-            eng = self.eng
             if self.rhat:
-                out = eng.posterior_partials(self.ref, self.d_g, self.s1, self.s2, self.n_seq, self.seq_stride, self.n_seq - 1, self.N)
+                self._partials = self.eng.posterior_partials(self.ref, self.d_g, self.s1, self.s2, self.n_seq, self.seq_stride,
+                                                             self.n_seq - 1, self.N)
             else:
-                out = torch.stack([self.s1, self.s2, torch.zeros_like(self.s1)])
-            self._partials = out
+                self._partials = torch.stack([self.s1, self.s2, torch.zeros_like(self.s1)])
         return self._partials
+
+    def local_sums(self):
+        """Everything of this accumulator that adds over ranks, as device tensors under the names finalize() takes the sums by:
+        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts and lag_sqdiff."""
+        import torch
+        out = dict(partials_sum=self.partials(), M=torch.tensor([self.n_sequences], dtype=torch.int64, device=self.d_g.device))
+        if self.hist is not None:
+            out["hist_counts"] = self.hist_counts
+        if self.n_lags:
+            out["lag_sqdiff"] = self.lag_sqdiff
+        return out
 
     def sample_values(self):
         """[n_chains, n_points, T] numpy array of the traces, or None."""
         return None if self.d_samples is None else np.ascontiguousarray(self.d_samples.permute(1, 2, 0).cpu().numpy())
 
     def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None):
-        """PosteriorSummary from partials summed over ranks and their sequence count (default: this accumulator's own);
-        hist_counts: the histogram summed over ranks (all_reduce_counts; default: this accumulator's own); lag_sqdiff: the
-        lagged sums summed over ranks (all_reduce_sum; default: this accumulator's own)."""
+        """PosteriorSummary from the sums of local_sums() added over ranks (all_reduce_posterior, all_reduce_counts, all_reduce_sum);
+        each defaults to this accumulator's own."""
+        self._require_complete()
         if partials_sum is None:
             partials_sum, M = self.partials(), self.n_sequences
         M = int(M)
+        grid = self.common_ref.shape
         meta = {}
         if self.hist is not None:
-            if self.n_added != self.T:
-                raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
-            hc = self.hist_counts if hist_counts is None else hist_counts
-            hc = np.asarray(hc.detach().cpu().numpy() if hasattr(hc, "detach") else hc).astype(np.int64)
-            if hc.shape != (self.hist_slots,) + self.common_ref.shape:
-                raise ValueError(f"histogram counts of shape {hc.shape}, expected {(self.hist_slots,) + self.common_ref.shape}")
+            hc = _host_array(self.hist_counts if hist_counts is None else hist_counts, (self.hist_slots,) + grid, np.int64, "histogram counts")
             B = self.hist["bins"]
             meta = dict(hist_counts=hc[:B + 3].copy(), hist_half_width=self.hist["half_width"], hist_centre=self.common_ref.copy(),
                         level_values=np.asarray(self.hist["levels"], dtype=np.float64), level_counts=hc[B + 3:].copy())
         if self.n_lags:
-            if self.n_added != self.T:
-                raise RuntimeError(f"{self.n_added} of {self.T} snapshots added")
-            ls = self.lag_sqdiff if lag_sqdiff is None else lag_sqdiff
-            ls = np.array(ls.detach().cpu().numpy() if hasattr(ls, "detach") else ls, dtype=np.float64)
-            if ls.shape != (self.n_lags,) + self.common_ref.shape:
-                raise ValueError(f"lagged sums of shape {ls.shape}, expected {(self.n_lags,) + self.common_ref.shape}")
-            meta["lag_sqdiff"] = ls
+            meta["lag_sqdiff"] = _host_array(self.lag_sqdiff if lag_sqdiff is None else lag_sqdiff, (self.n_lags,) + grid, np.float64, "lagged sums")
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)

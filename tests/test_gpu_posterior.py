@@ -67,6 +67,28 @@ def test_kernels_against_numpy(shape, T, state_dtype):
                 assert s.rhat is None
 
 
+@pytest.mark.parametrize("state_dtype", ["f64", "f32"])
+@pytest.mark.parametrize("rhat, split, hist, ess, points", [
+    (True, True, None, None, False),
+    (True, False, dict(bins=64, half_width=50.0, levels=(-300.0, -250.0)), dict(max_lag=3), True),
+    (False, False, dict(bins=2, half_width=50.0), None, True)])
+def test_memory_budget_is_what_is_allocated(rhat, split, hist, ess, points, state_dtype):
+    """The bytes the accumulator holds against the free device memory are those of the tensors it then owns, exactly."""
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    H, W, Cn, T = 37, 41, 5, 10
+    eng = GsmEngine(H, W, Cn, state_dtype=state_dtype)
+    try:
+        acc = posterior.PosteriorAccumulator(eng, T, 0, 1, split=split, rhat=rhat, hist=hist, ess=ess,
+                                             sample_cells=np.array([0, 5 * W + 7, H * W - 1]) if points else None)
+        held = {k: v for k, v in vars(acc).items() if isinstance(v, torch.Tensor)}
+        print(f"budget {acc.device_bytes} B; held {({k: v.nbytes for k, v in held.items()})}")
+        assert acc.device_bytes == sum(v.nbytes for v in held.values())
+        assert len({v.data_ptr() for v in held.values()}) == len(held)      # no tensor counted twice under two names
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("T", [9, 10])
 def test_conditioning_large_offset(T):
     """Beds 1e6 + N(0, 1): an unshifted sum of squares loses about u * 1e12 = 1e-4 of a variance of 1.  Expected maps from
