@@ -651,7 +651,28 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
  * Errors: GSM_E_ARG for a NULL beds, ring or lag_sqdiff, n_lags outside [1, 15], head outside [0, n_lags), n_valid outside
  * [0, n_lags], beds or ring not 16-byte aligned; nothing is written then.
  * Replaces: autocorrelations of bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
- * All seven are asynchronous on `stream`. */
+ *
+ * gsm_posterior_project and gsm_posterior_cross: the posterior covariance matrix C (H*W x H*W) applied to n_probes <= 15 weight
+ * fields ("probes") of the grid's shape, probes [dev, n_probes*H*W] fp64, probe-major: an indicator gives the covariance map with
+ * a point, a normalised mask that with a region mean, random fields the sketch of a low-rank factorisation.  With d_c[cell] =
+ * (double)bed_c[cell] - g[cell], g [dev, H*W] fp64 the common field:
+ *   project   proj[c*n_probes + k] = sum over the cells with probes[k][cell] != 0 of probes[k][cell] * d_c[cell]     (written)
+ *   cross     cross[k*H*W + cell] += sum_c d_c[cell] * proj[c*n_probes + k]                                          (ADDED to)
+ * proj [dev, n_chains*n_probes] fp64, chain-major; cross [dev, n_probes*H*W] fp64: zero it once, call project then cross once
+ * per snapshot with the same beds; sums of several handles (ranks) add.  With n values per cell in all, S1 = sum d and q_k = sum
+ * of proj over the same values, the covariance of cell and functional k is (cross_k - S1 q_k / n) / (n - 1).
+ * A cell with weight zero is skipped, not multiplied: a NaN bed outside a probe's support does not touch that probe, one inside
+ * it makes proj[c, k] NaN.  In cross a NaN d or a NaN proj makes the entries it enters NaN: a NaN bed its cell for every k, a NaN
+ * proj[c, k] the whole field k.  Differences, products and sums are fp64 with either state type; cross uses fused multiply-adds.
+ * No atomics: project sums a chain's cells in a fixed tree (lane, wave, workgroup, then the plane parts in part order); cross
+ * sums the chains in index order within a part of the chain axis and the parts in part order (a second kernel):
+ * bit-reproducible from run to run.  Bytes per chain-cell: project reads one state value from memory and (1 + n_probes) * 8 bytes
+ * of g and the probes, which every chain re-reads and which are expected to stay in the caches (7.5 MiB of probes at 256 x 256 x 15);
+ * cross reads one state value (8 bytes with fp64 state, 4 with fp32) and, per chain and wave, n_probes * 8 bytes of proj.
+ * Errors: GSM_E_ARG for a NULL pointer, n_probes outside [1, 15], beds not 16-byte aligned; GSM_E_UNSUPPORTED for project with
+ * more than 65535 chains; nothing is written then.
+ * Replaces: np.cov of bed_cache[burn_in::thin] of every chain of a pool against functionals of it (MCMC.py:1198, :1363).
+ * All nine are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -666,6 +687,10 @@ int gsm_posterior_histogram(gsm_handle h, const void* beds, const double* g, dou
                             int32_t n_levels, int32_t* counts, void* stream);
 int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, int32_t n_lags, int32_t head, int32_t n_valid,
                          double* lag_sqdiff, void* stream);
+int gsm_posterior_project(gsm_handle h, const void* beds, const double* g, const double* probes, int32_t n_probes,
+                          double* proj /* [dev, n_chains*n_probes], written */, void* stream);
+int gsm_posterior_cross(gsm_handle h, const void* beds, const double* g, const double* proj, int32_t n_probes,
+                        double* cross /* [dev, n_probes*H*W], ADDED to */, void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

@@ -595,7 +595,7 @@ def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
                                  sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
-                                 ess=opt['ess'])
+                                 ess=opt['ess'], cov=opt['cov'])
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -629,7 +629,13 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     the squared differences at the lags 1 .. max_lag to per-cell sums (summary.lag_sqdiff).  The summary then answers
     autocorrelation(), ess() -> (effective sample size of the M N values per cell, `truncated`: no negative Geyer pair up to
     max_lag, so ess is an upper bound: raise max_lag or thin) and mcse() = sd / sqrt(ess), the error bar of `mean`.  The chains
-    and every other map are bit-identical with and without it."""
+    and every other map are bit-identical with and without it.
+    posterior['cov']: None, or dict(probes=<[K, H, W] weight fields, K <= 15>, names=<K strings, optional>): the posterior
+    covariance matrix of the bed applied to the probes.  Every snapshot projects every chain's bed onto the probes and adds the
+    products with the bed to per-cell cross sums on the device (summary.probe_cross; summary.probe_values holds the functionals
+    themselves).  The summary then answers covariance(), correlation(), probe_stats() and sketch(); posterior.point_probes and
+    posterior.region_mean_probes build the usual probes.  Works with rhat=True and rhat=False.  The chains and every other map are
+    bit-identical with and without it."""
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     n_iter = _check_args(RF, n_iter, False, n_chains, (seeds,))

@@ -1,4 +1,5 @@
-// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip).  Every
+// C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip,
+// posterior_cov_kernel.hip).  Every
 // argument is validated here, once, where the error text is; the launchers take what they are given.
 #include "gsm_context.h"
 #include "posterior_device.h"
@@ -109,6 +110,47 @@ extern "C" int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, 
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_lagged(beds, ring, h->d_post_slab.get(), lag_sqdiff, plane, h->n_chains, parts, n_lags, head, n_valid, h->f32_state,
                                     h->n_cu, (hipStream_t)stream));
+  return GSM_OK;
+}
+
+// the slab of the two covariance passes, sized for the larger of them so that their alternating calls never reallocate it:
+// project holds n_chains * plane parts * n_probes partial projections, cross *parts x n_probes planes
+static int posterior_cov_slab(gsm_handle h, int n_probes, int* parts) {
+  int rc = posterior_device(h);
+  if (rc != GSM_OK) return rc;
+  const int64_t plane = (int64_t)h->H * h->W;
+  *parts = posterior_parts(posterior_cell_blocks(plane, posterior_vec(plane, h->f32_state)), h->n_chains, h->n_cu);
+  const size_t project = (size_t)h->n_chains * posterior_project_parts(plane, h->n_chains, h->n_cu) * n_probes;
+  HIPCHK(h, h->d_post_slab.ensure(std::max(project, (size_t)*parts * n_probes * plane)));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_project(gsm_handle h, const void* beds, const double* g, const double* probes, int32_t n_probes, double* proj,
+                                     void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !g || !probes || !proj) return fail(h, GSM_E_ARG, "gsm_posterior_project: NULL pointer");
+  if (n_probes < 1 || n_probes > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_project: n_probes must be in [1, 15]");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_project: beds must be 16-byte aligned");
+  if (h->n_chains > 65535) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_project: more than 65535 chains");
+  int parts = 1;
+  int rc = posterior_cov_slab(h, n_probes, &parts);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_project(beds, g, probes, h->d_post_slab.get(), proj, (int64_t)h->H * h->W, h->n_chains, n_probes, h->f32_state,
+                                     h->n_cu, (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_cross(gsm_handle h, const void* beds, const double* g, const double* proj, int32_t n_probes, double* cross,
+                                   void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !g || !proj || !cross) return fail(h, GSM_E_ARG, "gsm_posterior_cross: NULL pointer");
+  if (n_probes < 1 || n_probes > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_cross: n_probes must be in [1, 15]");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_cross: beds must be 16-byte aligned");
+  int parts = 1;
+  int rc = posterior_cov_slab(h, n_probes, &parts);
+  if (rc != GSM_OK) return rc;
+  HIPCHK(h, launch_posterior_cross(beds, g, proj, h->d_post_slab.get(), cross, (int64_t)h->H * h->W, h->n_chains, parts, n_probes, h->f32_state,
+                                   h->n_cu, (hipStream_t)stream));
   return GSM_OK;
 }
 

@@ -1,4 +1,4 @@
-// What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip) and what
+// What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip, posterior_cov_kernel.hip) and what
 // gsm_api_posterior.hip sizes the slab by: the workgroup size, the 16-byte pack, the cut of the chain axis into parts, the cells
 // per lane and the choice of a kernel's instantiation by state type and cells per lane.
 #pragma once
@@ -87,5 +87,15 @@ hipError_t launch_posterior_histogram(const void* beds, const double* g, double 
 // posterior_lag_kernel.hip
 hipError_t launch_posterior_lagged(const void* beds, void* ring, double* slab, double* lag_sqdiff, int64_t plane, int n_chains, int parts,
                                    int n_lags, int head, int n_valid, int f32_state, int n_cu, hipStream_t st);
+// posterior_cov_kernel.hip.  n_probes <= kLagMaxLags: the fields one PostOut / combine launch carries
+// cells per lane of the project kernel: 16 bytes of g and of every probe where the plane allows it, with either state type
+inline int posterior_project_vec(int64_t plane) { return plane % 2 == 0 ? 2 : 1; }
+// the most parts the project kernel cuts the plane into, so that parts * n_chains workgroups fill the CUs about eight times over;
+// its slab holds n_chains * parts * n_probes partial projections
+int posterior_project_parts(int64_t plane, int n_chains, int n_cu);
+hipError_t launch_posterior_project(const void* beds, const double* g, const double* probes, double* slab, double* proj, int64_t plane,
+                                    int n_chains, int n_probes, int f32_state, int n_cu, hipStream_t st);
+hipError_t launch_posterior_cross(const void* beds, const double* g, const double* proj, double* slab, double* cross, int64_t plane,
+                                  int n_chains, int parts, int n_probes, int f32_state, int n_cu, hipStream_t st);
 
 }  // namespace gsm

@@ -140,15 +140,18 @@ def _segment_label(prev, n_iter):
 
 def _merge_posterior(accum, local_sums, n_chains, base, label):
     """Sum this rank's additive posterior quantities (PosteriorAccumulator.local_sums) with the other ranks', integers as int64,
-    gather the sample traces, and let rank 0 write the summary."""
+    gather the sample traces and the projections, and let rank 0 write the summary."""
     import torch.distributed as dist
     sums = {k: (parallel.all_reduce_sum if v.is_floating_point() else parallel.all_reduce_counts)(v) for k, v in local_sums.items()}
     sv = None
     if accum.d_samples is not None:                # [T, local chains, points] on the device -> [n_chains, points, T]
         sv = parallel.all_gather_chains(accum.d_samples.permute(1, 2, 0).contiguous(), n_chains).cpu().numpy()
+    pv = None
+    if accum.d_proj is not None:                   # [T, local chains, probes] on the device -> [n_chains, probes, T]
+        pv = parallel.all_gather_chains(accum.d_proj.permute(1, 2, 0).contiguous(), n_chains).cpu().numpy()
     if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
         base.mkdir(parents=True, exist_ok=True)
-        accum.finalize(sample_values=sv, **sums).save(base / f'posterior_{label}.npz')
+        accum.finalize(sample_values=sv, projections=pv, **sums).save(base / f'posterior_{label}.npz')
 
 
 def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, n_workers,
@@ -275,13 +278,14 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     starts its own ranks (one fresh process per GPU, RCCL) -- the caller brings no launcher, like the reference's driver;
     under torchrun (or inside such a rank) the initialised group is used and this process runs its shard.
 
-    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`, `hist`, `ess`).  Philox mode with all
+    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`, `hist`, `ess`, `cov`).  Philox mode with all
     chains sharing n_iter and the Philox step only (any other combination is a ValueError).  Return value and per-seed
     checkpoint files are unchanged; rank 0 also writes <output_path>/LargeScaleChain/posterior_{k}k.npz (posterior.
     PosteriorSummary.load reads it; {k}k as in the first chain's bed_{k}k.npy) with the mean, sd and split-R-hat maps over the
     chains of ALL ranks (one all-reduce of [3, H, W]) and the traces at the template's sample points; with `hist` also the
     per-cell histogram and level counts of all chains (one int64 all-reduce of the counts); with `ess` also lag_sqdiff, the lagged
-    squared differences of all chains (one fp64 all-reduce of [max_lag, H, W]), behind the summary's ess().  The summary covers THIS
+    squared differences of all chains (one fp64 all-reduce of [max_lag, H, W]), behind the summary's ess(); with `cov` also the probes, probe_cross (one fp64 all-reduce of [K, H, W]) and
+    probe_values of all chains (gathered like the traces), behind the summary's covariance().  The summary covers THIS
     call's segment: iteration 0 is the bed the segment starts from, and accumulators are not carried across driver calls."""
     tic = time.time()
     mode = mode or getattr(largeScaleChain, 'rng_mode', 'replay')

@@ -260,6 +260,38 @@ class GsmEngine:
         self._check_sums(n_lags * self.H * self.W, lag_sqdiff=lag_sqdiff)
         self.call(self.lib.gsm_posterior_lagged, self.beds, ring, n_lags, int(head), int(n_valid), lag_sqdiff)
 
+    def _probe_count(self, n_probes):
+        n_probes = int(n_probes)
+        if not 1 <= n_probes <= 15:
+            raise ValueError(f"n_probes must be in [1, 15], got {n_probes}")
+        return n_probes
+
+    def posterior_project(self, g, probes, out):
+        """One snapshot of self.beds projected onto the K <= 15 weight fields probes [K, H, W] float64: out[c, k] = sum over the
+        cells with probes[k] != 0 of probes[k] * (bed_c - g); out [n_chains, K] float64 is written.  g [H, W] float64.  Asynchronous."""
+        self._need_beds()
+        self._check_sums(self.H * self.W, g=g)
+        if probes.dim() != 3 or tuple(probes.shape[1:]) != (self.H, self.W):
+            raise ValueError(f"probes must have shape [K, {self.H}, {self.W}], got {tuple(probes.shape)}")
+        K = self._probe_count(probes.shape[0])
+        self._check_sums(K * self.H * self.W, probes=probes)
+        if out.numel() != self.n_chains * K:
+            raise ValueError(f"out must hold n_chains x K = {self.n_chains * K} elements")
+        self._check_sums(self.n_chains * K, out=out)
+        self.call(self.lib.gsm_posterior_project, self.beds, g, probes, K, out)
+
+    def posterior_cross(self, g, proj, n_probes, cross):
+        """One snapshot of self.beds into the per-cell cross sums with the projections proj [n_chains, K] float64 of the same
+        snapshot (posterior_project): cross[k] += sum_c (bed_c - g) * proj[c, k]; cross [K, H, W] float64.  Asynchronous."""
+        self._need_beds()
+        K = self._probe_count(n_probes)
+        self._check_sums(self.H * self.W, g=g)
+        if proj.numel() != self.n_chains * K or cross.numel() != K * self.H * self.W:
+            raise ValueError(f"proj must hold n_chains x K = {self.n_chains * K} elements and cross K x H x W = {K * self.H * self.W}")
+        self._check_sums(self.n_chains * K, proj=proj)
+        self._check_sums(K * self.H * self.W, cross=cross)
+        self.call(self.lib.gsm_posterior_cross, self.beds, g, proj, K, cross)
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

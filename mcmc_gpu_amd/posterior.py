@@ -26,6 +26,14 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               rho_(2k+1), k = 0 .. (K - 1)/2; tau = -1 + 2 sum of the pairs before the first negative one, floored at
               1 / log10(M N); ess = M N / tau and mcse = sd / sqrt(ess).  A cell without a negative pair sums them all and is
               flagged `truncated`: its ess is an upper bound (raise max_lag or thin).  NaN where W == 0 and where the cell saw a NaN.
+  cov         optional covariance of every cell with K <= 15 linear functionals of the bed, f_k = sum over the support of Omega_k
+              of Omega_k * bed: the posterior covariance matrix applied to the weight fields ("probes") Omega [K, H, W].  Per
+              snapshot and chain, with d = bed - g, the device computes the projection p[c, k] = sum over the cells with Omega_k
+              != 0 of Omega_k * d (gsm_posterior_project; zero weights are skipped, so a NaN bed outside a probe's support does
+              not touch it) and adds d * p[c, k] to the cross sum Y [K, H, W] (gsm_posterior_cross) at the snapshots that belong
+              to a sequence; Y adds over ranks.  With n = M N, S1 = n (mean - g) and q_k = sum of p over the same values:
+              cov_k = (Y_k - S1 q_k / n) / (n - 1), pooled over all chains and snapshots, ddof=1.  probe_values[c, k, t] = f_k
+              of chain c at snapshot t (Omega_k . g over the support, summed on the host, plus p), for all T snapshots.
 """
 from __future__ import annotations
 
@@ -85,6 +93,77 @@ class PosteriorSummary:
     level_counts: np.ndarray | None = None
     # with ess=: lag_sqdiff [K, H, W] float64, S_t of the lags t = 1 .. K over all M sequences
     lag_sqdiff: np.ndarray | None = None
+    # with cov=: probes [K, H, W] float64 weight fields, probe_names K strings or None, probe_values [n_chains, K, T] the
+    # functionals at all T snapshots, probe_cross [K, H, W] the cross sums Y about probe_centre = g [H, W]
+    probes: np.ndarray | None = None
+    probe_names: tuple | None = None
+    probe_values: np.ndarray | None = None
+    probe_cross: np.ndarray | None = None
+    probe_centre: np.ndarray | None = None
+
+    def _need_cov(self):
+        if self.probes is None or self.probe_cross is None or self.probe_values is None:
+            raise ValueError("this summary holds no probes: run with posterior=dict(..., cov=dict(probes=...))")
+        return self.n_sequences * self.n_per_sequence
+
+    def _probe_sequences(self):
+        """[M, N, K] the functionals at the M N values that mean and sd describe: probe_values without the snapshots that split drops,
+        every chain cut into its sequences."""
+        v = np.asarray(self.probe_values, dtype=np.float64)
+        C, K, T = v.shape
+        N = self.n_per_sequence
+        n_seq = 2 if self.split else 1
+        return v[:, :, T - n_seq * N:].transpose(0, 2, 1).reshape(C * n_seq, N, K)
+
+    def covariance(self):
+        """[K, H, W] covariance of every cell with every functional over the M N values, ddof=1: (Y_k - S1 q_k / n) / (n - 1) with
+        S1 = n (mean - g) and q_k the sum of the projections.  NaN where `mean` is NaN and for a probe that saw a NaN."""
+        n = self._need_cov()
+        g = np.asarray(self.probe_centre, dtype=np.float64)
+        P = np.asarray(self.probes, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            off = np.array([(w[w != 0] * g[w != 0]).sum() for w in P])
+            q = np.array([math.fsum(v) for v in (self._probe_sequences().reshape(n, -1) - off).T])   # exactly rounded: no order to depend on
+            S1 = n * (np.asarray(self.mean, dtype=np.float64) - g)
+            cov = (np.asarray(self.probe_cross, dtype=np.float64) - S1[None] * q[:, None, None] / n) / (n - 1)
+        cov[:, np.isnan(self.mean)] = np.nan
+        return cov
+
+    def probe_stats(self):
+        """dict of host statistics of the functionals over the same M N values: mean [K], sd [K] (ddof=1), rhat [K] (split R-hat over
+        the summary's sequences, NaN where the within-sequence variance is 0 or there is one sequence) and cov [K, K], the ddof=1
+        covariance of the functionals with each other."""
+        n = self._need_cov()
+        s = self._probe_sequences()
+        M, N, K = s.shape
+        flat = s.reshape(n, K)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = flat.mean(axis=0)
+            dev = flat - mean
+            cov = dev.T @ dev / (n - 1)
+            mu = s.mean(axis=1)
+            v = np.where((s == s[:, :1]).all(axis=1), 0.0, s.var(axis=1, ddof=1))
+            W = v.mean(axis=0)
+            B_over_N = mu.var(axis=0, ddof=1) if M > 1 else np.full(K, np.nan)
+            rhat = np.where(W == 0, np.nan, np.sqrt(((N - 1) / N * W + B_over_N) / W))
+        return dict(mean=mean, sd=np.sqrt(np.diagonal(cov)), rhat=rhat, cov=cov)
+
+    def correlation(self):
+        """[K, H, W] covariance() / (sd of the cell * sd of the functional).  NaN where either sd is 0."""
+        cov = self.covariance()
+        sd = np.asarray(self.sd, dtype=np.float64)
+        sd_f = self.probe_stats()["sd"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rho = cov / (sd[None] * sd_f[:, None, None])
+        rho[:, sd == 0] = np.nan
+        rho[sd_f == 0] = np.nan
+        return rho
+
+    def sketch(self):
+        """(probes [K, H, W], covariance() [K, H, W]) = (Omega, (C Omega^T)^T): the pair a randomized low-rank factorisation of the
+        posterior covariance matrix C consumes (range finder: an orthonormal basis of the columns of C Omega^T; with Gaussian
+        probes its span approaches that of the leading eigenvectors of C).  The factorisation itself is not part of this class."""
+        return np.asarray(self.probes, dtype=np.float64), self.covariance()
 
     def _need_hist(self):
         if self.hist_counts is None:
@@ -173,6 +252,8 @@ class PosteriorSummary:
         kw["split"] = bool(kw["split"])
         if kw["hist_half_width"] is not None:
             kw["hist_half_width"] = float(kw["hist_half_width"])
+        if kw["probe_names"] is not None:
+            kw["probe_names"] = tuple(str(v) for v in kw["probe_names"])
         return cls(**kw)
 
 
@@ -241,6 +322,70 @@ def check_ess(ess, N=None, rhat=True):
     return dict(max_lag=int(K))
 
 
+COV_KEYS = ("probes", "names")
+COV_MAX_PROBES = 15
+
+
+def check_cov(cov, H=None, W=None):
+    """Validate the `cov` option: None, or dict(probes=<[K, H, W] or [H, W] finite floats>, names=<K strings, optional>) with 1 <= K
+    <= 15 and at least one non-zero weight in every probe.  Returns None or dict(probes=<[K, h, w] float64, contiguous>, names=<tuple
+    of K str, or None>); with H and W given the probes must have the grid's shape."""
+    if cov is None:
+        return None
+    if not isinstance(cov, dict):
+        raise ValueError("cov must be None or a dict with the key probes and optionally names")
+    unknown = set(cov) - set(COV_KEYS)
+    if unknown:
+        raise ValueError(f"unknown cov option(s) {sorted(unknown)}; the options are {COV_KEYS}")
+    if "probes" not in cov:
+        raise ValueError("cov needs probes: an array [K, H, W] of weight fields")
+    try:
+        P = np.array(cov["probes"], dtype=np.float64, order="C")
+    except (TypeError, ValueError):
+        raise ValueError("cov probes must be an array of numbers of shape [K, H, W] or [H, W]") from None
+    if P.ndim == 2:
+        P = P[None]
+    if P.ndim != 3 or 0 in P.shape:
+        raise ValueError(f"cov probes must have shape [K, H, W] or [H, W] with K >= 1, got {P.shape}")
+    if H is not None and P.shape[1:] != (int(H), int(W)):
+        raise ValueError(f"cov probes of shape {P.shape}, the grid is {(int(H), int(W))}")
+    K = P.shape[0]
+    if K > COV_MAX_PROBES:
+        raise ValueError(f"cov takes at most {COV_MAX_PROBES} probes, got {K}")
+    if not np.isfinite(P).all():
+        raise ValueError("cov probes must be finite")
+    if not (P != 0).any(axis=(1, 2)).all():
+        raise ValueError("every cov probe needs at least one non-zero weight")
+    names = cov.get("names")
+    if names is not None:
+        if isinstance(names, str) or not all(isinstance(v, str) for v in names) or len(names) != K:
+            raise ValueError(f"cov names must be a sequence of {K} strings, one per probe")
+        names = tuple(names)
+    return dict(probes=P, names=names)
+
+
+def point_probes(H, W, cells):
+    """[K, H, W] indicator probes at the flat cell indices `cells` (row * W + col): the covariance and correlation maps with
+    those points."""
+    cells = np.asarray(cells, dtype=np.int64).ravel()
+    if cells.size == 0 or (cells < 0).any() or (cells >= int(H) * int(W)).any():
+        raise ValueError("point_probes: cell outside the grid")
+    P = np.zeros((cells.size, int(H) * int(W)))
+    P[np.arange(cells.size), cells] = 1.0
+    return P.reshape(cells.size, int(H), int(W))
+
+
+def region_mean_probes(masks):
+    """[K, H, W] probes of region means: each mask of `masks` ([K, H, W] or [H, W], non-zero = inside) divided by its cell count."""
+    m = np.asarray(masks) != 0
+    if m.ndim == 2:
+        m = m[None]
+    count = m.sum(axis=(1, 2)) if m.ndim == 3 else np.zeros(1)
+    if m.ndim != 3 or (count == 0).any():
+        raise ValueError("region_mean_probes: masks must be [K, H, W] or [H, W] with at least one cell inside each")
+    return m / count[:, None, None].astype(np.float64)
+
+
 HIST_KEYS = ("bins", "half_width", "levels")
 HIST_MAX_BINS, HIST_MAX_LEVELS = 128, 8
 HIST_MAX_COUNT = 2 ** 31 - 1
@@ -303,10 +448,13 @@ class PosteriorAccumulator:
     to which add() adds the histogram of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_counts).
     ess (see check_ess): also `ring` [K, n_chains, H * W] in the state dtype, every chain's last K snapshots of the sequence being
     filled, and `lag_sqdiff` [K, H, W] float64, to which add() adds the squared differences at the lags 1 .. K (sum it over ranks
-    with all_reduce_sum).  The ring is released with the last snapshot."""
+    with all_reduce_sum).  The ring is released with the last snapshot.
+    cov (see check_cov): also, all float64, `d_probes` [K, H, W], `d_proj` [T, n_chains, K], the projections of all T snapshots, and
+    `probe_cross` [K, H, W], to which add() adds the cross sums of every snapshot that belongs to a sequence (sum it over ranks
+    with all_reduce_sum; gather d_proj over ranks like the sample traces)."""
 
     def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None,
-                 ess=None):
+                 ess=None, cov=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -321,6 +469,8 @@ class PosteriorAccumulator:
             self.hist_slots = self.hist["bins"] + 3 + len(self.hist["levels"])
         self.ess = check_ess(ess, self.N, self.rhat)
         self.n_lags = 0 if self.ess is None else self.ess["max_lag"]
+        self.cov = check_cov(cov, H, W)
+        self.n_probes = 0 if self.cov is None else int(self.cov["probes"].shape[0])
         # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
         g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
         if g.shape != (H, W) or not np.isfinite(g).all():
@@ -345,17 +495,23 @@ class PosteriorAccumulator:
             table += [("hist_counts", (self.hist_slots, H, W), torch.int32, True)]
         if self.n_lags:
             table += [("ring", (self.n_lags, n, H * W), sd, False), ("lag_sqdiff", (self.n_lags, H, W), f64, True)]
+        if self.n_probes:
+            table += [("d_probes", (self.n_probes, H, W), f64, False), ("d_proj", (self.T, n, self.n_probes), f64, False),
+                      ("probe_cross", (self.n_probes, H, W), f64, True)]
         self.device_bytes = need = sum(math.prod(shape) * dtype.itemsize for _, shape, dtype, _ in table)
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
                               f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
         self.ref = self.d_cells = self.d_samples = self.hist_counts = self.ring = self.lag_sqdiff = None
+        self.d_probes = self.d_proj = self.probe_cross = None
         for name, shape, dtype, zeroed in table:
             setattr(self, name, (torch.zeros if zeroed else torch.empty)(shape, dtype=dtype, device=eng.dev))
         self.d_g.copy_(torch.as_tensor(g))
         if self.n_samples:
             self.d_cells.copy_(torch.as_tensor(cells))
+        if self.n_probes:
+            self.d_probes.copy_(torch.as_tensor(self.cov["probes"]))
         self.ring_head = self.ring_valid = 0
         self.n_added = 0
         self._partials = None
@@ -394,6 +550,10 @@ class PosteriorAccumulator:
             eng.posterior_accumulate_pooled(self.d_g, self.s1, self.s2, self.d_cells, smp)
         if self.hist is not None and t >= self.dropped:      # the values that mean and sd describe, each counted once
             eng.posterior_histogram(self.d_g, self.hist_inv_w, self.hist["bins"], self.hist["levels"], self.hist_counts)
+        if self.n_probes:                  # the projections of every snapshot, the cross sums of those that mean and sd describe
+            eng.posterior_project(self.d_g, self.d_probes, self.d_proj[t])
+            if t >= self.dropped:
+                eng.posterior_cross(self.d_g, self.d_proj[t], self.n_probes, self.probe_cross)
         self.n_added += 1
         self._partials = None
 
@@ -416,22 +576,28 @@ class PosteriorAccumulator:
 
     def local_sums(self):
         """Everything of this accumulator that adds over ranks, as device tensors under the names finalize() takes the sums by:
-        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts and lag_sqdiff."""
+        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts, lag_sqdiff and probe_cross."""
         import torch
         out = dict(partials_sum=self.partials(), M=torch.tensor([self.n_sequences], dtype=torch.int64, device=self.d_g.device))
         if self.hist is not None:
             out["hist_counts"] = self.hist_counts
         if self.n_lags:
             out["lag_sqdiff"] = self.lag_sqdiff
+        if self.n_probes:
+            out["probe_cross"] = self.probe_cross
         return out
 
     def sample_values(self):
         """[n_chains, n_points, T] numpy array of the traces, or None."""
         return None if self.d_samples is None else np.ascontiguousarray(self.d_samples.permute(1, 2, 0).cpu().numpy())
 
-    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None):
+    def projections(self):
+        """[n_chains, K, T] numpy array of the projections p of all snapshots, or None."""
+        return None if self.d_proj is None else np.ascontiguousarray(self.d_proj.permute(1, 2, 0).cpu().numpy())
+
+    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None, probe_cross=None, projections=None):
         """PosteriorSummary from the sums of local_sums() added over ranks (all_reduce_posterior, all_reduce_counts, all_reduce_sum);
-        each defaults to this accumulator's own."""
+        each defaults to this accumulator's own.  projections: [n_chains, K, T] of all ranks' chains (projections(), gathered)."""
         self._require_complete()
         if partials_sum is None:
             partials_sum, M = self.partials(), self.n_sequences
@@ -445,27 +611,36 @@ class PosteriorAccumulator:
                         level_values=np.asarray(self.hist["levels"], dtype=np.float64), level_counts=hc[B + 3:].copy())
         if self.n_lags:
             meta["lag_sqdiff"] = _host_array(self.lag_sqdiff if lag_sqdiff is None else lag_sqdiff, (self.n_lags,) + grid, np.float64, "lagged sums")
+        if self.n_probes:
+            P, g = self.cov["probes"], self.common_ref
+            p = _host_array(self.projections() if projections is None else projections, (M // self.n_seq, self.n_probes, self.T), np.float64,
+                            "projections")
+            off = np.array([(w[w != 0] * g[w != 0]).sum() for w in P])           # Omega_k . g over the support
+            meta.update(probes=P.copy(), probe_names=self.cov["names"], probe_values=off[None, :, None] + p, probe_centre=g.copy(),
+                        probe_cross=_host_array(self.probe_cross if probe_cross is None else probe_cross, (self.n_probes,) + grid, np.float64,
+                                                "cross sums"))
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov")
 
 
 def check_options(posterior, n_iter, n_chains=None):
     """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
     n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None)
     opt.update(posterior)
     _, N, _ = sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
     opt["ess"] = check_ess(opt["ess"], N, opt["rhat"])
     opt["hist"] = check_hist(opt["hist"])
+    opt["cov"] = check_cov(opt["cov"])
     if opt["hist"] is not None and n_chains is not None:
         check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])
     return opt

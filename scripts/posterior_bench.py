@@ -14,8 +14,15 @@
               full: time per snapshot beside gsm_debug_stream_copy moving the same bytes, (K + 2) state values per chain-cell
               (K + 1 read, 1 written), and beside the pooled pass and ITS stream copy, all timed in the same process; then the
               wall time of MCMC_gpu.run_many without `posterior`, with it, and with `ess` (7 and 15 lags) at thin=100.
+  --cov K     only the two covariance passes (gsm_posterior_project, gsm_posterior_cross) with K probes at 1024 chains of 256 x 256,
+              fp64 and fp32 state: time per snapshot of each beside gsm_debug_stream_copy moving the same bytes and beside the
+              pooled pass and ITS stream copy, all timed in the same process; then the wall time of MCMC_gpu.run_many without
+              `posterior`, with it, and with `cov` (K Gaussian probes) at thin=100.  Counted bytes.  project: the beds, and g and
+              the probes once (every chain re-reads them from the caches: `cache_bytes` is that traffic).  cross: the beds, every
+              part's [K, H, W] slab written and read back, `cross` read and written, and the projections.  The default --out is
+              profiles/posterior_bench_cov.json.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess]
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K]
 """
 import argparse
 import json
@@ -189,13 +196,78 @@ def ess_rows(n_chains, H, W, state, lags, reps):
     return rows
 
 
-def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None):
+def cov_rows(n_chains, H, W, state, K, reps):
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd.engine import GsmEngine
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        dev, plane, sb = eng.dev, H * W, 8 if state == "f64" else 4
+        n = n_chains * plane
+        eng.beds = (1000.0 + torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+        def copy_row(nbytes, label):
+            m = nbytes // 16                                   # doubles: 8 B read + 8 B written each
+            src = torch.ones(m, dtype=torch.float64, device=dev)
+            dst = torch.empty(m, dtype=torch.float64, device=dev)
+            r = _rate(label, 16 * m, _timed(lambda: eng._check(eng.lib.gsm_debug_stream_copy(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st)), reps))
+            del src, dst
+            return r
+
+        def share(row, cp):
+            row["ms_per_snapshot"] = row["ms_median"]
+            row["fraction_of_copy"] = row["TB_per_s_median"] / cp["TB_per_s_median"]
+            row["fraction_of_copy_range"] = [row["TB_per_s_range"][0] / cp["TB_per_s_median"], row["TB_per_s_range"][1] / cp["TB_per_s_median"]]
+
+        g = torch.full((H, W), 1000.0, dtype=torch.float64, device=dev)
+        p1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        po = _rate(f"pooled accumulate {shape}", sb * n, _timed(lambda: eng.posterior_accumulate_pooled(g, p1, p2), reps))
+        cp = copy_row(sb * n, f"stream copy of the pooled form's bytes ({shape})")
+        share(po, cp)
+        rows += [po, cp]
+        probes = torch.randn((K, H, W), dtype=torch.float64, device=dev)
+        proj = torch.empty((n_chains, K), dtype=torch.float64, device=dev)
+        cross = torch.zeros((K, H, W), dtype=torch.float64, device=dev)
+        pj_bytes = sb * n + (K + 1) * 8 * plane + 8 * n_chains * K
+        pj = _rate(f"project pass {K} probes {shape}", pj_bytes, _timed(lambda: eng.posterior_project(g, probes, proj), reps))
+        cpj = copy_row(pj_bytes, f"stream copy of the project pass's bytes ({K} probes, {shape})")
+        share(pj, cpj)
+        pj["cache_bytes"] = (K + 1) * 8 * n                    # g and the probes, re-read by every chain
+        pj["cache_TB_per_s_median"] = (pj["cache_bytes"] + sb * n) / pj["ms_median"] / 1e9
+        vec = (4 if plane % 4 == 0 else 2 if plane % 2 == 0 else 1) if sb == 4 else (2 if plane % 2 == 0 else 1)
+        cell_blocks = (plane // vec + 255) // 256
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        parts = max(1, min(-(-4 * n_cu // cell_blocks), n_chains))           # the rule of posterior_parts (posterior_device.h)
+        cr_bytes = sb * n + 2 * parts * K * plane * 8 + 2 * K * plane * 8 + 8 * n_chains * K
+        cr = _rate(f"cross pass {K} probes {shape}", cr_bytes, _timed(lambda: eng.posterior_cross(g, proj, K, cross), reps))
+        ccr = copy_row(cr_bytes, f"stream copy of the cross pass's bytes ({K} probes, {shape})")
+        share(cr, ccr)
+        cr["parts"], cr["bed_bytes"] = parts, sb * n
+        cr["bed_bytes_fraction_of_pooled_copy"] = (sb * n / cr["ms_median"] / 1e9) / cp["TB_per_s_median"]
+        cr["sums_check"] = bool(torch.isfinite(cross).all().item())
+        rows += [pj, cpj, cr, ccr]
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
     prob, ch, rf = synthetic.template(H)
     beds = synthetic.initial_beds(prob, n_chains)
     seeds = list(range(1000, 1000 + n_chains))
-    if ess_lags is None:
+    if cov_probes is not None:
+        P = np.random.default_rng(0).normal(size=(cov_probes, H, H))
+        configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
+                  [(f"thin={t} rhat=True cov {cov_probes} probes", dict(burn_in=0, thin=t, cov=dict(probes=P))) for t in thins]
+    elif ess_lags is None:
         configs = [("no posterior", None)] + [(f"thin={t} rhat={r}", dict(burn_in=0, thin=t, rhat=r)) for t in thins for r in (True, False)]
     else:
         configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
@@ -245,13 +317,24 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--hist", action="store_true", help="only the histogram pass beside the pooled pass and the stream copy")
     ap.add_argument("--ess", action="store_true", help="only the lagged pass beside its stream copy, and run_many with and without ess")
+    ap.add_argument("--cov", type=int, default=0, metavar="K", help="only the two covariance passes with K probes beside their stream copies, "
+                    "and run_many with and without cov")
     args = ap.parse_args()
+    if args.cov and not 1 <= args.cov <= 15:
+        raise SystemExit("--cov takes 1 .. 15 probes")
+    if args.cov and args.out is None and not args.quick:
+        args.out = str(ROOT / "profiles" / "posterior_bench_cov.json")
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
     rows = []
     if args.hist:
         for state in ("f64", "f32"):
             rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
+    elif args.cov:
+        for state in ("f64", "f32"):
+            rows += cov_rows(8, 64, 64, state, args.cov, 3) if args.quick else cov_rows(1024, 256, 256, state, args.cov, max(args.reps, 20))
+        rows += end_to_end_rows(64, 8, 1701, [100], 1, cov_probes=args.cov) if args.quick else \
+            end_to_end_rows(256, 1024, 20001, [100], args.repeats, cov_probes=args.cov)
     elif args.ess:
         for state in ("f64", "f32"):
             rows += ess_rows(8, 64, 64, state, (7, 15), 3) if args.quick else ess_rows(1024, 256, 256, state, (7, 15), max(args.reps, 20))
