@@ -353,7 +353,8 @@ int gsm_sgs_loss(gsm_handle h, const double* beds, const double* trend, double* 
 
 /* The Metropolis decision of one small-scale iteration on the device, so that a batch of iterations needs no host round
  * trip: loss_next[c] (set to +inf where bad[c] > 0), p = 1 if loss_prev[c] > loss_next[c] else min(1, exp(loss_prev[c] -
- * loss_next[c])) (a NaN stays a rejection, as with numpy.minimum), accept[c] = u[c] <= p; an accepted chain's loss_prev[c]
+ * loss_next[c])) (a NaN exponential -- a NaN loss, or inf - inf -- gives p = 1 as the reference's built-in min(1, nan) does,
+ * and as the large-scale step's fmin), accept[c] = u[c] <= p; an accepted chain's loss_prev[c]
  * becomes loss_next[c].  loss_rec[c * rec_stride] = loss_prev[c] after the decision and acc_rec[c * rec_stride] =
  * accept[c] (the iteration's column of the caller's [n_chains][rec_stride] record arrays; either may be NULL).  All [dev].
  * Replaces: chain_sgs.run's acceptance test (MCMC.py:1797-1812). */

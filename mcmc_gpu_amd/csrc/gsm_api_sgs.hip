@@ -380,6 +380,7 @@ extern "C" int gsm_sgs_finish(gsm_handle h, double* cur, double* next, const dou
                               uint8_t* acc_rec, int64_t rec_stride, void* stream) {
   if (!h) return GSM_E_ARG;
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_sgs_finish: call gsm_set_static first");
+  if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_finish: fp64 beds only");
   if (!cur || !next || !energy || !state || !windows || !u || !resampled || !accept) return fail(h, GSM_E_ARG, "gsm_sgs_finish: NULL pointer");
   if ((loss_rec || acc_rec) && rec_stride < 1) return fail(h, GSM_E_ARG, "gsm_sgs_finish: rec_stride must be >= 1");
   HIPCHK(h, hipSetDevice(h->device));

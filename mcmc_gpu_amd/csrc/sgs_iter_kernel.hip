@@ -25,11 +25,12 @@ struct BlockWin {
   // cell p of the window (row-major) as an index of the chain's map
   __device__ __forceinline__ size_t flat(int p) const { const int ww = c1 - c0; return (size_t)(r0 + p / ww) * W + c0 + p % ww; }
 };
-// the Metropolis test (MCMC.py:1797-1801): a smaller loss is taken, another with probability min(1, exp(loss_prev - loss_next))
+// the Metropolis test (MCMC.py:1797-1801): a smaller loss is taken, another with probability min(1, exp(loss_prev - loss_next)),
+// Python's built-in min as the reference calls it: a NaN exponential gives 1 (step_common.h decides the large-scale step likewise)
 __device__ __forceinline__ bool metropolis_accept(double lp, double ln, double u) {       // lp, ln: the loss of the state and of the proposal
   if (lp > ln) return true;
   const double p = exp(lp - ln);
-  return u <= ((p > 1.0) ? 1.0 : p);        // p NaN: the comparison is false (numpy.minimum propagates the NaN)
+  return u <= fmin(1.0, p);                 // p NaN (a NaN loss, or inf - inf): Python's min(1, nan) is 1, the reference accepts
 }
 // the squared residual of cell g = (r, c) as it enters the loss: 0 where mc_mask != 1 or the residual is NaN (nansum)
 template <class BedAt>
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, d
                                                          double* state, const int32_t* win, const double* u, uint32_t* resampled,
                                                          uint8_t* accept, double* loss_rec, uint8_t* acc_rec, int64_t rec_stride, int32_t* err) {
   __shared__ double e_new[kSgsHaloMax];
-  __shared__ double red[8];
+  __shared__ double red[16];
   __shared__ int redb[8];
   __shared__ int acc_s;
   const int chain = blockIdx.x, tid = threadIdx.x;
@@ -191,14 +192,17 @@ __global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, d
   }
   const double* nb = next + base;
   auto next_at = [&](int rr, int cc) { const int q = rr * W + cc; return trend ? nb[q] + trend[q] : nb[q]; };
-  double s_old = 0.0, s_new = 0.0;
+  // the halo's old and new sums as compensated pairs, like the carried sum they update: a plain sum here would leave its rounding
+  // (up to the halo's share of the whole sum) in the carried pair at every accepted iteration, and those add up over a run
+  double s_old = 0.0, l_old = 0.0, s_new = 0.0, l_new = 0.0;
   int bad_old = 0, bad_new = 0;
   for (int p = tid; p < hn; p += 256) {
     const int r = hr0 + p / hww, c = hc0 + p % hww, g = r * W + c;
     const double e = cell_energy(S, g, r, c, next_at);
     e_new[p] = e;
-    s_new += e;
-    s_old += energy[base + g];
+    double sm, er;
+    dev::two_sum(s_new, e, sm, er); s_new = sm; l_new += er;
+    dev::two_sum(s_old, energy[base + g], sm, er); s_old = sm; l_old += er;
     if (bw.holds(r, c) && S.upd[g] == 1) {
       const double t = trend ? trend[g] : 0.0;
       bad_new += (S.surf[g] - next_at(r, c)) <= 0.0;
@@ -207,18 +211,26 @@ __global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, d
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    s_old += __shfl_xor(s_old, off, 64); s_new += __shfl_xor(s_new, off, 64);
+    const double oso = __shfl_xor(s_old, off, 64), olo = __shfl_xor(l_old, off, 64), osn = __shfl_xor(s_new, off, 64), oln = __shfl_xor(l_new, off, 64);
+    double sm, er;
+    dev::two_sum(s_old, oso, sm, er); s_old = sm; l_old += olo + er;
+    dev::two_sum(s_new, osn, sm, er); s_new = sm; l_new += oln + er;
     bad_old += __shfl_xor(bad_old, off, 64); bad_new += __shfl_xor(bad_new, off, 64);
   }
-  if ((tid & 63) == 0) { red[2 * (tid >> 6)] = s_old; red[2 * (tid >> 6) + 1] = s_new; redb[2 * (tid >> 6)] = bad_old; redb[2 * (tid >> 6) + 1] = bad_new; }
+  if ((tid & 63) == 0) {
+    const int w = tid >> 6;
+    red[4 * w] = s_old; red[4 * w + 1] = l_old; red[4 * w + 2] = s_new; red[4 * w + 3] = l_new;
+    redb[2 * w] = bad_old; redb[2 * w + 1] = bad_new;
+  }
   __syncthreads();
   if (tid == 0) {
-    const double so = ((red[0] + red[2]) + red[4]) + red[6], sn = ((red[1] + red[3]) + red[5]) + red[7];
     const int bo = redb[0] + redb[2] + redb[4] + redb[6], bn = redb[1] + redb[3] + redb[5] + redb[7];
     double hi = state[4 * chain], lo = state[4 * chain + 1];
     double sm, er;
-    dev::two_sum(hi, -so, sm, er); hi = sm; lo += er;
-    dev::two_sum(hi, sn, sm, er); hi = sm; lo += er;
+    for (int w = 0; w < 4; ++w) {                               // minus the halo's old energies, plus its new ones
+      dev::two_sum(hi, -red[4 * w], sm, er); hi = sm; lo += er - red[4 * w + 1];
+      dev::two_sum(hi, red[4 * w + 2], sm, er); hi = sm; lo += er + red[4 * w + 3];
+    }
     dev::two_sum(hi, lo, sm, er); hi = sm; lo = er;
     const double bad_next = state[4 * chain + 3] - (double)bo + (double)bn;
     const double lp = state[4 * chain + 2];

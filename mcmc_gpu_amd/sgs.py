@@ -714,7 +714,8 @@ class _SgsRun:
             loss_next, bad = score_proposal(st)
             loss_next = np.where(bad > 0, np.inf, loss_next)
             with np.errstate(over='ignore', invalid='ignore'):
-                p_acc = np.where(self.loss_prev > loss_next, 1.0, np.minimum(1.0, np.exp(self.loss_prev - loss_next)))
+                # np.fmin: a NaN exponential gives 1, as the reference's built-in min(1, nan) and the device's decision
+                p_acc = np.where(self.loss_prev > loss_next, 1.0, np.fmin(1.0, np.exp(self.loss_prev - loss_next)))
             acc = us <= p_acc
             commit(d, wins, acc, torch.as_tensor(acc.astype(np.uint8)).to(self.dev), st)
             self.loss_prev = np.where(acc, loss_next, self.loss_prev)
