@@ -673,7 +673,27 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
  * Errors: GSM_E_ARG for a NULL pointer, n_probes outside [1, 15], beds not 16-byte aligned; GSM_E_UNSUPPORTED for project with
  * more than 65535 chains; nothing is written then.
  * Replaces: np.cov of bed_cache[burn_in::thin] of every chain of a pool against functionals of it (MCMC.py:1198, :1363).
- * All nine are asynchronous on `stream`. */
+ *
+ * gsm_posterior_residual: one snapshot into per-cell sums of the mass-conservation residual over ALL chains -- where the ensemble
+ * fails to meet mass conservation, by how much, and how much of that the chains agree on.  For every chain c, r_c is the residual
+ * of (double)bed_c from the static fields and the resolution of gsm_set_static, np.gradient differences, one-sided at the four
+ * borders: the value, bit for bit, that gsm_residual writes for the same bed.  sums [dev, (3 + n_levels)*H*W] fp64, plane-major,
+ * is ADDED to: zero it once, call once per snapshot; sums of several handles (ranks) add.  Per cell, over the chains whose r_c is
+ * finite (a NaN or an infinity is skipped: the loss's nansum, MCMC.py:1041) and with d = r_c - rg[cell], rg [dev, H*W] fp64 any
+ * finite field (a shift that keeps S2 - S1^2 / cnt free of cancellation against the residual's magnitude):
+ *   plane 0   cnt += the number of those chains          plane 1   S1 += sum d          plane 2   S2 += sum d*d
+ *   plane 3 + l   A_l += the number of them with |r_c| > levels[l]   (a NaN compares false)
+ * levels [host, n_levels], 0 <= n_levels <= 4, finite and >= 0, in the residual's unit, read during the call.  The counts are
+ * exact integers in fp64.  One pass: the stencil and the sums in one kernel, no per-chain residual is stored; each bed value is
+ * read by its own lane and as the neighbour of four others, from memory about once (8 bytes per chain-cell with fp64 state, 4
+ * with fp32, plus the halo of a workgroup's tile).  Differences, products and sums are fp64 with either state type, without
+ * fused multiply-adds.  No atomics: chains are summed in index order within a part of the chain axis and the parts in part order
+ * (a second kernel): bit-reproducible from run to run.
+ * Errors: GSM_E_ARG for a NULL beds, rg or sums, n_levels outside [0, 4], NULL levels with n_levels > 0, a level that is negative
+ * or not finite, beds not 16-byte aligned; GSM_E_STATE before gsm_set_static; nothing is written then.
+ * Replaces: Topography.get_mass_conservation_residual (Topography.py:592-612) over bed_cache[burn_in::thin] of every chain of a
+ * pool, and the statistics of that stack.
+ * All ten are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -692,6 +712,8 @@ int gsm_posterior_project(gsm_handle h, const void* beds, const double* g, const
                           double* proj /* [dev, n_chains*n_probes], written */, void* stream);
 int gsm_posterior_cross(gsm_handle h, const void* beds, const double* g, const double* proj, int32_t n_probes,
                         double* cross /* [dev, n_probes*H*W], ADDED to */, void* stream);
+int gsm_posterior_residual(gsm_handle h, const void* beds, const double* rg, const double* levels, int32_t n_levels,
+                           double* sums /* [dev, (3+n_levels)*H*W], ADDED to */, void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

@@ -595,7 +595,7 @@ def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
                                  sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
-                                 ess=opt['ess'], cov=opt['cov'])
+                                 ess=opt['ess'], cov=opt['cov'], residual=opt['residual'])
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -635,7 +635,13 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     products with the bed to per-cell cross sums on the device (summary.probe_cross; summary.probe_values holds the functionals
     themselves).  The summary then answers covariance(), correlation(), probe_stats() and sketch(); posterior.point_probes and
     posterior.region_mean_probes build the usual probes.  Works with rhat=True and rhat=False.  The chains and every other map are
-    bit-identical with and without it."""
+    bit-identical with and without it.
+    posterior['residual']: None, True or dict(levels=(l1, ...)) (up to 4 finite thresholds >= 0 on |r|): maps of the
+    mass-conservation residual r, the quantity the chains are scored on, over the same values.  Every snapshot that the moments use
+    evaluates every chain's residual (gsm_residual's bits) and adds per-cell sums on the device in one pass, no per-chain residual
+    is stored (summary.residual_sums).  The summary then answers residual_mean(), residual_sd(), residual_rms(), residual_count(),
+    prob_residual_above(level) (exact), loss_density() and expected_loss(), the mean of the chains' loss over those states.  Works
+    with rhat=True and rhat=False and beside hist, ess and cov.  The chains and every other map are bit-identical with and without it."""
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     n_iter = _check_args(RF, n_iter, False, n_chains, (seeds,))

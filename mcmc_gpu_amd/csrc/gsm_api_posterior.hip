@@ -1,5 +1,5 @@
 // C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip,
-// posterior_cov_kernel.hip).  Every
+// posterior_cov_kernel.hip, posterior_residual_kernel.hip).  Every
 // argument is validated here, once, where the error text is; the launchers take what they are given.
 #include "gsm_context.h"
 #include "posterior_device.h"
@@ -151,6 +151,25 @@ extern "C" int gsm_posterior_cross(gsm_handle h, const void* beds, const double*
   if (rc != GSM_OK) return rc;
   HIPCHK(h, launch_posterior_cross(beds, g, proj, h->d_post_slab.get(), cross, (int64_t)h->H * h->W, h->n_chains, parts, n_probes, h->f32_state,
                                    h->n_cu, (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_residual(gsm_handle h, const void* beds, const double* rg, const double* levels, int32_t n_levels,
+                                      double* sums, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !rg || !sums) return fail(h, GSM_E_ARG, "gsm_posterior_residual: NULL pointer");
+  if (n_levels < 0 || n_levels > kResMaxLevels) return fail(h, GSM_E_ARG, "gsm_posterior_residual: n_levels must be in [0, 4]");
+  if (n_levels > 0 && !levels) return fail(h, GSM_E_ARG, "gsm_posterior_residual: NULL levels with n_levels > 0");
+  for (int l = 0; l < n_levels; ++l)
+    if (!(levels[l] >= 0.0) || !std::isfinite(levels[l])) return fail(h, GSM_E_ARG, "gsm_posterior_residual: levels must be finite and >= 0");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_residual: beds must be 16-byte aligned");
+  if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_posterior_residual: call gsm_set_static first");
+  int rc = posterior_device(h);
+  if (rc != GSM_OK) return rc;
+  const int parts = posterior_residual_parts(posterior_residual_tile(h->H, h->W, h->f32_state), h->n_chains, h->n_cu);
+  HIPCHK(h, h->d_post_slab.ensure((size_t)parts * (3 + n_levels) * h->H * h->W));
+  HIPCHK(h, launch_posterior_residual(h->S, beds, rg, levels, n_levels, h->d_post_slab.get(), sums, h->n_chains, parts, h->f32_state, h->n_cu,
+                                      (hipStream_t)stream));
   return GSM_OK;
 }
 

@@ -1,4 +1,5 @@
-// What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip, posterior_cov_kernel.hip) and what
+// What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip, posterior_cov_kernel.hip,
+// posterior_residual_kernel.hip) and what
 // gsm_api_posterior.hip sizes the slab by: the workgroup size, the 16-byte pack, the cut of the chain axis into parts, the cells
 // per lane and the choice of a kernel's instantiation by state type and cells per lane.
 #pragma once
@@ -97,5 +98,19 @@ hipError_t launch_posterior_project(const void* beds, const double* g, const dou
                                     int n_chains, int n_probes, int f32_state, int n_cu, hipStream_t st);
 hipError_t launch_posterior_cross(const void* beds, const double* g, const double* proj, double* slab, double* cross, int64_t plane,
                                   int n_chains, int parts, int n_probes, int f32_state, int n_cu, hipStream_t st);
+// posterior_residual_kernel.hip.  3 + n_levels <= 7 fields: cnt, S1, S2, then one count per level
+constexpr int kResMaxLevels = 4;
+constexpr int kResMaxLanesXLog2 = 5;   // a tile is at most 32 lanes wide: 512 bytes of a row at 16 bytes per lane
+constexpr int kResMinChains = 8;       // a part's workgroups load about 13 doubles per cell before their first chain: not for fewer chains than this
+// the tile of the residual pass: vec cells of a row per lane (16 bytes where W allows it), 1 << lx_log2 lanes across and
+// 256 >> lx_log2 rows, tiles_x * tiles_y tiles on the grid
+struct ResTile { int vec, lx_log2, tiles_x, tiles_y; };
+ResTile posterior_residual_tile(int H, int W, int f32_state);
+// parts of the chain axis: posterior_parts over the tiles, but at least kResMinChains chains to a part; the slab holds parts x (3 +
+// n_levels) planes
+int posterior_residual_parts(const ResTile& t, int n_chains, int n_cu);
+// levels [host, n_levels]
+hipError_t launch_posterior_residual(const StaticFields& S, const void* beds, const double* rg, const double* levels, int n_levels,
+                                     double* slab, double* sums, int n_chains, int parts, int f32_state, int n_cu, hipStream_t st);
 
 }  // namespace gsm

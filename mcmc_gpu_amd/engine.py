@@ -45,7 +45,7 @@ class GsmEngine:
         if rc != 0:
             raise GsmError(rc, self.lib.gsm_last_error(None).decode())
         self.h = h
-        self.beds = self.energy = self.resampled = self.loss_sum = None
+        self.beds = self.energy = self.resampled = self.loss_sum = self.static = None
         self.field_stride = 0
         self.n_sizes = 0
 
@@ -102,6 +102,9 @@ class GsmEngine:
         if um.shape != shp or mm.shape != shp:
             raise ValueError("mask has the wrong shape")
         self.call(self.lib.gsm_set_static, *arrs, w, um, mm, float(resolution), float(sigma_mc))
+        # host copies of what the residual and the loss are made of (posterior.PosteriorAccumulator, `residual`)
+        self.static = dict(zip(("surf", "velx", "vely", "dhdt", "smb"), (np.array(a, dtype=np.float64) for a in (surf, velx, vely, dhdt, smb))),
+                           mc_mask=np.asarray(mc_mask) == 1, resolution=float(resolution), sigma_mc=float(sigma_mc))
 
     def set_blocks(self, pairs, edge_masks=None):
         """pairs: (2, n) int array, row 0 widths, row 1 heights (RandField.pairs, MCMC.py:576-579)."""
@@ -291,6 +294,24 @@ class GsmEngine:
         self._check_sums(self.n_chains * K, proj=proj)
         self._check_sums(K * self.H * self.W, cross=cross)
         self.call(self.lib.gsm_posterior_cross, self.beds, g, proj, K, cross)
+
+    def posterior_residual(self, rg, levels, sums):
+        """One snapshot of self.beds into the per-cell sums of the mass-conservation residual r over all chains (set_static's fields;
+        gsm_residual's bits): over the chains with finite r, sums[0] += their number, sums[1] += sum d, sums[2] += sum d * d with d =
+        r - rg, sums[3 + l] += the number with |r| > levels[l].  rg [H, W] and sums [3 + L, H, W] float64 on the device, levels a
+        host sequence of L <= 4 finite floats >= 0.  Asynchronous."""
+        self._need_beds()
+        if self.static is None:
+            raise RuntimeError("set_static() first")
+        lv = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+        if lv.size > 4 or not (np.isfinite(lv).all() and (lv >= 0).all()):
+            raise ValueError(f"levels must be at most 4 finite values >= 0, got {lv.tolist()}")
+        n = (3 + lv.size) * self.H * self.W
+        if rg.numel() != self.H * self.W or sums.numel() != n:
+            raise ValueError(f"rg must hold H x W = {self.H * self.W} elements and sums (3 + L) x H x W = {n}")
+        self._check_sums(self.H * self.W, rg=rg)
+        self._check_sums(n, sums=sums)
+        self.call(self.lib.gsm_posterior_residual, self.beds, rg, lv.ctypes.data if lv.size else None, int(lv.size), sums)
 
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):

@@ -34,6 +34,20 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               to a sequence; Y adds over ranks.  With n = M N, S1 = n (mean - g) and q_k = sum of p over the same values:
               cov_k = (Y_k - S1 q_k / n) / (n - 1), pooled over all chains and snapshots, ddof=1.  probe_values[c, k, t] = f_k
               of chain c at snapshot t (Omega_k . g over the support, summed on the host, plus p), for all T snapshots.
+  residual    optional maps of the mass-conservation residual r = d/dx(velx (surf - bed)) + d/dy(vely (surf - bed)) + dhdt - smb,
+              the quantity every chain is scored on, over the same M*N values: the posterior predictive check of the sampler.  For
+              chain c at a snapshot that belongs to a sequence, r is the residual of (double)bed_c with np.gradient's differences
+              (one-sided at the four borders), bit for bit what gsm_residual gives for that bed.  rg [H, W] is the residual of the
+              common field g, non-finite values set to 0 (residual_field, NumPy): a shift only, no result depends on it beyond
+              rounding.  Per cell, over the values with finite r (the loss's nansum, MCMC.py:1041), the device keeps the fp64
+              planes residual_sums [3 + L, H, W] (gsm_posterior_residual): cnt = their number, S1 = sum d, S2 = sum d d with d =
+              r - rg, and for each of the L <= 4 `levels` (finite, >= 0, in the residual's unit) A_l = the number with |r| > level_l
+              (a NaN compares false).  Counts are exact integers; no atomics, a fixed order (chains in index order within a part
+              of the chain axis, parts in part order, snapshots in schedule order); the planes add over ranks.  On the host:
+              residual_mean = rg + S1 / cnt, residual_sd = sqrt((S2 - S1^2 / cnt) / (cnt - 1)) (NaN where cnt < 2), residual_rms
+              = sqrt(sum r^2 / cnt) with sum r^2 = S2 + 2 rg S1 + cnt rg^2, prob_residual_above(level) = A_l / cnt (exact),
+              loss_density = sum r^2 / (2 sigma_mc^2 M N) on the cells with mc_mask == 1 (0 on the others) and expected_loss = its
+              sum: the mean of chain.loss over the same M*N states.  A cell with cnt == 0 is NaN in the maps and adds 0 to the loss.
 """
 from __future__ import annotations
 
@@ -100,6 +114,72 @@ class PosteriorSummary:
     probe_values: np.ndarray | None = None
     probe_cross: np.ndarray | None = None
     probe_centre: np.ndarray | None = None
+    # with residual=: residual_sums [3 + L, H, W] float64 (cnt, S1, S2, then A_l per level) about residual_ref = rg [H, W];
+    # residual_levels [L]; residual_sigma_mc and residual_mc_mask [H, W] bool: what the loss is made of
+    residual_sums: np.ndarray | None = None
+    residual_ref: np.ndarray | None = None
+    residual_levels: np.ndarray | None = None
+    residual_sigma_mc: float | None = None
+    residual_mc_mask: np.ndarray | None = None
+
+    def _need_residual(self):
+        if self.residual_sums is None or self.residual_ref is None:
+            raise ValueError("this summary holds no residual sums: run with posterior=dict(..., residual=True)")
+        P = np.asarray(self.residual_sums, dtype=np.float64)
+        return P[0], P[1], P[2], np.asarray(self.residual_ref, dtype=np.float64)
+
+    def residual_count(self):
+        """[H, W] int64: how many of the M*N values of every cell have a finite residual."""
+        return self._need_residual()[0].astype(np.int64)
+
+    def residual_mean(self):
+        """[H, W] mean of the finite residuals of every cell: rg + S1 / cnt.  NaN where cnt == 0."""
+        cnt, S1, _, rg = self._need_residual()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, rg + S1 / cnt, np.nan)
+
+    def residual_sd(self):
+        """[H, W] ddof=1 standard deviation of the finite residuals of every cell: how far the chains disagree.  NaN where cnt < 2."""
+        cnt, S1, S2, _ = self._need_residual()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var = np.maximum(S2 - S1 * S1 / cnt, 0.0) / (cnt - 1)
+            return np.where(cnt > 1, np.sqrt(var), np.nan)
+
+    def _residual_sumsq(self):
+        cnt, S1, S2, rg = self._need_residual()
+        return S2 + 2.0 * rg * S1 + cnt * rg * rg
+
+    def residual_rms(self):
+        """[H, W] root mean square of the finite residuals of every cell.  NaN where cnt == 0."""
+        cnt = self._need_residual()[0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, np.sqrt(np.maximum(self._residual_sumsq(), 0.0) / cnt), np.nan)
+
+    def prob_residual_above(self, level):
+        """[H, W] share of the finite residuals of every cell with |r| > level (exact: a ratio of counts; NaN where cnt == 0).
+        KeyError for a level that the run was not asked to count."""
+        cnt = self._need_residual()[0]
+        levels = [] if self.residual_levels is None else [float(v) for v in np.asarray(self.residual_levels).ravel()]
+        if float(level) not in levels:
+            raise KeyError(f"level {level!r} was not counted; the levels of this summary are {levels}")
+        above = np.asarray(self.residual_sums, dtype=np.float64)[3 + levels.index(float(level))]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, above / cnt, np.nan)
+
+    def loss_density(self):
+        """[H, W] every cell's term of expected_loss(): sum r^2 / (2 sigma_mc^2 M N) where mc_mask == 1, 0 elsewhere; NaN where cnt == 0."""
+        cnt = self._need_residual()[0]
+        if self.residual_sigma_mc is None or self.residual_mc_mask is None:
+            raise ValueError("this summary holds no sigma_mc / mc_mask")
+        n = self.n_sequences * self.n_per_sequence
+        dens = self._residual_sumsq() / (2.0 * float(self.residual_sigma_mc) ** 2 * n)
+        dens = np.where(np.asarray(self.residual_mc_mask) == 1, dens, 0.0)
+        return np.where(cnt > 0, dens, np.nan)
+
+    def expected_loss(self):
+        """The mean of the chains' loss over the M*N states: the sum of loss_density() (a cell without a finite residual adds 0, as
+        the loss's nansum does)."""
+        return float(np.nansum(self.loss_density()))
 
     def _need_cov(self):
         if self.probes is None or self.probe_cross is None or self.probe_values is None:
@@ -254,6 +334,8 @@ class PosteriorSummary:
             kw["hist_half_width"] = float(kw["hist_half_width"])
         if kw["probe_names"] is not None:
             kw["probe_names"] = tuple(str(v) for v in kw["probe_names"])
+        if kw["residual_sigma_mc"] is not None:
+            kw["residual_sigma_mc"] = float(kw["residual_sigma_mc"])
         return cls(**kw)
 
 
@@ -386,6 +468,42 @@ def region_mean_probes(masks):
     return m / count[:, None, None].astype(np.float64)
 
 
+RESIDUAL_KEYS = ("levels",)
+RESIDUAL_MAX_LEVELS = 4
+
+
+def check_residual(residual):
+    """Validate the `residual` option: None (also False), True or dict(levels=(l1, ...)) with up to 4 finite thresholds >= 0 on |r|.
+    Returns None or dict(levels=<tuple of floats>)."""
+    if residual is None or residual is False:
+        return None
+    if residual is True:
+        residual = {}
+    if not isinstance(residual, dict):
+        raise ValueError("residual must be None, True or a dict with the key levels")
+    unknown = set(residual) - set(RESIDUAL_KEYS)
+    if unknown:
+        raise ValueError(f"unknown residual option(s) {sorted(unknown)}; the options are {RESIDUAL_KEYS}")
+    try:
+        levels = tuple(float(v) for v in np.asarray(residual.get("levels", ()), dtype=np.float64).ravel())
+    except (TypeError, ValueError):
+        raise ValueError("residual levels must be a sequence of numbers") from None
+    if len(levels) > RESIDUAL_MAX_LEVELS:
+        raise ValueError(f"residual takes at most {RESIDUAL_MAX_LEVELS} levels, got {len(levels)}")
+    if not all(np.isfinite(v) and v >= 0.0 for v in levels):
+        raise ValueError(f"residual levels must be finite and >= 0, got {levels}")
+    return dict(levels=levels)
+
+
+def residual_field(bed, surf, velx, vely, dhdt, smb, resolution):
+    """[H, W] mass-conservation residual of one bed in NumPy's np.gradient form (Topography.py:592-600)."""
+    thick = np.asarray(surf, dtype=np.float64) - np.asarray(bed, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dx = np.gradient(np.asarray(velx, dtype=np.float64) * thick, float(resolution), axis=1)
+        dy = np.gradient(np.asarray(vely, dtype=np.float64) * thick, float(resolution), axis=0)
+        return dx + dy + np.asarray(dhdt, dtype=np.float64) - np.asarray(smb, dtype=np.float64)
+
+
 HIST_KEYS = ("bins", "half_width", "levels")
 HIST_MAX_BINS, HIST_MAX_LEVELS = 128, 8
 HIST_MAX_COUNT = 2 ** 31 - 1
@@ -451,10 +569,13 @@ class PosteriorAccumulator:
     with all_reduce_sum).  The ring is released with the last snapshot.
     cov (see check_cov): also, all float64, `d_probes` [K, H, W], `d_proj` [T, n_chains, K], the projections of all T snapshots, and
     `probe_cross` [K, H, W], to which add() adds the cross sums of every snapshot that belongs to a sequence (sum it over ranks
-    with all_reduce_sum; gather d_proj over ranks like the sample traces)."""
+    with all_reduce_sum; gather d_proj over ranks like the sample traces).
+    residual (see check_residual; needs eng.set_static): also, float64, `d_rg` [H, W], the residual of common_ref, and `residual_sums`
+    [3 + L, H, W], to which add() adds the residual sums of every snapshot that belongs to a sequence (sum it over ranks with
+    all_reduce_sum)."""
 
     def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None,
-                 ess=None, cov=None):
+                 ess=None, cov=None, residual=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -471,6 +592,9 @@ class PosteriorAccumulator:
         self.n_lags = 0 if self.ess is None else self.ess["max_lag"]
         self.cov = check_cov(cov, H, W)
         self.n_probes = 0 if self.cov is None else int(self.cov["probes"].shape[0])
+        self.residual = check_residual(residual)
+        if self.residual is not None and getattr(eng, "static", None) is None:
+            raise ValueError("residual needs the engine's static fields: call set_static() first")
         # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
         g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
         if g.shape != (H, W) or not np.isfinite(g).all():
@@ -498,13 +622,15 @@ class PosteriorAccumulator:
         if self.n_probes:
             table += [("d_probes", (self.n_probes, H, W), f64, False), ("d_proj", (self.T, n, self.n_probes), f64, False),
                       ("probe_cross", (self.n_probes, H, W), f64, True)]
+        if self.residual is not None:
+            table += [("d_rg", (H, W), f64, False), ("residual_sums", (3 + len(self.residual["levels"]), H, W), f64, True)]
         self.device_bytes = need = sum(math.prod(shape) * dtype.itemsize for _, shape, dtype, _ in table)
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
                               f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
         self.ref = self.d_cells = self.d_samples = self.hist_counts = self.ring = self.lag_sqdiff = None
-        self.d_probes = self.d_proj = self.probe_cross = None
+        self.d_probes = self.d_proj = self.probe_cross = self.d_rg = self.residual_sums = None
         for name, shape, dtype, zeroed in table:
             setattr(self, name, (torch.zeros if zeroed else torch.empty)(shape, dtype=dtype, device=eng.dev))
         self.d_g.copy_(torch.as_tensor(g))
@@ -512,6 +638,12 @@ class PosteriorAccumulator:
             self.d_cells.copy_(torch.as_tensor(cells))
         if self.n_probes:
             self.d_probes.copy_(torch.as_tensor(self.cov["probes"]))
+        if self.residual is not None:
+            st = eng.static
+            rg = residual_field(g, st["surf"], st["velx"], st["vely"], st["dhdt"], st["smb"], st["resolution"])
+            rg[~np.isfinite(rg)] = 0.0
+            self.residual_ref = rg
+            self.d_rg.copy_(torch.as_tensor(rg))
         self.ring_head = self.ring_valid = 0
         self.n_added = 0
         self._partials = None
@@ -554,6 +686,8 @@ class PosteriorAccumulator:
             eng.posterior_project(self.d_g, self.d_probes, self.d_proj[t])
             if t >= self.dropped:
                 eng.posterior_cross(self.d_g, self.d_proj[t], self.n_probes, self.probe_cross)
+        if self.residual is not None and t >= self.dropped:  # the states that mean and sd describe, each scored once
+            eng.posterior_residual(self.d_rg, self.residual["levels"], self.residual_sums)
         self.n_added += 1
         self._partials = None
 
@@ -576,7 +710,8 @@ class PosteriorAccumulator:
 
     def local_sums(self):
         """Everything of this accumulator that adds over ranks, as device tensors under the names finalize() takes the sums by:
-        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts, lag_sqdiff and probe_cross."""
+        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts, lag_sqdiff, probe_cross and
+        residual_sums."""
         import torch
         out = dict(partials_sum=self.partials(), M=torch.tensor([self.n_sequences], dtype=torch.int64, device=self.d_g.device))
         if self.hist is not None:
@@ -585,6 +720,8 @@ class PosteriorAccumulator:
             out["lag_sqdiff"] = self.lag_sqdiff
         if self.n_probes:
             out["probe_cross"] = self.probe_cross
+        if self.residual is not None:
+            out["residual_sums"] = self.residual_sums
         return out
 
     def sample_values(self):
@@ -595,7 +732,8 @@ class PosteriorAccumulator:
         """[n_chains, K, T] numpy array of the projections p of all snapshots, or None."""
         return None if self.d_proj is None else np.ascontiguousarray(self.d_proj.permute(1, 2, 0).cpu().numpy())
 
-    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None, probe_cross=None, projections=None):
+    def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None, probe_cross=None, projections=None,
+                 residual_sums=None):
         """PosteriorSummary from the sums of local_sums() added over ranks (all_reduce_posterior, all_reduce_counts, all_reduce_sum);
         each defaults to this accumulator's own.  projections: [n_chains, K, T] of all ranks' chains (projections(), gathered)."""
         self._require_complete()
@@ -619,28 +757,36 @@ class PosteriorAccumulator:
             meta.update(probes=P.copy(), probe_names=self.cov["names"], probe_values=off[None, :, None] + p, probe_centre=g.copy(),
                         probe_cross=_host_array(self.probe_cross if probe_cross is None else probe_cross, (self.n_probes,) + grid, np.float64,
                                                 "cross sums"))
+        if self.residual is not None:
+            L = len(self.residual["levels"])
+            st = self.eng.static
+            meta.update(residual_sums=_host_array(self.residual_sums if residual_sums is None else residual_sums, (3 + L,) + grid, np.float64,
+                                                  "residual sums"),
+                        residual_ref=self.residual_ref.copy(), residual_levels=np.asarray(self.residual["levels"], dtype=np.float64),
+                        residual_sigma_mc=st["sigma_mc"], residual_mc_mask=np.array(st["mc_mask"], dtype=bool))
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov", "residual")
 
 
 def check_options(posterior, n_iter, n_chains=None):
     """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
     n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov, residual")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None, residual=None)
     opt.update(posterior)
     _, N, _ = sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
     opt["ess"] = check_ess(opt["ess"], N, opt["rhat"])
     opt["hist"] = check_hist(opt["hist"])
     opt["cov"] = check_cov(opt["cov"])
+    opt["residual"] = check_residual(opt["residual"])
     if opt["hist"] is not None and n_chains is not None:
         check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])
     return opt

@@ -22,7 +22,15 @@
               part's [K, H, W] slab written and read back, `cross` read and written, and the projections.  The default --out is
               profiles/posterior_bench_cov.json.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K]
+  --residual  only the fused residual pass (gsm_posterior_residual, 2 levels) at 1024 chains of 256 x 256, fp64 and fp32 state: (a) the
+              pass, (b) the pooled pass of the same run, (c) gsm_debug_stream_copy moving the bytes the pass must move (the state once,
+              the slabs and the planes) and (d), fp64 state only, the composition of existing entry points -- gsm_residual into a
+              scratch array of the state's size, then gsm_posterior_accumulate_pooled on that scratch (three state-sized transfers).
+              Each the median of 20 calls, three repeats, the four alternating; then the wall time of MCMC_gpu.run_many without
+              `posterior`, with it, and with `residual` at thin=100 (--no-end-to-end leaves that out).  The default --out is
+              profiles/posterior_bench_residual.json.
+
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K | --residual]
 """
 import argparse
 import json
@@ -257,13 +265,89 @@ def cov_rows(n_chains, H, W, state, K, reps):
     return rows
 
 
-def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None):
+def residual_rows(n_chains, H, state, reps, repeats, levels=(2.0, 10.0)):
+    """The fused residual pass (a) beside the pooled pass of the same run (b), a stream copy of the bytes the fused pass must move (c:
+    the state once, every part's slab written and read back, the planes read and written) and, with fp64 state, the composition that
+    needs no new kernel (d: gsm_residual into a scratch array of the state's size, then gsm_posterior_accumulate_pooled on that
+    scratch).  Each is the median of `reps` calls, `repeats` times over, the four alternating within a repeat."""
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd import synthetic
+    from mcmc_gpu_amd.engine import GsmEngine
+    prob, ch, rf = synthetic.template(H)
+    W = H
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        eng.set_static(ch.surf, ch.velx, ch.vely, ch.dhdt, ch.smb, None, np.ones((H, W), dtype=np.uint8), ch.mc_region_mask, ch.resolution, ch.sigma_mc)
+        dev, plane, sb = eng.dev, H * W, 8 if state == "f64" else 4
+        n = n_chains * plane
+        bed0 = torch.as_tensor(np.ascontiguousarray(prob["bed"], dtype=np.float64)).to(dev)
+        eng.beds = (bed0[None] + 20.0 * torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nf = 3 + len(levels)
+        g = bed0.clone()
+        rg = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p1 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        p2 = torch.zeros((H, W), dtype=torch.float64, device=dev)
+        sums = torch.zeros((nf, H, W), dtype=torch.float64, device=dev)
+        # the cut of the chain axis: the rule of posterior_residual_parts (posterior_device.h, posterior_residual_kernel.hip)
+        vec = (4 if W % 4 == 0 else 2 if W % 2 == 0 else 1) if sb == 4 else (2 if W % 2 == 0 else 1)
+        lx = 1
+        while lx < 32 and lx < W // vec:
+            lx *= 2
+        tiles = -(-(W // vec) // lx) * -(-H // (256 // lx))
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        parts = max(1, min(-(-4 * n_cu // tiles), n_chains, n_chains // 8))
+        fused_bytes = sb * n + 2 * parts * nf * plane * 8 + 2 * nf * plane * 8
+        m = fused_bytes // 16
+        src = torch.ones(m, dtype=torch.float64, device=dev)
+        dst = torch.empty(m, dtype=torch.float64, device=dev)
+        calls = {"a fused residual pass": (fused_bytes, lambda: eng.posterior_residual(rg, levels, sums)),
+                 "b pooled accumulate": (sb * n, lambda: eng.posterior_accumulate_pooled(g, p1, p2)),
+                 "c stream copy of the fused pass's bytes": (16 * m, lambda: eng._check(eng.lib.gsm_debug_stream_copy(
+                     C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st)))}
+        if state == "f64":
+            scratch = torch.empty_like(eng.beds)
+
+            def composition():
+                eng.call(eng.lib.gsm_residual, eng.beds, scratch)
+                eng.call(eng.lib.gsm_posterior_accumulate_pooled, scratch, rg, p1, p2, None, 0, None)
+
+            calls["d gsm_residual into scratch, then the pooled pass on it"] = (3 * sb * n, composition)
+        med = {name: [] for name in calls}
+        for _ in range(repeats):
+            for name, (nbytes, fn) in calls.items():
+                row = _rate(f"{name} ({shape})", nbytes, _timed(fn, reps))
+                med[name].append(row["ms_median"])
+                rows.append(row)
+        names = list(calls)
+        summary = {"what": f"residual pass summary {shape}", "tiles": tiles, "parts": parts, "levels": list(levels), "bed_bytes": sb * n,
+                   "ms_median_per_repeat": med, "fused_over_pooled": statistics.median(med[names[0]]) / statistics.median(med[names[1]]),
+                   "fused_fraction_of_copy": statistics.median(med[names[2]]) / statistics.median(med[names[0]]),
+                   "sums_check": bool((sums[0] <= (3 + reps) * repeats * n_chains).all().item() and torch.isfinite(sums).all().item())}
+        if state == "f64":
+            summary["fused_faster_than_composition_in_all_repeats"] = all(a < d for a, d in zip(med[names[0]], med[names[3]]))
+            summary["composition_over_fused"] = statistics.median(med[names[3]]) / statistics.median(med[names[0]])
+        rows.append(summary)
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None, residual=False):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
     prob, ch, rf = synthetic.template(H)
     beds = synthetic.initial_beds(prob, n_chains)
     seeds = list(range(1000, 1000 + n_chains))
-    if cov_probes is not None:
+    if residual:
+        configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
+                  [(f"thin={t} rhat=True residual 2 levels", dict(burn_in=0, thin=t, residual=dict(levels=(2.0, 10.0)))) for t in thins]
+    elif cov_probes is not None:
         P = np.random.default_rng(0).normal(size=(cov_probes, H, H))
         configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
                   [(f"thin={t} rhat=True cov {cov_probes} probes", dict(burn_in=0, thin=t, cov=dict(probes=P))) for t in thins]
@@ -319,17 +403,28 @@ def main():
     ap.add_argument("--ess", action="store_true", help="only the lagged pass beside its stream copy, and run_many with and without ess")
     ap.add_argument("--cov", type=int, default=0, metavar="K", help="only the two covariance passes with K probes beside their stream copies, "
                     "and run_many with and without cov")
+    ap.add_argument("--residual", action="store_true", help="only the fused residual pass beside the pooled pass, its stream copy and the "
+                    "composition of existing entry points, and run_many with and without residual")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --residual: the kernel rows alone")
     args = ap.parse_args()
     if args.cov and not 1 <= args.cov <= 15:
         raise SystemExit("--cov takes 1 .. 15 probes")
     if args.cov and args.out is None and not args.quick:
         args.out = str(ROOT / "profiles" / "posterior_bench_cov.json")
+    if args.residual and args.out is None and not args.quick:
+        args.out = str(ROOT / "profiles" / "posterior_bench_residual.json")
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
     rows = []
     if args.hist:
         for state in ("f64", "f32"):
             rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
+    elif args.residual:
+        for state in ("f64", "f32"):
+            rows += residual_rows(8, 64, state, 3, 1) if args.quick else residual_rows(1024, 256, state, max(args.reps, 20), args.repeats)
+        if not args.no_end_to_end:
+            rows += end_to_end_rows(64, 8, 1701, [100], 1, residual=True) if args.quick else \
+                end_to_end_rows(256, 1024, 20001, [100], args.repeats, residual=True)
     elif args.cov:
         for state in ("f64", "f32"):
             rows += cov_rows(8, 64, 64, state, args.cov, 3) if args.quick else cov_rows(1024, 256, 256, state, args.cov, max(args.reps, 20))
