@@ -693,7 +693,30 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
  * or not finite, beds not 16-byte aligned; GSM_E_STATE before gsm_set_static; nothing is written then.
  * Replaces: Topography.get_mass_conservation_residual (Topography.py:592-612) over bed_cache[burn_in::thin] of every chain of a
  * pool, and the statistics of that stack.
- * All ten are asynchronous on `stream`. */
+ *
+ * gsm_posterior_local: one snapshot into the per-cell cross sums of the bed with its neighbours over ALL chains -- the short-range
+ * structure of the uncertainty, from which the variance of anything local and linear follows (a slope, a block mean, a correlation
+ * length).  reach R in [1, 4]; the K = 2 R^2 + 2 R offsets (di, dj) of the upper half plane in this order: (0, 1) .. (0, R), then for
+ * di = 1 .. R: (di, -R) .. (di, R) (K = 4, 12, 24, 40; the lower half plane holds the same pairs).  With d_c[cell] = (double)bed_c[cell]
+ * - g[cell], g [dev, H*W] fp64 the common field:
+ *   cross[k*H*W + i*W + j] += sum_c d_c[i, j] * d_c[i + di_k, j + dj_k]     where (i + di_k, j + dj_k) lies inside the grid
+ * cross [dev, K*H*W] fp64, offset-major, is ADDED to: zero it once, call once per snapshot; sums of several handles (ranks) add.
+ * With n values per cell in all, m = S1 / n at the cell and m' at its partner (S1 = sum d of the pooled moments), the covariance of
+ * the pair is (cross_k - n m m') / (n - 1).  An entry whose partner lies outside the grid is never touched: it stays exactly 0.  A
+ * NaN bed of chain c at a cell makes NaN exactly the entries that pair that cell -- its own K entries and entry k of the cell at
+ * minus offset k, where those lie inside the grid -- and nothing else.  Differences, products and sums are fp64 with either state
+ * type, the products and sums fused multiply-adds.  No atomics: chains are summed in index order within a part of the chain axis
+ * and the parts in part order (a second kernel, one launch per group of at most 15 offsets): bit-reproducible from run to run.
+ * One pass: each bed value is read from memory about once (8 bytes per chain-cell with fp64 state, 4 with fp32, plus the halo of a
+ * workgroup's 8 x 64 tile: R rows below, R columns left and right), turned into d once and shared through LDS among the up to 2 K
+ * multiply-adds that use it.  The part merge writes and reads back parts x K planes of the handle's slab.  The rule that bounds it:
+ * parts = the parts that fill the device (as for the other passes, over the tiles), but at most 160 / K (4 at reach 4) and at
+ * most what keeps parts x K x H x W doubles within 1 GiB; the call is refused where K planes alone exceed 1 GiB.  The cut changes
+ * the order of the sum, never which terms enter it.
+ * Errors: GSM_E_ARG for a NULL beds, g or cross, reach outside [1, 4], beds not 16-byte aligned; GSM_E_UNSUPPORTED where K x H x W
+ * doubles exceed 1 GiB; nothing is written then.
+ * Replaces: np.cov between neighbouring cells of bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
+ * All eleven are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -714,6 +737,8 @@ int gsm_posterior_cross(gsm_handle h, const void* beds, const double* g, const d
                         double* cross /* [dev, n_probes*H*W], ADDED to */, void* stream);
 int gsm_posterior_residual(gsm_handle h, const void* beds, const double* rg, const double* levels, int32_t n_levels,
                            double* sums /* [dev, (3+n_levels)*H*W], ADDED to */, void* stream);
+int gsm_posterior_local(gsm_handle h, const void* beds, const double* g, int32_t reach,
+                        double* cross /* [dev, K*H*W], ADDED to */, void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

@@ -595,7 +595,7 @@ def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
                                  sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
-                                 ess=opt['ess'], cov=opt['cov'], residual=opt['residual'])
+                                 ess=opt['ess'], cov=opt['cov'], residual=opt['residual'], local=opt['local'])
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -641,7 +641,13 @@ def run_many(chain, RF, initial_beds, seeds, n_iter, batch=8, device=None, step0
     evaluates every chain's residual (gsm_residual's bits) and adds per-cell sums on the device in one pass, no per-chain residual
     is stored (summary.residual_sums).  The summary then answers residual_mean(), residual_sd(), residual_rms(), residual_count(),
     prob_residual_above(level) (exact), loss_density() and expected_loss(), the mean of the chains' loss over those states.  Works
-    with rhat=True and rhat=False and beside hist, ess and cov.  The chains and every other map are bit-identical with and without it."""
+    with rhat=True and rhat=False and beside hist, ess and cov.  The chains and every other map are bit-identical with and without it.
+    posterior['local']: None, True (reach 1) or dict(reach=R), R in 1 .. 4: the covariance of every cell with its neighbours within R
+    cells, over the same values.  Every snapshot that the moments use adds, on the device in one pass, the products of bed - g with
+    itself at the 2 R^2 + 2 R offsets of the upper half plane (posterior.local_offsets) to per-cell cross sums
+    (summary.local_cross).  The summary then answers local_covariance(), local_correlation(), difference_sd(di, dj),
+    gradient_sd(resolution) (reach >= 2) and block_mean_sd(k) (reach >= k - 1).  Works with rhat=True and rhat=False and beside hist,
+    ess, cov and residual.  The chains and every other map are bit-identical with and without it."""
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     n_iter = _check_args(RF, n_iter, False, n_chains, (seeds,))

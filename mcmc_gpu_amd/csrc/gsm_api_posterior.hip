@@ -1,5 +1,5 @@
 // C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip,
-// posterior_cov_kernel.hip, posterior_residual_kernel.hip).  Every
+// posterior_cov_kernel.hip, posterior_residual_kernel.hip, posterior_local_kernel.hip).  Every
 // argument is validated here, once, where the error text is; the launchers take what they are given.
 #include "gsm_context.h"
 #include "posterior_device.h"
@@ -170,6 +170,25 @@ extern "C" int gsm_posterior_residual(gsm_handle h, const void* beds, const doub
   HIPCHK(h, h->d_post_slab.ensure((size_t)parts * (3 + n_levels) * h->H * h->W));
   HIPCHK(h, launch_posterior_residual(h->S, beds, rg, levels, n_levels, h->d_post_slab.get(), sums, h->n_chains, parts, h->f32_state, h->n_cu,
                                       (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_local(gsm_handle h, const void* beds, const double* g, int32_t reach, double* cross, void* stream) {
+  if (!h) return GSM_E_ARG;
+  if (!beds || !g || !cross) return fail(h, GSM_E_ARG, "gsm_posterior_local: NULL pointer");
+  if (reach < 1 || reach > kLocalMaxReach) return fail(h, GSM_E_ARG, "gsm_posterior_local: reach must be in [1, 4]");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_local: beds must be 16-byte aligned");
+  int rc = posterior_device(h);
+  if (rc != GSM_OK) return rc;
+  const int K = 2 * reach * reach + 2 * reach;
+  const int parts = posterior_local_parts(h->H, h->W, reach, h->n_chains, h->n_cu);
+  if (parts < 1)
+    return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_local: the K planes of one part of the chain axis exceed the 1 GiB the part merge may take: "
+                                      "use a shorter reach");
+  if (posterior_local_tiles(h->H, h->W) * parts > INT32_MAX) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_local: more than 2^31 - 1 workgroups");
+  HIPCHK(h, h->d_post_slab.ensure((size_t)parts * K * h->H * h->W));
+  HIPCHK(h, launch_posterior_local(beds, g, h->d_post_slab.get(), cross, h->H, h->W, h->n_chains, parts, reach, h->f32_state, h->n_cu,
+                                   (hipStream_t)stream));
   return GSM_OK;
 }
 

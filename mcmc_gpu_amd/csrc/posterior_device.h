@@ -1,5 +1,5 @@
 // What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip, posterior_cov_kernel.hip,
-// posterior_residual_kernel.hip) and what
+// posterior_residual_kernel.hip, posterior_local_kernel.hip) and what
 // gsm_api_posterior.hip sizes the slab by: the workgroup size, the 16-byte pack, the cut of the chain axis into parts, the cells
 // per lane and the choice of a kernel's instantiation by state type and cells per lane.
 #pragma once
@@ -35,6 +35,15 @@ struct ChainRange { int c0, c1; };
 __device__ __forceinline__ ChainRange chain_range(int cpp, int n_chains) {
   const int c0 = blockIdx.y * cpp;
   return {c0, min(n_chains, c0 + cpp)};
+}
+
+// Workgroup id -> work item so that the ids that share an L2 (id % 8: the workgroups are dealt over the 8 L2s round-robin by id) take
+// a contiguous run of the n work items (bijective for any n: the first n % 8 runs are one longer).  For the tiled passes, whose
+// neighbouring tiles read each other's halo.
+constexpr int kXcds = 8;
+__device__ __forceinline__ int xcd_contiguous(int id, int n) {
+  const int q = n / kXcds, r = n % kXcds, x = id % kXcds;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + id / kXcds;
 }
 
 // workgroups of a grid-stride pass: one per per_block work items, at most eight to a CU
@@ -112,5 +121,16 @@ int posterior_residual_parts(const ResTile& t, int n_chains, int n_cu);
 // levels [host, n_levels]
 hipError_t launch_posterior_residual(const StaticFields& S, const void* beds, const double* rg, const double* levels, int n_levels,
                                      double* slab, double* sums, int n_chains, int parts, int f32_state, int n_cu, hipStream_t st);
+// posterior_local_kernel.hip.  reach in [1, 4], K = 2 reach^2 + 2 reach offsets; the slab holds parts x K planes
+constexpr int kLocalMaxReach = 4;
+constexpr int kLocalSlabPlanes = 160;                        // parts x K stays at or below this: 4 parts at reach 4, 6 at 3, 13 at 2, 40 at 1
+constexpr int64_t kLocalMaxSlabDoubles = (int64_t)1 << 27;   // and the slab at or below 1 GiB, by fewer parts
+// tiles of 8 rows x 64 columns on the grid
+int64_t posterior_local_tiles(int H, int W);
+// parts of the chain axis: posterior_parts over the tiles, at most kLocalSlabPlanes / K and at most what keeps parts x K x H x W
+// doubles within kLocalMaxSlabDoubles; 0 where one part's K planes alone exceed that (the call is refused)
+int posterior_local_parts(int H, int W, int reach, int n_chains, int n_cu);
+hipError_t launch_posterior_local(const void* beds, const double* g, double* slab, double* cross, int H, int W, int n_chains, int parts,
+                                  int reach, int f32_state, int n_cu, hipStream_t st);
 
 }  // namespace gsm

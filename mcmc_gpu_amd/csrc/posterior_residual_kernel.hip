@@ -30,20 +30,12 @@ namespace gsm {
 namespace {
 
 constexpr int kResChains = 4;      // chains whose five loads per lane are in flight together
-constexpr int kXcds = 8;           // L2s the workgroups are dealt over, round-robin by workgroup id
 
 struct ResLevels { double v[kResMaxLevels]; };
 
 // what a lane reads of one chain: its V cells, the V cells above and below, the cell left of the first and right of the last
 template <typename T, int V>
 struct ResWindow { Pack<T, V> mid, up, dn; T left, right; };
-
-// Workgroup id -> work item so that the ids that share an L2 (id % 8) take a contiguous run of the n work items (bijective for
-// any n: the first n % 8 runs are one longer).
-__device__ __forceinline__ int xcd_contiguous(int id, int n) {
-  const int q = n / kXcds, r = n % kXcds, x = id % kXcds;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + id / kXcds;
-}
 
 template <typename T, int V>
 __global__ __launch_bounds__(kPostBlock) void post_residual_kernel(const StaticFields S, const T* __restrict__ beds,

@@ -278,7 +278,7 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     starts its own ranks (one fresh process per GPU, RCCL) -- the caller brings no launcher, like the reference's driver;
     under torchrun (or inside such a rank) the initialised group is used and this process runs its shard.
 
-    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`, `hist`, `ess`, `cov`, `residual`).  Philox mode with all
+    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`, `hist`, `ess`, `cov`, `residual`, `local`).  Philox mode with all
     chains sharing n_iter and the Philox step only (any other combination is a ValueError).  Return value and per-seed
     checkpoint files are unchanged; rank 0 also writes <output_path>/LargeScaleChain/posterior_{k}k.npz (posterior.
     PosteriorSummary.load reads it; {k}k as in the first chain's bed_{k}k.npy) with the mean, sd and split-R-hat maps over the
@@ -287,7 +287,9 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     squared differences of all chains (one fp64 all-reduce of [max_lag, H, W]), behind the summary's ess(); with `cov` also the probes, probe_cross (one fp64 all-reduce of [K, H, W]) and
     probe_values of all chains (gathered like the traces), behind the summary's covariance(); with `residual` also residual_sums, the
     mass-conservation residual sums of all chains (one fp64 all-reduce of [3 + levels, H, W]), behind the summary's residual_mean(),
-    residual_sd(), prob_residual_above() and expected_loss().  The summary covers THIS
+    residual_sd(), prob_residual_above() and expected_loss(); with `local` also local_cross, the cross sums of every cell with its
+    neighbours over all chains (one fp64 all-reduce of [2 reach^2 + 2 reach, H, W]), and the reach, behind the summary's
+    local_covariance(), difference_sd(), gradient_sd() and block_mean_sd().  The summary covers THIS
     call's segment: iteration 0 is the bed the segment starts from, and accumulators are not carried across driver calls."""
     tic = time.time()
     mode = mode or getattr(largeScaleChain, 'rng_mode', 'replay')

@@ -313,6 +313,20 @@ class GsmEngine:
         self._check_sums(n, sums=sums)
         self.call(self.lib.gsm_posterior_residual, self.beds, rg, lv.ctypes.data if lv.size else None, int(lv.size), sums)
 
+    def posterior_local(self, g, reach, cross):
+        """One snapshot of self.beds into the per-cell cross sums with the neighbours within `reach` (1 .. 4): cross[k] += sum_c d_c *
+        d_c shifted by offset k of posterior.local_offsets(reach), d_c = bed_c - g, where the partner lies inside the grid (the other
+        entries are not touched).  g [H, W] and cross [K, H, W] float64 on the device, K = 2 reach^2 + 2 reach.  Asynchronous."""
+        self._need_beds()
+        if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or not 1 <= reach <= 4:
+            raise ValueError(f"reach must be an integer in [1, 4], got {reach!r}")
+        K = 2 * int(reach) * int(reach) + 2 * int(reach)
+        if g.numel() != self.H * self.W or cross.numel() != K * self.H * self.W:
+            raise ValueError(f"g must hold H x W = {self.H * self.W} elements and cross K x H x W = {K * self.H * self.W}")
+        self._check_sums(self.H * self.W, g=g)
+        self._check_sums(K * self.H * self.W, cross=cross)
+        self.call(self.lib.gsm_posterior_local, self.beds, g, int(reach), cross)
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

@@ -48,6 +48,16 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               = sqrt(sum r^2 / cnt) with sum r^2 = S2 + 2 rg S1 + cnt rg^2, prob_residual_above(level) = A_l / cnt (exact),
               loss_density = sum r^2 / (2 sigma_mc^2 M N) on the cells with mc_mask == 1 (0 on the others) and expected_loss = its
               sum: the mean of chain.loss over the same M*N states.  A cell with cnt == 0 is NaN in the maps and adds 0 to the loss.
+  local       optional covariance of every cell with its neighbours within `reach` R in 1 .. 4: the short-range structure of the
+              uncertainty, which turns the per-cell sd into the sd of anything local and linear (a slope, a block mean).  The K = 2 R^2
+              + 2 R offsets of the upper half plane (local_offsets: (0, 1) .. (0, R), then for di = 1 .. R: (di, -R) .. (di, R); the
+              lower half plane holds the same pairs).  Per snapshot that belongs to a sequence, with d = bed - g, the device adds
+              sum_c d_c[i, j] d_c[i + di, j + dj] to local_cross [K, H, W] where the partner lies inside the grid
+              (gsm_posterior_local; the other entries stay exactly 0): fp64 fused multiply-adds, no atomics, a fixed order; the planes
+              add over ranks.  On the host, with n = M N, m = mean - g at the cell and m' at its partner: local_covariance =
+              (X_k - n m m') / (n - 1), pooled over all chains and snapshots, ddof=1 -- the expression that gives sd^2 at offset
+              (0, 0) --, NaN where the partner is outside the grid.  From it local_correlation, difference_sd(di, dj),
+              gradient_sd(resolution) and block_mean_sd(k).  A NaN bed makes NaN exactly the entries that pair its cell.
 """
 from __future__ import annotations
 
@@ -121,6 +131,101 @@ class PosteriorSummary:
     residual_levels: np.ndarray | None = None
     residual_sigma_mc: float | None = None
     residual_mc_mask: np.ndarray | None = None
+    # with local=: local_cross [K, H, W] float64, the cross sums of d = bed - local_centre (= g [H, W]) with d at the K = 2 R^2 + 2 R
+    # offsets local_offsets(local_reach)
+    local_cross: np.ndarray | None = None
+    local_reach: int | None = None
+    local_centre: np.ndarray | None = None
+
+    def _need_local(self, reach=1, what=None):
+        if self.local_cross is None or self.local_reach is None or self.local_centre is None:
+            raise ValueError("this summary holds no local cross sums: run with posterior=dict(..., local=dict(reach=...))")
+        if int(self.local_reach) < reach:
+            raise ValueError(f"{what} needs local reach >= {reach}, this summary was made with reach {int(self.local_reach)}")
+        return self.n_sequences * self.n_per_sequence
+
+    def local_covariance(self):
+        """[K, H, W] covariance of every cell with its partner at offset k of local_offsets(local_reach) over the M N values, ddof=1:
+        (X_k - n m m') / (n - 1), m = mean - g at the cell and m' at the partner.  NaN where the partner is outside the grid and
+        where either mean is NaN."""
+        n = self._need_local()
+        X = np.asarray(self.local_cross, dtype=np.float64)
+        m = np.asarray(self.mean, dtype=np.float64) - np.asarray(self.local_centre, dtype=np.float64)
+        out = np.empty_like(X)
+        with np.errstate(invalid="ignore"):
+            for k, (di, dj) in enumerate(local_offsets(self.local_reach)):
+                mp = _shifted(m, di, dj)
+                out[k] = np.where(np.isnan(mp), np.nan, (X[k] - n * m * mp) / (n - 1))
+        return out
+
+    def local_correlation(self):
+        """[K, H, W] local_covariance() / (sd of the cell * sd of its partner).  NaN where either sd is 0."""
+        cov = self.local_covariance()
+        sd = np.asarray(self.sd, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for k, (di, dj) in enumerate(local_offsets(self.local_reach)):
+                sp = _shifted(sd, di, dj)
+                cov[k] = np.where((sd == 0) | (sp == 0), np.nan, cov[k] / (sd * sp))
+        return cov
+
+    def _pair_covariance(self, di, dj, what):
+        """[H, W] covariance of bed[i, j] with bed[i + di, j + dj] for any offset within reach, either sign; sd^2 at (0, 0)."""
+        di, dj = int(di), int(dj)
+        self._need_local(max(abs(di), abs(dj), 1), what)
+        if di == 0 and dj == 0:
+            return np.asarray(self.sd, dtype=np.float64) ** 2
+        table = [tuple(o) for o in local_offsets(self.local_reach).tolist()]
+        cov = self.local_covariance()
+        if (di, dj) in table:
+            return cov[table.index((di, dj))]
+        return _shifted(cov[table.index((-di, -dj))], di, dj)          # the pair is held at the partner, under the opposite offset
+
+    def difference_sd(self, di, dj):
+        """[H, W] standard deviation of bed[i + di, j + dj] - bed[i, j] over the M N values (ddof=1), for any offset within reach,
+        either sign: sqrt(var + var' - 2 cov).  NaN where the partner is outside the grid."""
+        what = f"difference_sd({int(di)}, {int(dj)})"
+        cov = self._pair_covariance(di, dj, what)
+        var = np.asarray(self.sd, dtype=np.float64) ** 2
+        with np.errstate(invalid="ignore"):
+            v = var + _shifted(var, int(di), int(dj)) - 2.0 * cov
+            return np.sqrt(np.where(np.isnan(v), np.nan, np.maximum(v, 0.0)))
+
+    def gradient_sd(self, resolution):
+        """(sd along axis 0, sd along axis 1), each [H, W]: the standard deviation of the central differences np.gradient(bed,
+        resolution) takes in the interior, (bed[i + 1] - bed[i - 1]) / (2 resolution).  NaN in the first and last row (column), where
+        np.gradient takes one-sided differences.  Needs reach >= 2."""
+        h = float(resolution)
+        if not (h > 0.0 and np.isfinite(h)):
+            raise ValueError(f"resolution must be finite and > 0, got {resolution!r}")
+        self._need_local(2, "gradient_sd")
+        # sd of bed[i + 2] - bed[i] is held at i: moved to i + 1, the cell the difference is centred on
+        return tuple(_shifted(self.difference_sd(di, dj), -di // 2, -dj // 2) / (2.0 * h) for di, dj in ((2, 0), (0, 2)))
+
+    def block_mean_sd(self, k):
+        """[H - k + 1, W - k + 1] standard deviation of the mean of the bed over every k x k block (entry [i, j]: the block with its
+        first cell at (i, j)): sqrt of the sum of all pair covariances in the block over k^4.  Needs reach >= k - 1."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"block_mean_sd: k must be an integer >= 1, got {k!r}")
+        k = int(k)
+        self._need_local(max(k - 1, 1), f"block_mean_sd({k})")
+        H, W = np.asarray(self.sd).shape
+        if k > H or k > W:
+            raise ValueError(f"block_mean_sd: a {k} x {k} block does not fit the {H} x {W} grid")
+        nh, nw = H - k + 1, W - k + 1
+        var = np.asarray(self.sd, dtype=np.float64) ** 2
+        total = np.zeros((nh, nw))
+        for a in range(k):
+            for b in range(k):
+                total += var[a:a + nh, b:b + nw]
+        cov = self.local_covariance()
+        for idx, (di, dj) in enumerate(local_offsets(self.local_reach).tolist()):
+            if di > k - 1 or abs(dj) > k - 1:
+                continue
+            for a in range(k - di):                                    # the cells of the block whose partner is in the block too
+                for b in range(max(0, -dj), min(k, k - dj)):
+                    total += 2.0 * cov[idx][a:a + nh, b:b + nw]
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(np.where(np.isnan(total), np.nan, np.maximum(total, 0.0))) / (k * k)
 
     def _need_residual(self):
         if self.residual_sums is None or self.residual_ref is None:
@@ -336,6 +441,8 @@ class PosteriorSummary:
             kw["probe_names"] = tuple(str(v) for v in kw["probe_names"])
         if kw["residual_sigma_mc"] is not None:
             kw["residual_sigma_mc"] = float(kw["residual_sigma_mc"])
+        if kw["local_reach"] is not None:
+            kw["local_reach"] = int(kw["local_reach"])
         return cls(**kw)
 
 
@@ -504,6 +611,47 @@ def residual_field(bed, surf, velx, vely, dhdt, smb, resolution):
         return dx + dy + np.asarray(dhdt, dtype=np.float64) - np.asarray(smb, dtype=np.float64)
 
 
+LOCAL_KEYS = ("reach",)
+LOCAL_MAX_REACH = 4
+
+
+def local_offsets(reach):
+    """[K, 2] int64 table of the K = 2 R^2 + 2 R offsets (di, dj) of the upper half plane within reach R, in the order of the planes
+    of local_cross: (0, 1) .. (0, R), then for di = 1 .. R: (di, -R) .. (di, R)."""
+    if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or reach < 1 or reach > LOCAL_MAX_REACH:
+        raise ValueError(f"local reach must be an integer in [1, {LOCAL_MAX_REACH}], got {reach!r}")
+    R = int(reach)
+    return np.array([(0, dj) for dj in range(1, R + 1)] + [(di, dj) for di in range(1, R + 1) for dj in range(-R, R + 1)], dtype=np.int64)
+
+
+def check_local(local):
+    """Validate the `local` option: None (also False), True (reach 1) or dict(reach=R), R an integer in [1, 4].  Returns None or
+    dict(reach=R)."""
+    if local is None or local is False:
+        return None
+    if local is True:
+        local = {}
+    if not isinstance(local, dict):
+        raise ValueError("local must be None, True or a dict with the key reach")
+    unknown = set(local) - set(LOCAL_KEYS)
+    if unknown:
+        raise ValueError(f"unknown local option(s) {sorted(unknown)}; the options are {LOCAL_KEYS}")
+    R = local.get("reach", 1)
+    local_offsets(R)
+    return dict(reach=int(R))
+
+
+def _shifted(a, di, dj):
+    """b[i, j] = a[i + di, j + dj], NaN where that cell is outside the grid."""
+    a = np.asarray(a, dtype=np.float64)
+    H, W = a.shape
+    b = np.full((H, W), np.nan)
+    i0, i1, j0, j1 = max(0, -di), min(H, H - di), max(0, -dj), min(W, W - dj)
+    if i0 < i1 and j0 < j1:
+        b[i0:i1, j0:j1] = a[i0 + di:i1 + di, j0 + dj:j1 + dj]
+    return b
+
+
 HIST_KEYS = ("bins", "half_width", "levels")
 HIST_MAX_BINS, HIST_MAX_LEVELS = 128, 8
 HIST_MAX_COUNT = 2 ** 31 - 1
@@ -572,10 +720,12 @@ class PosteriorAccumulator:
     with all_reduce_sum; gather d_proj over ranks like the sample traces).
     residual (see check_residual; needs eng.set_static): also, float64, `d_rg` [H, W], the residual of common_ref, and `residual_sums`
     [3 + L, H, W], to which add() adds the residual sums of every snapshot that belongs to a sequence (sum it over ranks with
-    all_reduce_sum)."""
+    all_reduce_sum).
+    local (see check_local): also, float64, `local_cross` [K, H, W], K = 2 reach^2 + 2 reach, to which add() adds the cross sums with
+    the neighbours of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_sum)."""
 
     def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None,
-                 ess=None, cov=None, residual=None):
+                 ess=None, cov=None, residual=None, local=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -592,6 +742,8 @@ class PosteriorAccumulator:
         self.n_lags = 0 if self.ess is None else self.ess["max_lag"]
         self.cov = check_cov(cov, H, W)
         self.n_probes = 0 if self.cov is None else int(self.cov["probes"].shape[0])
+        self.local = check_local(local)
+        self.n_local = 0 if self.local is None else int(local_offsets(self.local["reach"]).shape[0])
         self.residual = check_residual(residual)
         if self.residual is not None and getattr(eng, "static", None) is None:
             raise ValueError("residual needs the engine's static fields: call set_static() first")
@@ -624,13 +776,15 @@ class PosteriorAccumulator:
                       ("probe_cross", (self.n_probes, H, W), f64, True)]
         if self.residual is not None:
             table += [("d_rg", (H, W), f64, False), ("residual_sums", (3 + len(self.residual["levels"]), H, W), f64, True)]
+        if self.n_local:
+            table += [("local_cross", (self.n_local, H, W), f64, True)]
         self.device_bytes = need = sum(math.prod(shape) * dtype.itemsize for _, shape, dtype, _ in table)
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
             raise MemoryError(f"the posterior accumulators need {need / 2**30:.2f} GiB ({n} chains x {H} x {W}, split={self.split}), "
                               f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
         self.ref = self.d_cells = self.d_samples = self.hist_counts = self.ring = self.lag_sqdiff = None
-        self.d_probes = self.d_proj = self.probe_cross = self.d_rg = self.residual_sums = None
+        self.d_probes = self.d_proj = self.probe_cross = self.d_rg = self.residual_sums = self.local_cross = None
         for name, shape, dtype, zeroed in table:
             setattr(self, name, (torch.zeros if zeroed else torch.empty)(shape, dtype=dtype, device=eng.dev))
         self.d_g.copy_(torch.as_tensor(g))
@@ -688,6 +842,8 @@ class PosteriorAccumulator:
                 eng.posterior_cross(self.d_g, self.d_proj[t], self.n_probes, self.probe_cross)
         if self.residual is not None and t >= self.dropped:  # the states that mean and sd describe, each scored once
             eng.posterior_residual(self.d_rg, self.residual["levels"], self.residual_sums)
+        if self.n_local and t >= self.dropped:               # the values that mean and sd describe, each paired once
+            eng.posterior_local(self.d_g, self.local["reach"], self.local_cross)
         self.n_added += 1
         self._partials = None
 
@@ -710,8 +866,8 @@ class PosteriorAccumulator:
 
     def local_sums(self):
         """Everything of this accumulator that adds over ranks, as device tensors under the names finalize() takes the sums by:
-        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts, lag_sqdiff, probe_cross and
-        residual_sums."""
+        partials_sum, the sequence count M (one int64) and, where the options ask for them, hist_counts, lag_sqdiff, probe_cross,
+        residual_sums and local_cross."""
         import torch
         out = dict(partials_sum=self.partials(), M=torch.tensor([self.n_sequences], dtype=torch.int64, device=self.d_g.device))
         if self.hist is not None:
@@ -722,6 +878,8 @@ class PosteriorAccumulator:
             out["probe_cross"] = self.probe_cross
         if self.residual is not None:
             out["residual_sums"] = self.residual_sums
+        if self.n_local:
+            out["local_cross"] = self.local_cross
         return out
 
     def sample_values(self):
@@ -733,7 +891,7 @@ class PosteriorAccumulator:
         return None if self.d_proj is None else np.ascontiguousarray(self.d_proj.permute(1, 2, 0).cpu().numpy())
 
     def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None, probe_cross=None, projections=None,
-                 residual_sums=None):
+                 residual_sums=None, local_cross=None):
         """PosteriorSummary from the sums of local_sums() added over ranks (all_reduce_posterior, all_reduce_counts, all_reduce_sum);
         each defaults to this accumulator's own.  projections: [n_chains, K, T] of all ranks' chains (projections(), gathered)."""
         self._require_complete()
@@ -764,29 +922,34 @@ class PosteriorAccumulator:
                                                   "residual sums"),
                         residual_ref=self.residual_ref.copy(), residual_levels=np.asarray(self.residual["levels"], dtype=np.float64),
                         residual_sigma_mc=st["sigma_mc"], residual_mc_mask=np.array(st["mc_mask"], dtype=bool))
+        if self.n_local:
+            meta.update(local_cross=_host_array(self.local_cross if local_cross is None else local_cross, (self.n_local,) + grid, np.float64,
+                                                "local cross sums"),
+                        local_reach=self.local["reach"], local_centre=self.common_ref.copy())
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov", "residual")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov", "residual", "local")
 
 
 def check_options(posterior, n_iter, n_chains=None):
     """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
     n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov, residual")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov, residual, local")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None, residual=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None, residual=None, local=None)
     opt.update(posterior)
     _, N, _ = sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
     opt["ess"] = check_ess(opt["ess"], N, opt["rhat"])
     opt["hist"] = check_hist(opt["hist"])
     opt["cov"] = check_cov(opt["cov"])
     opt["residual"] = check_residual(opt["residual"])
+    opt["local"] = check_local(opt["local"])
     if opt["hist"] is not None and n_chains is not None:
         check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])
     return opt

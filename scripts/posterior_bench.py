@@ -30,7 +30,16 @@
               `posterior`, with it, and with `residual` at thin=100 (--no-end-to-end leaves that out).  The default --out is
               profiles/posterior_bench_residual.json.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K | --residual]
+  --local R [R ...]  only the pass of the covariance with the neighbours (gsm_posterior_local) at 1024 chains of 256 x 256, for every reach
+              given (1 2 4 for the published table), fp64 and fp32 state: (a) the pass, (b) gsm_debug_stream_copy moving the beds'
+              bytes and (c) the composition that needs no new kernel, in torch on the same beds: d = beds - g once, then for each of
+              the K = 2 R^2 + 2 R offsets a sliced multiply and a sum over the chains added to that offset's plane (the beds are read K
+              times over).  (a) and (b) are the median of 20 calls, (c) of 5, three repeats, the three alternating; then the wall
+              time of MCMC_gpu.run_many without `posterior`, with it, and with `local` at every reach given, at thin=100
+              (--no-end-to-end leaves that out).  Counted bytes of (a): the beds, every part's [K, H, W] slab written and read back,
+              `cross` read and written.  The default --out is profiles/posterior_bench_local.json.
+
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K | --residual | --local R ...]
 """
 import argparse
 import json
@@ -338,13 +347,86 @@ def residual_rows(n_chains, H, state, reps, repeats, levels=(2.0, 10.0)):
     return rows
 
 
-def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None, residual=False):
+def local_rows(n_chains, H, state, reaches, reps, repeats):
+    """The pass of the covariance with the neighbours at every reach of `reaches` beside (b) a stream copy of the beds' bytes and (c)
+    the composition in torch that needs no new kernel: K sliced multiply-and-sum passes over d = beds - g.  (a) and (b) are the median
+    of `reps` calls, (c) of 5, `repeats` times over, the three alternating within a repeat.  (a) and (c) are compared on their
+    results too: the same sums within 1e-9 of sum |d||d'| (an fp64 reduction in another order)."""
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd import synthetic
+    from mcmc_gpu_amd.engine import GsmEngine
+    prob, ch, rf = synthetic.template(H)
+    W = H
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        dev, plane, sb = eng.dev, H * W, 8 if state == "f64" else 4
+        n = n_chains * plane
+        bed0 = torch.as_tensor(np.ascontiguousarray(prob["bed"], dtype=np.float64)).to(dev)
+        eng.beds = (bed0[None] + 20.0 * torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        g = bed0.clone()
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        tiles = -(-H // 8) * -(-W // 64)
+        m = sb * n // 16
+        src = torch.ones(m, dtype=torch.float64, device=dev)
+        dst = torch.empty(m, dtype=torch.float64, device=dev)
+        for R in reaches:
+            K = 2 * R * R + 2 * R
+            offs = [(0, dj) for dj in range(1, R + 1)] + [(di, dj) for di in range(1, R + 1) for dj in range(-R, R + 1)]
+            # the cut of the chain axis: the rule of posterior_local_parts (include/gsm.h, posterior_device.h)
+            parts = max(1, min(-(-4 * n_cu // tiles), n_chains, 160 // K, (1 << 27) // (K * plane)))
+            fused_bytes = sb * n + 2 * parts * K * plane * 8 + 2 * K * plane * 8
+            cross = torch.zeros((K, H, W), dtype=torch.float64, device=dev)
+            comp = torch.zeros((K, H, W), dtype=torch.float64, device=dev)
+
+            def composition():
+                d = eng.beds.to(torch.float64) - g
+                for k, (di, dj) in enumerate(offs):
+                    i1, j0, j1 = H - di, max(0, -dj), min(W, W - dj)
+                    comp[k, :i1, j0:j1] += (d[:, :i1, j0:j1] * d[:, di:, j0 + dj:j1 + dj]).sum(dim=0)
+
+            calls = {"a fused local pass": (fused_bytes, reps, lambda: eng.posterior_local(g, R, cross)),
+                     "b stream copy of the beds' bytes": (16 * m, reps, lambda: eng._check(eng.lib.gsm_debug_stream_copy(
+                         C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st))),
+                     "c torch composition, K sliced multiply-and-sum passes": ((1 + 2 * K) * 8 * n + sb * n, min(reps, 5), composition)}
+            med = {name: [] for name in calls}
+            n_calls = {name: 0 for name in calls}
+            for _ in range(repeats):
+                for name, (nbytes, r, fn) in calls.items():
+                    row = _rate(f"{name} (reach {R}, {shape})", nbytes, _timed(fn, r))
+                    n_calls[name] += r + 3
+                    med[name].append(row["ms_median"])
+                    rows.append(row)
+            names = list(calls)
+            # both were added to from zeros, a different number of times: compared per call
+            a, c = cross / n_calls[names[0]], comp / n_calls[names[2]]
+            scale = c.abs().max().item()
+            rows.append({"what": f"local pass summary reach {R} {shape}", "reach": R, "offsets": K, "tiles": tiles, "parts": parts, "bed_bytes": sb * n,
+                         "fma_per_snapshot": K * n, "ms_median_per_repeat": med,
+                         "composition_over_fused": statistics.median(med[names[2]]) / statistics.median(med[names[0]]),
+                         "fused_faster_than_composition_in_all_repeats": all(x < y for x, y in zip(med[names[0]], med[names[2]])),
+                         "fused_over_copy": statistics.median(med[names[0]]) / statistics.median(med[names[1]]),
+                         "largest_difference_from_composition_over_largest_sum": (a - c).abs().max().item() / scale})
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None, residual=False, local=None):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
     prob, ch, rf = synthetic.template(H)
     beds = synthetic.initial_beds(prob, n_chains)
     seeds = list(range(1000, 1000 + n_chains))
-    if residual:
+    if local:
+        configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
+                  [(f"thin={t} rhat=True local reach {R}", dict(burn_in=0, thin=t, local=dict(reach=R))) for t in thins for R in local]
+    elif residual:
         configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
                   [(f"thin={t} rhat=True residual 2 levels", dict(burn_in=0, thin=t, residual=dict(levels=(2.0, 10.0)))) for t in thins]
     elif cov_probes is not None:
@@ -405,7 +487,9 @@ def main():
                     "and run_many with and without cov")
     ap.add_argument("--residual", action="store_true", help="only the fused residual pass beside the pooled pass, its stream copy and the "
                     "composition of existing entry points, and run_many with and without residual")
-    ap.add_argument("--no-end-to-end", action="store_true", help="with --residual: the kernel rows alone")
+    ap.add_argument("--local", type=int, nargs="+", default=None, metavar="R", help="only the pass of the covariance with the neighbours at "
+                    "every reach given, beside the stream copy of the beds and the torch composition, and run_many with and without local")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --residual or --local: the kernel rows alone")
     args = ap.parse_args()
     if args.cov and not 1 <= args.cov <= 15:
         raise SystemExit("--cov takes 1 .. 15 probes")
@@ -413,12 +497,22 @@ def main():
         args.out = str(ROOT / "profiles" / "posterior_bench_cov.json")
     if args.residual and args.out is None and not args.quick:
         args.out = str(ROOT / "profiles" / "posterior_bench_residual.json")
+    if args.local and not all(1 <= R <= 4 for R in args.local):
+        raise SystemExit("--local takes reaches in 1 .. 4")
+    if args.local and args.out is None and not args.quick:
+        args.out = str(ROOT / "profiles" / "posterior_bench_local.json")
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
     rows = []
     if args.hist:
         for state in ("f64", "f32"):
             rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
+    elif args.local:
+        for state in ("f64", "f32"):
+            rows += local_rows(8, 64, state, args.local, 3, 1) if args.quick else local_rows(1024, 256, state, args.local, max(args.reps, 20), args.repeats)
+        if not args.no_end_to_end:
+            rows += end_to_end_rows(64, 8, 1701, [100], 1, local=args.local) if args.quick else \
+                end_to_end_rows(256, 1024, 20001, [100], args.repeats, local=args.local)
     elif args.residual:
         for state in ("f64", "f32"):
             rows += residual_rows(8, 64, state, 3, 1) if args.quick else residual_rows(1024, 256, state, max(args.reps, 20), args.repeats)
