@@ -306,7 +306,8 @@ struct Stream {
   // code everywhere -- and knows the rank its normals start at, whether its window counts at all (no cut before it), and the new
   // rank; the last window that counts hands the state behind its consumed draws to the others through LDS.  A tail start at the
   // head of window 0 is resolved by all wavefronts redundantly with sequential draws (1 normal in 3 700).
-  // A_wl / C_wl: jump constants of THIS lane of THIS wavefront (mult^(64 w + l + 1), inc * G_(64 w + l + 1)); xch: LDS, 2 NW + 4 words.
+  // A_wl / C_wl: jump constants of THIS lane of THIS wavefront (mult^(64 w + l + 1), inc * G_(64 w + l + 1)); xch: LDS, NW + 2 words
+  // (NW words hold the 2 NW ints of info[], the last two the state handed on).
   template <int NW>
   __device__ __forceinline__ void normals_mw(int count, double loc, double scale, double* dst, int lane, int wave, u128 A_wl, u128 C_wl,
                                              uint64_t* xch) {
