@@ -503,6 +503,46 @@ int gsm_krige_grid_local(gsm_handle h, const double* grid, const int32_t* cells,
                          int32_t hw, double radius, int32_t num_points,
                          double* est, double* var, int32_t* n_neighbours, void* stream);
 
+/* ---- kriging cross-validation: leave-one-out, buffered and fold hold-outs (interpolate.cross_validate) ----------------------
+ * Every listed DATA cell of one grid kriged from the other data under a hold-out, in normal-score space, for n_models candidate
+ * variograms at once (gstat's krige.cv / GSLIB's jackknife; the reference has no such function -- search, widening and solve
+ * are its krige's).  gsm_krige_grid with three differences.
+ * The target: cells[k] must HOLD a value (gsm_krige_grid: must not).
+ * The hold-out: cell c conditions target t only if grid[c] is a value, c != t, and
+ *   fold     [dev, H*W] int32 or NULL   not (fold[t] >= 0 and fold[c] == fold[t]): a target in a fold is estimated without
+ *                                       that fold; a negative label means "in no fold" (held out only as the target itself)
+ *   exclude_radius                      not (exclude_radius > 0 and d(c, t) <= exclude_radius), d = sqrt((x_t - x_c)^2 +
+ *                                       (y_t - y_c)^2) as the search computes it, no fused multiply-add.  0 with fold = NULL is
+ *                                       leave-one-out.  Choose it off the lattice distances (2.5 cells on a square grid)
+ * What is left is searched as in gsm_krige_grid, radius widening included: the result for target t equals, bit for bit,
+ * gsm_krige_grid on a copy of the grid with the held-out cells set to NaN -- one copy per fold, but one per TARGET for the
+ * buffer and for leave-one-out, which is why this is a kernel.  The global mean of simple kriging (gsm_sgs_set_kriging) is
+ * taken as given: the mean of all data, the target's included, as the kriging run that follows will use it.
+ * The models: the neighbour set does not depend on the covariance, so each target is searched once and then solved per model.
+ *   n_models                            1 .. 8
+ *   lag_cov  [dev, n_models * (2 lag_mi + 1) * (2 lag_mj + 1)]  model m's table after model m - 1's, one (lag_mi, lag_mj) for all.
+ *                                       Which neighbours a hold-out leaves is not known on the host: pass whole-grid tables
+ *                                       (lag_mi = H - 1, lag_mj = W - 1)
+ *   sill     [HOST, n_models]           sill of each model (read before the launch)
+ *   est, var [dev, n_models * n_cells]  model m's results at m * n_cells + k; var SIGNED as in gsm_krige_grid
+ *   n_neighbours [dev, n_cells]         size of the solved systems, the same for every model
+ * gsm_krige_cv_local: n_models per-cell tables, local [dev, n_models * H*W*6], and vtype [HOST, n_models], each as in
+ * gsm_krige_grid_local (GSM_VTYPE_MATERN: GSM_E_UNSUPPORTED).
+ * Refused before any launch: GSM_E_ARG for a NULL pointer (fold may be NULL), n_cells outside [0, H * W], n_models outside
+ * [1, 8], exclude_radius negative or NaN; num_points, hw, radius, grid sides and the handle as in gsm_krige_grid.
+ * Errors found on the device, GSM_E_DEVICE_DATA with one text per cause: a listed cell outside the grid or holding no value,
+ * and no value anywhere outside a target's hold-out -- est = var = NaN for every model and n_neighbours = 0 at that cell; a lag
+ * table too small ("lag covariance table") and a singular system -- est = var = NaN for that (model, cell) alone.  Everything
+ * else of the call is still completed.  Synchronises the stream. */
+int gsm_krige_cv(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const int32_t* fold,
+                 double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models,
+                 const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius, int32_t num_points,
+                 const double* sill, double* est, double* var, int32_t* n_neighbours, void* stream);
+int gsm_krige_cv_local(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const int32_t* fold,
+                       double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models,
+                       const double* local, const int32_t* vtype, int32_t hw, double radius, int32_t num_points,
+                       double* est, double* var, int32_t* n_neighbours, void* stream);
+
 /* ---- gsm_sgs_grid's path and draws from the callers' OWN NumPy generators ('pcg64' mode of interpolate.sgs) -----------------
  * What interpolate.sgs takes from its numpy.random.Generator(PCG64), made on the device for all R = n_chains realisations side by
  * side (one wavefront each), bit for bit what NumPy returns (mcmc_gpu_amd/csrc/pcg64_device.h):

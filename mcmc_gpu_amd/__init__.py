@@ -5,5 +5,6 @@ Python here is host plumbing; the compute is hand-written HIP for gfx950 in csrc
 C ABI of include/gsm.h (libgsm_hip.so).  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
+from .interpolate import CrossValidation, block_folds, cross_validate, random_folds  # noqa: F401
 
-__all__ = ["_lib", "variogram"]
+__all__ = ["_lib", "variogram", "cross_validate", "CrossValidation", "block_folds", "random_folds"]

@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libgsm_hip.so"
 HEADER = PKG_DIR.parent / "include" / "gsm.h"
-SOURCES = ["gsm_api.hip", "gsm_api_chain.hip", "gsm_api_sgs.hip", "gsm_api_posterior.hip", "gsm_api_variogram.hip", "gsm_version.hip", "step_kernel.hip", "step_flux_kernel.hip", "chain_fused_kernel.hip", "chain_strip_kernel.hip", "proposal_kernel.hip", "cholesky_kernel.hip", "sgs_kernel.hip", "sgs_iter_kernel.hip", "sgs_grid_kernel.hip", "sgs_grid_draw_kernel.hip", "krige_grid_kernel.hip", "pcg64_kernel.hip", "posterior_kernel.hip", "posterior_hist_kernel.hip", "posterior_lag_kernel.hip", "posterior_cov_kernel.hip", "posterior_residual_kernel.hip", "posterior_local_kernel.hip", "variogram_kernel.hip"]
+SOURCES = ["gsm_api.hip", "gsm_api_chain.hip", "gsm_api_sgs.hip", "gsm_api_posterior.hip", "gsm_api_variogram.hip", "gsm_version.hip", "step_kernel.hip", "step_flux_kernel.hip", "chain_fused_kernel.hip", "chain_strip_kernel.hip", "proposal_kernel.hip", "cholesky_kernel.hip", "sgs_kernel.hip", "sgs_iter_kernel.hip", "sgs_grid_kernel.hip", "sgs_grid_draw_kernel.hip", "krige_grid_kernel.hip", "krige_cv_kernel.hip", "pcg64_kernel.hip", "posterior_kernel.hip", "posterior_hist_kernel.hip", "posterior_lag_kernel.hip", "posterior_cov_kernel.hip", "posterior_residual_kernel.hip", "posterior_local_kernel.hip", "variogram_kernel.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                "-Wno-unused-value", "-Wno-unused-result"]
 # per-file extras.  step_flux_kernel: without machine LICM the fp64 polynomial constants of exp() are materialised at
@@ -207,6 +207,9 @@ def load() -> C.CDLL:
     lib.gsm_krige_grid.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, dbl, i32, dbl, vp, vp, vp, vp]
     lib.gsm_sgs_grid_local.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, dbl, i32, i32, vp, vp]
     lib.gsm_krige_grid_local.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, i32, dbl, i32, vp, vp, vp, vp]
+    # sill / vtype of gsm_krige_cv*: HOST arrays of n_models entries
+    lib.gsm_krige_cv.argtypes = [vp, vp, vp, i32, vp, dbl, vp, vp, i32, vp, i32, i32, i32, dbl, i32, C.POINTER(dbl), vp, vp, vp, vp]
+    lib.gsm_krige_cv_local.argtypes = [vp, vp, vp, i32, vp, dbl, vp, vp, i32, vp, C.POINTER(i32), i32, dbl, i32, vp, vp, vp, vp]
     lib.gsm_sgs_grid_draw_pcg64.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp]
     lib.gsm_draw_pcg64.argtypes = [vp, i32, C.POINTER(RfParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.gsm_sgs_state_init.argtypes = [vp, vp, vp, vp, vp, vp]

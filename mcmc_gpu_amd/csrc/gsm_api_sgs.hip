@@ -1,4 +1,4 @@
-// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid and gsm_krige_grid, each with its per-cell-variogram twin (gsm_*_local), and gsm_sgs_grid's draws from NumPy generators (gsm_sgs_grid_draw_pcg64).
+// C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid, gsm_krige_grid and the cross-validation gsm_krige_cv, each with its per-cell-variogram twin (gsm_*_local), and gsm_sgs_grid's draws from NumPy generators (gsm_sgs_grid_draw_pcg64).
 #include "gsm_context.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -238,6 +238,61 @@ extern "C" int gsm_krige_grid_local(gsm_handle h, const double* grid, const int3
   if (int rc = local_vtype_check(h, "gsm_krige_grid_local", vtype)) return rc;
   return krige_grid_run(h, "gsm_krige_grid_local", grid, cells, n_cells, x_axis, y_axis, nullptr, 0, 0, local, vtype, hw, radius,
                         num_points, 0.0, est, var, n_neighbours, stream);
+}
+
+// gsm_krige_cv (lag_cov and sill, local and vtype NULL) and gsm_krige_cv_local (local and vtype, lag_cov and sill NULL; lag_mi, lag_mj
+// unused): n_models tables one after the other, sill / vtype [n_models] on the host
+static const SgsFlagRow kKrigeCvFlags[] = {
+  {kSgsFlagCell, GSM_E_DEVICE_DATA, ": a listed cell outside the grid or holding no value"},
+  {kSgsFlagNoValue, GSM_E_DEVICE_DATA, ": a cell to validate has no value anywhere on the grid outside its hold-out (its fold "
+                                       "holds all the data, or the exclusion radius covers them)"},
+  {kSgsFlagSingular, GSM_E_DEVICE_DATA, ": singular kriging system (a pivot below eps * N * max|diag|)"},
+  {kSgsFlagLagTable, GSM_E_DEVICE_DATA, ": the lag covariance table does not reach the lag between two chosen neighbours "
+                                        "(it must cover twice the widest search radius)"}};
+static int krige_cv_run(gsm_handle h, const std::string& w, const double* grid, const int32_t* cells, int32_t n_cells, const int32_t* fold,
+                        double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models, const double* lag_cov,
+                        int32_t lag_mi, int32_t lag_mj, const double* sill, const double* local, const int32_t* vtype, int32_t hw,
+                        double radius, int32_t num_points, double* est, double* var, int32_t* n_neighbours, void* stream) {
+  if (n_cells < 0 || (int64_t)n_cells > (int64_t)h->H * h->W) return fail(h, GSM_E_ARG, w + ": n_cells must be in [0, H * W]");
+  if (n_models < 1 || n_models > kKrigeCvMaxModels) return fail(h, GSM_E_ARG, w + ": n_models must be in [1, 8]");
+  if (!(exclude_radius >= 0.0)) return fail(h, GSM_E_ARG, w + ": exclude_radius must be >= 0 (0: no buffer around the target)");
+  if (n_cells == 0) return GSM_OK;
+  if (!grid || !cells || !x_axis || !y_axis || (!lag_cov && !local) || (lag_cov && !sill) || (local && !vtype) || !est || !var || !n_neighbours)
+    return fail(h, GSM_E_ARG, w + ": NULL pointer");
+  KrigeCvArgs a{};
+  if (int rc = krige_search_fill(h, w, a.K, x_axis, y_axis, lag_cov, lag_mi, lag_mj, local, 0, hw, radius, num_points, 0.0)) return rc;
+  if (h->H < 2 || h->W < 2 || h->H > 32767 || h->W > 32767) return fail(h, GSM_E_ARG, w + ": grid sides must be in [2, 32767]");
+  if (h->n_chains != 1) return fail(h, GSM_E_ARG, w + ": one grid per handle (create it with n_chains = 1)");
+  if (h->sgs_ktype == GSM_KRIGING_SIMPLE && !h->sgs_gmean) return fail(h, GSM_E_STATE, w + ": simple kriging without a global mean");
+  for (int m = 0; m < n_models; ++m) {
+    if (local) { if (int rc = local_vtype_check(h, w, vtype[m])) return rc; a.vtype[m] = vtype[m]; }
+    else a.sill[m] = sill[m];
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  a.n_cells = n_cells; a.grid = grid; a.cells = cells; a.fold = fold; a.exclude_radius = exclude_radius; a.n_models = n_models;
+  a.model_stride = local ? (int64_t)h->H * h->W * 6 : (int64_t)(2 * lag_mi + 1) * (2 * lag_mj + 1);
+  a.est = est; a.var = var; a.n = n_neighbours;
+  HIPCHK(h, launch_krige_cv(a, st));
+  return sgs_report_flags(h, st, w, kKrigeCvFlags);
+}
+
+extern "C" int gsm_krige_cv(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const int32_t* fold,
+                            double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models, const double* lag_cov,
+                            int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius, int32_t num_points, const double* sill,
+                            double* est, double* var, int32_t* n_neighbours, void* stream) {
+  if (!h) return GSM_E_ARG;
+  return krige_cv_run(h, "gsm_krige_cv", grid, cells, n_cells, fold, exclude_radius, x_axis, y_axis, n_models, lag_cov, lag_mi, lag_mj, sill,
+                      nullptr, nullptr, hw, radius, num_points, est, var, n_neighbours, stream);
+}
+
+extern "C" int gsm_krige_cv_local(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const int32_t* fold,
+                                  double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models, const double* local,
+                                  const int32_t* vtype, int32_t hw, double radius, int32_t num_points, double* est, double* var,
+                                  int32_t* n_neighbours, void* stream) {
+  if (!h) return GSM_E_ARG;
+  return krige_cv_run(h, "gsm_krige_cv_local", grid, cells, n_cells, fold, exclude_radius, x_axis, y_axis, n_models, nullptr, 0, 0, nullptr,
+                      local, vtype, hw, radius, num_points, est, var, n_neighbours, stream);
 }
 
 extern "C" int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const double* x0, const double* x1, const double* x2,

@@ -219,7 +219,7 @@ enum SgsFlag : int32_t {
 constexpr int kSgsMaxPts = 48;      // neighbours of a kriging system
 constexpr int kSgsMaxWin = 1024;    // cells of a block window of the small-scale chain
 // The grid, the variogram and the search of one SGS / kriging call: what sgs_search.h's octant_ring_search and krige_solve_at take
-// (first member of SgsArgs, SgsGridArgs and KrigeGridArgs; filled by gsm_api_sgs.hip's krige_search_fill).
+// (first member of SgsArgs, SgsGridArgs, KrigeGridArgs and KrigeCvArgs; filled by gsm_api_sgs.hip's krige_search_fill).
 struct KrigeSearch {
   int H, W;
   const double* xs;        // [W] x coordinate of every column
@@ -327,6 +327,26 @@ struct KrigeGridArgs {
   const int32_t* cells;    // [n_cells] flat indices of the cells to estimate (each NaN in grid)
 };
 hipError_t launch_krige_grid(const KrigeGridArgs& a, hipStream_t st);
+// interpolate.cross_validate: every listed DATA cell kriged from the other data, under a hold-out, with up to kKrigeCvMaxModels
+// candidate variograms per neighbour search (krige_cv_kernel.hip)
+constexpr int kKrigeCvMaxModels = 8;
+struct KrigeCvArgs {
+  KrigeSearch K;           // gmean [1]; lag / local: model 0's table, model m's `model_stride` doubles further; sill and vtype unused
+  int n_cells;
+  int cell0;               // first entry of `cells` of this launch (set by launch_krige_cv)
+  double* est;             // [n_models][n_cells] kriging estimate, in the order of `cells`; NaN where (model, cell) raised an error
+  double* var;             // [n_models][n_cells] sill - sum w rho, signed
+  int32_t* n;              // [n_cells] size of the solved systems (one neighbour set for all models); 0 where no search succeeded
+  const double* grid;      // [H*W] normal scores, NaN where there is no datum
+  const int32_t* cells;    // [n_cells] flat indices of the cells to validate (each holding a value)
+  const int32_t* fold;     // [H*W] fold label of every cell (negative: in no fold), or nullptr
+  double exclude_radius;   // > 0: cells within this distance of the target condition nothing
+  int n_models;
+  int64_t model_stride;    // doubles between two models' lag tables / per-cell tables
+  double sill[kKrigeCvMaxModels];
+  int vtype[kKrigeCvMaxModels];
+};
+hipError_t launch_krige_cv(const KrigeCvArgs& a, hipStream_t st);
 hipError_t launch_sgs_grid_ranks(const SgsGridArgs& a, int max_path, hipStream_t st);
 hipError_t launch_sgs_grid_segment(const SgsGridArgs& a, hipStream_t st);   // weights, then values of one segment
 // gsm_debug_special: hipErrorInvalidValue for an unknown `which`, a NULL pointer it reads or n outside [1, 2^31 - 256)

@@ -6,6 +6,9 @@ and its deterministic twin, the kriging estimate and spread on the whole grid (k
     sgs_many      many realisations in one call, row r == sgs(..., seed=seeds[r]) bit for bit
     krige         interpolate.krige's arguments and return value, plus `device`
     krige_scores  the same call in normal-score space: estimate, variance and neighbour count per cell
+    cross_validate  every measured cell kriged from the others under a hold-out (leave-one-out, a buffer, folds from
+                  block_folds / random_folds), several candidate variograms per call (gsm_krige_cv, csrc/krige_cv_kernel.hip);
+                  not in the reference
 
 The generator is consumed as the reference consumes it, in its order -- one rng.shuffle of the cells of sim_mask, then one
 standard normal per simulated cell (rng.normal(est, sd, 1) = est + sd * z) or, with bounds, one uniform per simulated cell whose
@@ -45,7 +48,7 @@ import numpy as np
 
 from .sgs import _axes, _generator, lag_cov_table
 
-__all__ = ["sgs", "sgs_many", "krige", "krige_scores"]
+__all__ = ["sgs", "sgs_many", "krige", "krige_scores", "cross_validate", "CrossValidation", "block_folds", "random_folds"]
 
 RECORD_BYTES = 800          # one path cell's record on the device: 48 (value, weight) pairs + a 32-byte header
 WIDEN_STEP = 100e3          # interpolate.py:155
@@ -485,3 +488,289 @@ def krige(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', sim_
     plan = _krige_plan(xx, yy, grid, variogram, radius, num_points, ktype, sim_mask, stencil)
     est_ns, var_ns, _ = _scores(plan, device)
     return _data_maps(plan, est_ns, var_ns)
+
+
+# ---- cross-validation -------------------------------------------------------------------------------------------------------------
+CV_MAX_MODELS = 8            # models per gsm_krige_cv call (kKrigeCvMaxModels); more are sent in groups
+
+
+def block_folds(shape, block=(8, 8), k=5, seed=None, mask=None):
+    """Spatial folds: the grid is cut into blocks of block = (bh, bw) cells (the last row and column of blocks may be smaller),
+    the blocks are shuffled with numpy.random.default_rng(seed) and dealt to the k folds in turn, so the folds hold the same
+    number of blocks to within one.  The hold-out that means something for data on lines: a whole neighbourhood leaves
+    together.  Returns int32 [H, W] labels in 0 .. k - 1; -1 (in no fold) outside `mask` if one is given."""
+    H, W = (int(v) for v in shape)
+    bh, bw = (int(v) for v in block)
+    k = int(k)
+    if H < 1 or W < 1 or bh < 1 or bw < 1:
+        raise ValueError("shape and block must be positive")
+    nbi, nbj = -(-H // bh), -(-W // bw)
+    if not 2 <= k <= nbi * nbj:
+        raise ValueError(f"k must be in [2, number of blocks = {nbi * nbj}]")
+    of_block = np.empty(nbi * nbj, dtype=np.int32)
+    of_block[np.random.default_rng(seed).permutation(nbi * nbj)] = np.arange(nbi * nbj, dtype=np.int32) % k
+    out = np.ascontiguousarray(of_block.reshape(nbi, nbj)[np.arange(H)[:, None] // bh, np.arange(W)[None, :] // bw], dtype=np.int32)
+    if mask is not None:
+        mask = np.asarray(mask, dtype=bool)
+        if mask.shape != (H, W):
+            raise ValueError("mask must have the grid's shape")
+        out[~mask] = -1
+    return out
+
+
+def random_folds(mask, k=5, seed=None):
+    """Random folds of the cells of `mask` (bool [H, W]: the data cells, ~numpy.isnan(grid)): shuffled with
+    numpy.random.default_rng(seed) and dealt to the k folds in turn (equal sizes to within one).  Returns int32 [H, W]
+    labels in 0 .. k - 1, -1 (in no fold) outside the mask."""
+    mask = np.asarray(mask)
+    if mask.ndim != 2 or mask.dtype != np.bool_:
+        raise ValueError("mask must be a 2D bool array")
+    k = int(k)
+    cells = np.flatnonzero(mask)
+    if not 2 <= k <= max(cells.size, 1) or cells.size < 2:
+        raise ValueError(f"k must be in [2, number of cells of the mask = {cells.size}]")
+    out = np.full(mask.size, -1, dtype=np.int32)
+    out[cells[np.random.default_rng(seed).permutation(cells.size)]] = np.arange(cells.size, dtype=np.int32) % k
+    return out.reshape(mask.shape)
+
+
+class CrossValidation:
+    """What cross_validate returns: per validated data cell the held-back value and, per model, the estimate made without it.
+        cells [n]            flat indices (row * W + column) of the validated cells, ascending unless given otherwise
+        names [M]            the models' names
+        z_ns [n]             the held-back values, normal scores
+        est_ns [M, n]        the kriging estimates, normal scores; NaN where a model's system was singular
+        var_ns [M, n]        the kriging variances clipped at 0 (as krige_scores clips them); var_signed: as computed
+        n_neighbours [n]     size of the solved systems (one neighbour set for all models)
+        z, est               the same values and estimates in data units (the transformer's inverse_transform)"""
+
+    def __init__(self, plan, cells, names, est_ns, var_signed, n_neighbours):
+        self.shape = (plan.H, plan.W)
+        self._nst = plan.nst
+        self.cells = np.asarray(cells)
+        self.names = list(names)
+        self.z_ns = plan.grid_ns.ravel()[self.cells] if self.cells.size else np.zeros(0)
+        self.est_ns = np.asarray(est_ns, dtype=np.float64).reshape(len(self.names), self.cells.size)
+        self.var_signed = np.asarray(var_signed, dtype=np.float64).reshape(self.est_ns.shape)
+        self.var_ns = np.where(self.var_signed < 0, 0, self.var_signed)                  # NaN stays NaN
+        self.n_neighbours = np.asarray(n_neighbours, dtype=np.int32)
+
+    def _to_data(self, ns):
+        if ns.size == 0:
+            return ns.copy()
+        return self._nst.inverse_transform(ns.reshape(-1, 1)).reshape(ns.shape)
+
+    @property
+    def z(self):
+        return self._to_data(self.z_ns)
+
+    @property
+    def est(self):
+        return self._to_data(self.est_ns)
+
+    def _index(self, m):
+        return self.names.index(m) if isinstance(m, str) else int(m)
+
+    def error(self, data_units=False):
+        """estimate - held-back value, [M, n]: in normal scores, or in data units."""
+        return self.est - self.z[None, :] if data_units else self.est_ns - self.z_ns[None, :]
+
+    def standardized(self):
+        """error / kriging standard deviation in normal scores, [M, n]; NaN where the (clipped) variance is 0."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.var_ns > 0, self.error() / np.sqrt(self.var_ns), np.nan)
+
+    def maps(self, m=0):
+        """Model m (index or name) scattered to the grid: dict of [H, W] maps est_ns, var_ns, error, standardized (NaN at every
+        cell that was not validated) and n_neighbours (int32, 0 there)."""
+        m = self._index(m)
+        out = {}
+        for key, v in (("est_ns", self.est_ns[m]), ("var_ns", self.var_ns[m]), ("error", self.error()[m]),
+                       ("standardized", self.standardized()[m])):
+            a = np.full(self.shape, np.nan)
+            a.ravel()[self.cells] = v
+            out[key] = a
+        n = np.zeros(self.shape, dtype=np.int32)
+        n.ravel()[self.cells] = self.n_neighbours
+        out["n_neighbours"] = n
+        return out
+
+    def summary(self):
+        """Per model name a dict: n (cells with an estimate), mean_error, mae, rmse (normal scores), rmse_data (data units),
+        mean_standardized, msdr (mean squared standardized error: about 1 where the kriging variance is calibrated), r (Pearson
+        correlation of estimate and held-back score) and coverage95 (share of |standardized error| <= 1.96).  Cells without an
+        estimate (NaN) are left out, and cells with variance 0 out of the three standardized figures; a figure over no cell is
+        NaN."""
+        e, ed, s = self.error(), self.error(data_units=True), self.standardized()
+        out = {}
+        for m, name in enumerate(self.names):
+            ok = np.isfinite(e[m])
+            sm = s[m][np.isfinite(s[m])]
+            nan = float("nan")
+            row = {"n": int(ok.sum())}
+            row["mean_error"] = float(np.mean(e[m][ok])) if ok.any() else nan
+            row["mae"] = float(np.mean(np.abs(e[m][ok]))) if ok.any() else nan
+            row["rmse"] = float(np.sqrt(np.mean(e[m][ok] ** 2))) if ok.any() else nan
+            row["rmse_data"] = float(np.sqrt(np.mean(ed[m][ok] ** 2))) if ok.any() else nan
+            row["mean_standardized"] = float(np.mean(sm)) if sm.size else nan
+            row["msdr"] = float(np.mean(sm ** 2)) if sm.size else nan
+            row["coverage95"] = float(np.mean(np.abs(sm) <= 1.96)) if sm.size else nan
+            a, b = self.est_ns[m][ok], self.z_ns[ok]
+            row["r"] = float(np.corrcoef(a, b)[0, 1]) if ok.sum() >= 2 and np.std(a) > 0 and np.std(b) > 0 else nan
+            out[name] = row
+        return out
+
+    def best(self, by="rmse"):
+        """Name of the model with the smallest mae / rmse / rmse_data, the largest r, or the msdr closest to 1."""
+        s = self.summary()
+        if by in ("rmse", "mae", "rmse_data"):
+            key = lambda n: s[n][by]
+        elif by == "r":
+            key = lambda n: -s[n]["r"]
+        elif by == "msdr":
+            key = lambda n: abs(s[n]["msdr"] - 1.0)
+        else:
+            raise ValueError("by must be 'rmse', 'mae', 'rmse_data', 'r' or 'msdr'")
+        ranked = [n for n in self.names if not math.isnan(key(n))]
+        if not ranked:
+            raise ValueError("no model has an estimate to rank")
+        return min(ranked, key=key)
+
+
+def _cv_models(variogram):
+    """(names, variogram dicts) of cross_validate's `variogram`: one variogram, a dict name -> variogram (variograms(...)[0])
+    or a list of variograms (named '0', '1', ...)."""
+    if isinstance(variogram, dict) and "vtype" in variogram:
+        return [str(variogram["vtype"]).lower()], [variogram]
+    if isinstance(variogram, dict):
+        names, models = [str(k) for k in variogram.keys()], list(variogram.values())
+    elif isinstance(variogram, (list, tuple)):
+        names, models = [str(i) for i in range(len(variogram))], list(variogram)
+    else:
+        raise ValueError("variogram must be a variogram dict, a dict of them or a list of them")
+    if not models or not all(isinstance(v, dict) for v in models):
+        raise ValueError("variogram must hold at least one variogram dict")
+    return names, models
+
+
+def _cv_cells(plan, cells):
+    """The flat indices cross_validate validates: every data cell, those of a bool mask, or the listed ones as they are."""
+    cond = plan.cond.ravel()
+    if cells is None:
+        flat = np.flatnonzero(cond)
+    else:
+        cells = np.asarray(cells)
+        if cells.dtype == np.bool_:
+            if cells.shape != (plan.H, plan.W):
+                raise ValueError("a cells mask must have the grid's shape")
+            flat = np.flatnonzero(cells)
+        elif np.issubdtype(cells.dtype, np.integer) and cells.ndim == 1:
+            flat = cells.astype(np.int64)
+            if flat.size and (flat.min() < 0 or flat.max() >= cond.size):
+                raise ValueError("cells holds an index outside the grid")
+        else:
+            raise ValueError("cells must be None, a bool mask of the grid's shape or a 1D array of flat indices")
+        if not cond[flat].all():
+            raise ValueError("cells lists a cell without a value: only data cells can be validated")
+    return np.ascontiguousarray(flat, dtype=np.int32)
+
+
+def _cv_run(plan, models, cells, fold, exclude_radius, device=None):
+    """gsm_krige_cv / gsm_krige_cv_local on `cells` for the variograms `models` (all scalar or all with maps), CV_MAX_MODELS per
+    call.  Returns est [M, n], the signed variance [M, n] and the neighbour counts [n]."""
+    import torch
+    from .engine import GsmEngine, _ptr
+    H, W, M, n = plan.H, plan.W, len(models), int(cells.size)
+    est, var, cnt = np.full((M, n), np.nan), np.full((M, n), np.nan), np.zeros(n, dtype=np.int32)
+    if n == 0:
+        return est, var, cnt
+    local = plan.local is not None
+    hw = int(math.ceil(plan.radius / abs(plan.dx)))
+    eng = GsmEngine(H, W, 1, device)
+    try:
+        dev, lib, h = eng.dev, eng.lib, eng.h
+        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        per_model = H * W * 6 * 8 if local else (2 * H - 1) * (2 * W - 1) * 8
+        group = min(M, CV_MAX_MODELS)
+        if per_model * group > torch.cuda.mem_get_info(dev)[0] // 4:
+            raise MemoryError(f"the {'per-cell variogram' if local else 'whole-grid lag covariance'} tables of {group} models "
+                              f"({per_model * group} bytes) do not fit the device; pass fewer models per call")
+        d_xs, d_ys, d_gm = f64(plan.xs), f64(plan.ys), f64(np.full(1, plan.global_mean))
+        d_grid = f64(plan.grid_ns)
+        d_cells = torch.as_tensor(cells).to(dev)
+        d_fold = None if fold is None else torch.as_tensor(fold).to(dev)
+        d_n = torch.empty(n, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            eng._check(lib.gsm_sgs_set_kriging(h, 1 if plan.ktype == "sk" else 0, _ptr(d_gm)))
+        for m0 in range(0, M, CV_MAX_MODELS):
+            part = models[m0:m0 + CV_MAX_MODELS]
+            d_est = torch.empty((len(part), n), dtype=torch.float64, device=dev)
+            d_var = torch.empty((len(part), n), dtype=torch.float64, device=dev)
+            head = (h, _ptr(d_grid), _ptr(d_cells), n, _ptr(d_fold), float(exclude_radius), _ptr(d_xs), _ptr(d_ys), len(part))
+            tail = (_ptr(d_est), _ptr(d_var), _ptr(d_n), eng._stream())
+            with torch.cuda.device(dev):
+                if local:
+                    d_tab = f64(np.stack([_local_table(v, (H, W)) for v in part]))
+                    vt = (C.c_int32 * len(part))(*[LOCAL_VTYPES[v["vtype"].lower()] for v in part])
+                    rc = lib.gsm_krige_cv_local(*head, _ptr(d_tab), vt, hw, plan.radius, plan.num_points, *tail)
+                else:
+                    scal = [{k: (v if k == "vtype" else float(v)) for k, v in vv.items()} for vv in part]
+                    d_tab = f64(np.stack([lag_cov_table(v, hw, plan.dx, plan.dy, H - 1, W - 1) for v in scal]))
+                    sill = (C.c_double * len(part))(*[v["sill"] for v in scal])
+                    rc = lib.gsm_krige_cv(*head, _ptr(d_tab), H - 1, W - 1, hw, plan.radius, plan.num_points, sill, *tail)
+            # a singular system leaves NaN at its (model, cell) and the rest of the call complete: keep what was computed
+            est[m0:m0 + len(part)], var[m0:m0 + len(part)] = d_est.cpu().numpy(), d_var.cpu().numpy()
+            eng._check(rc)
+        cnt = d_n.cpu().numpy()
+    finally:
+        eng.close()
+    return est, var, cnt
+
+
+def cross_validate(xx, yy, grid, variogram, radius=100e3, num_points=20, ktype='ok', folds=None, exclude_radius=0.0, cells=None,
+                   device=None):
+    """Kriging cross-validation on the device (gsm_krige_cv, csrc/krige_cv_kernel.hip): every measured cell is kriged from the
+    other measurements and compared with the value that was held back -- gstat's krige.cv, GSLIB's jackknife -- with krige's
+    search, radius widening and solve.  The step between variograms(...) and krige / sgs: which model, which radius and
+    num_points, and whether parameter maps beat one stationary model.
+
+    variogram: one variogram dict, a dict name -> variogram (variograms(...)[0] goes in directly) or a list of them.  All models
+    share one neighbour search per cell; more than eight are sent in groups of eight.  Either every model has scalar parameters
+    or every model has at least one parameter map (ValueError otherwise).
+    The hold-out of a target cell t, beside t itself:
+        folds            int [H, W] labels (block_folds, random_folds): every cell of t's fold; a negative label is "in no fold"
+        exclude_radius   > 0: every cell within this distance (in the units of xx, yy) of t -- the buffered hold-out for data
+                         on lines, where the next cell of t's own line all but predicts it.  Choose it off the grid's distances
+                         (2.5 cell widths on square cells)
+    With neither, plain leave-one-out.  A target that is left no value at all raises GsmError.
+    cells: the data cells to validate, a bool mask or flat indices (row * W + column); default: every data cell.
+
+    The normal-score transformer is fitted ONCE on all data, the target's included (_Plan's), and neither it nor the global
+    mean of simple kriging is refitted per hold-out.  That is the convention here because the transform is marginal -- it
+    carries no spatial information from the target to its estimate -- and because it is the transform the krige / sgs call
+    that follows will use: the errors are those of that call's scores.
+    Cost: the held-out neighbours are not known on the host, so each model gets a covariance table over every lag of the grid,
+    (2H - 1)(2W - 1) * 8 bytes; MemoryError beyond a quarter of the free device memory.
+    Arguments, ValueErrors and NotImplementedErrors otherwise as krige (no stencil; Matern with parameter maps is refused).
+    Returns a CrossValidation."""
+    names, models = _cv_models(variogram)
+    plan = _Plan(xx, yy, grid, models[0], radius, num_points, ktype, None, None, None, None)
+    for v in models[1:]:
+        _sanity_checks(xx, yy, grid, v, radius, num_points, ktype, None)
+    mapped = [any(isinstance(x, np.ndarray) for k, x in v.items() if k != "vtype") for v in models]
+    if any(mapped) and not all(mapped):
+        raise ValueError("the models must all have scalar parameters or all have a parameter map (two calls otherwise)")
+    if all(mapped):
+        for v in models[1:]:
+            _local_table(v, grid.shape)                                               # its errors before any device work
+    if not isinstance(exclude_radius, numbers.Number) or not exclude_radius >= 0:
+        raise ValueError("exclude_radius must be a number >= 0")
+    fold = None
+    if folds is not None:
+        folds = np.asarray(folds)
+        if folds.shape != grid.shape or not np.issubdtype(folds.dtype, np.integer):
+            raise ValueError("folds must be an integer array of the grid's shape")
+        fold = np.ascontiguousarray(np.clip(folds, -1, np.iinfo(np.int32).max), dtype=np.int32).ravel()
+    flat = _cv_cells(plan, cells)
+    est, var, n = _cv_run(plan, models, flat, fold, float(exclude_radius), device)
+    return CrossValidation(plan, flat, names, est, var, n)
