@@ -813,7 +813,8 @@ int gsm_variogram_map(gsm_handle h, const double* fields, int32_t n_fields, cons
 int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream);
 
 /* Test hook: the device's standard-normal pairs (Philox4x32-10 counters (idx, stream, step), Box-Muller with the table-driven
- * log / sincos of the coefficient phase) for idx = idx0 .. idx0 + n - 1: out[2 i], out[2 i + 1] [dev].  Checked against
+ * log / sincos, 53 bits per uniform: normals2, as the nugget pass and the Cholesky generator draw; the coefficient phase's normals4
+ * is reached through gsm_debug_proposal_math) for idx = idx0 .. idx0 + n - 1: out[2 i], out[2 i + 1] [dev].  Checked against
  * oracle/philox_oracle.normals2 (numpy log / sqrt / cos / sin). */
 int gsm_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int32_t n, double* out, void* stream);
 
@@ -845,6 +846,32 @@ enum {
 };
 int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const double* x0, const double* x1, const double* x2, const double* x3,
                       const double* x4, double* out, int32_t* flag, void* stream);
+
+/* Test hook: the scalar arithmetic of the Philox proposal path on the device, element by element, on caller-supplied arguments --
+ * the very inline functions the proposal, chain and Cholesky kernels call (csrc/proposal_device.h, csrc/math_tables.h, csrc/philox.h),
+ * with the math table staged in LDS as those kernels stage it.  Takes no handle.
+ *   which          GSM_PMATH_*: the function, the layout of x0 and of out (below); i < n throughout
+ *   model          GSM_MODEL_* and
+ *   smoothness     the Matern nu (0 stands for 1, as in gsm_rf_params): GSM_PMATH_SPECTRAL_AMP only, ignored otherwise
+ *   x0             [dev] fp64 [n], or uint32 words where the selector says so
+ *   x1, x2, x3     [dev, n] fp64: GSM_PMATH_SPECTRAL_AMP only; may be NULL otherwise
+ *   out            [dev] fp64 (uint32 for GSM_PMATH_PHILOX), n times the selector's values per element
+ * Returns after the stream has drained.  Errors: GSM_E_ARG for an unknown `which`, n < 1 or n >= 2^31 - 256, a NULL x0 / out, and for
+ * GSM_PMATH_SPECTRAL_AMP a NULL x1 / x2 / x3 or an unknown model -- nothing is written then; GSM_E_HIP for a runtime failure.
+ * Checked against mpmath at constructed arguments by tests/test_gpu_proposal_math.py (point sets and bars: tests/proposal_math_common.py). */
+enum {
+  GSM_PMATH_PHILOX = 0,         /* x0 uint32 [n][6] = (seed lo, seed hi, step lo, step hi, stream, idx) -> out uint32 [n][4]: philox_draw */
+  GSM_PMATH_LOG_TAB = 1,        /* x0 = x (positive, finite, normal) -> log_tab(x) */
+  GSM_PMATH_SINCOS_TAB = 2,     /* x0 = u in [0, 1) -> out [n][2] = (sin, cos)(2 pi u) of sincos_tab */
+  GSM_PMATH_SQRT_LEAN = 3,      /* x0 = t in [0, 2^500) -> sqrt_lean(t) */
+  GSM_PMATH_EXP_LEAN = 4,       /* x0 = x -> exp_lean(x) */
+  GSM_PMATH_NORMALS4_WORDS = 5, /* x0 uint32 [n][4] = one Philox block -> out [n][4] = (g1, g2, h1, h2) of normals4 (coefficient phase) */
+  GSM_PMATH_NORMALS2_WORDS = 6, /* x0 uint32 [n][4] = one Philox block -> out [n][2] = (g1, g2) of normals2 / normals2_key */
+  GSM_PMATH_SPECTRAL_AMP = 7,   /* (x0, x1, x2, x3) = (aa, m_kappa, m_const, k2) -> spectral_amp of `model`, `smoothness` */
+  GSM_PMATH_COUNT = 8
+};
+int gsm_debug_proposal_math(int32_t which, int32_t model, double smoothness, int64_t n, const void* x0, const double* x1, const double* x2,
+                            const double* x3, void* out, void* stream);
 
 /* Test hook: one Philox4x32-10 block on the host (ctr[4], key[2] -> out[4]); the device generator uses
  * the same inline function.  Checked against the Random123 known-answer vectors. */

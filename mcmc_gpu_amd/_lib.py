@@ -235,6 +235,7 @@ def load() -> C.CDLL:
     lib.gsm_debug_stream_copy.argtypes = [vp, vp, i64, vp]
     lib.gsm_debug_normals.argtypes = [C.c_uint64, i64, C.c_uint32, C.c_uint32, i32, vp, vp]
     lib.gsm_debug_special.argtypes = [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsm_debug_proposal_math.argtypes = [i32, i32, dbl, i64, vp, vp, vp, vp, vp, vp]
     lib.gsm_philox_selftest.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.gsm_struct_size.argtypes = [i32]
     for which, cls in ((0, RfParams), (1, SgsBatch), (2, Vario)):       # the ctypes restatements of the header's structs have the library's layout

@@ -446,6 +446,17 @@ extern "C" int gsm_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id
   return GSM_OK;
 }
 
+extern "C" int gsm_debug_proposal_math(int32_t which, int32_t model, double smoothness, int64_t n, const void* x0, const double* x1,
+                                       const double* x2, const double* x3, void* out, void* stream) {
+  if (which < 0 || which >= GSM_PMATH_COUNT || n < 1 || n >= ((int64_t)1 << 31) - 256 || !x0 || !out) return GSM_E_ARG;
+  DevBuf<double> tab;
+  if (ensure_mathtab(tab) != hipSuccess) return GSM_E_HIP;
+  const hipError_t e = launch_debug_proposal_math(which, model, smoothness, n, x0, x1, x2, x3, tab.get(), out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return GSM_E_ARG;
+  if (e != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return GSM_E_HIP;
+  return GSM_OK;
+}
+
 extern "C" int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream) {
   if (!src || !dst || n < 0) return GSM_E_ARG;
   return launch_stream_copy(src, dst, n, (hipStream_t)stream) == hipSuccess ? GSM_OK : GSM_E_HIP;

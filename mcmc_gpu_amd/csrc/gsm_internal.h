@@ -411,6 +411,10 @@ hipError_t launch_propose(const ProposeArgs& a, hipStream_t st);
 hipError_t launch_propose_scalars(const ProposeArgs& a, hipStream_t st);
 hipError_t launch_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int n, const double* mathtab, double* out,
                                 hipStream_t st);
+// gsm_debug_proposal_math: hipErrorInvalidValue for an unknown `which`, a NULL pointer it reads, n outside [1, 2^31 - 256) or an
+// unknown model with GSM_PMATH_SPECTRAL_AMP; nothing is launched then
+hipError_t launch_debug_proposal_math(int which, int model, double smoothness, int64_t n, const void* x0, const double* x1, const double* x2,
+                                      const double* x3, const double* mathtab, void* out, hipStream_t st);
 hipError_t launch_k2_tables(const BlockTable& B, const int32_t* k2_off, double resolution, double* k2tab, hipStream_t st);
 hipError_t launch_spectral_from_noise(const ProposeArgs& a, const int32_t* size_idx, const double* rf_scalars, const double* noise_re,
                                       const double* noise_im, const double* nugget_field, hipStream_t st);

@@ -36,7 +36,11 @@ GSM_MT_FN double double_of(uint64_t b) { double x; memcpy(&x, &b, 8); return x; 
 // log(x) for positive, finite, normal x.  x = 2^e m, m in [1, 2); interval i = top 7 mantissa bits; r = m / c_i - 1 in
 // (-1/129, 0] (exactly m / 2 - 1 in the last interval, c = 2); log x = e ln2 + log c_i + log1p(r), log1p by its series to
 // r^7 (next term < 2e-18).  Absolute error < 3e-16 + 2.5e-16 |log x|; for x -> 1 from below (e = -1, c = 2: the first two
-// terms cancel exactly) the error is relative, so sqrt(-2 log u) keeps its accuracy for uniforms next to 1.
+// terms cancel exactly) the error is relative, so sqrt(-2 log u) keeps its accuracy for uniforms next to 1.  At x = 1 itself
+// (e = 0, interval 0, r = 1 / c_0 - 1) the result is exactly 0: the table's log c_0 is the negative of what the series gives there
+// (build_math_tables), 1.2e-17 from the rounded logarithm.  The Box-Muller radius of u == 1 -- a radius word of 0xFFFFFFFF in the
+// 32-bit layout of normals4, probability 2^-32 per draw; 2^-53 in the 53-bit layout of normals2 -- is then sqrt_lean's stand-in
+// for 0 and not sqrt(2.4e-17) = 4.9e-9.
 GSM_MT_FN double log_tab(double x, const double* tab) {
   const uint64_t b = mt::bits_of(x);
   const int e = (int)(b >> 52) - 1023;
@@ -83,6 +87,10 @@ inline void build_math_tables(double* tab) {
     tab[2 * i] = (double)(1.0L / c);
     tab[2 * i + 1] = (i == 127) ? 6.93147180559945286227e-01 : (double)logl(c);     // c = 2: the constant log_tab multiplies e by
   }
+  // log c_0 := -(series at m = 1), so that log_tab(1.0) = (0 ln2 + log c_0) + series = 0 exactly.  The host's fmas round as the
+  // device's do: the same bits come out there.  (log_tab reads tab[0], tab[1] only for this argument.)
+  tab[1] = 0.0;
+  tab[1] = -log_tab(1.0, tab);
   for (int j = 0; j < 64; ++j) {
     const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)j / 64.0L;
     tab[256 + 2 * j] = (j % 32 == 0) ? 0.0 : (double)sinl(ang);

@@ -1,7 +1,8 @@
 // Philox4x32-10 counter-based RNG (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
 // 1, 2, 3", SC'11) for host and gfx950 device code, plus the uniform / Box-Muller conversions the
 // proposal generator uses.  Known-answer vectors of the Random123 distribution are checked in
-// tests/test_philox.py through gsm_philox_selftest().
+// tests/test_host_api.py through gsm_philox_selftest() (host compile) and in tests/test_gpu_proposal_math.py through
+// gsm_debug_proposal_math (device compile of philox_draw).
 //
 // Counter layout used by the sampler (key = 64-bit chain seed):
 //   ctr = { draw index, stream id, absolute step (low 32), absolute step (high 32) }

@@ -14,7 +14,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t pmagic(uint32_t d) { return (uint32_t)(0xFFFFFFFFu / d) + 1u; }
 
-// a * b + C and a * C with the constant C read from a scalar register pair.  Written as inline assembly because the
+// a * b + C, a * C and max(a, C) with the constant C read from a scalar register pair.  Written as inline assembly because the
 // compiler otherwise copies every fp64 literal into a VGPR pair first (two v_mov_b32 per constant, re-done at every use
 // since machine LICM is off for this file): with ~35 polynomial constants per work item that was a tenth of the
 // coefficient phase's vector instructions.  s_mov_b32 on the scalar unit issues beside another wave's vector instruction.
@@ -28,11 +28,22 @@ __device__ __forceinline__ double mul_sc(double a, double C) {
   asm("v_mul_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(C));
   return r;
 }
+__device__ __forceinline__ double max_sc(double a, double C) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(C));
+  return r;
+}
 
-// exp(x) for finite x, |x| < 700 (spectral amplitudes): k = rint(x / ln 2), r = x - k ln2_hi - k ln2_lo (|r| <= 0.3466),
-// degree-12 Taylor polynomial of exp(r) (truncation 1.7e-16 relative), scaled by 2^k with v_ldexp_f64 (which also takes
-// care of underflow towards 0).  About half the instructions of the library routine; error < 1.5 ulp.
+// exp(x) for x <= 709 (spectral amplitudes; the Gaussian model sends x down to -1e4 and far below): k = rint(x / ln 2),
+// r = x - k ln2_hi - k ln2_lo (|r| <= 0.3466), degree-12 Taylor polynomial of exp(r) (truncation 1.7e-16 relative), scaled by 2^k with
+// v_ldexp_f64, which rounds once into the subnormal range and gives 0 from x = -745.2 down.  About half the instructions of the
+// library routine.  Relative error < 1.7e-16 + 3 * 2^-53 = 5.0e-16 (truncation, the rounding of r and of the last two fmas; 3.7e-16 =
+// 2.3 ulp met) where the result is normal, one subnormal spacing more below.  x is raised to -1100 first (the result is 0 from
+// there on): without that, r is no longer small once k ln2_hi stops being exact -- the polynomial overflows and exp_lean(-1e300) was
+// +inf -- and (int)k is out of range below x = -1.5e9 (10 m cells with ranges of a few hundred km), which happened to work because
+// v_cvt_i32_f64 saturates.
 __device__ __forceinline__ double exp_lean(double x) {
+  x = max_sc(x, -1100.0);
   const double kf = __builtin_rint(mul_sc(x, 1.44269504088896338700e+00));
   const double r = fma_sc(kf, -1.90821492927058770002e-10, fma_sc(kf, -6.93147180369123816490e-01, x));
   double p = fma_sc(r, 2.08767569878680989792e-09, 2.50521083854417187751e-08);      // 1/12!, 1/11!
@@ -51,8 +62,9 @@ __device__ __forceinline__ double exp_lean(double x) {
 }
 
 // sqrt(t) for 0 <= t < 2^500 (here t = -2 log u <= 73.5): v_rsq_f64, one Goldschmidt step and one residual correction (error
-// < 1 ulp) -- the library routine's range scaling, special-case selects and second correction left out.  t = 0 (u = 1,
-// probability 2^-53) is raised to 1e-300: the result 1e-150 stands for 0.
+// < 1 ulp) -- the library routine's range scaling, special-case selects and second correction left out.  t = 0 is raised to
+// 1e-300: the result 1e-150 stands for 0.  That is u == 1, where log_tab gives exactly 0 (math_tables.h): probability 2^-32 per
+// draw of normals4 (a radius word of 0xFFFFFFFF), 2^-53 per draw of normals2.
 __device__ __forceinline__ double sqrt_lean(double t) {
   t = fmax(t, 1e-300);
   const double y = __builtin_amdgcn_rsq(t);
@@ -63,7 +75,19 @@ __device__ __forceinline__ double sqrt_lean(double t) {
   return __fma_rn(__fma_rn(-g, g, t), h, g);
 }
 
-// mt: the table of math_tables.h, in LDS
+// mt: the table of math_tables.h, in LDS.  Box-Muller pair from the four words of one Philox block, 53 bits per uniform: (x, y) -> the
+// radius uniform in (0, 1], (z, w) -> the angle uniform in [0, 1).  The body of normals2 and normals2_key; gsm_debug_proposal_math
+// calls it on caller-supplied words.  The words are passed by value: by reference the same instructions come out in another order.
+__device__ __forceinline__ void normals2_words(const u32x4 r, double& g1, double& g2, const double* mt) {
+  const double u1 = u01_open0_from(r.x, r.y);
+  const double u2 = u01_from(r.z, r.w);
+  const double rad = sqrt_lean(-2.0 * log_tab(u1, mt));
+  double s, c;
+  sincos_tab(u2, mt, s, c);
+  g1 = rad * c;
+  g2 = rad * s;
+}
+
 __device__ __forceinline__ void normals2(uint64_t seed, int64_t step, uint32_t stream, uint32_t idx, double& g1,
                                          double& g2, const double* mt) {
   // The 20 round keys are uniform functions of the seed: left alone, the compiler computes them once per kernel and
@@ -72,13 +96,7 @@ __device__ __forceinline__ void normals2(uint64_t seed, int64_t step, uint32_t s
   uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFu), k1 = (uint32_t)(seed >> 32);
   asm volatile("" : "+s"(k0), "+s"(k1));
   const u32x4 r = philox_draw(((uint64_t)k1 << 32) | k0, step, stream, idx);
-  const double u1 = u01_open0_from(r.x, r.y);
-  const double u2 = u01_from(r.z, r.w);
-  const double rad = sqrt_lean(-2.0 * log_tab(u1, mt));
-  double s, c;
-  sincos_tab(u2, mt, s, c);
-  g1 = rad * c;
-  g2 = rad * s;
+  normals2_words(r, g1, g2, mt);
 }
 
 // Four standard normals from ONE Philox block, a 32-bit word per uniform: (x, y) -> (g1, g2), (z, w) -> (h1, h2).  The spectrum's
@@ -86,11 +104,7 @@ __device__ __forceinline__ void normals2(uint64_t seed, int64_t step, uint32_t s
 // quarter of the coefficient phase's instructions and the phase 28 % of the fused kernel's.  2^-32 steps in the uniforms bound
 // |normal| by sqrt(64 ln 2) = 6.66 (probability 2.7e-11 per draw beyond it with exact normals) -- each normal is one of thousands of
 // coefficients of a field that is standardised afterwards.  Restated by oracle/philox_oracle.normals4.
-__device__ __forceinline__ void normals4(uint64_t seed, int64_t step, uint32_t stream, uint32_t idx, double& g1, double& g2,
-                                         double& h1, double& h2, const double* mt) {
-  uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFu), k1 = (uint32_t)(seed >> 32);
-  asm volatile("" : "+s"(k0), "+s"(k1));                       // see normals2
-  const u32x4 r = philox_draw(((uint64_t)k1 << 32) | k0, step, stream, idx);
+__device__ __forceinline__ void normals4_words(const u32x4 r, double& g1, double& g2, double& h1, double& h2, const double* mt) {
   const double ra = sqrt_lean(-2.0 * log_tab(u01_open0_from32(r.x), mt));
   const double rb = sqrt_lean(-2.0 * log_tab(u01_open0_from32(r.z), mt));
   double s, c;
@@ -99,18 +113,19 @@ __device__ __forceinline__ void normals4(uint64_t seed, int64_t step, uint32_t s
   sincos_tab(u01_from32(r.w), mt, s, c);
   h1 = rb * c; h2 = rb * s;
 }
+__device__ __forceinline__ void normals4(uint64_t seed, int64_t step, uint32_t stream, uint32_t idx, double& g1, double& g2,
+                                         double& h1, double& h2, const double* mt) {
+  uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFu), k1 = (uint32_t)(seed >> 32);
+  asm volatile("" : "+s"(k0), "+s"(k1));                       // see normals2
+  const u32x4 r = philox_draw(((uint64_t)k1 << 32) | k0, step, stream, idx);
+  normals4_words(r, g1, g2, h1, h2, mt);
+}
 
 // normals2 for per-LANE seeds (the Cholesky generator's z: every lane of a wave serves another chain)
 __device__ __forceinline__ void normals2_key(uint64_t seed, int64_t step, uint32_t stream, uint32_t idx, double& g1, double& g2,
                                              const double* mt) {
   const u32x4 r = philox_draw(seed, step, stream, idx);
-  const double u1 = u01_open0_from(r.x, r.y);
-  const double u2 = u01_from(r.z, r.w);
-  const double rad = sqrt_lean(-2.0 * log_tab(u1, mt));
-  double s, c;
-  sincos_tab(u2, mt, s, c);
-  g1 = rad * c;
-  g2 = rad * s;
+  normals2_words(r, g1, g2, mt);
 }
 
 // 2*pi*fftfreq(n, d=res)[k] with inv = 1 / (n * res): numpy.fft.fftfreq multiplies the integer frequency by that

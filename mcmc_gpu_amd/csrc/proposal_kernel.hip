@@ -212,7 +212,8 @@ hipError_t launch_spectral_from_noise(const ProposeArgs& a, const int32_t* size_
                                                                                   noise_re, noise_im, nugget_field);
 }
 
-// test hook (gsm_debug_normals): normals2 exactly as the coefficient phase calls it
+// test hook (gsm_debug_normals): normals2 exactly as the nugget pass and the Cholesky generator call it (the coefficient phase draws
+// with normals4: gsm_debug_proposal_math, GSM_PMATH_NORMALS4_WORDS)
 __global__ __launch_bounds__(256) void debug_normals_kernel(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int n,
                                                             const double* __restrict__ mathtab, double* __restrict__ out) {
   __shared__ double mt[kMathTabDoubles];
@@ -227,6 +228,72 @@ __global__ __launch_bounds__(256) void debug_normals_kernel(uint64_t seed, int64
 hipError_t launch_debug_normals(uint64_t seed, int64_t step, uint32_t stream_id, uint32_t idx0, int n, const double* mathtab, double* out,
                                 hipStream_t st) {
   hipLaunchKernelGGL(debug_normals_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seed, step, stream_id, idx0, n, mathtab, out);
+  return hipGetLastError();
+}
+
+// test hook (gsm_debug_proposal_math): the scalar functions of the Philox proposal path, element by element, on caller-supplied
+// arguments -- the very inline functions the kernels call, with the math table read from LDS as they read it
+__global__ __launch_bounds__(256) void debug_proposal_math_kernel(int which, int model, double smoothness, int64_t n, const void* __restrict__ x0,
+                                                                  const double* __restrict__ x1, const double* __restrict__ x2,
+                                                                  const double* __restrict__ x3, const double* __restrict__ mathtab,
+                                                                  void* __restrict__ out) {
+  __shared__ double mt[kMathTabDoubles];
+  for (int i = threadIdx.x; i < kMathTabDoubles; i += 256) mt[i] = mathtab[i];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* xd = (const double*)x0;
+  const uint32_t* xw = (const uint32_t*)x0;
+  double* od = (double*)out;
+  switch (which) {
+    case GSM_PMATH_PHILOX: {
+      const uint32_t* c = xw + 6 * i;      // seed lo, seed hi, step lo, step hi, stream, idx
+      const u32x4 r = philox_draw(((uint64_t)c[1] << 32) | c[0], (int64_t)(((uint64_t)c[3] << 32) | c[2]), c[4], c[5]);
+      uint32_t* ow = (uint32_t*)out + 4 * i;
+      ow[0] = r.x; ow[1] = r.y; ow[2] = r.z; ow[3] = r.w;
+      break;
+    }
+    case GSM_PMATH_LOG_TAB: od[i] = log_tab(xd[i], mt); break;
+    case GSM_PMATH_SINCOS_TAB: {
+      double s, c;
+      sincos_tab(xd[i], mt, s, c);
+      od[2 * i] = s; od[2 * i + 1] = c;
+      break;
+    }
+    case GSM_PMATH_SQRT_LEAN: od[i] = sqrt_lean(xd[i]); break;
+    case GSM_PMATH_EXP_LEAN: od[i] = exp_lean(xd[i]); break;
+    case GSM_PMATH_NORMALS4_WORDS: {
+      const u32x4 r{xw[4 * i], xw[4 * i + 1], xw[4 * i + 2], xw[4 * i + 3]};
+      double g1, g2, h1, h2;
+      normals4_words(r, g1, g2, h1, h2, mt);
+      od[4 * i] = g1; od[4 * i + 1] = g2; od[4 * i + 2] = h1; od[4 * i + 3] = h2;
+      break;
+    }
+    case GSM_PMATH_NORMALS2_WORDS: {
+      const u32x4 r{xw[4 * i], xw[4 * i + 1], xw[4 * i + 2], xw[4 * i + 3]};
+      double g1, g2;
+      normals2_words(r, g1, g2, mt);
+      od[2 * i] = g1; od[2 * i + 1] = g2;
+      break;
+    }
+    default: {      // GSM_PMATH_SPECTRAL_AMP
+      gsm_rf_params P{};
+      P.model = model; P.smoothness = smoothness;
+      PropScalars sc{};
+      sc.aa = xd[i]; sc.m_kappa = x1[i]; sc.m_const = x2[i];
+      od[i] = spectral_amp(P, sc, x3[i], mt);
+      break;
+    }
+  }
+}
+hipError_t launch_debug_proposal_math(int which, int model, double smoothness, int64_t n, const void* x0, const double* x1, const double* x2,
+                                      const double* x3, const double* mathtab, void* out, hipStream_t st) {
+  if (which < 0 || which >= GSM_PMATH_COUNT || n < 1 || n >= ((int64_t)1 << 31) - 256 || !x0 || !out) return hipErrorInvalidValue;
+  if (which == GSM_PMATH_SPECTRAL_AMP &&
+      (!x1 || !x2 || !x3 || (model != GSM_MODEL_GAUSSIAN && model != GSM_MODEL_EXPONENTIAL && model != GSM_MODEL_MATERN)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(debug_proposal_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, which, model, smoothness, n, x0, x1, x2,
+                     x3, mathtab, out);
   return hipGetLastError();
 }
 

@@ -7,7 +7,7 @@ its parity is pinned in two ways:
     numpy.fft.irfft2 instead of the device DFT), tolerance 1e-10 relative to the field scale;
   * in distribution against the reference's spectral proposal restated in mcmc_oracle.spectral_field
     (gstatsMCMC/MCMC.py:176-254), which the golden vectors pin to the reference.
-Philox4x32-10 itself is checked against the Random123 known-answer vectors (tests/test_philox.py).
+Philox4x32-10 itself is checked against the Random123 known-answer vectors (tests/test_host_api.py).
 """
 from __future__ import annotations
 

@@ -107,8 +107,10 @@ def test_tiny_and_odd_shaped_blocks_match_oracle():
 
 
 def test_device_normals_match_oracle():
-    """gsm_debug_normals: the device's Box-Muller pairs (table-driven log / sincos, lean sqrt) against numpy's on the same
-    Philox counters: absolute error < 5e-15 over 2e5 pairs (|normal| <= 8.6), including both streams."""
+    """gsm_debug_normals: the device's Box-Muller pairs of normals2 (53 bits per uniform: the nugget pass and the Cholesky generator;
+    table-driven log / sincos, lean sqrt) against numpy's on the same Philox counters: absolute error < 5e-15 over 2e5 pairs
+    (|normal| <= 8.6), including both streams.  The coefficient phase draws with normals4 (a 32-bit word per uniform): both bodies are
+    held to mpmath at constructed words in tests/test_gpu_proposal_math.py."""
     import ctypes as C
     import torch
     from mcmc_gpu_amd import _lib

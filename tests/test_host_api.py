@@ -19,7 +19,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     names = _lib.declared_symbols()
     assert {"gsm_create", "gsm_destroy", "gsm_set_static", "gsm_set_blocks", "gsm_set_centres", "gsm_init_loss",
             "gsm_residual", "gsm_run_replay", "gsm_propose_philox", "gsm_run_philox", "gsm_last_error",
-            "gsm_version", "gsm_enable_timing", "gsm_last_timing", "gsm_philox_selftest"} <= set(names)
+            "gsm_version", "gsm_enable_timing", "gsm_last_timing", "gsm_philox_selftest", "gsm_debug_proposal_math"} <= set(names)
     for n in names:
         assert hasattr(lib, n), n
     v = lib.gsm_version().decode()
