@@ -587,15 +587,21 @@ def _result_tuples(eng, loss0, loss, acc, blk, n_iter):
     return out
 
 
-def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
-    """The Philox run of run_many advanced from snapshot to snapshot: a run split into stretches reproduces the unsplit run bit
-    for bit (include/gsm.h, gsm_propose_philox), so the snapshots change no chain.  Iteration k is the bed after k proposals."""
+def _accumulator(chain, eng, n_iter, opt):
+    """The PosteriorAccumulator of a large-scale run on `eng` for the checked options `opt`: common_ref defaults to the template's
+    initial bed, the traces are taken at chain.sample_loc."""
     from .posterior import PosteriorAccumulator, default_common_ref
     g = opt['common_ref'] if opt['common_ref'] is not None else default_common_ref(chain.initial_bed)
     ij = chain._sample_indices() if chain.sample_loc is not None else None
-    accum = PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
-                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
-                                 ess=opt['ess'], cov=opt['cov'], residual=opt['residual'], local=opt['local'])
+    return PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
+                                sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
+                                ess=opt['ess'], cov=opt['cov'], residual=opt['residual'], local=opt['local'])
+
+
+def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):
+    """The Philox run of run_many advanced from snapshot to snapshot: a run split into stretches reproduces the unsplit run bit
+    for bit (include/gsm.h, gsm_propose_philox), so the snapshots change no chain.  Iteration k is the bed after k proposals."""
+    accum = _accumulator(chain, eng, n_iter, opt)
     n_chains = eng.n_chains
     parts = [(np.zeros((n_chains, 0)), np.zeros((n_chains, 0), np.uint8), np.zeros((n_chains, 0, 4), np.int32))]
     done = 0                                   # eng.beds holds iteration `done`
@@ -759,7 +765,7 @@ def run_many_replay(chain, RF, initial_beds, rf_states, chain_states, n_iter, ch
 
 
 def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, batch=None, device=None, progress=False, fused=None,
-                   timing=None):
+                   timing=None, posterior=None, return_accumulator=False):
     """The 'pcg64' draw mode: run_many_replay with NO host draws.  Chain c's two NumPy generators (rf_states[c], chain_states[c]:
     `Generator.bit_generator.state` dicts of PCG64 generators) are advanced ON THE DEVICE, bit for bit as NumPy advances them
     (gsm_draw_pcg64: PCG64, the 32-bit half cache of integers(), Lemire's bounded integers, uniform, the ziggurat normal), in
@@ -771,16 +777,28 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
     fused (default: whenever the block table goes to the strip kernels): synthesis and step in ONE kernel per batch
     (gsm_run_noise: the field never leaves the CU) -- bit-identical to the two calls.
     timing: a dict that receives 'loop_seconds' -- the draw / synthesis / step batches alone, chain state resident in HBM
-    (synchronised before and after) -- and 'fused'."""
+    (synchronised before and after) -- and 'fused'.
+    posterior: None, or the dict of run_many (same options, same definitions: iteration k is the bed after k proposals, iteration 0
+    the initial bed).  The batches are cut so that every snapshot iteration ends one, and the snapshot is folded into the
+    accumulators on the stream that stepped the batch, behind its last step; the chains, the records and the generator states are
+    those of the run without it, bit for bit, in the fused and in the two-call form.  The call then returns (results, rf states,
+    chain states, PosteriorSummary), with return_accumulator=True the PosteriorAccumulator in place of the summary (readable after
+    the call: local_sums(), sample_values(), projections(), finalize(), to be merged over ranks first)."""
     import torch
     beds = np.asarray(initial_beds, dtype=np.float64)
     n_chains = beds.shape[0]
     n_iter = _check_args(RF, n_iter, True, n_chains, (rf_states, chain_states), 'RandField and one chain generator state')
     n_steps = n_iter - 1
+    if posterior is not None:
+        from .posterior import check_options
+        posterior = check_options(posterior, n_iter, n_chains=n_chains)
     eng = chain._make_engine(RF, n_chains, device)
+    accum = None
     try:
         dev = eng.dev
         loss0 = eng.set_state(beds)
+        if posterior is not None:
+            accum = _accumulator(chain, eng, n_iter, posterior)
         gens = _Pcg64Streams(eng, chain, RF, list(rf_states), list(chain_states))
         stride = eng.field_stride
         if fused is None:
@@ -809,19 +827,43 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
         ev_drawn = [torch.cuda.Event(), torch.cuda.Event()]
         ev_free = [None, None]
         sizes = [min(batch, n_steps - lo) for lo in range(0, n_steps, batch)]
+        snap_steps = frozenset()                   # the step counts after which eng.beds is a snapshot
+        if accum is not None:
+            from .sgs import batch_plan
+            snap_steps = frozenset(int(k) for k in accum.snapshot_iterations)
+            if n_steps > 0:                        # step j gives iteration j + 1
+                sizes = batch_plan(n_steps, batch, [k - 1 for k in snap_steps if k >= 1])
+
+        def prefix(b, n):
+            """draw buffers for n < batch steps in the leading part of the set b: records are field_stride apart in any layout"""
+            r = n_chains * n
+            cut = lambda t, w: None if t is None else t.view(-1)[:r * w]
+            return dict(size_idx=cut(b['size_idx'], 1), centre=cut(b['centre'], 2), u=cut(b['u'], 1), rf_scalars=cut(b['rf_scalars'], 4),
+                        noise_re=cut(b['noise_re'], stride), noise_im=cut(b['noise_im'], stride), nugget=cut(b['nugget'], stride), n_steps=n)
 
         def draw(k):
             with torch.cuda.stream(s_draw):
                 if ev_free[k & 1] is not None:
                     s_draw.wait_event(ev_free[k & 1])
                 n = sizes[k]
-                d = gens.draw(n, buffers=bufs[k & 1] if n == batch else None)
+                # a shorter batch: the last one draws into buffers of its own; the cuts at snapshots are many and reuse the sets
+                d = gens.draw(n, buffers=bufs[k & 1] if n == batch else prefix(bufs[k & 1], n) if accum is not None else None)
                 ev_drawn[k & 1].record(s_draw)
             return d
+
+        def snapshot():
+            """eng.beds into the accumulators on s_step, behind the steps issued there so far"""
+            with torch.cuda.stream(s_step):
+                ring = accum.ring
+                accum.add()
+                if ring is not None and accum.ring is None:      # released with the last snapshot: s_step still reads it
+                    ring.record_stream(s_step)
 
         torch.cuda.synchronize(dev)
         t0 = time.time()
         done = 0
+        if 0 in snap_steps:
+            snapshot()                             # iteration 0: the initial beds (s_step is behind set_state)
         nxt = draw(0) if sizes else None
         for k, n in enumerate(sizes):
             d = nxt
@@ -839,6 +881,8 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
                 ev_free[k & 1] = torch.cuda.Event()
                 ev_free[k & 1].record(s_step)
             done += n
+            if done in snap_steps:
+                snapshot()
             if progress:
                 s_step.synchronize()
                 print(f"{n_chains} chains: {100 * done / n_steps:3.0f}% | chain-it/s: {n_chains * done / max(time.time() - t0, 1e-9):9.1f}",
@@ -852,9 +896,12 @@ def run_many_pcg64(chain, RF, initial_beds, rf_states, chain_states, n_iter, bat
         blocks = eng.blocks_of(si_all[:, :n_steps].cpu().numpy(), ce_all[:, :n_steps].cpu().numpy())
         rf_out, ch_out = gens.states()
         out = _result_tuples(eng, loss0, loss[:, :n_steps].cpu().numpy(), acc[:, :n_steps].cpu().numpy(), blocks, n_iter)
+        if accum is not None:
+            accum.partials()                       # made while the handle is open; the accumulator keeps them
+            summary = accum if return_accumulator else accum.finalize()
     finally:
         eng.close()
-    return out, rf_out, ch_out
+    return (out, rf_out, ch_out) if accum is None else (out, rf_out, ch_out, summary)
 
 
 def init_lsc_chain_by_instance(param_dict):

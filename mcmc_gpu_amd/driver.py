@@ -173,9 +173,9 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
         steps0 = [int(p['philox']['step']) if (p and 'philox' in p) else 0 for p in prevs]
         seeds = [int(rng_seeds[i]) for i in idx]
         accum = None
-        if posterior is not None and not (mode == 'philox' and len(set(steps0)) == 1):
-            raise ValueError("posterior= is built for Philox mode with all chains at the same Philox step (one shared handle); "
-                             f"this call is mode '{mode}' with steps {sorted(set(steps0))}")
+        if posterior is not None and not (mode == 'pcg64' or (mode == 'philox' and len(set(steps0)) == 1)):
+            raise ValueError("posterior= is built for 'pcg64' mode and for Philox mode with all chains at the same Philox step (one "
+                             f"shared handle); this call is mode '{mode}' with steps {sorted(set(steps0))}")
         if mode == 'philox' and len(set(steps0)) == 1 and posterior is not None:
             dev, accum = MCMC_gpu.run_many(largeScaleChain, rf, beds, seeds, n_iter, batch=batch, step0=steps0[0],
                                            return_device=True, posterior=posterior)
@@ -191,6 +191,11 @@ def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, ou
         elif mode == 'replay':
             local, rf_st, ch_st = MCMC_gpu.run_many_replay(largeScaleChain, rf, beds, rf_st, ch_st, n_iter,
                                                            n_workers=n_workers if n_workers and n_workers > 0 else None)
+            steps1 = steps0
+        elif mode == 'pcg64' and posterior is not None:
+            local, rf_st, ch_st, accum = MCMC_gpu.run_many_pcg64(largeScaleChain, rf, beds, rf_st, ch_st, n_iter, posterior=posterior,
+                                                                 return_accumulator=True)
+            local_sums = accum.local_sums()
             steps1 = steps0
         elif mode == 'pcg64':
             local, rf_st, ch_st = MCMC_gpu.run_many_pcg64(largeScaleChain, rf, beds, rf_st, ch_st, n_iter)
@@ -279,7 +284,8 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     under torchrun (or inside such a rank) the initialised group is used and this process runs its shard.
 
     posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin`, `split`, `rhat`, `common_ref`, `hist`, `ess`, `cov`, `residual`, `local`).  Philox mode with all
-    chains sharing n_iter and the Philox step only (any other combination is a ValueError).  Return value and per-seed
+    chains sharing n_iter and the Philox step, or 'pcg64' mode with all chains sharing n_iter (MCMC_gpu.run_many_pcg64); any other
+    combination is a ValueError.  Return value and per-seed
     checkpoint files are unchanged; rank 0 also writes <output_path>/LargeScaleChain/posterior_{k}k.npz (posterior.
     PosteriorSummary.load reads it; {k}k as in the first chain's bed_{k}k.npy) with the mean, sd and split-R-hat maps over the
     chains of ALL ranks (one all-reduce of [3, H, W]) and the traces at the template's sample points; with `hist` also the
@@ -295,8 +301,8 @@ def largeScaleChain_mp(n_chains, n_workers, largeScaleChain, rf, initial_beds, r
     mode = mode or getattr(largeScaleChain, 'rng_mode', 'replay')
     if posterior is not None:
         from .posterior import check_options
-        if mode != 'philox':
-            raise ValueError(f"posterior= is built for mode 'philox' only (shared-handle runs); got mode '{mode}'")
+        if mode not in ('philox', 'pcg64'):
+            raise ValueError(f"posterior= is built for the modes 'philox' and 'pcg64' (device draws in a shared handle); got mode '{mode}'")
         if len(set(int(v) for v in n_iters[:n_chains])) != 1:
             raise ValueError('posterior= needs the same n_iter for every chain')
         check_options(posterior, n_iters[0], n_chains=n_chains)
@@ -408,7 +414,7 @@ def msc_run_wrapper(param_chain, param_run):
 
 
 def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters,
-                       output_path='./Data/output', mode=None, n_gpus=None):
+                       output_path='./Data/output', mode=None, n_gpus=None, posterior=None):
     """Run n_chains small-scale chains and return the list of their result tuples (reference :211-274); files under
     <output_path>/LargeScaleChain/<lsc seed>/SmallScaleChain/<ssc seed>/ as the reference writes them.  Chains that share
     n_iter run together in one libgsm_hip handle (one workgroup per chain in every launch); `n_workers` is accepted for
@@ -418,18 +424,29 @@ def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_r
     reference's workers do -- results and files follow the CPU driver.  mode 'philox': the draws are made on the device (Philox
     counters keyed by the chain's seed, continuing at the iteration count of the seed folder's checkpoint): no host work per
     iteration.  mode 'pcg64': the draws of 'replay' (each chain's numpy.random.default_rng(its seed) stream, bit for bit) made on the
-    device: the reference's chains and files without host work per iteration."""
-    from . import sgs
+    device: the reference's chains and files without host work per iteration.
+
+    posterior: None, or the dict of sgs.run_many_sgs / MCMC_gpu.run_many, in every mode.  Needs the same n_iter for every chain (in
+    Philox mode the seed folders' iteration counts must agree, as without it) and at least one chain on every rank; anything else
+    is a ValueError before a chain runs or a file is written.  Return value and text checkpoint files are unchanged; rank 0 also
+    writes <output_path>/LargeScaleChain/<lsc seed>/SmallScaleChain/posterior_{k}k.npz (posterior.PosteriorSummary.load reads it;
+    {k}k as in the first chain's bed_{k}k.txt) over the chains of ALL ranks: every additive quantity is summed over the ranks and the
+    traces are gathered, as largeScaleChain_mp does.  The beds are in bed units, trend included.  The summary covers THIS call's
+    segment: iteration 0 is the first iteration of the call, and accumulators are not carried across driver calls."""
     mode_eff = mode or getattr(smallScaleChain, 'rng_mode', 'replay')
-    philox = mode_eff == 'philox'
     if mode not in (None, 'replay', 'philox', 'pcg64'):
         raise ValueError("mode must be 'replay', 'pcg64' or 'philox'")
+    if posterior is not None:
+        from .posterior import check_options
+        if n_chains < 1 or len(set(int(v) for v in n_iters[:n_chains])) != 1:
+            raise ValueError('posterior= needs the same n_iter for every chain')
+        check_options(posterior, n_iters[0], n_chains=n_chains)
     # n_gpus as in largeScaleChain_mp: the chains are independent, so they are sharded contiguously over the ranks (one per
     # GPU, started here when the caller brought no launcher) and the result tuples are gathered at the end
     import os
     import torch.distributed as dist
-    sharded = n_gpus != -1 and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-    if n_gpus != -1 and not sharded and 'RANK' not in os.environ:
+    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    if not sharded and 'RANK' not in os.environ:
         import torch
         if n_gpus is None:
             n_gpus = max(1, torch.cuda.device_count())
@@ -437,15 +454,26 @@ def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_r
         if n_gpus > 1:
             return _self_launch(n_gpus, dict(n_chains=n_chains, n_workers=n_workers, smallScaleChain=smallScaleChain, initial_beds=initial_beds,
                                              ssc_rng_seeds=ssc_rng_seeds, lsc_rng_seed=lsc_rng_seed, n_iters=n_iters,
-                                             output_path=output_path, mode=mode), which='smallScaleChain_mp')
+                                             output_path=output_path, mode=mode, posterior=posterior), which='smallScaleChain_mp')
     if sharded:
         rank, world = dist.get_rank(), dist.get_world_size()
+        if posterior is not None and world > n_chains:
+            raise ValueError(f'posterior= needs at least one chain on every rank: {n_chains} chains on {world} ranks')
         lo, hi = parallel.shard_bounds(n_chains, world, rank)
-        local = smallScaleChain_mp(hi - lo, n_workers, smallScaleChain, list(initial_beds[lo:hi]), list(ssc_rng_seeds[lo:hi]), lsc_rng_seed,
-                                   list(n_iters[lo:hi]), output_path=output_path, mode=mode, n_gpus=-1) if hi > lo else []
+        local = _msc_run_chains(hi - lo, smallScaleChain, list(initial_beds[lo:hi]), list(ssc_rng_seeds[lo:hi]), lsc_rng_seed,
+                                list(n_iters[lo:hi]), output_path, mode_eff, posterior, n_chains) if hi > lo else []
         gathered = [None] * world
         dist.all_gather_object(gathered, local)
         return [r for part in gathered for r in part]
+    return _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters, output_path, mode_eff, posterior,
+                           n_chains)
+
+
+def _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters, output_path, mode, posterior, all_chains):
+    """The n_chains small-scale chains of this process: one libgsm_hip handle for all of them when they share n_iter, otherwise chain
+    by chain through msc_run_wrapper.  all_chains: the chains of all ranks (the posterior summary covers them)."""
+    from . import sgs
+    mode_eff, philox = mode, mode == 'philox'
     tic = time.time()
     base = Path(output_path) / 'LargeScaleChain' / str(lsc_rng_seed)[:6] / 'SmallScaleChain'
     if len(set(int(v) for v in n_iters[:n_chains])) == 1 and n_chains > 0:
@@ -457,11 +485,16 @@ def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_r
         starts = set(p['cumulative'] if p else 0 for p in prevs)
         if philox and len(starts) != 1:
             raise ValueError('Philox mode runs the chains of a call in lock-step: their seed folders must hold the same iteration count')
-        result, _ = sgs.run_many_sgs(smallScaleChain, beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=10, progress_bar=None,
-                                     philox_seeds=[int(v) for v in ssc_rng_seeds[:n_chains]] if philox else None,
-                                     philox_iter0=starts.pop() if philox else 0, pcg64=(mode_eff == 'pcg64'))
+        out = sgs.run_many_sgs(smallScaleChain, beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=10, progress_bar=None,
+                               philox_seeds=[int(v) for v in ssc_rng_seeds[:n_chains]] if philox else None,
+                               philox_iter0=starts.pop() if philox else 0, pcg64=(mode_eff == 'pcg64'), posterior=posterior,
+                               return_accumulator=posterior is not None)
+        result = out[0]
         for i in range(n_chains):
             _msc_save(folders[i], result[i], n_iter, prevs[i])
+        if posterior is not None:
+            # only rank 0 writes, and its first chain is chain 0: the label is that of chain 0's files
+            _merge_posterior(out[2], out[2].local_sums(), all_chains, base, _segment_label(prevs[0], n_iter))
     else:
         if philox:
             raise ValueError('Philox mode needs the same n_iter for every chain of a call')

@@ -33,7 +33,7 @@ from copy import deepcopy
 
 import numpy as np
 
-__all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "sgs", "cov_norm", "lag_cov_table"]
+__all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "batch_plan", "sgs", "cov_norm", "lag_cov_table"]
 
 
 def cov_norm(h, vtype, sill, nugget, s=None):
@@ -362,6 +362,24 @@ def host_draws(chain, rngs, cond_is_data, it0, kb, n):
     return dict(it0=it0, kb=kb, wins=wins, offs=offs, us=us, bases=bases, cells=cells, z=z), blocks
 
 
+def batch_plan(n_iter, batch, snapshot_iterations=None):
+    """The sizes of the batches that n_iter iterations are run in: at most `batch` iterations each, and every snapshot iteration
+    (posterior=) is the last iteration of its batch, so that the chains' state after it is on the device when the batch ends.
+    Without snapshots: full batches and one shorter last one."""
+    n_iter, batch = int(n_iter), int(batch)
+    if n_iter < 1 or batch < 1:
+        raise ValueError("n_iter and batch must be >= 1")
+    ends = [] if snapshot_iterations is None else sorted({int(k) + 1 for k in snapshot_iterations if 0 <= int(k) < n_iter})
+    sizes, done, e = [], 0, 0
+    while done < n_iter:
+        while e < len(ends) and ends[e] <= done:
+            e += 1
+        end = min(done + batch, n_iter, ends[e] if e < len(ends) else n_iter)
+        sizes.append(end - done)
+        done = end
+    return sizes
+
+
 # The draws of some iterations as gsm_sgs_iterate / gsm_sgs_blocks_batch read them.  Device draws: views of a buffer set, blk the
 # block records, cell counts in cnt, off_stride n.  Uploaded host draws: blk and cnt None, off_stride n + 1, cell_base on the host.
 _Draws = namedtuple('_Draws', 'win blk off cnt cells z us off_stride cell_base')
@@ -374,16 +392,26 @@ class _SgsRun:
     windowed, batch, grid_finite, the draw source ('replay', 'pcg64' or 'philox').
     Device state (None where it does not apply): cur / nxt / prop, resampled, d_loss / d_bad, d_lprev / d_acc, d_energy / d_state
     (windowed iteration end), d_q / d_ref (transformer tables), d_region / d_isdata, d_gen or d_seeds and the draw buffer sets.
-    Records: loss_cache, step_cache, blocks_cache, bed_cache, sample_values."""
+    Records: loss_cache, step_cache, blocks_cache, bed_cache, sample_values.
+    posterior (checked options or None): sizes, the batch sizes of the run (batch_plan: a snapshot iteration ends its batch), snap_its,
+    accum (posterior.PosteriorAccumulator on this run's handle) and snap, the scratch tensor of a snapshot in bed units."""
 
     def __init__(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source,
-                 philox_seeds, philox_iter0):
+                 philox_seeds, philox_iter0, posterior=None):
         from .engine import GsmEngine
         self._plan(chain, initial_beds, rngs, int(n_iter), only_save_last_bed, source)
         self.info_per_iter, self.progress_bar, self.philox_iter0 = max(int(info_per_iter), 1), progress_bar, int(philox_iter0)
+        self.snap_its = frozenset()
+        if posterior is not None:
+            from .posterior import snapshot_iterations
+            self.snap_its = frozenset(int(k) for k in snapshot_iterations(self.n_iter, posterior['burn_in'], posterior['thin']))
+        self.sizes = batch_plan(self.n_iter, self.batch, self.snap_its)
+        self.accum = self.snap = None
         self.eng = GsmEngine(self.H, self.W, self.n, device)
         try:
             self._device_state(philox_seeds)
+            if posterior is not None:
+                self._posterior_state(posterior)
         except BaseException:
             self.eng.close()
             raise
@@ -505,6 +533,40 @@ class _SgsRun:
             self.draw_sets.append(dict(win=i32(kn * 4), blk=i32(kn * 4), off=i32(kn), cnt=i32(kn), cells=i32(kn * self.max_cells, 2),
                                        z=torch.empty(kn * self.max_cells, dtype=torch.float64, device=dev),
                                        us=torch.empty(kn, dtype=torch.float64, device=dev)))
+
+    def _posterior_state(self, opt):
+        """The accumulator of the snapshots on this run's handle (set_static was called: `residual` has its fields).  Sample traces
+        are taken at chain.sample_loc, of the beds in bed units."""
+        import torch
+        from .posterior import PosteriorAccumulator, default_common_ref
+        chain, eng = self.chain, self.eng
+        g = opt['common_ref'] if opt['common_ref'] is not None else default_common_ref(chain.initial_bed)
+        self.accum = PosteriorAccumulator(eng, self.n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
+                                          sample_cells=None if self.ij is None else self.ij[:, 0] * self.W + self.ij[:, 1],
+                                          sample_loc=chain.sample_loc, hist=opt['hist'], ess=opt['ess'], cov=opt['cov'],
+                                          residual=opt['residual'], local=opt['local'])
+        if self.trend is not None or self.bed_host is not None:
+            self.snap = torch.empty((self.n, self.H, self.W), dtype=torch.float64, device=self.dev)
+
+    def snapshot(self, it, st):
+        """If iteration `it` is a snapshot: the chains' state after its decision, in bed units (what store_bed keeps in
+        bed_cache[:, it]), folded into the accumulator on stream st.  `cur` is detrended: cur + trend is ONE fp64 add on the device,
+        the bits of NumPy's add; a host-side transformer's state is uploaded.  The caller orders st behind the iteration and ahead
+        of whatever writes `cur` next."""
+        if it not in self.snap_its:
+            return
+        import torch
+        accum = self.accum
+        with torch.cuda.stream(st):
+            if self.bed_host is not None:
+                self.snap.copy_(torch.as_tensor(self.bed_host + self.trend if self.trend is not None else self.bed_host))
+            elif self.snap is not None:
+                torch.add(self.cur, self.d_trend, out=self.snap)
+            self.eng.beds = self.snap if self.snap is not None else self.cur
+            ring = accum.ring
+            accum.add()
+            if ring is not None and accum.ring is None:          # released with the last snapshot: st still reads it
+                ring.record_stream(st)
 
     # ---- the library calls, each on the stream it is given -----------------------------------------------------------------
     def qt(self, src, dst, inverse, st):
@@ -628,26 +690,27 @@ class _SgsRun:
         """Batch b iterates on the side stream while (two buffer sets) batch b + 1 is drawn on the draw stream; with one set the next
         draws follow the batch's record download.  kb is 1 with per-iteration bed records."""
         import torch
-        n, n_iter, batch, dev, sets = self.n, self.n_iter, self.batch, self.dev, self.draw_sets
-        kmax = min(batch, n_iter)
+        n, n_iter, sizes, dev, sets = self.n, self.n_iter, self.sizes, self.dev, self.draw_sets
+        kmax = max(sizes)
         b_lrec = torch.empty(n * kmax, dtype=torch.float64, device=dev); b_arec = torch.empty(n * kmax, dtype=torch.uint8, device=dev)
         main = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(main)
         draw_st = torch.cuda.Stream(dev) if len(sets) == 2 else side
         draw_st.wait_stream(main)
-        self.draw(0, kmax, sets[0], draw_st)
+        self.draw(0, sizes[0], sets[0], draw_st)
         it_done = n_batch = 0
         while it_done < n_iter:
-            kb = min(batch, n_iter - it_done)
+            kb = sizes[n_batch]
             d = self.views(sets[n_batch % len(sets)], kb)
             d_lrec, d_arec = b_lrec[:n * kb].view(n, kb), b_arec[:n * kb].view(n, kb)
             side.wait_stream(draw_st)                                  # this batch's draws
-            nxt_kb = min(batch, n_iter - it_done - kb)
+            nxt_kb = sizes[n_batch + 1] if n_batch + 1 < len(sizes) else 0
             if nxt_kb > 0 and len(sets) == 2:                          # the other set: the batch that used it is over (its records were downloaded)
                 self.draw(it_done + kb, nxt_kb, sets[(n_batch + 1) % 2], draw_st)
             self.iterate(d, kb, d_lrec, d_arec, side)
             self.check(side)
+            self.snapshot(it_done + kb - 1, side)                      # ahead of the next batch on the same stream
             with torch.cuda.stream(side):
                 lrec_h, arec_h, blk_h = d_lrec.cpu().numpy(), d_arec.cpu().numpy(), d.blk.cpu().numpy()
             if nxt_kb > 0 and len(sets) == 1:
@@ -667,13 +730,13 @@ class _SgsRun:
         and the record download of batch b come after the draws of b + 1."""
         import torch
         st = torch.cuda.current_stream(self.dev)
-        running = self._launch(self.host_draws(0, min(self.batch, self.n_iter)), st)
+        running = self._launch(self.host_draws(0, self.sizes[0]), st)
         it_done = running[1]
-        while it_done < self.n_iter:
-            hd = self.host_draws(it_done, min(self.batch, self.n_iter - it_done))      # overlaps the device work of `running`
+        for kb in self.sizes[1:]:
+            hd = self.host_draws(it_done, kb)                          # overlaps the device work of `running`
             self._finish(running, st)
             running = self._launch(hd, st)
-            it_done += running[1]
+            it_done += kb
         self._finish(running, st)
 
     def _launch(self, hd, st):
@@ -688,6 +751,7 @@ class _SgsRun:
     def _finish(self, running, st):
         it0, kb, _, d_lrec, d_arec = running
         self.check(st)
+        self.snapshot(it0 + kb - 1, st)                                # ahead of the next batch's launch
         self.store(it0, kb, d_lrec.cpu().numpy(), d_arec.cpu().numpy())
         self.progress(it0 + kb)
 
@@ -721,6 +785,7 @@ class _SgsRun:
             self.loss_prev = np.where(acc, loss_next, self.loss_prev)
             self.store(it, 1, self.loss_prev[:, None], acc[:, None])
             self.store_bed(it)
+            self.snapshot(it, st)
             if it % self.info_per_iter == 0 or it == self.n_iter - 1:
                 self.progress(it + 1)
 
@@ -761,13 +826,27 @@ class _SgsRun:
 
 
 def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=100, progress_bar=None, device=None,
-                 philox_seeds=None, philox_iter0=0, pcg64=False):
+                 philox_seeds=None, philox_iter0=0, pcg64=False, posterior=None, return_accumulator=False):
     """n small-scale chains of one template (same static fields, variogram, block sizes) in ONE handle.  rngs: one NumPy
     Generator per chain (consumed exactly as chain_sgs.run consumes chain.rng).  philox_seeds (one 64-bit key per chain): Philox
     mode -- the draws of iterations philox_iter0 .. are made on the device and rngs are not touched.  pcg64=True: the draws of
     replay mode (rngs' own PCG64 streams, bit for bit) are made on the device and the generators are left where NumPy would leave
     them.
-    Returns (list of result tuples, rngs)."""
+    Returns (list of result tuples, rngs).
+
+    posterior: None, or the dict of MCMC_gpu.run_many (`burn_in`, `thin` and optionally `split`, `rhat`, `common_ref`, `hist`, `ess`,
+    `cov`, `residual`, `local`; mcmc_gpu_amd/posterior.py), in every draw mode and with every transformer kind.  Snapshot k, for the
+    iterations k = burn_in, burn_in + thin, ... < n_iter, is all chains' state after iteration k's decision in bed units, trend
+    included: the bed that only_save_last_bed=False stores at bed_cache[:, k].  A snapshot iteration ends its batch (batch_plan) and
+    is folded into the accumulators on the device where the batch ran; no bed comes to the host for it.  `common_ref` defaults to
+    the template's initial bed, `residual` uses the template's static fields.  With chain.sample_loc set the summary's
+    sample_values [n, points, T] are the thinned traces of those beds, trend included, while the per-iteration sample_values of
+    the result tuples stay the detrended values they are without `posterior` (and, as without it, sample points mean one
+    iteration per batch).  The call then returns (results, rngs,
+    PosteriorSummary), or with return_accumulator=True the PosteriorAccumulator in place of the summary: its local_sums(),
+    sample_values(), projections() and finalize() are readable after the call, to be merged over ranks first.  The chains are
+    those of the run without `posterior`: beds, accept masks, blocks, counts and generator states bit for bit; the losses bit for
+    bit with device draws and to the agreement of the batched with the one-by-one path (1e-12 relative) with host draws."""
     n = len(initial_beds)
     if len(rngs) != n:
         raise ValueError('need one random generator per chain')
@@ -775,8 +854,12 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
         raise ValueError("choose one of philox_seeds / pcg64")
     if philox_seeds is not None and len(philox_seeds) != n:
         raise ValueError('need one Philox seed per chain')
+    if posterior is not None:
+        from .posterior import check_options
+        posterior = check_options(posterior, n_iter, n_chains=n)
     source = 'pcg64' if pcg64 else 'philox' if philox_seeds is not None else 'replay'
-    run = _SgsRun(chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source, philox_seeds, philox_iter0)
+    run = _SgsRun(chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source, philox_seeds, philox_iter0,
+                  posterior=posterior)
     try:
         if run.source != 'replay' and run.transformer != 'host_nst':
             run.drive_device_draws()                 # batch is 1 with keep_all / track
@@ -784,7 +867,12 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
             run.drive_host_draw_batches()            # batch is 1 with a host-side transformer, keep_all / track or GSM_SGS_BATCH=1
         else:
             run.drive_one_by_one()                   # a host-side transformer in any draw mode; replay with batch 1
-        return run.results(), rngs
+        if run.accum is None:
+            return run.results(), rngs
+        if return_accumulator:
+            run.accum.partials()                     # made while the handle is open; the accumulator keeps them
+            return run.results(), rngs, run.accum
+        return run.results(), rngs, run.accum.finalize()
     finally:
         run.close()
 
