@@ -78,6 +78,8 @@ const char* gsm_last_error(gsm_handle h);
  * dtype: 0 = fp64 state; 1 = fp32 state with fp64 arithmetic (beds and energy are float arrays; every value is
  * rounded to float before it is used, so the carried loss sum always equals the sum of what is stored --
  * BASELINE configs[4]; the reference's torch class is all-fp32, MCMC_gpu.py:261).
+ * H, W >= 1; a handle whose grid has a side below 3 cells serves gsm_gaussian_filter alone (axes of one or two cells are cases of
+ * its reflection) and every other entry point returns GSM_E_ARG on it: their stencils and searches need 3 x 3 cells.
  * Replaces: the per-process chain construction of lsc_run_wrapper
  * (largeScaleChain_multiprocessing_GPU.py:126-127) -- one handle holds all chains of one GPU. */
 int gsm_create(gsm_handle* out, int32_t H, int32_t W, int32_t n_chains, int32_t dtype, int32_t device);
@@ -402,6 +404,23 @@ int gsm_sgs_commit_map(gsm_handle h, double* cur, const double* proposed, uint32
 int gsm_sgs_commit(gsm_handle h, double* cur, double* next, uint32_t* resampled, const int32_t* windows,
                    const uint8_t* accept, void* stream);
 
+/* Chain groups of the small-scale chain: chains that continue DIFFERENT large-scale beds in one handle.  The reference's driver
+ * derives the trend, the normal-score transformer and the transformed conditioning data from the large-scale bed it starts from
+ * (smallScaleChain_multiprocessing.py:479-496), so they belong to the bed, not to the problem.  group [HOST, n_chains]: the group of
+ * every chain, each in [0, n_groups) (GSM_E_ARG otherwise; nothing changes then); the values are copied.  While groups are set, these
+ * arguments hold one plane or table per GROUP and chain c reads the one of group[c]:
+ *   trend                      [dev, n_groups*H*W]   gsm_sgs_loss, gsm_sgs_state_init, gsm_sgs_finish, gsm_sgs_iterate (batch->trend)
+ *   zcond                      [dev, n_groups*H*W]   gsm_sgs_blocks, gsm_sgs_blocks_batch, gsm_sgs_iterate (batch->zcond)
+ *   quantiles, references      [dev, n_groups*nq]    gsm_qt_transform, gsm_sgs_iterate (batch->qt_quantiles, batch->qt_references; one nq)
+ * (NULL keeps its meaning).  gsm_qt_transform then takes whole maps of all chains only: n == n_chains * H * W, anything else is
+ * GSM_E_ARG (and at most 65535 chains).  Every result of chain c equals, bit for bit, the result of the same call on a handle that
+ * holds only the chains of group[c] and is given that group's plane and tables.  gsm_sgs_batch keeps its layout: the groups live in
+ * the handle.  group == NULL or n_groups == 1 removes the groups; with none set every entry point runs the kernels it ran before
+ * groups existed, on the caller's pointers.  Waits for the device (the table may be in use).  Groups of a handle whose chains do
+ * not all share one variogram are out of scope: the reference asks for one consistent V1_p.
+ * Replaces: one process per large-scale bed in smallScaleChain_multiprocessing.py (:479-496 run once per bed). */
+int gsm_sgs_set_groups(gsm_handle h, const int32_t* group, int32_t n_groups);
+
 /* Kriging type of the gsm_sgs_blocks* calls that follow on this handle.  GSM_KRIGING_ORDINARY (the default; what
  * chain_sgs.run uses, MCMC.py:1774 passes no ktype): ok_solve, the (n+1) x (n+1) system with the Lagrange row, estimate around
  * the LOCAL mean of the neighbours (_krige.py:5-44).  GSM_KRIGING_SIMPLE: sk_solve, Sigma w = rho, estimate
@@ -617,6 +636,30 @@ int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* batch, int32_t n_iters, v
  * chain_crf.set_crf_data_weight (MCMC.py:689-714, :1124-1134). */
 int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, const uint8_t* mask, double* dist,
                            void* stream);
+
+/* Gaussian trend of a stack of beds: out[r] = scipy.ndimage.gaussian_filter(x[r], sigma, mode='reflect', truncate=t) for the
+ * n fields x [dev, n*H*W] at once (H, W must be the handle's; n is the call's own and need not be n_chains), fp64, out [dev, n*H*W]
+ * must not alias x.  Asynchronous on `stream`.
+ *   w0 [HOST, 2 lw0 + 1], w1 [HOST, 2 lw1 + 1]   the weights of axis 0 (down the rows) and axis 1 (along a row), read before the
+ *                                       call returns.  The caller makes them in scipy's NumPy arithmetic (_gaussian_kernel1d):
+ *                                       lw = int(truncate * sigma + 0.5), x = arange(-lw, lw + 1), phi = exp(-0.5 / sigma^2 * x^2),
+ *                                       w = phi / phi.sum().  The device evaluates no exponential.  0 <= lw <= 128
+ * Passes as in scipy: axis 0 first, then axis 1 on its result.  Each pass, for every cell i of its axis of n cells:
+ *   acc = 0;  for k = 0, 1, .. 2 lw in this order:  acc = fma(w[k], x[refl(i + k - lw)], acc)
+ * one fused multiply-add per tap into one accumulator; refl is the half-sample-symmetric reflection of period 2 n
+ * (d c b a | a b c d | d c b a), folded as often as it takes (n < lw, n = 1).  scipy pairs the symmetric taps instead: the two agree
+ * to within the rounding of either order ((2 lw0 + 2 lw1 + 6) * 2^-53 times the filter of |x|, tests/trend_common.py), not bit for bit.
+ * The order is the same for every cell and no sum is split or shared: field r of a batch has the bits of the one-field call, and
+ * the same call twice gives the same bits.  No atomics.  NaN and infinities propagate by this arithmetic alone (the cells within
+ * lw of a NaN along either pass).
+ * Scratch: the result of the axis-0 pass, n*H*W doubles, is owned by the handle (grow-only, released by gsm_destroy; growing it
+ * frees the smaller buffer, which waits for the device).
+ * Errors (GSM_E_ARG, nothing launched): a NULL pointer, out == x, n < 1, H or W not the handle's, lw0 or lw1 outside [0, 128], H * W
+ * above 2^30, n * H * W beyond one launch's 2^31 workgroups.
+ * Replaces: trend = sp.ndimage.gaussian_filter(initial_bed, sigma=10) (smallScaleChain_multiprocessing.py:486) for every
+ * large-scale bed of an ensemble at once; scipy/ndimage/_filters.py gaussian_filter, gaussian_filter1d, correlate1d. */
+int gsm_gaussian_filter(gsm_handle h, const double* x, double* out, int32_t n, int32_t H, int32_t W, const double* w0, int32_t lw0,
+                        const double* w1, int32_t lw1, void* stream);
 
 /* ---- posterior accumulator: moments of the bed over all chains and a thinned set of iterations --------------------------
  * The reference looks inside a run through host caches of one chain: bed_cache[i] = bed_c (only_save_last_bed=False,

@@ -21,7 +21,7 @@ extern "C" const char* gsm_last_error(gsm_handle h) { return h ? h->err.c_str() 
 extern "C" int gsm_create(gsm_handle* out, int32_t H, int32_t W, int32_t n_chains, int32_t dtype, int32_t device) {
   if (!out) return fail(nullptr, GSM_E_ARG, "gsm_create: out is NULL");
   *out = nullptr;
-  if (H < 3 || W < 3 || n_chains < 1) return fail(nullptr, GSM_E_ARG, "gsm_create: need H,W >= 3 and n_chains >= 1");
+  if (H < 1 || W < 1 || n_chains < 1) return fail(nullptr, GSM_E_ARG, "gsm_create: need H,W >= 1 and n_chains >= 1");
   if ((int64_t)H * W > (1LL << 30)) return fail(nullptr, GSM_E_ARG, "gsm_create: grid too large");
   if (dtype != 0 && dtype != 1) return fail(nullptr, GSM_E_UNSUPPORTED, "gsm_create: dtype must be 0 (fp64 state) or 1 (fp32 state)");
   int ndev = 0;
@@ -51,7 +51,7 @@ extern "C" int gsm_set_static(gsm_handle h, const double* surf, const double* ve
                               const double* dhdt, const double* smb, const double* crf_weight,
                               const uint8_t* update_mask, const uint8_t* mc_mask, double resolution,
                               double sigma_mc, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!surf || !velx || !vely || !dhdt || !smb || !update_mask || !mc_mask)
     return fail(h, GSM_E_ARG, "gsm_set_static: NULL field");
   if (!(resolution > 0.0) || !(sigma_mc > 0.0)) return fail(h, GSM_E_ARG, "gsm_set_static: resolution and sigma_mc must be > 0");
@@ -122,7 +122,7 @@ extern "C" int gsm_set_static(gsm_handle h, const double* surf, const double* ve
 
 extern "C" int gsm_set_blocks(gsm_handle h, int32_t n_sizes, const int32_t* bh, const int32_t* bw,
                               const double* edge_masks_packed, const int64_t* mask_offsets, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (n_sizes < 1 || !bh || !bw) return fail(h, GSM_E_ARG, "gsm_set_blocks: empty block table");
   if (n_sizes > 64) return fail(h, GSM_E_UNSUPPORTED, "gsm_set_blocks: at most 64 block sizes");
   hipStream_t st = (hipStream_t)stream;
@@ -287,7 +287,7 @@ extern "C" int gsm_set_blocks(gsm_handle h, int32_t n_sizes, const int32_t* bh, 
 }
 
 extern "C" int gsm_set_centres(gsm_handle h, const int32_t* cells, int32_t n_cells, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!cells || n_cells < 1) return fail(h, GSM_E_ARG, "gsm_set_centres: empty centre list");
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(h, hipSetDevice(h->device));
@@ -299,7 +299,7 @@ extern "C" int gsm_set_centres(gsm_handle h, const int32_t* cells, int32_t n_cel
 }
 
 extern "C" int gsm_init_loss(gsm_handle h, const void* beds, void* energy, double* loss_sum, double* loss0, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_init_loss: call gsm_set_static first");
   if (!beds || !energy || !loss_sum) return fail(h, GSM_E_ARG, "gsm_init_loss: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
@@ -308,7 +308,7 @@ extern "C" int gsm_init_loss(gsm_handle h, const void* beds, void* energy, doubl
 }
 
 extern "C" int gsm_residual(gsm_handle h, const double* beds, double* residual, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_residual: call gsm_set_static first");
   if (!beds || !residual) return fail(h, GSM_E_ARG, "gsm_residual: NULL pointer");
   if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_residual: fp64 beds only (create the handle with dtype 0)");
@@ -324,7 +324,7 @@ int gsm::strip_for(gsm_handle h) {
 }
 
 extern "C" int gsm_strip_active(gsm_handle h) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static || !h->have_blocks) return fail(h, GSM_E_STATE, "gsm_strip_active: call gsm_set_static and gsm_set_blocks first");
   return strip_for(h);
 }
@@ -352,7 +352,7 @@ hipError_t gsm::ensure_mathtab(DevBuf<double>& d) {
 
 extern "C" int gsm_cov_assemble(gsm_handle h, int32_t bh, int32_t bw, double resolution, const gsm_vario* vario,
                                 const double* lag_table, double* sigma, int64_t ld, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!vario || !sigma || bh < 1 || bw < 1 || ld < (int64_t)bh * bw || ld > 0x7fffffff)
     return fail(h, GSM_E_ARG, "gsm_cov_assemble: bad argument");
   if (vario->vtype < 0 || vario->vtype > 3) return fail(h, GSM_E_ARG, "gsm_cov_assemble: unknown vtype");
@@ -366,7 +366,7 @@ extern "C" int gsm_cov_assemble(gsm_handle h, int32_t bh, int32_t bw, double res
 }
 
 extern "C" int gsm_set_factors(gsm_handle h, int32_t n_classes, const double* const* factors, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_blocks) return fail(h, GSM_E_STATE, "gsm_set_factors: call gsm_set_blocks first");
   if (n_classes < 1 || !factors) return fail(h, GSM_E_ARG, "gsm_set_factors: bad argument");
   if ((int64_t)h->B.n_sizes * n_classes > 4096)      // cz_bucket_kernel keeps its per-group counters in LDS
@@ -391,18 +391,26 @@ std::pair<double, double> gsm::qt_clip() {
 
 extern "C" int gsm_qt_transform(gsm_handle h, const double* quantiles, const double* references, int32_t nq, const double* x,
                                 double* out, int64_t n, int32_t inverse, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!quantiles || !references || !x || !out || nq < 1 || n < 0) return fail(h, GSM_E_ARG, "gsm_qt_transform: bad argument");
+  const int64_t plane = (int64_t)h->H * h->W;
+  if (h->sgs_group() && (n != plane * h->n_chains || h->n_chains > 65535))
+    return fail(h, GSM_E_ARG, "gsm_qt_transform: with chain groups set, n must be n_chains * H * W (and n_chains <= 65535)");
   if (n == 0) return GSM_OK;
   const auto [clip_min, clip_max] = qt_clip();
   HIPCHK(h, hipSetDevice(h->device));
+  if (h->sgs_group()) {                                       // chain groups: the tables of the element's chain
+    HIPCHK(h, launch_qt_groups(quantiles, references, nq, clip_min, clip_max, x, out, h->n_chains, (int)plane, h->sgs_group(), inverse,
+                               (hipStream_t)stream));
+    return GSM_OK;
+  }
   HIPCHK(h, launch_qt(quantiles, references, nq, clip_min, clip_max, x, out, n, inverse, (hipStream_t)stream));
   return GSM_OK;
 }
 
 extern "C" int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, const uint8_t* mask,
                                       double* dist, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!xx || !yy || !mask || !dist) return fail(h, GSM_E_ARG, "gsm_min_dist_from_mask: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
   const int n = h->H * h->W;
@@ -421,8 +429,30 @@ extern "C" int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const doub
   return GSM_OK;
 }
 
+extern "C" int gsm_gaussian_filter(gsm_handle h, const double* x, double* out, int32_t n, int32_t H, int32_t W, const double* w0, int32_t lw0,
+                                   const double* w1, int32_t lw1, void* stream) {
+  if (!h) return GSM_E_ARG;                              // the one entry point that takes a grid with a side below 3 cells
+  if (!x || !out || !w0 || !w1) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: NULL pointer");
+  if (x == out) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: out must not alias x");
+  if (n < 1) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: n must be >= 1");
+  if (H != h->H || W != h->W) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: H, W are not the handle's");
+  if (lw0 < 0 || lw1 < 0 || lw0 > kTrendMaxLw || lw1 > kTrendMaxLw)
+    return fail(h, GSM_E_ARG, "gsm_gaussian_filter: lw0, lw1 must be in [0, " + std::to_string(kTrendMaxLw) + "]");
+  if ((int64_t)H * W > ((int64_t)1 << 30)) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: at most 2^30 cells per field");
+  TrendTaps t0{}, t1{};
+  t0.lw = lw0; t1.lw = lw1;
+  for (int k = 0; k <= 2 * lw0; ++k) t0.w[k] = w0[k];
+  for (int k = 0; k <= 2 * lw1; ++k) t1.w[k] = w1[k];
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, h->d_trend_tmp.ensure((size_t)n * H * W));
+  const hipError_t e = launch_gaussian_filter(t0, t1, x, h->d_trend_tmp.get(), out, n, H, W, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(h, GSM_E_ARG, "gsm_gaussian_filter: n * H * W is more than one launch takes (2^31 workgroups)");
+  HIPCHK(h, e);
+  return GSM_OK;
+}
+
 extern "C" int gsm_cholesky_upper(gsm_handle h, double* a, int32_t n, int64_t ld, double jitter, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!a || n < 64 || (n % 64) != 0 || ld < n || ld > 0x7fffffff)
     return fail(h, GSM_E_ARG, "gsm_cholesky_upper: n must be a positive multiple of 64 and ld >= n");
   HIPCHK(h, hipSetDevice(h->device));

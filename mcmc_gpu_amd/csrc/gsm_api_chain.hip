@@ -34,7 +34,7 @@ extern "C" int gsm_run_replay(gsm_handle h, int32_t n_steps, void* beds, void* e
                               const int32_t* size_idx, const int32_t* centre, const double* u,
                               const double* fields, int64_t field_stride, double* loss, uint8_t* accept,
                               void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static || !h->have_blocks) return fail(h, GSM_E_STATE, "gsm_run_replay: call gsm_set_static and gsm_set_blocks first");
   if (n_steps < 0) return fail(h, GSM_E_ARG, "gsm_run_replay: n_steps < 0");
   if (n_steps == 0) return GSM_OK;
@@ -130,7 +130,7 @@ static ProposeArgs make_propose(gsm_handle h, const gsm_rf_params* rf, int n_ste
 extern "C" int gsm_propose_philox(gsm_handle h, int32_t n_steps, int64_t step0, const uint64_t* seeds,
                                   const gsm_rf_params* rf, int32_t* size_idx, int32_t* centre, double* u,
                                   double* fields, int64_t field_stride, double* rf_scalars, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   int rc = check_propose_ready(h, rf, "gsm_propose_philox", true);
   if (rc) return rc;
   if (n_steps < 1 || n_steps > 65535) return fail(h, GSM_E_ARG, "gsm_propose_philox: n_steps must be in [1, 65535]");
@@ -148,7 +148,7 @@ extern "C" int gsm_propose_philox(gsm_handle h, int32_t n_steps, int64_t step0, 
 extern "C" int gsm_spectral_from_noise(gsm_handle h, int32_t n_fields, const int32_t* size_idx, const double* rf_scalars,
                                        const gsm_rf_params* rf, const double* noise_re, const double* noise_im,
                                        const double* nugget_field, double* fields, int64_t field_stride, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   gsm_rf_params rfs = rf ? *rf : gsm_rf_params{};      // the spectral generator, whatever rf names
   rfs.generator = GSM_GEN_SPECTRAL;
   int rc = check_propose_ready(h, rf ? &rfs : nullptr, "gsm_spectral_from_noise", false);   // no centre is drawn here
@@ -176,7 +176,7 @@ extern "C" int gsm_run_noise(gsm_handle h, int32_t n_steps, void* beds, void* en
                              const int32_t* size_idx, const int32_t* centre, const double* u, const double* rf_scalars,
                              const gsm_rf_params* rf, const double* noise_re, const double* noise_im, const double* nugget_field,
                              int64_t field_stride, double* loss, uint8_t* accept, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_run_noise: call gsm_set_static first");
   gsm_rf_params rfs = rf ? *rf : gsm_rf_params{};
   rfs.generator = GSM_GEN_SPECTRAL;
@@ -207,19 +207,19 @@ extern "C" int gsm_run_noise(gsm_handle h, int32_t n_steps, void* beds, void* en
 extern "C" int gsm_last_run_fused(gsm_handle h) { return h ? h->last_fused : GSM_E_ARG; }
 
 extern "C" int gsm_set_fused(gsm_handle h, int32_t on) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   h->use_fused = on ? 1 : 0;
   return GSM_OK;
 }
 
 extern "C" int gsm_enable_timing(gsm_handle h, int32_t on) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   h->timing = on != 0;
   return GSM_OK;
 }
 
 extern "C" int gsm_last_timing(gsm_handle h, double* step_ms, int32_t* step_launches, double* prop_ms, int32_t* prop_launches) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (step_ms) *step_ms = h->n_step_launch ? h->t_step_ms / h->n_step_launch : 0.0;
   if (step_launches) *step_launches = h->n_step_launch;
   if (prop_ms) *prop_ms = h->n_prop_launch ? h->t_prop_ms / h->n_prop_launch : 0.0;
@@ -356,7 +356,7 @@ static int run_philox_pipelined(gsm_handle h, int32_t n_steps, int64_t step0, in
 extern "C" int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int32_t batch, const uint64_t* seeds,
                               const gsm_rf_params* rf, void* beds, void* energy, uint32_t* resampled, double* loss_sum,
                               double* loss, uint8_t* accept, int32_t* blocks, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_run_philox: call gsm_set_static first");
   int rc = check_propose_ready(h, rf, "gsm_run_philox", true);
   if (rc) return rc;
@@ -400,7 +400,7 @@ int gsm::ensure_pcg_tables(gsm_handle h) {
 extern "C" int gsm_draw_pcg64(gsm_handle h, int32_t n_steps, const gsm_rf_params* rf, uint64_t* rf_state, uint64_t* chain_state,
                               const uint8_t* region_mask, int32_t* size_idx, int32_t* centre, double* u, double* rf_scalars,
                               double* noise_re, double* noise_im, double* nugget_field, int64_t field_stride, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_blocks) return fail(h, GSM_E_STATE, "gsm_draw_pcg64: call gsm_set_blocks first");
   if (!rf || !rf_state || !chain_state || !size_idx || !centre || !u || !rf_scalars || !noise_re || !noise_im)
     return fail(h, GSM_E_ARG, "gsm_draw_pcg64: NULL pointer");

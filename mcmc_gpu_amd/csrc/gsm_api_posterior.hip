@@ -39,7 +39,7 @@ static int posterior_sample(gsm_handle h, const char* who, const void* beds, con
 
 extern "C" int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                                         const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !ref || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: NULL pointer");
   if (!aligned16(beds) || !aligned16(ref) || !aligned16(s1) || !aligned16(s2))
     return fail(h, GSM_E_ARG, "gsm_posterior_accumulate: beds, ref, s1 and s2 must be 16-byte aligned");
@@ -52,7 +52,7 @@ extern "C" int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* re
 
 extern "C" int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
                                                const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !g || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: NULL pointer");
   if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_accumulate_pooled: beds must be 16-byte aligned");
   const int64_t plane = (int64_t)h->H * h->W;
@@ -65,14 +65,14 @@ extern "C" int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, c
 
 extern "C" int gsm_posterior_sample(gsm_handle h, const void* beds, const int32_t* sample_cells, int32_t n_samples, double* sample_out,
                                     void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !sample_out) return fail(h, GSM_E_ARG, "gsm_posterior_sample: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
   return posterior_sample(h, "gsm_posterior_sample", beds, sample_cells, n_samples, sample_out, (hipStream_t)stream);
 }
 
 extern "C" int gsm_posterior_close(gsm_handle h, const void* ref, const double* g, double* s1, double* s2, int32_t n_per_seq, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!ref || !g || !s1 || !s2) return fail(h, GSM_E_ARG, "gsm_posterior_close: NULL pointer");
   if (n_per_seq < 2) return fail(h, GSM_E_ARG, "gsm_posterior_close: n_per_seq must be >= 2 (a variance needs two snapshots)");
   if (h->n_chains > 65535) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_close: more than 65535 chains");
@@ -83,7 +83,7 @@ extern "C" int gsm_posterior_close(gsm_handle h, const void* ref, const double* 
 
 extern "C" int gsm_posterior_histogram(gsm_handle h, const void* beds, const double* g, double inv_width, int32_t n_bins, const double* levels,
                                        int32_t n_levels, int32_t* counts, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !g || !counts) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: NULL pointer");
   if (n_bins < 2 || n_bins > kHistMaxBins || n_bins % 2) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: n_bins must be even and in [2, 128]");
   if (n_levels < 0 || n_levels > kHistMaxLevels) return fail(h, GSM_E_ARG, "gsm_posterior_histogram: n_levels must be in [0, 8]");
@@ -98,7 +98,7 @@ extern "C" int gsm_posterior_histogram(gsm_handle h, const void* beds, const dou
 
 extern "C" int gsm_posterior_lagged(gsm_handle h, const void* beds, void* ring, int32_t n_lags, int32_t head, int32_t n_valid,
                                     double* lag_sqdiff, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !ring || !lag_sqdiff) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: NULL pointer");
   if (n_lags < 1 || n_lags > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: n_lags must be in [1, 15]");
   if (head < 0 || head >= n_lags) return fail(h, GSM_E_ARG, "gsm_posterior_lagged: head must be in [0, n_lags)");
@@ -127,7 +127,7 @@ static int posterior_cov_slab(gsm_handle h, int n_probes, int* parts) {
 
 extern "C" int gsm_posterior_project(gsm_handle h, const void* beds, const double* g, const double* probes, int32_t n_probes, double* proj,
                                      void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !g || !probes || !proj) return fail(h, GSM_E_ARG, "gsm_posterior_project: NULL pointer");
   if (n_probes < 1 || n_probes > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_project: n_probes must be in [1, 15]");
   if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_project: beds must be 16-byte aligned");
@@ -142,7 +142,7 @@ extern "C" int gsm_posterior_project(gsm_handle h, const void* beds, const doubl
 
 extern "C" int gsm_posterior_cross(gsm_handle h, const void* beds, const double* g, const double* proj, int32_t n_probes, double* cross,
                                    void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !g || !proj || !cross) return fail(h, GSM_E_ARG, "gsm_posterior_cross: NULL pointer");
   if (n_probes < 1 || n_probes > kLagMaxLags) return fail(h, GSM_E_ARG, "gsm_posterior_cross: n_probes must be in [1, 15]");
   if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_cross: beds must be 16-byte aligned");
@@ -156,7 +156,7 @@ extern "C" int gsm_posterior_cross(gsm_handle h, const void* beds, const double*
 
 extern "C" int gsm_posterior_residual(gsm_handle h, const void* beds, const double* rg, const double* levels, int32_t n_levels,
                                       double* sums, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !rg || !sums) return fail(h, GSM_E_ARG, "gsm_posterior_residual: NULL pointer");
   if (n_levels < 0 || n_levels > kResMaxLevels) return fail(h, GSM_E_ARG, "gsm_posterior_residual: n_levels must be in [0, 4]");
   if (n_levels > 0 && !levels) return fail(h, GSM_E_ARG, "gsm_posterior_residual: NULL levels with n_levels > 0");
@@ -174,7 +174,7 @@ extern "C" int gsm_posterior_residual(gsm_handle h, const void* beds, const doub
 }
 
 extern "C" int gsm_posterior_local(gsm_handle h, const void* beds, const double* g, int32_t reach, double* cross, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!beds || !g || !cross) return fail(h, GSM_E_ARG, "gsm_posterior_local: NULL pointer");
   if (reach < 1 || reach > kLocalMaxReach) return fail(h, GSM_E_ARG, "gsm_posterior_local: reach must be in [1, 4]");
   if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_local: beds must be 16-byte aligned");
@@ -195,7 +195,7 @@ extern "C" int gsm_posterior_local(gsm_handle h, const void* beds, const double*
 extern "C" int gsm_posterior_partials(gsm_handle h, const void* ref, const double* g, const double* s1, const double* s2,
                                       int32_t n_seq_per_chain, int64_t seq_stride, int32_t n_closed, int32_t n_per_seq, double* partials,
                                       void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!ref || !g || !s1 || !s2 || !partials) return fail(h, GSM_E_ARG, "gsm_posterior_partials: NULL pointer");
   if (n_seq_per_chain != 1 && n_seq_per_chain != 2) return fail(h, GSM_E_ARG, "gsm_posterior_partials: n_seq_per_chain must be 1 or 2");
   if (n_per_seq < 2) return fail(h, GSM_E_ARG, "gsm_posterior_partials: n_per_seq must be >= 2 (a variance needs two snapshots)");

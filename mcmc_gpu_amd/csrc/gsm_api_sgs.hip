@@ -92,7 +92,7 @@ static int sgs_fill(gsm_handle h, SgsArgs& a, double* grids, const double* zcond
   a.rank = (int32_t*)p; p += n * 1024 * 4;
   a.rank_ok = (int32_t*)p;
   a.n_chains = h->n_chains; a.grid = grids; a.zcond = zcond; a.win = windows;
-  a.cell_off = cell_off; a.cells = cells; a.z = z; a.max_cells = max_cells; a.defer = 0;
+  a.cell_off = cell_off; a.cells = cells; a.z = z; a.max_cells = max_cells; a.defer = 0; a.group = h->sgs_group();
   return GSM_OK;
 }
 
@@ -100,7 +100,7 @@ extern "C" int gsm_sgs_blocks(gsm_handle h, double* grids, const double* zcond, 
                               const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                               int32_t num_points, double sill, const int32_t* cell_off, const int32_t* cells, const double* z,
                               int32_t max_cells, double* trace, int32_t* nbr_trace, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   SgsArgs a{};
   HIPCHK(h, hipSetDevice(h->device));
   int rc = sgs_fill(h, a, grids, zcond, windows, x_axis, y_axis, lag_cov, lag_mi, lag_mj, hw, radius, num_points, sill, cell_off, cells, z,
@@ -116,7 +116,7 @@ extern "C" int gsm_sgs_blocks_batch(gsm_handle h, double* grids, const double* z
                                     const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                                     int32_t num_points, double sill, const int32_t* cell_off, const int32_t* cell_cnt, const int32_t* cells,
                                     const double* z, int32_t max_cells, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   SgsArgs a{};
   HIPCHK(h, hipSetDevice(h->device));
   int rc = sgs_fill(h, a, grids, zcond, windows, x_axis, y_axis, lag_cov, lag_mi, lag_mj, hw, radius, num_points, sill, cell_off, cells, z,
@@ -127,8 +127,29 @@ extern "C" int gsm_sgs_blocks_batch(gsm_handle h, double* grids, const double* z
   return GSM_OK;
 }
 
+extern "C" int gsm_sgs_set_groups(gsm_handle h, const int32_t* group, int32_t n_groups) {
+  GSM_GRID_HANDLE(h);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!group || n_groups == 1) {                              // one group is no groups: the entry points run as they always have
+    HIPCHK(h, hipDeviceSynchronize());                        // nothing in flight reads the table that goes
+    h->sgs_n_groups = 0;
+    h->d_sgs_group.reset();
+    return GSM_OK;
+  }
+  if (n_groups < 1) return fail(h, GSM_E_ARG, "gsm_sgs_set_groups: n_groups must be >= 1");
+  for (int c = 0; c < h->n_chains; ++c)
+    if (group[c] < 0 || group[c] >= n_groups)
+      return fail(h, GSM_E_ARG, "gsm_sgs_set_groups: group[" + std::to_string(c) + "] = " + std::to_string(group[c]) + " is outside [0, n_groups)");
+  HIPCHK(h, hipDeviceSynchronize());
+  h->sgs_n_groups = 0;
+  HIPCHK(h, h->d_sgs_group.ensure((size_t)h->n_chains));
+  HIPCHK(h, hipMemcpy(h->d_sgs_group.get(), group, (size_t)h->n_chains * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->sgs_n_groups = n_groups;
+  return GSM_OK;
+}
+
 extern "C" int gsm_sgs_set_kriging(gsm_handle h, int32_t ktype, const double* global_mean) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (ktype != GSM_KRIGING_ORDINARY && ktype != GSM_KRIGING_SIMPLE) return fail(h, GSM_E_ARG, "gsm_sgs_set_kriging: ktype must be GSM_KRIGING_ORDINARY or GSM_KRIGING_SIMPLE");
   if (ktype == GSM_KRIGING_SIMPLE && !global_mean) return fail(h, GSM_E_ARG, "gsm_sgs_set_kriging: simple kriging needs the global mean of every chain");
   h->sgs_ktype = ktype; h->sgs_gmean = ktype == GSM_KRIGING_SIMPLE ? global_mean : nullptr;
@@ -188,7 +209,7 @@ extern "C" int gsm_sgs_grid(gsm_handle h, double* grids, const int32_t* path, co
                             const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
                             const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                             int32_t num_points, double sill, int32_t seg_cells, double* trace, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   return sgs_grid_run(h, "gsm_sgs_grid", grids, path, path_off, max_path, draws, lower, upper, draw_kind, x_axis, y_axis, lag_cov, lag_mi,
                       lag_mj, nullptr, 0, hw, radius, num_points, sill, seg_cells, trace, stream);
 }
@@ -197,7 +218,7 @@ extern "C" int gsm_sgs_grid_local(gsm_handle h, double* grids, const int32_t* pa
                                   const double* draws, const double* lower, const double* upper, int32_t draw_kind, const double* x_axis,
                                   const double* y_axis, const double* local, int32_t vtype, int32_t hw, double radius,
                                   int32_t num_points, int32_t seg_cells, double* trace, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (int rc = local_vtype_check(h, "gsm_sgs_grid_local", vtype)) return rc;
   return sgs_grid_run(h, "gsm_sgs_grid_local", grids, path, path_off, max_path, draws, lower, upper, draw_kind, x_axis, y_axis, nullptr, 0,
                       0, local, vtype, hw, radius, num_points, 0.0, seg_cells, trace, stream);
@@ -226,7 +247,7 @@ static int krige_grid_run(gsm_handle h, const std::string& w, const double* grid
 extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
                               const double* y_axis, const double* lag_cov, int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius,
                               int32_t num_points, double sill, double* est, double* var, int32_t* n_neighbours, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   return krige_grid_run(h, "gsm_krige_grid", grid, cells, n_cells, x_axis, y_axis, lag_cov, lag_mi, lag_mj, nullptr, 0, hw, radius,
                         num_points, sill, est, var, n_neighbours, stream);
 }
@@ -234,7 +255,7 @@ extern "C" int gsm_krige_grid(gsm_handle h, const double* grid, const int32_t* c
 extern "C" int gsm_krige_grid_local(gsm_handle h, const double* grid, const int32_t* cells, int32_t n_cells, const double* x_axis,
                                     const double* y_axis, const double* local, int32_t vtype, int32_t hw, double radius,
                                     int32_t num_points, double* est, double* var, int32_t* n_neighbours, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (int rc = local_vtype_check(h, "gsm_krige_grid_local", vtype)) return rc;
   return krige_grid_run(h, "gsm_krige_grid_local", grid, cells, n_cells, x_axis, y_axis, nullptr, 0, 0, local, vtype, hw, radius,
                         num_points, 0.0, est, var, n_neighbours, stream);
@@ -281,7 +302,7 @@ extern "C" int gsm_krige_cv(gsm_handle h, const double* grid, const int32_t* cel
                             double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models, const double* lag_cov,
                             int32_t lag_mi, int32_t lag_mj, int32_t hw, double radius, int32_t num_points, const double* sill,
                             double* est, double* var, int32_t* n_neighbours, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   return krige_cv_run(h, "gsm_krige_cv", grid, cells, n_cells, fold, exclude_radius, x_axis, y_axis, n_models, lag_cov, lag_mi, lag_mj, sill,
                       nullptr, nullptr, hw, radius, num_points, est, var, n_neighbours, stream);
 }
@@ -290,7 +311,7 @@ extern "C" int gsm_krige_cv_local(gsm_handle h, const double* grid, const int32_
                                   double exclude_radius, const double* x_axis, const double* y_axis, int32_t n_models, const double* local,
                                   const int32_t* vtype, int32_t hw, double radius, int32_t num_points, double* est, double* var,
                                   int32_t* n_neighbours, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   return krige_cv_run(h, "gsm_krige_cv_local", grid, cells, n_cells, fold, exclude_radius, x_axis, y_axis, n_models, nullptr, 0, 0, nullptr,
                       local, vtype, hw, radius, num_points, est, var, n_neighbours, stream);
 }
@@ -306,7 +327,7 @@ extern "C" int gsm_debug_special(int32_t which, int32_t vtype, int64_t n, const 
 }
 
 extern "C" int gsm_sgs_check(gsm_handle h, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   HIPCHK(h, hipSetDevice(h->device));
   return sgs_report_flags(h, (hipStream_t)stream, "gsm_sgs_check", kBlockFlags, kBlockFlagsRest);
 }
@@ -322,7 +343,7 @@ extern "C" int gsm_sgs_draw_philox(gsm_handle h, const uint64_t* seeds, int64_t 
                                    const uint8_t* is_data, int32_t min_x, int32_t max_x, int32_t min_y, int32_t max_y, int32_t max_cells,
                                    int32_t* windows, int32_t* blocks, int32_t* cell_off, int32_t* cell_cnt, int32_t* cells, double* z,
                                    double* u, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!seeds || !is_data || !windows || !blocks || !cell_off || !cell_cnt || !cells || !z || !u)
     return fail(h, GSM_E_ARG, "gsm_sgs_draw_philox: NULL pointer");
   if (n_iters < 1 || n_iters > 65535 || iter0 < 0) return fail(h, GSM_E_ARG, "gsm_sgs_draw_philox: n_iters must be in [1, 65535], iter0 >= 0");
@@ -343,7 +364,7 @@ extern "C" int gsm_sgs_draw_pcg64(gsm_handle h, uint64_t* chain_state, int32_t n
                                   const uint8_t* is_data, int32_t min_x, int32_t max_x, int32_t min_y, int32_t max_y, int32_t max_cells,
                                   int32_t* windows, int32_t* blocks, int32_t* cell_off, int32_t* cell_cnt, int32_t* cells, double* z,
                                   double* u, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!chain_state || !is_data || !windows || !blocks || !cell_off || !cell_cnt || !cells || !z || !u)
     return fail(h, GSM_E_ARG, "gsm_sgs_draw_pcg64: NULL pointer");
   if (n_iters < 1 || n_iters > 65535) return fail(h, GSM_E_ARG, "gsm_sgs_draw_pcg64: n_iters must be in [1, 65535]");
@@ -364,7 +385,7 @@ extern "C" int gsm_sgs_draw_pcg64(gsm_handle h, uint64_t* chain_state, int32_t n
 extern "C" int gsm_sgs_grid_draw_pcg64(gsm_handle h, uint64_t* states, const int32_t* cells, int32_t n_cells, const uint8_t* has_value,
                                        const double* lower, const double* upper, int32_t draw_kind, int32_t* work, int32_t* path,
                                        double* draws, int32_t path_len, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   const std::string w = "gsm_sgs_grid_draw_pcg64";
   const int64_t n_grid = (int64_t)h->H * h->W;
   if (n_grid > INT32_MAX) return fail(h, GSM_E_ARG, w + ": flat cell indices are 32-bit (H * W < 2^31)");
@@ -400,19 +421,20 @@ static int sgs_parts_ensure(gsm_handle h) {
 }
 
 extern "C" int gsm_sgs_loss(gsm_handle h, const double* beds, const double* trend, double* loss, int32_t* bad, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_sgs_loss: call gsm_set_static first");
   if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_loss: fp64 beds only");
   if (!beds || !loss || !bad) return fail(h, GSM_E_ARG, "gsm_sgs_loss: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = sgs_parts_ensure(h)) return rc;
-  HIPCHK(h, launch_sgs_loss(h->S, h->n_chains, beds, trend, loss, bad, h->sgs_parts.sum.get(), h->sgs_parts.bad.get(), (hipStream_t)stream));
+  HIPCHK(h, launch_sgs_loss(h->S, h->n_chains, beds, trend, loss, bad, h->sgs_parts.sum.get(), h->sgs_parts.bad.get(), h->sgs_group(),
+                            (hipStream_t)stream));
   return GSM_OK;
 }
 
 extern "C" int gsm_sgs_decide(gsm_handle h, const double* loss_next, const int32_t* bad, const double* u, double* loss_prev,
                               uint8_t* accept, double* loss_rec, uint8_t* acc_rec, int64_t rec_stride, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!loss_next || !bad || !u || !loss_prev || !accept) return fail(h, GSM_E_ARG, "gsm_sgs_decide: NULL pointer");
   if ((loss_rec || acc_rec) && rec_stride < 1) return fail(h, GSM_E_ARG, "gsm_sgs_decide: rec_stride must be >= 1");
   HIPCHK(h, hipSetDevice(h->device));
@@ -421,32 +443,32 @@ extern "C" int gsm_sgs_decide(gsm_handle h, const double* loss_next, const int32
 }
 
 extern "C" int gsm_sgs_state_init(gsm_handle h, const double* beds, const double* trend, double* energy, double* state, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_sgs_state_init: call gsm_set_static first");
   if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_state_init: fp64 beds only");
   if (!beds || !energy || !state) return fail(h, GSM_E_ARG, "gsm_sgs_state_init: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, launch_sgs_state_init(h->S, h->n_chains, beds, trend, energy, state, (hipStream_t)stream));
+  HIPCHK(h, launch_sgs_state_init(h->S, h->n_chains, beds, trend, energy, state, h->sgs_group(), (hipStream_t)stream));
   return GSM_OK;
 }
 
 extern "C" int gsm_sgs_finish(gsm_handle h, double* cur, double* next, const double* trend, double* energy, double* state,
                               const int32_t* windows, const double* u, uint32_t* resampled, uint8_t* accept, double* loss_rec,
                               uint8_t* acc_rec, int64_t rec_stride, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_sgs_finish: call gsm_set_static first");
   if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_finish: fp64 beds only");
   if (!cur || !next || !energy || !state || !windows || !u || !resampled || !accept) return fail(h, GSM_E_ARG, "gsm_sgs_finish: NULL pointer");
   if ((loss_rec || acc_rec) && rec_stride < 1) return fail(h, GSM_E_ARG, "gsm_sgs_finish: rec_stride must be >= 1");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, launch_sgs_finish(h->S, h->n_chains, cur, next, trend, energy, state, windows, u, resampled, accept, loss_rec, acc_rec, rec_stride,
-                              h->d_err.get(), (hipStream_t)stream));
+                              h->d_err.get(), h->sgs_group(), (hipStream_t)stream));
   return GSM_OK;
 }
 
 extern "C" int gsm_sgs_commit_map(gsm_handle h, double* cur, const double* proposed, uint32_t* resampled, const int32_t* windows,
                                   const uint8_t* accept, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!cur || !proposed || !resampled || !windows || !accept) return fail(h, GSM_E_ARG, "gsm_sgs_commit_map: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, launch_sgs_commit_map(h->H, h->W, h->n_chains, cur, proposed, resampled, windows, accept, (hipStream_t)stream));
@@ -455,7 +477,7 @@ extern "C" int gsm_sgs_commit_map(gsm_handle h, double* cur, const double* propo
 
 extern "C" int gsm_sgs_commit(gsm_handle h, double* cur, double* next, uint32_t* resampled, const int32_t* windows,
                               const uint8_t* accept, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!cur || !next || !resampled || !windows || !accept) return fail(h, GSM_E_ARG, "gsm_sgs_commit: NULL pointer");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, launch_sgs_commit(h->H, h->W, h->n_chains, cur, next, resampled, windows, accept, (hipStream_t)stream));
@@ -562,7 +584,7 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
     if (h->f32_state) return fail(h, GSM_E_UNSUPPORTED, "gsm_sgs_iterate: fp64 beds only");
     if ((rc = sgs_parts_ensure(h))) return rc;
     SgsTailArgs t{};
-    t.trend = b->trend; t.part_sum = h->sgs_parts.sum.get(); t.part_bad = h->sgs_parts.bad.get(); t.ticket = h->sgs_parts.ticket.get();
+    t.group = h->sgs_group(); t.trend = b->trend; t.part_sum = h->sgs_parts.sum.get(); t.part_bad = h->sgs_parts.bad.get(); t.ticket = h->sgs_parts.ticket.get();
     t.loss = b->loss; t.bad = b->bad; t.u = u; t.loss_prev = b->loss_prev; t.accept = b->accept;
     t.loss_rec = b->loss_rec ? b->loss_rec + j : nullptr; t.acc_rec = b->acc_rec ? b->acc_rec + j : nullptr; t.rec_stride = n_iters;
     t.mode = qt ? 1 : 2; t.cur = b->cur; t.beds = qt ? b->proposed : b->next; t.resampled = b->resampled; t.win = win;
@@ -574,7 +596,7 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
 }
 
 extern "C" int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!b || n_iters < 1) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: NULL batch / n_iters < 1");
   if (!b->cur || !b->next || !b->windows || !b->cell_off || !b->cells || !b->z || !b->u || !b->resampled || !b->accept)
     return fail(h, GSM_E_ARG, "gsm_sgs_iterate: NULL pointer");

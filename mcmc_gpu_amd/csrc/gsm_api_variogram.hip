@@ -6,7 +6,7 @@ using namespace gsm;
 
 extern "C" int gsm_variogram_map(gsm_handle h, const double* fields, int32_t n_fields, const uint8_t* mask, int32_t mi, int32_t mj,
                                  int32_t rows_per_part, double* sum, int64_t* count, void* stream) {
-  if (!h) return GSM_E_ARG;
+  GSM_GRID_HANDLE(h);
   if (!fields || !sum || !count) return fail(h, GSM_E_ARG, "gsm_variogram_map: NULL pointer (fields, sum, count)");
   if (n_fields < 1) return fail(h, GSM_E_ARG, "gsm_variogram_map: n_fields must be >= 1");
   if (mi < 0 || mj < 0) return fail(h, GSM_E_ARG, "gsm_variogram_map: mi and mj must be >= 0");

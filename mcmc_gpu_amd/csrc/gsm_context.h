@@ -84,6 +84,8 @@ struct gsm_context {
   gsm::DevBuf<double> d_sgs_next_acc;                                            // T(proposed) of every chain (sgs_loss_tail_kernel<true>)
   gsm::Stream sgs_side, sgs_side2; gsm::Event sgs_ev[kSgsDepth + 2];             // gsm_sgs_iterate's second stream (records of later iterations beside the current one)
   int sgs_ktype = 0; const double* sgs_gmean = nullptr;        // gsm_sgs_set_kriging (the caller's array)
+  gsm::DevBuf<int32_t> d_sgs_group; int sgs_n_groups = 0;      // gsm_sgs_set_groups: the group of every chain; 0 groups: none set
+  const int32_t* sgs_group() const { return sgs_n_groups ? d_sgs_group.get() : nullptr; }
   gsm::DevBuf<uint64_t> d_pcg_tab;   // gsm_draw_pcg64: LCG jump table (kPcgJumpWords) + ziggurat tables (768 words)
   gsm::DevBuf<int32_t> d_k2_off;
   double k2_resolution = 0.0;
@@ -101,6 +103,7 @@ struct gsm_context {
   int n_cu = 0;                                               // compute units of the device (grid sizing of the posterior kernels)
   gsm::DevBuf<double> d_post_slab;                            // gsm_posterior_*: per-part sums before they are combined in part order
   gsm::DevBuf<double> d_vario_sum; gsm::DevBuf<int64_t> d_vario_count;   // gsm_variogram_map: per-part sums and counts before they are combined in part order
+  gsm::DevBuf<double> d_trend_tmp;                            // gsm_gaussian_filter: the axis-0 pass of every field (grow-only)
   // philox-mode scratch (two buffers)
   struct Scratch {
     gsm::DevBuf<int32_t> size_idx, centre;
@@ -126,6 +129,16 @@ int fail(gsm_handle h, int code, const std::string& msg);     // records msg (pe
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess)                                                                     \
       return fail(h, GSM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
+  } while (0)
+
+// First statement of every entry point that takes a handle, gsm_gaussian_filter excepted: the stencils, searches and tiles behind them
+// assume a grid of at least 3 x 3 cells.  gsm_create takes smaller grids for the filter alone (an axis of one or two cells is a
+// case of scipy's reflection), and everything else refuses such a handle here.
+#define GSM_GRID_HANDLE(h)                                                                                                   \
+  do {                                                                                                                       \
+    if (!(h)) return GSM_E_ARG;                                                                                              \
+    if ((h)->H < 3 || (h)->W < 3)                                                                                            \
+      return gsm::fail(h, GSM_E_ARG, std::string(__func__) + ": the handle's grid has a side below 3 cells (gsm_gaussian_filter only)"); \
   } while (0)
 
 // helpers of more than one translation unit (defined in gsm_api.hip unless noted)

@@ -270,6 +270,7 @@ struct SgsArgs {
   double2* rec_vw;         // [n_chains*max_cells/64][48][64]: entry e of 64 consecutive cell slots side by side -- (the neighbour's value,
                            //  or NaN-boxed (visiting slot << 16 | block-local index) where the neighbour is a cell simulated earlier in
                            //  the block; its kriging weight)
+  const int32_t* group;    // [n_chains] or nullptr: the chain's group (gsm_sgs_set_groups); zcond is then [n_groups][H*W]
 };
 // interpolate.sgs on whole grids, many realisations at once (sgs_grid_kernel.hip)
 struct SgsGridHdr {          // one per (realisation, path slot of the segment), written by sgs_grid_weights_kernel
@@ -368,8 +369,10 @@ struct SgsDrawArgs {
 };
 hipError_t launch_sgs_draw(const SgsDrawArgs& a, hipStream_t st);
 int sgs_loss_parts(const StaticFields& S);      // workgroups per chain of the loss kernel; scratch = n_chains * parts doubles + ints
+// `group` of the launchers below: [n_chains] on the device or nullptr (gsm_sgs_set_groups).  With it trend is [n_groups][H*W] and the
+// transformer's tables are [n_groups][nq], each read at the chain's group; without it the kernels are the ones they were.
 hipError_t launch_sgs_loss(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* loss, int32_t* bad,
-                           double* part_sum, int32_t* part_bad, hipStream_t st);
+                           double* part_sum, int32_t* part_bad, const int32_t* group, hipStream_t st);
 // the operands of sgs_loss_tail_kernel (sgs_iter_kernel.hip), filled by gsm_sgs_iterate; `parts` is the launcher's
 struct SgsTailArgs {
   const double* trend; int parts; double* part_sum; int32_t* part_bad; int32_t* ticket;
@@ -377,18 +380,22 @@ struct SgsTailArgs {
   int mode; double* cur; double* beds; uint32_t* resampled; const int32_t* win;
   // QT (qt_q non-null): the two normal-score transforms of an iteration in this launch as well (see the kernel)
   const double* qt_q; const double* qt_ref; int qt_n; double clip_min, clip_max; double* next; double* next_acc;
+  const int32_t* group;    // [n_chains] or nullptr (gsm_sgs_set_groups): trend, qt_q and qt_ref then hold one plane / table per group
 };
 hipError_t launch_sgs_loss_tail(const StaticFields& S, int n_chains, const SgsTailArgs& args, hipStream_t st);
 bool sgs_tail_takes_qt(const StaticFields& S, int nq);
 hipError_t launch_sgs_state_init(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* energy, double* state,
-                                 hipStream_t st);
+                                 const int32_t* group, hipStream_t st);
 hipError_t launch_sgs_finish(const StaticFields& S, int n_chains, double* cur, double* next, const double* trend, double* energy, double* state,
                              const int32_t* win, const double* u, uint32_t* resampled, uint8_t* accept, double* loss_rec, uint8_t* acc_rec,
-                             int64_t rec_stride, int32_t* err, hipStream_t st);
+                             int64_t rec_stride, int32_t* err, const int32_t* group, hipStream_t st);
 hipError_t launch_sgs_decide(int n_chains, const double* loss_next, const int32_t* bad, const double* u, double* loss_prev,
                              uint8_t* accept, double* loss_rec, uint8_t* acc_rec, int64_t rec_stride, hipStream_t st);
 hipError_t launch_qt(const double* quantiles, const double* references, int nq, double clip_min, double clip_max, const double* x,
                      double* out, int64_t n, int inverse, hipStream_t st);
+// the same per chain with the tables of its group: x, out [n_chains][plane]
+hipError_t launch_qt_groups(const double* quantiles, const double* references, int nq, double clip_min, double clip_max, const double* x,
+                            double* out, int n_chains, int plane, const int32_t* group, int inverse, hipStream_t st);
 hipError_t launch_sgs_commit_map(int H, int W, int n_chains, double* cur, const double* proposed, uint32_t* resampled, const int32_t* win,
                                  const uint8_t* accept, hipStream_t st);
 hipError_t launch_sgs_commit(int H, int W, int n_chains, double* cur, double* next, uint32_t* resampled, const int32_t* win,
@@ -435,6 +442,11 @@ size_t step_lds_bytes(int tile_cap);
 hipError_t launch_min_dist(const double* xx, const double* yy, const uint8_t* mask, int n, double2* pts, int* count,
                            double* dist, hipStream_t st);
 hipError_t launch_stream_copy(const double* src, double* dst, int64_t n, hipStream_t st);
+// trend_kernel.hip: the weights of one axis of gsm_gaussian_filter, passed to its kernels by value
+constexpr int kTrendMaxLw = 128;
+struct TrendTaps { double w[2 * kTrendMaxLw + 1]; int lw; };
+hipError_t launch_gaussian_filter(const TrendTaps& t0, const TrendTaps& t1, const double* x, double* tmp, double* out, int n, int H, int W,
+                                  hipStream_t st);
 // variogram_kernel.hip
 constexpr int kVariogramMaxLag = 1 << 20;
 int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part

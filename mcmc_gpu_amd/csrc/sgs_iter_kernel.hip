@@ -32,6 +32,12 @@ __device__ __forceinline__ bool metropolis_accept(double lp, double ln, double u
   const double p = exp(lp - ln);
   return u <= fmin(1.0, p);                 // p NaN (a NaN loss, or inf - inf): Python's min(1, nan) is 1, the reference accepts
 }
+// Chain groups (gsm_sgs_set_groups; G of the kernels below): trend is [n_groups][H*W] and the transformer's tables are [n_groups][nq],
+// each read at the chain's group.  Without groups (G = false) every kernel is the one it was.
+template <bool G>
+__device__ __forceinline__ const double* group_plane(const double* p, const int32_t* group, int chain, size_t stride) {
+  return (G && p) ? p + (size_t)group[chain] * stride : p;
+}
 // the squared residual of cell g = (r, c) as it enters the loss: 0 where mc_mask != 1 or the residual is NaN (nansum)
 template <class BedAt>
 __device__ __forceinline__ double cell_energy(const StaticFields& S, int g, int r, int c, const BedAt& bed_at) {
@@ -89,15 +95,16 @@ __device__ __forceinline__ void sgs_loss_part(const StaticFields& S, const doubl
   sum_out = ((red[0] + red[1]) + red[2]) + red[3];
   bad_out = redb[0] + redb[1] + redb[2] + redb[3];
 }
+template <bool G>
 __global__ __launch_bounds__(256) void sgs_loss_kernel(const StaticFields S, const double* beds, const double* trend, int parts,
-                                                       double* part_sum, int32_t* part_bad) {
+                                                       double* part_sum, int32_t* part_bad, const int32_t* group) {
   __shared__ double red[8];
   __shared__ int redb[4];
   const int chain = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
   const int plane = S.H * S.W;
   const int per = (plane + parts - 1) / parts, g_lo = part * per, g_hi = min(plane, g_lo + per);
   double t; int nb;
-  sgs_loss_part(S, beds + (size_t)chain * plane, 0, trend, g_lo, g_hi, tid, red, redb, t, nb);
+  sgs_loss_part(S, beds + (size_t)chain * plane, 0, group_plane<G>(trend, group, chain, plane), g_lo, g_hi, tid, red, redb, t, nb);
   if (tid == 0) { part_sum[chain * parts + part] = t; part_bad[chain * parts + part] = nb; }
 }
 __global__ __launch_bounds__(64) void sgs_loss_finish_kernel(int n_chains, int parts, double two_sigma2, const double* __restrict__ part_sum,
@@ -116,9 +123,10 @@ __global__ __launch_bounds__(64) void sgs_loss_finish_kernel(int n_chains, int p
 int sgs_loss_parts(const StaticFields& S) { return std::max(1, std::min(64, (S.H * S.W + 1023) / 1024)); }
 
 hipError_t launch_sgs_loss(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* loss, int32_t* bad,
-                           double* part_sum, int32_t* part_bad, hipStream_t st) {
+                           double* part_sum, int32_t* part_bad, const int32_t* group, hipStream_t st) {
   const int parts = sgs_loss_parts(S);
-  hipLaunchKernelGGL(sgs_loss_kernel, dim3(n_chains, parts), dim3(256), 0, st, S, beds, trend, parts, part_sum, part_bad);
+  if (group) hipLaunchKernelGGL(sgs_loss_kernel<true>, dim3(n_chains, parts), dim3(256), 0, st, S, beds, trend, parts, part_sum, part_bad, group);
+  else hipLaunchKernelGGL(sgs_loss_kernel<false>, dim3(n_chains, parts), dim3(256), 0, st, S, beds, trend, parts, part_sum, part_bad, group);
   hipLaunchKernelGGL(sgs_loss_finish_kernel, dim3((n_chains + 63) / 64), dim3(64), 0, st, n_chains, parts, S.two_sigma2, part_sum, part_bad, loss, bad);
   return hipGetLastError();
 }
@@ -132,13 +140,15 @@ hipError_t launch_sgs_loss(const StaticFields& S, int n_chains, const double* be
 //   state[4 c .. 4 c + 3] = (sum hi, sum lo, loss = sum / (2 sigma^2), bad cells)
 // One 256-thread workgroup per chain: loss / guard of the proposal from the halo window, the acceptance test, the commit.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sgs_state_init_kernel(const StaticFields S, const double* beds, const double* trend, double* energy,
-                                                             double* state) {
+template <bool G>
+__global__ __launch_bounds__(256) void sgs_state_init_kernel(const StaticFields S, const double* beds, const double* trend_all, double* energy,
+                                                             double* state, const int32_t* group) {
   __shared__ double red[8];
   __shared__ int redb[4];
   const int chain = blockIdx.x, tid = threadIdx.x;
   const int plane = S.H * S.W;
   const double* bed = beds + (size_t)chain * plane;
+  const double* trend = group_plane<G>(trend_all, group, chain, plane);
   double* en = energy + (size_t)chain * plane;
   auto bed_at = [&](int rr, int cc) { const int q = rr * S.W + cc; return trend ? bed[q] + trend[q] : bed[q]; };
   double hi = 0.0, lo = 0.0;
@@ -173,9 +183,11 @@ __global__ __launch_bounds__(256) void sgs_state_init_kernel(const StaticFields 
 }
 
 constexpr int kSgsHaloMax = 36 * 36;       // cells of block + halo held in LDS: blocks up to 34 x 34 (or e.g. 16 x 70)
-__global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, double* cur, double* next, const double* trend, double* energy,
+template <bool G>
+__global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, double* cur, double* next, const double* trend_all, double* energy,
                                                          double* state, const int32_t* win, const double* u, uint32_t* resampled,
-                                                         uint8_t* accept, double* loss_rec, uint8_t* acc_rec, int64_t rec_stride, int32_t* err) {
+                                                         uint8_t* accept, double* loss_rec, uint8_t* acc_rec, int64_t rec_stride, int32_t* err,
+                                                         const int32_t* group) {
   __shared__ double e_new[kSgsHaloMax];
   __shared__ double red[16];
   __shared__ int redb[8];
@@ -183,6 +195,7 @@ __global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, d
   const int chain = blockIdx.x, tid = threadIdx.x;
   const int H = S.H, W = S.W;
   const size_t base = (size_t)chain * H * W;
+  const double* trend = group_plane<G>(trend_all, group, chain, (size_t)H * W);
   const BlockWin bw(win, chain, W);
   const int hr0 = max(0, bw.r0 - 1), hr1 = min(H, bw.r1 + 1), hc0 = max(0, bw.c0 - 1), hc1 = min(W, bw.c1 + 1);
   const int hww = hc1 - hc0, hn = (hr1 - hr0) * hww;
@@ -249,15 +262,18 @@ __global__ __launch_bounds__(256) void sgs_finish_kernel(const StaticFields S, d
 }
 
 hipError_t launch_sgs_state_init(const StaticFields& S, int n_chains, const double* beds, const double* trend, double* energy, double* state,
-                                 hipStream_t st) {
-  hipLaunchKernelGGL(sgs_state_init_kernel, dim3(n_chains), dim3(256), 0, st, S, beds, trend, energy, state);
+                                 const int32_t* group, hipStream_t st) {
+  if (group) hipLaunchKernelGGL(sgs_state_init_kernel<true>, dim3(n_chains), dim3(256), 0, st, S, beds, trend, energy, state, group);
+  else hipLaunchKernelGGL(sgs_state_init_kernel<false>, dim3(n_chains), dim3(256), 0, st, S, beds, trend, energy, state, group);
   return hipGetLastError();
 }
 hipError_t launch_sgs_finish(const StaticFields& S, int n_chains, double* cur, double* next, const double* trend, double* energy, double* state,
                              const int32_t* win, const double* u, uint32_t* resampled, uint8_t* accept, double* loss_rec, uint8_t* acc_rec,
-                             int64_t rec_stride, int32_t* err, hipStream_t st) {
-  hipLaunchKernelGGL(sgs_finish_kernel, dim3(n_chains), dim3(256), 0, st, S, cur, next, trend, energy, state, win, u, resampled, accept,
-                     loss_rec, acc_rec, rec_stride, err);
+                             int64_t rec_stride, int32_t* err, const int32_t* group, hipStream_t st) {
+  if (group) hipLaunchKernelGGL(sgs_finish_kernel<true>, dim3(n_chains), dim3(256), 0, st, S, cur, next, trend, energy, state, win, u, resampled, accept,
+                                loss_rec, acc_rec, rec_stride, err, group);
+  else hipLaunchKernelGGL(sgs_finish_kernel<false>, dim3(n_chains), dim3(256), 0, st, S, cur, next, trend, energy, state, win, u, resampled, accept,
+                          loss_rec, acc_rec, rec_stride, err, group);
   return hipGetLastError();
 }
 
@@ -359,6 +375,32 @@ hipError_t launch_qt(const double* quantiles, const double* references, int nq, 
   return hipGetLastError();
 }
 
+// the same for chains in groups: chain blockIdx.y with the tables of its group (the same functions on the same table values, LDS or not
+// by the same rule: an element's result is the one qt_kernel gives with that group's tables)
+__global__ __launch_bounds__(256) void qt_groups_kernel(const double* __restrict__ quantiles, const double* __restrict__ references, int nq,
+                                                        double clip_min, double clip_max, const double* x, double* out, int plane,
+                                                        const int32_t* __restrict__ group, int inverse) {
+  __shared__ double tab[2 * kQtLds];
+  const int chain = blockIdx.y;
+  const double* q = quantiles + (size_t)group[chain] * nq;
+  const double* ref = references + (size_t)group[chain] * nq;
+  if (nq <= kQtLds) {
+    for (int i = threadIdx.x; i < nq; i += 256) { tab[i] = q[i]; tab[kQtLds + i] = ref[i]; }
+    __syncthreads();
+    q = tab; ref = tab + kQtLds;
+  }
+  const size_t base = (size_t)chain * plane;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < plane; i += gridDim.x * 256)
+    out[base + i] = inverse ? ns::qt_inverse(x[base + i], q, ref, nq) : ns::qt_forward(x[base + i], q, ref, nq, clip_min, clip_max);
+}
+hipError_t launch_qt_groups(const double* quantiles, const double* references, int nq, double clip_min, double clip_max, const double* x,
+                            double* out, int n_chains, int plane, const int32_t* group, int inverse, hipStream_t st) {
+  const int blocks = std::max(1, std::min((plane + 255) / 256, 4096 / std::max(1, std::min(n_chains, 4096))));
+  hipLaunchKernelGGL(qt_groups_kernel, dim3(blocks, n_chains), dim3(256), 0, st, quantiles, references, nq, clip_min, clip_max, x, out, plane,
+                     group, inverse);
+  return hipGetLastError();
+}
+
 // gsm_sgs_commit_map: an accepted chain takes the whole proposed plane
 __global__ __launch_bounds__(256) void sgs_commit_map_kernel(int H, int W, double* cur, const double* proposed, uint32_t* resampled,
                                                              const int32_t* win, const uint8_t* accept) {
@@ -402,7 +444,7 @@ hipError_t launch_sgs_commit(int H, int W, int n_chains, double* cur, double* ne
 // so T(cur) = T(proposed)) and otherwise re-transforms the block window of `cur` (everything else of `next` still is T(cur)).  Two
 // elementwise launches per iteration less (MCMC.py:1766, :1777 stay where they are in the arithmetic).
 constexpr int kTailQt = 1024, kTailTile = 2048;
-template <bool QT>
+template <bool QT, bool G>
 __global__ __launch_bounds__(256) void sgs_loss_tail_kernel(const StaticFields S, const SgsTailArgs a) {
   __shared__ double red[8];
   __shared__ int redb[4];
@@ -414,9 +456,12 @@ __global__ __launch_bounds__(256) void sgs_loss_tail_kernel(const StaticFields S
   const int per = (plane + parts - 1) / parts, g_lo = part * per, g_hi = min(plane, g_lo + per);
   const size_t base = (size_t)chain * plane;
   const double* bed = a.beds + base;
+  const double* trend = group_plane<G>(a.trend, a.group, chain, plane);
   int off = 0;
   if (QT) {
-    for (int i = tid; i < a.qt_n; i += 256) { qtab[i] = a.qt_q[i]; qtab[kTailQt + i] = a.qt_ref[i]; }
+    const double* tq = group_plane<G>(a.qt_q, a.group, chain, a.qt_n);
+    const double* tref = group_plane<G>(a.qt_ref, a.group, chain, a.qt_n);
+    for (int i = tid; i < a.qt_n; i += 256) { qtab[i] = tq[i]; qtab[kTailQt + i] = tref[i]; }
     __syncthreads();
     const int lo_h = max(0, g_lo - W), hi_h = min(plane, g_hi + W);
     for (int idx = lo_h + tid; idx < hi_h; idx += 256) {
@@ -431,7 +476,7 @@ __global__ __launch_bounds__(256) void sgs_loss_tail_kernel(const StaticFields S
     bed = tile; off = lo_h;
   }
   double t; int nb;
-  sgs_loss_part(S, bed, off, a.trend, g_lo, g_hi, tid, red, redb, t, nb);
+  sgs_loss_part(S, bed, off, trend, g_lo, g_hi, tid, red, redb, t, nb);
   if (tid == 0) {
     __hip_atomic_store(&a.part_sum[chain * parts + part], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&a.part_bad[chain * parts + part], nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -493,9 +538,12 @@ hipError_t launch_sgs_loss_tail(const StaticFields& S, int n_chains, const SgsTa
   a.parts = sgs_loss_parts(S);
   if (a.qt_q) {
     if (a.mode != 1 || !sgs_tail_takes_qt(S, a.qt_n) || !a.next || !a.next_acc) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sgs_loss_tail_kernel<true>, dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
-  } else
-    hipLaunchKernelGGL(sgs_loss_tail_kernel<false>, dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
+    if (a.group) hipLaunchKernelGGL((sgs_loss_tail_kernel<true, true>), dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
+    else hipLaunchKernelGGL((sgs_loss_tail_kernel<true, false>), dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
+  } else if (a.group)
+    hipLaunchKernelGGL((sgs_loss_tail_kernel<false, true>), dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
+  else
+    hipLaunchKernelGGL((sgs_loss_tail_kernel<false, false>), dim3(n_chains, a.parts), dim3(256), 0, st, S, a);
   return hipGetLastError();
 }
 

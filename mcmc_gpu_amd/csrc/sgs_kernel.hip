@@ -81,9 +81,17 @@ __device__ __forceinline__ void wave_sum2_f64(double& a, double& b) {
 // sgs_rank_kernel: per chain, the visiting rank of every block cell (-1: the cell holds conditioning data and is never
 // simulated), so that the search of cell k knows which block cells hold a value when k is visited.  One workgroup per chain.
 // ---------------------------------------------------------------------------------------------------------------------
+// G (all three kernels of this file): the handle has chain groups (gsm_sgs_set_groups) and zcond is [n_groups][H*W], read at the plane of
+// the chain's group; without groups (G = false) the kernels are the ones they were.
+template <bool G>
+__device__ __forceinline__ const double* sgs_zcond_of(const SgsArgs& a, int chain) {
+  return (G && a.zcond) ? a.zcond + (size_t)a.group[chain] * a.K.H * a.K.W : a.zcond;
+}
+template <bool G>
 __global__ __launch_bounds__(256) void sgs_rank_kernel(const SgsArgs a) {
   const int chain = blockIdx.x, tid = threadIdx.x;
   const int H = a.K.H, W = a.K.W;
+  const double* zcond = sgs_zcond_of<G>(a, chain);
   const int r0 = a.win[4 * chain], r1 = a.win[4 * chain + 1], c0 = a.win[4 * chain + 2], c1 = a.win[4 * chain + 3];
   const int wh = r1 - r0, ww = c1 - c0;
   int32_t* rank = a.rank + (size_t)chain * kSgsMaxWin;
@@ -99,7 +107,7 @@ __global__ __launch_bounds__(256) void sgs_rank_kernel(const SgsArgs a) {
   for (int k = tid; k < cnt; k += 256) {
     const int i = a.cells[2 * (k_lo + k)], j = a.cells[2 * (k_lo + k) + 1];
     if (i < r0 || i >= r1 || j < c0 || j >= c1) { atomicOr(a.K.err, kSgsFlagCell); continue; }
-    const double v = a.zcond ? a.zcond[i * W + j] : g[i * W + j];
+    const double v = zcond ? zcond[i * W + j] : g[i * W + j];
     rank[(i - r0) * ww + (j - c0)] = isnan(v) ? k : -1;
   }
 }
@@ -107,9 +115,11 @@ __global__ __launch_bounds__(256) void sgs_rank_kernel(const SgsArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // sgs_weights_kernel: one 64-lane workgroup (one wavefront) per (cell slot, chain)
 // ---------------------------------------------------------------------------------------------------------------------
+template <bool G>
 __global__ __launch_bounds__(64) void sgs_weights_kernel(const SgsArgs a) {
   __shared__ SgsSearchLds L;
   const int slot = blockIdx.x, chain = blockIdx.y, lane = threadIdx.x;
+  const double* zcond = sgs_zcond_of<G>(a, chain);
   if (!a.rank_ok[chain]) return;
   const int k_lo = a.cell_off[chain], cnt = a.cell_cnt ? a.cell_cnt[chain] : a.cell_off[chain + 1] - k_lo;
   if (slot >= cnt) return;
@@ -157,7 +167,7 @@ __global__ __launch_bounds__(64) void sgs_weights_kernel(const SgsArgs a) {
       else if (a.defer)
         vw.x = __builtin_bit_cast(double, inblk ? (kSgsWindowTag | (uint64_t)nb_pos) : (kSgsGridTag | (uint64_t)(uint32_t)gg));
       else
-        vw.x = (inblk && a.zcond) ? a.zcond[gg] : g[gg];
+        vw.x = (inblk && zcond) ? zcond[gg] : g[gg];
     }
     // entry `lane` of 64 consecutive cell slots lies side by side: sgs_sequence_kernel reads one cell per lane
     a.rec_vw[((rec >> 6) * kSgsMaxPts + lane) * 64 + (rec & 63)] = vw;
@@ -190,6 +200,7 @@ __global__ __launch_bounds__(64) void sgs_weights_kernel(const SgsArgs a) {
 // cell of its chunk and every cell that lists one of those.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kSeqWaves = 4;
+template <bool G>
 __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsArgs a) {
   __shared__ double overlay[kSgsMaxWin];
   __shared__ double tile[65 * 64];                              // [cell of the chunk the value comes from][lane = cell that uses it]; row 64 takes the writes of absent entries
@@ -200,6 +211,7 @@ __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsA
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (!a.rank_ok[chain]) return;
   const int H = a.K.H, W = a.K.W;
+  const double* zcond = sgs_zcond_of<G>(a, chain);
   double* __restrict__ g = a.grid + (size_t)chain * H * W;
   const int r0 = a.win[4 * chain], r1 = a.win[4 * chain + 1], c0 = a.win[4 * chain + 2], c1 = a.win[4 * chain + 3];
   const int wh = r1 - r0, ww = c1 - c0;
@@ -219,7 +231,7 @@ __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsA
   if (cnt > 0) request(0);
   for (int p = threadIdx.x; p < wh * ww; p += 64 * kSeqWaves) {
     const int gi = (r0 + p / ww) * W + c0 + p % ww;
-    overlay[p] = a.zcond ? a.zcond[gi] : g[gi];
+    overlay[p] = zcond ? zcond[gi] : g[gi];
   }
   for (int kc = 0; kc < cnt; kc += 64) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of the chunk's records and its headers have landed
@@ -305,13 +317,19 @@ __global__ __launch_bounds__(64 * kSeqWaves) void sgs_sequence_kernel(const SgsA
 // the two halves of launch_sgs_blocks: the records of every cell (visiting ranks, then search + kriging weights), and the value pass
 hipError_t launch_sgs_weights(const SgsArgs& a, int launch_cells, hipStream_t st) {
   if (!krige_search_ok(a.K)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sgs_rank_kernel, dim3(a.n_chains), dim3(256), 0, st, a);
-  if (launch_cells > 0) hipLaunchKernelGGL(sgs_weights_kernel, dim3(launch_cells, a.n_chains), dim3(64), 0, st, a);
+  if (a.group) {
+    hipLaunchKernelGGL(sgs_rank_kernel<true>, dim3(a.n_chains), dim3(256), 0, st, a);
+    if (launch_cells > 0) hipLaunchKernelGGL(sgs_weights_kernel<true>, dim3(launch_cells, a.n_chains), dim3(64), 0, st, a);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(sgs_rank_kernel<false>, dim3(a.n_chains), dim3(256), 0, st, a);
+  if (launch_cells > 0) hipLaunchKernelGGL(sgs_weights_kernel<false>, dim3(launch_cells, a.n_chains), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_sgs_sequence(const SgsArgs& a, hipStream_t st) {
   if (!krige_search_ok(a.K)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sgs_sequence_kernel, dim3(a.n_chains), dim3(64 * kSeqWaves), 0, st, a);
+  if (a.group) hipLaunchKernelGGL(sgs_sequence_kernel<true>, dim3(a.n_chains), dim3(64 * kSeqWaves), 0, st, a);
+  else hipLaunchKernelGGL(sgs_sequence_kernel<false>, dim3(a.n_chains), dim3(64 * kSeqWaves), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_sgs_blocks(const SgsArgs& a, int launch_cells, hipStream_t st) {

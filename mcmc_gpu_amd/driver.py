@@ -414,7 +414,7 @@ def msc_run_wrapper(param_chain, param_run):
 
 
 def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters,
-                       output_path='./Data/output', mode=None, n_gpus=None, posterior=None):
+                       output_path='./Data/output', mode=None, n_gpus=None, posterior=None, groups=None):
     """Run n_chains small-scale chains and return the list of their result tuples (reference :211-274); files under
     <output_path>/LargeScaleChain/<lsc seed>/SmallScaleChain/<ssc seed>/ as the reference writes them.  Chains that share
     n_iter run together in one libgsm_hip handle (one workgroup per chain in every launch); `n_workers` is accepted for
@@ -432,8 +432,19 @@ def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_r
     writes <output_path>/LargeScaleChain/<lsc seed>/SmallScaleChain/posterior_{k}k.npz (posterior.PosteriorSummary.load reads it;
     {k}k as in the first chain's bed_{k}k.txt) over the chains of ALL ranks: every additive quantity is summed over the ranks and the
     traces are gathered, as largeScaleChain_mp does.  The beds are in bed units, trend included.  The summary covers THIS call's
-    segment: iteration 0 is the first iteration of the call, and accumulators are not carried across driver calls."""
+    segment: iteration 0 is the first iteration of the call, and accumulators are not carried across driver calls.
+
+    groups: None, or the dict of sgs.run_many_sgs (sgs.handoff makes it) -- chains that continue different large-scale beds, each with
+    the trend and the transformer of its own bed.  Needs the same n_iter for every chain (the chains share one handle).  Across ranks
+    every rank gets its chains' slice of `of` and only the groups that slice names, renumbered (sgs.slice_groups).  The groups are
+    NOT written to the seed folders: a call that resumes from them must be given the same dict again, or the chains would continue
+    with another trend and transformer than they started with."""
     mode_eff = mode or getattr(smallScaleChain, 'rng_mode', 'replay')
+    if groups is not None:
+        from . import sgs
+        if n_chains < 1 or len(set(int(v) for v in n_iters[:n_chains])) != 1:
+            raise ValueError('groups= needs the same n_iter for every chain')
+        sgs.check_groups(smallScaleChain, groups, n_chains)
     if mode not in (None, 'replay', 'philox', 'pcg64'):
         raise ValueError("mode must be 'replay', 'pcg64' or 'philox'")
     if posterior is not None:
@@ -454,22 +465,25 @@ def smallScaleChain_mp(n_chains, n_workers, smallScaleChain, initial_beds, ssc_r
         if n_gpus > 1:
             return _self_launch(n_gpus, dict(n_chains=n_chains, n_workers=n_workers, smallScaleChain=smallScaleChain, initial_beds=initial_beds,
                                              ssc_rng_seeds=ssc_rng_seeds, lsc_rng_seed=lsc_rng_seed, n_iters=n_iters,
-                                             output_path=output_path, mode=mode, posterior=posterior), which='smallScaleChain_mp')
+                                             output_path=output_path, mode=mode, posterior=posterior, groups=groups),
+                                which='smallScaleChain_mp')
     if sharded:
         rank, world = dist.get_rank(), dist.get_world_size()
         if posterior is not None and world > n_chains:
             raise ValueError(f'posterior= needs at least one chain on every rank: {n_chains} chains on {world} ranks')
         lo, hi = parallel.shard_bounds(n_chains, world, rank)
         local = _msc_run_chains(hi - lo, smallScaleChain, list(initial_beds[lo:hi]), list(ssc_rng_seeds[lo:hi]), lsc_rng_seed,
-                                list(n_iters[lo:hi]), output_path, mode_eff, posterior, n_chains) if hi > lo else []
+                                list(n_iters[lo:hi]), output_path, mode_eff, posterior, n_chains,
+                                None if groups is None else sgs.slice_groups(groups, lo, hi)) if hi > lo else []
         gathered = [None] * world
         dist.all_gather_object(gathered, local)
         return [r for part in gathered for r in part]
     return _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters, output_path, mode_eff, posterior,
-                           n_chains)
+                           n_chains, groups)
 
 
-def _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters, output_path, mode, posterior, all_chains):
+def _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_rng_seed, n_iters, output_path, mode, posterior, all_chains,
+                    groups=None):
     """The n_chains small-scale chains of this process: one libgsm_hip handle for all of them when they share n_iter, otherwise chain
     by chain through msc_run_wrapper.  all_chains: the chains of all ranks (the posterior summary covers them)."""
     from . import sgs
@@ -488,7 +502,7 @@ def _msc_run_chains(n_chains, smallScaleChain, initial_beds, ssc_rng_seeds, lsc_
         out = sgs.run_many_sgs(smallScaleChain, beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=10, progress_bar=None,
                                philox_seeds=[int(v) for v in ssc_rng_seeds[:n_chains]] if philox else None,
                                philox_iter0=starts.pop() if philox else 0, pcg64=(mode_eff == 'pcg64'), posterior=posterior,
-                               return_accumulator=posterior is not None)
+                               return_accumulator=posterior is not None, groups=groups)
         result = out[0]
         for i in range(n_chains):
             _msc_save(folders[i], result[i], n_iter, prevs[i])

@@ -168,6 +168,21 @@ class GsmEngine:
         self.call(self.lib.gsm_min_dist_from_mask, dx, dy, dm, out)
         return out.cpu().numpy()
 
+    def gaussian_filter(self, fields, w0, w1):
+        """gsm_gaussian_filter of a stack [n, H, W] (array or device tensor) with the two axes' weights (host arrays of odd
+        length); returns a device tensor."""
+        x = fields.to(device=self.dev, dtype=torch.float64).contiguous() if isinstance(fields, torch.Tensor) else self._f64(fields)
+        if x.dim() != 3 or tuple(x.shape[1:]) != (self.H, self.W) or x.shape[0] < 1:
+            raise ValueError(f"fields must have shape (n, {self.H}, {self.W})")
+        w0, w1 = (np.ascontiguousarray(w, dtype=np.float64) for w in (w0, w1))
+        if w0.ndim != 1 or w1.ndim != 1 or w0.size % 2 != 1 or w1.size % 2 != 1:
+            raise ValueError("the weights of an axis are a 1-D array of odd length")
+        out = torch.empty_like(x)
+        dp = C.POINTER(C.c_double)
+        self.call(self.lib.gsm_gaussian_filter, x, out, int(x.shape[0]), self.H, self.W, w0.ctypes.data_as(dp), w0.size // 2,
+                  w1.ctypes.data_as(dp), w1.size // 2)
+        return out
+
     def residual(self, beds):
         b = beds.to(device=self.dev, dtype=torch.float64).contiguous() if isinstance(beds, torch.Tensor) else self._f64(beds)
         if tuple(b.shape) != (self.n_chains, self.H, self.W):

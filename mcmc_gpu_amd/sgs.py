@@ -33,7 +33,63 @@ from copy import deepcopy
 
 import numpy as np
 
-__all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "batch_plan", "sgs", "cov_norm", "lag_cov_table"]
+__all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "batch_plan", "sgs", "cov_norm", "lag_cov_table", "trend_of",
+           "gaussian_weights", "check_groups", "slice_groups", "handoff"]
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """The weights of one axis of scipy.ndimage.gaussian_filter(order=0), in scipy's NumPy arithmetic
+    (scipy/ndimage/_filters.py: gaussian_filter1d, _gaussian_kernel1d)."""
+    sd = float(sigma)
+    lw = int(float(truncate) * sd + 0.5)
+    x = np.arange(-lw, lw + 1)
+    phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+    return phi / phi.sum()
+
+
+def trend_of(beds, sigma=10, truncate=4.0, device=None, mode="reflect"):
+    """The trend the reference's driver takes off a large-scale bed before the small-scale chain,
+    scipy.ndimage.gaussian_filter(bed, sigma) (smallScaleChain_multiprocessing.py:486), of one bed [H, W] or of a stack
+    [n, H, W] (each bed filtered on its own: the stack axis is not an axis of the filter).  `sigma` is a number or a
+    (rows, columns) pair; only mode='reflect', scipy's default, exists (ValueError otherwise).
+    device=True: the HIP kernels (gsm_gaussian_filter), all beds in one call; raises without a GPU.
+    device=False: scipy on the host, bed by bed.
+    device=None (default): the HIP kernels when a GPU is visible, else scipy -- the pattern of MCMC_gpu.min_dist_from_mask:
+    set-up code runs where there is no GPU.  The two agree to the rounding of their summation orders (gsm.h), not bit for bit.
+    A device tensor is taken and returned as one (device path only); arrays come back as arrays."""
+    if mode != "reflect":
+        raise ValueError("trend_of: only mode='reflect' (scipy's default, the reference's) is implemented")
+    sg = np.atleast_1d(np.asarray(sigma, dtype=np.float64))
+    if sg.shape not in ((1,), (2,)) or not np.all(np.isfinite(sg)) or np.any(sg <= 0) or not (float(truncate) > 0):
+        raise ValueError("trend_of: sigma must be a positive number or a pair of them, truncate positive")
+    s0, s1 = (float(sg[0]), float(sg[-1]))
+    import torch
+    is_tensor = isinstance(beds, torch.Tensor)
+    shape = tuple(beds.shape)
+    if len(shape) not in (2, 3) or 0 in shape:
+        raise ValueError("trend_of: beds must be one bed [H, W] or a stack [n, H, W]")
+    if device is None:
+        device = torch.cuda.is_available()
+    if device:
+        from .engine import GsmEngine
+        w0, w1 = gaussian_weights(s0, truncate), gaussian_weights(s1, truncate)
+        if max(w0.size, w1.size) // 2 > 128:
+            raise ValueError("trend_of: truncate * sigma above 128 cells is more than gsm_gaussian_filter takes")
+        x = beds if is_tensor else np.asarray(beds, dtype=np.float64)
+        x3 = x.reshape((-1,) + shape[-2:])
+        eng = GsmEngine(shape[-2], shape[-1], 1, device=x.device.index if is_tensor and x.is_cuda else None)      # raises RuntimeError without a GPU
+        try:
+            out = eng.gaussian_filter(x3, w0, w1).reshape(shape)
+            return out if is_tensor else out.cpu().numpy()
+        finally:
+            eng.close()
+    if is_tensor:
+        raise ValueError("trend_of: a tensor goes through the device path (device=True)")
+    from scipy.ndimage import gaussian_filter
+    x = np.asarray(beds, dtype=np.float64)
+    if x.ndim == 2:
+        return gaussian_filter(x, sigma=(s0, s1), truncate=float(truncate), mode="reflect")
+    return np.stack([gaussian_filter(b, sigma=(s0, s1), truncate=float(truncate), mode="reflect") for b in x])
 
 
 def cov_norm(h, vtype, sill, nugget, s=None):
@@ -380,6 +436,111 @@ def batch_plan(n_iter, batch, snapshot_iterations=None):
     return sizes
 
 
+def _is_device_qt(nst):
+    """scikit-learn's QuantileTransformer with normal output and one feature: the transformer gsm_qt_transform restates"""
+    return (type(nst).__name__ == 'QuantileTransformer' and getattr(nst, 'output_distribution', None) == 'normal'
+            and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1)
+
+
+def check_groups(chain, groups, n):
+    """The `groups` argument of run_many_sgs checked against the template chain and the number of chains; touches neither a device
+    nor a generator.  Returns None (no groups) or (of [n] int32, trend [G, H, W] float64 or None, nst_trans list of G or None).
+    groups = dict(of=<n ints>, trend=<[G, H, W]>, nst_trans=<list of G>): chain c continues the large-scale bed of group of[c] and
+    takes that group's trend and transformer, the way the reference's driver derives both from the bed it starts from
+    (smallScaleChain_multiprocessing.py:479-496).  `trend` is needed exactly when the template has detrend_map, `nst_trans` exactly
+    when it has do_transform; a group no chain names is allowed.
+    ValueError: a missing or uncalled-for key, wrong shapes, `of` out of range, a non-finite trend, transformers whose n_quantiles_
+    differ.  NotImplementedError: a transformer that is not scikit-learn's QuantileTransformer with normal output (the host-side
+    kind has no grouped path)."""
+    if groups is None:
+        return None
+    if not isinstance(groups, dict) or 'of' not in groups:
+        raise ValueError("groups must be a dict with the key 'of' (the group of every chain) and 'trend' / 'nst_trans' as the template calls for")
+    extra = set(groups) - {'of', 'trend', 'nst_trans'}
+    if extra:
+        raise ValueError(f"groups: unknown keys {sorted(extra)}")
+    H, W = np.asarray(chain.xx).shape
+    of = np.asarray(groups['of'])
+    if of.ndim != 1 or of.shape[0] != n or of.dtype.kind not in 'iu':
+        raise ValueError(f"groups['of'] must hold one integer per chain ({n})")
+    want_trend, want_nst = bool(chain.detrend_map), bool(chain.do_transform)
+    for key, want, flag in (('trend', want_trend, 'detrend_map'), ('nst_trans', want_nst, 'do_transform')):
+        if want and groups.get(key) is None:
+            raise ValueError(f"groups[{key!r}] is needed: the template chain has {flag}")
+        if not want and groups.get(key) is not None:
+            raise ValueError(f"groups[{key!r}] is given but the template chain has no {flag}")
+    if not want_trend and not want_nst:
+        raise ValueError("groups: the template chain has neither detrend_map nor do_transform, so nothing differs between groups")
+    trend = nst = None
+    G = None
+    if want_trend:
+        trend = np.asarray(groups['trend'], dtype=np.float64)
+        if trend.ndim != 3 or trend.shape[1:] != (H, W) or trend.shape[0] < 1:
+            raise ValueError(f"groups['trend'] must have shape (G, {H}, {W})")
+        if not np.isfinite(trend).all():
+            raise ValueError("groups['trend'] must be finite: the conditioning data must sit at the same cells in every group")
+        G = trend.shape[0]
+    if want_nst:
+        nst = list(groups['nst_trans'])
+        if len(nst) < 1 or (G is not None and len(nst) != G):
+            raise ValueError("groups['nst_trans'] must hold one transformer per group" + (f" ({G})" if G is not None else ""))
+        G = len(nst)
+        if not all(_is_device_qt(t) for t in nst):
+            raise NotImplementedError("groups: every transformer must be scikit-learn's fitted QuantileTransformer(output_distribution="
+                                      "'normal') of one feature; a transformer called on the host has no grouped path")
+        if len({int(t.quantiles_.shape[0]) for t in nst}) != 1:
+            raise ValueError("groups['nst_trans']: the transformers' n_quantiles_ differ (the device holds one table length)")
+    if of.size and (int(of.min()) < 0 or int(of.max()) >= G):
+        raise ValueError(f"groups['of'] must lie in [0, {G})")
+    return np.ascontiguousarray(of, dtype=np.int32), trend, nst
+
+
+def slice_groups(groups, lo, hi):
+    """The groups of chains lo .. hi - 1 (one rank's share): `of` of those chains renumbered densely in ascending order of the old
+    numbers, and only the trends and transformers those chains name, in that order.  Pure host code; None stays None."""
+    if groups is None:
+        return None
+    of = np.asarray(groups['of'])[lo:hi]
+    used, new_of = np.unique(of, return_inverse=True)
+    out = dict(of=new_of.astype(np.int32).reshape(-1))
+    if groups.get('trend') is not None:
+        out['trend'] = np.ascontiguousarray(np.asarray(groups['trend'])[used])
+    if groups.get('nst_trans') is not None:
+        out['nst_trans'] = [groups['nst_trans'][int(g)] for g in used]
+    return out
+
+
+def handoff(chain, lsc_beds, of, sigma=10, n_quantiles=1000, random_state=None, device=None):
+    """From large-scale beds to small-scale chains, the lines of the reference's driver that sit between the two samplers
+    (smallScaleChain_multiprocessing.py:479-496), once per large-scale bed:
+        bed = where((surf - bed <= 0) & (grounded_ice_mask == 1), surf - 1, bed)       the bed clamped under the surface
+        trend = gaussian_filter(bed, sigma)                                            trend_of: all beds in one device call
+        nst = QuantileTransformer(n_quantiles, 'normal', subsample=None, random_state).fit((bed - trend).reshape(-1, 1))     on the host
+    lsc_beds [G, H, W]: the final beds of a large-scale ensemble (run_many); of [n]: the large-scale bed each small-scale chain
+    continues.  `chain` is the small-scale template (its surf and grounded_ice_mask are used; set detrend_map / do_transform on it
+    as the run should have them: a key the template does not call for is left out of the dict).
+    Returns (initial_beds, groups): initial_beds[c] is the clamped bed of group of[c], and run_many_sgs(chain, initial_beds, rngs,
+    n_iter, groups=groups) continues every bed with its own trend and transformer."""
+    beds = np.array(lsc_beds, dtype=np.float64)
+    if beds.ndim != 3 or beds.shape[1:] != np.asarray(chain.xx).shape:
+        raise ValueError("lsc_beds must have shape (G, H, W) of the chain's grid")
+    of = np.asarray(of)
+    if of.ndim != 1 or of.dtype.kind not in 'iu' or (of.size and (of.min() < 0 or of.max() >= beds.shape[0])):
+        raise ValueError(f"`of` must hold integers in [0, {beds.shape[0]})")
+    surf = np.asarray(chain.surf, dtype=np.float64)
+    clamp = ((surf[None] - beds) <= 0) & (np.asarray(chain.grounded_ice_mask)[None] == 1)
+    beds = np.where(clamp, surf[None] - 1, beds)
+    groups = dict(of=np.ascontiguousarray(of, dtype=np.int32))
+    trend = trend_of(beds, sigma=sigma, device=device)
+    if chain.detrend_map:
+        groups['trend'] = trend
+    if chain.do_transform:
+        from sklearn.preprocessing import QuantileTransformer
+        groups['nst_trans'] = [QuantileTransformer(n_quantiles=n_quantiles, output_distribution='normal', subsample=None,
+                                                   random_state=random_state).fit((b - t).reshape(-1, 1)) for b, t in zip(beds, trend)]
+    return [beds[int(g)].copy() for g in of], groups
+
+
 # The draws of some iterations as gsm_sgs_iterate / gsm_sgs_blocks_batch read them.  Device draws: views of a buffer set, blk the
 # block records, cell counts in cnt, off_stride n.  Uploaded host draws: blk and cnt None, off_stride n + 1, cell_base on the host.
 _Draws = namedtuple('_Draws', 'win blk off cnt cells z us off_stride cell_base')
@@ -397,9 +558,9 @@ class _SgsRun:
     accum (posterior.PosteriorAccumulator on this run's handle) and snap, the scratch tensor of a snapshot in bed units."""
 
     def __init__(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source,
-                 philox_seeds, philox_iter0, posterior=None):
+                 philox_seeds, philox_iter0, posterior=None, groups=None):
         from .engine import GsmEngine
-        self._plan(chain, initial_beds, rngs, int(n_iter), only_save_last_bed, source)
+        self._plan(chain, initial_beds, rngs, int(n_iter), only_save_last_bed, source, groups)
         self.info_per_iter, self.progress_bar, self.philox_iter0 = max(int(info_per_iter), 1), progress_bar, int(philox_iter0)
         self.snap_its = frozenset()
         if posterior is not None:
@@ -420,9 +581,20 @@ class _SgsRun:
     def close(self):
         self.eng.close()
 
-    def _plan(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, source):
+    def _plan(self, chain, initial_beds, rngs, n_iter, only_save_last_bed, source, groups=None):
+        """groups: None or check_groups' triple.  With more than one group, `of` [n] is the group of every chain, trend_g [G, H, W],
+        z_cond [G, H, W] and the transformers hold one entry per group, and `trend` is the chains' own planes [n, H, W] (trend_g[of]);
+        one group is the ungrouped run with that group's trend and transformer in the template's place."""
         H, W = chain.xx.shape
         n = len(initial_beds)
+        self.of = self.trend_g = self.nst_g = None
+        chain_trend, chain_nst = chain.trend, chain.nst_trans
+        if groups is not None:
+            of, trend_g, nst_g = groups
+            if (trend_g.shape[0] if trend_g is not None else len(nst_g)) == 1:
+                chain_trend, chain_nst = (trend_g[0] if trend_g is not None else chain_trend), (nst_g[0] if nst_g is not None else chain_nst)
+            else:
+                self.of, self.trend_g, self.nst_g = of, trend_g, nst_g
         self.chain, self.rngs, self.source, self.n, self.n_iter, self.H, self.W = chain, rngs, source, n, n_iter, H, W
         self.xs, self.ys, self.dx, self.dy = _axes(np.asarray(chain.xx, dtype=np.float64), np.asarray(chain.yy, dtype=np.float64))
         self.rad, self.npts = float(chain.sgs_param[1]), int(chain.sgs_param[0])
@@ -431,19 +603,33 @@ class _SgsRun:
         self.lag_mi, self.lag_mj = lag_extents(self.hw, H, W)
         self.lag = lag_cov_table(self.vario, self.hw, self.dx, self.dy, self.lag_mi, self.lag_mj)
         self.max_cells = min(1024, max(1, (int(chain.block_max_x) - 1) * (int(chain.block_max_y) - 1)))
-        self.trend = np.asarray(chain.trend, dtype=np.float64) if chain.detrend_map else None
-        detrended = lambda a: np.asarray(a, dtype=np.float64) - self.trend if self.trend is not None else np.array(a, dtype=np.float64)
-        nst = self.nst = chain.nst_trans if chain.do_transform else None
-        cond_c = detrended(chain.cond_bed)
-        self.z_cond = nst.transform(cond_c.reshape(-1, 1)).reshape(H, W) if nst is not None else cond_c
-        self.cond_is_data = ~np.isnan(self.z_cond)
+        nst = self.nst = chain_nst if chain.do_transform else None
+        if self.of is None:
+            self.trend = np.asarray(chain_trend, dtype=np.float64) if chain.detrend_map else None
+            detrended = lambda a, c=None: np.asarray(a, dtype=np.float64) - self.trend if self.trend is not None else np.array(a, dtype=np.float64)
+            cond_c = detrended(chain.cond_bed)
+            self.z_cond = nst.transform(cond_c.reshape(-1, 1)).reshape(H, W) if nst is not None else cond_c
+            self.cond_is_data = ~np.isnan(self.z_cond)
+        else:
+            # per group what the ungrouped run makes once: the conditioning data minus the group's trend, through the group's transformer
+            G = self.trend_g.shape[0] if self.trend_g is not None else len(self.nst_g)
+            self.trend = self.trend_g[self.of] if self.trend_g is not None else None
+            detrended = lambda a, c=None: (np.asarray(a, dtype=np.float64) - (self.trend_g[c] if c is not None else 0.0)
+                                           if self.trend_g is not None else np.array(a, dtype=np.float64))
+            cond_g = [detrended(chain.cond_bed, g) for g in range(G)]
+            self.z_cond = np.stack([self.nst_g[g].transform(cond_g[g].reshape(-1, 1)).reshape(H, W) if self.nst_g is not None else cond_g[g]
+                                    for g in range(G)])
+            data = ~np.isnan(self.z_cond)
+            if not (data == data[0]).all():
+                raise ValueError("groups: the conditioning data do not sit at the same cells in every group")
+            self.cond_is_data = data[0]
+            nst = self.nst = self.nst_g[0] if self.nst_g is not None else None      # stands for the kind; the tables are per group
         # scikit-learn's QuantileTransformer with normal output and one feature (what the reference's drivers attach,
         # smallScaleChain_multiprocessing.py:493-496) runs on the device (gsm_qt_transform); any other transformer object is
         # called on the host once per iteration, where the reference calls it
         if nst is None:
             self.transformer = None
-        elif (type(nst).__name__ == 'QuantileTransformer' and getattr(nst, 'output_distribution', None) == 'normal'
-              and getattr(nst, 'quantiles_', None) is not None and nst.quantiles_.ndim == 2 and nst.quantiles_.shape[1] == 1):
+        elif _is_device_qt(nst):
             self.transformer = 'device_qt'
         else:
             self.transformer = 'host_nst'
@@ -467,7 +653,7 @@ class _SgsRun:
         # Only for few chains (4 chains, pcg64 mode: 38.7 -> 56.2 k chain-iterations/s): with the chip full (256 chains) the draw
         # kernel fits into the gap where the host downloads a batch's records, and drawing ahead measured 10 % slower (same box)
         self.draw_ahead = os.environ.get('GSM_SGS_DRAW_AHEAD', '1' if n <= 64 else '0') != '0'
-        self.bed0 = np.stack([detrended(b) for b in initial_beds])
+        self.bed0 = np.stack([detrended(b, None if self.of is None else self.of[c]) for c, b in enumerate(initial_beds)])
         # no NaN in the beds (and none can appear: every cell of a block is simulated): gsm_sgs_iterate may then make the records of
         # iteration j + 1 while iteration j is still running (include/gsm.h: grid_finite).  GSM_SGS_OVERLAP=0 turns that off.
         self.grid_finite = os.environ.get('GSM_SGS_OVERLAP', '1') != '0' and bool(np.isfinite(self.bed0).all())
@@ -492,7 +678,13 @@ class _SgsRun:
         eng.set_static(chain.surf, chain.velx, chain.vely, chain.dhdt, chain.smb, None, chain.grounded_ice_mask,
                        chain.mc_region_mask, chain.resolution, chain.sigma_mc)
         self.d_xs, self.d_ys, self.d_lag, self.d_zcond = f64(self.xs), f64(self.ys), f64(self.lag), f64(self.z_cond)
-        self.d_trend = f64(self.trend) if self.trend is not None else None
+        self.d_trend_n = None                                    # the chains' own trend planes [n, H, W] (snapshot)
+        if self.of is None:
+            self.d_trend = f64(self.trend) if self.trend is not None else None
+        else:
+            # chain groups: trend, z_cond and the transformer tables hold one plane / table per group and the handle knows each chain's group
+            self.d_trend = f64(self.trend_g) if self.trend_g is not None else None
+            eng._check(self.lib.gsm_sgs_set_groups(eng.h, self.of.ctypes.data_as(C.POINTER(C.c_int32)), int(self.z_cond.shape[0])))
         self.cur = f64(self.bed0)
         self.nxt = self.cur.clone()
         self.bed_host = self.bed0 if self.transformer == 'host_nst' else None     # host-side transformer: the chains' state lives here
@@ -500,8 +692,9 @@ class _SgsRun:
         self.d_q = self.d_ref = self.prop = None
         self.nq = 0
         if self.transformer == 'device_qt':
-            self.d_q, self.d_ref = f64(self.nst.quantiles_[:, 0]), f64(self.nst.references_)
-            self.nq = int(self.d_q.numel())
+            tabs = [self.nst] if self.of is None else self.nst_g
+            self.d_q, self.d_ref = f64(np.stack([t.quantiles_[:, 0] for t in tabs])), f64(np.stack([t.references_ for t in tabs]))
+            self.nq = int(self.d_q.shape[1])
             self.prop = self.cur.clone()                         # proposed beds in data space (inverse transform of nxt)
         self.resampled = torch.zeros((n, H, W), dtype=torch.int32, device=dev)
         self.d_loss = torch.empty(n, dtype=torch.float64, device=dev)
@@ -547,6 +740,8 @@ class _SgsRun:
                                           residual=opt['residual'], local=opt['local'])
         if self.trend is not None or self.bed_host is not None:
             self.snap = torch.empty((self.n, self.H, self.W), dtype=torch.float64, device=self.dev)
+        if self.of is not None and self.d_trend is not None:
+            self.d_trend_n = self.d_trend[torch.as_tensor(self.of.astype(np.int64)).to(self.dev)]
 
     def snapshot(self, it, st):
         """If iteration `it` is a snapshot: the chains' state after its decision, in bed units (what store_bed keeps in
@@ -561,7 +756,7 @@ class _SgsRun:
             if self.bed_host is not None:
                 self.snap.copy_(torch.as_tensor(self.bed_host + self.trend if self.trend is not None else self.bed_host))
             elif self.snap is not None:
-                torch.add(self.cur, self.d_trend, out=self.snap)
+                torch.add(self.cur, self.d_trend if self.d_trend_n is None else self.d_trend_n, out=self.snap)
             self.eng.beds = self.snap if self.snap is not None else self.cur
             ring = accum.ring
             accum.add()
@@ -679,7 +874,7 @@ class _SgsRun:
                 g.bit_generator.state = st
         out = []
         for c in range(self.n):
-            last = bed_c[c] + self.trend if self.trend is not None else bed_c[c]
+            last = bed_c[c] + (self.trend if self.of is None else self.trend[c]) if self.trend is not None else bed_c[c]
             tup = (self.bed_cache[c] if self.keep_all else last, self.loss_cache[c].copy(), np.zeros(self.n_iter), self.loss_cache[c],
                    self.step_cache[c], res[c], self.blocks_cache[c])
             out.append(tup + (self.sample_values[c],) if self.track else tup)
@@ -826,7 +1021,7 @@ class _SgsRun:
 
 
 def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, info_per_iter=100, progress_bar=None, device=None,
-                 philox_seeds=None, philox_iter0=0, pcg64=False, posterior=None, return_accumulator=False):
+                 philox_seeds=None, philox_iter0=0, pcg64=False, posterior=None, return_accumulator=False, groups=None):
     """n small-scale chains of one template (same static fields, variogram, block sizes) in ONE handle.  rngs: one NumPy
     Generator per chain (consumed exactly as chain_sgs.run consumes chain.rng).  philox_seeds (one 64-bit key per chain): Philox
     mode -- the draws of iterations philox_iter0 .. are made on the device and rngs are not touched.  pcg64=True: the draws of
@@ -846,8 +1041,18 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
     PosteriorSummary), or with return_accumulator=True the PosteriorAccumulator in place of the summary: its local_sums(),
     sample_values(), projections() and finalize() are readable after the call, to be merged over ranks first.  The chains are
     those of the run without `posterior`: beds, accept masks, blocks, counts and generator states bit for bit; the losses bit for
-    bit with device draws and to the agreement of the batched with the one-by-one path (1e-12 relative) with host draws."""
+    bit with device draws and to the agreement of the batched with the one-by-one path (1e-12 relative) with host draws.
+
+    groups: None, or dict(of=<n ints>, trend=<[G, H, W]>, nst_trans=<list of G>) -- chains that continue DIFFERENT large-scale beds
+    in this one handle (check_groups has the rules; sgs.handoff makes the dict from a run_many ensemble).  Chain c is detrended with
+    trend[of[c]], transformed with nst_trans[of[c]] and conditioned on the data as that pair transforms them, everywhere the
+    ungrouped run uses the template's trend and transformer: initial beds and conditioning scores, the loss and the guard, both
+    transforms, the posterior snapshots, the stored beds and the returned beds.  Every chain is, bit for bit, the chain of a
+    run_many_sgs call on its group alone with a template set up with that group's trend and transformer (losses to 1e-12 relative
+    with host draws, as above).  All draw modes, drivers and `posterior`; one group is the run without groups on that group's trend
+    and transformer.  Refused before a handle exists or a generator is touched (check_groups)."""
     n = len(initial_beds)
+    groups = check_groups(chain, groups, n)
     if len(rngs) != n:
         raise ValueError('need one random generator per chain')
     if pcg64 and philox_seeds is not None:
@@ -859,7 +1064,7 @@ def run_many_sgs(chain, initial_beds, rngs, n_iter, only_save_last_bed=True, inf
         posterior = check_options(posterior, n_iter, n_chains=n)
     source = 'pcg64' if pcg64 else 'philox' if philox_seeds is not None else 'replay'
     run = _SgsRun(chain, initial_beds, rngs, n_iter, only_save_last_bed, info_per_iter, progress_bar, device, source, philox_seeds, philox_iter0,
-                  posterior=posterior)
+                  posterior=posterior, groups=groups)
     try:
         if run.source != 'replay' and run.transformer != 'host_nst':
             run.drive_device_draws()                 # batch is 1 with keep_all / track
