@@ -851,6 +851,29 @@ int gsm_posterior_local(gsm_handle h, const void* beds, const double* g, int32_t
 int gsm_variogram_map(gsm_handle h, const double* fields, int32_t n_fields, const uint8_t* mask, int32_t mi, int32_t mj,
                       int32_t rows_per_part, double* sum, int64_t* count, void* stream);
 
+/* ---- local variogram maps: one table per tile, or per window of tiles ---------------------------------------------------------
+ * The grid is cut into tiles of tile x tile cells, Ty = ceil(H / tile) by Tx = ceil(W / tile), the last row and column ragged.
+ * A pair (i, j), (i + di, j + dj) of gsm_variogram_map's half plane belongs to the tile that holds its midpoint,
+ *   ti = (2 i + di) / (2 tile),  tj = (2 j + dj) / (2 tile)       (integer division; both numerators are >= 0),
+ * whichever end is called first: every pair belongs to exactly one tile, and the tile tables add up to gsm_variogram_map's.
+ * The window of a tile is the (2 half_window + 1)^2 tiles centred on it, clipped at the lattice's edge; its table is the sum of
+ * its tiles' tables in ascending (ti, tj).  half_window = 0 returns the tile tables themselves.
+ *   sum, count [dev, n_fields*Ty*Tx*(mi+1)*(2*mj+1)]   per field, window and offset, at
+ *                                                      (((r*Ty + ti)*Tx + tj)*(mi+1) + di)*(2*mj+1) + dj + mj; fp64 / int64
+ *   fields, mask, mi, mj                               as gsm_variogram_map: (0, dj <= 0) and offsets beyond the grid hold 0 / 0
+ *   tile                                               >= 2; a tile beyond the grid is one tile
+ * No atomics; no sum's order depends on n_fields or on the device: the same call twice gives the same bits, and field r of a
+ * batched call gives the bits of the call on that field alone.  Terms as gsm_variogram_map's (three roundings each).
+ * With half_window > 0 the tile tables are a scratch of the call (fields go through in slices of at most 1 GiB of it) and the
+ * call returns when `stream` has drained; with half_window == 0 it is asynchronous on `stream`.
+ * Errors (a refused call writes nothing): GSM_E_ARG for NULL fields / sum / count, n_fields < 1, mi < 0 or mj < 0, tile < 2,
+ * half_window < 0; GSM_E_UNSUPPORTED for mi or mj above 2^20, more than 2^31 entries per field, more than 65535 tile rows or
+ * 2^30 workgroups per tile row; GSM_E_HIP (with the size) when the scratch cannot be allocated.
+ * Replaces: one gsm_variogram_map call per cropped window, which counts every pair once per window that holds it.  The
+ * reference takes per-cell variogram parameters (interpolate.py:56-62) and has no estimator for them. */
+int gsm_variogram_local(gsm_handle h, const double* fields, int32_t n_fields, const uint8_t* mask, int32_t mi, int32_t mj,
+                        int32_t tile, int32_t half_window, double* sum, int64_t* count, void* stream);
+
 /* Diagnostics: stream-copy n doubles src -> dst [dev] with the step kernel's access shape (8 bytes per lane,
  * coalesced).  A known byte count for calibrating rocprofv3's FETCH_SIZE / WRITE_SIZE (MI355X_MICROARCH.md, HBM). */
 int gsm_debug_stream_copy(const double* src, double* dst, int64_t n, void* stream);

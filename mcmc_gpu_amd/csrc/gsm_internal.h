@@ -454,5 +454,9 @@ int variogram_default_rows_per_part(int H, int W, int mi, int mj);     // a func
 int variogram_parts(int H, int rows_per_part);
 hipError_t launch_variogram_map(const double* fields, int n_fields, const uint8_t* mask, int H, int W, int mi, int mj, int rows_per_part,
                                 double* psum, int64_t* pcount, double* sum, int64_t* count, hipStream_t st);
+// variogram_local_kernel.hip: per-tile tables (k == 0: written to sum / count, tsum / tcount unused), then per-window sums of them
+int64_t variogram_local_workgroups(int mi, int mj, int Tx);             // workgroups per field and tile row
+hipError_t launch_variogram_local(const double* fields, int n_fields, const uint8_t* mask, int H, int W, int mi, int mj, int T, int k,
+                                  double* tsum, int64_t* tcount, double* sum, int64_t* count, hipStream_t st);
 
 }  // namespace gsm

@@ -13,6 +13,15 @@ arithmetic on a few thousand offsets.  Many fields (chains, realisations) go thr
     fit             a covariance model of sgs.cov_norm fitted to an experimental variogram (host)
     variograms      utilities.variograms's arguments and return tuple, plus `device`
 
+The reference's SGS and kriging take every variogram parameter per cell (local_vario, interpolate.py:56-62, :141-147) and the
+reference has nothing that estimates such maps.  Here the device makes the variogram map per WINDOW of tiles in one pass over the
+pairs (gsm_variogram_local, csrc/variogram_local_kernel.hip), and an anisotropic model is fitted to each window's table:
+
+    local_variogram_map   the map of every window of tiles, of one field or a batch
+    fit_anisotropic       major and minor range, azimuth and sill fitted to a 2-D offset table (host); also for a VariogramMap
+    fit_local             fit_anisotropic per window, expanded to [H, W] parameter maps (host)
+    local_variograms      the three in one call: the `variogram` dict of interpolate.sgs / krige with parameter maps
+
 Conventions.  scikit-gstat is not available where this package is built and tested, so its binning and fitting conventions
 cannot be pinned by a test; the ones stated in `experimental` and `fit` are this package's own.
 """
@@ -25,7 +34,8 @@ import numpy as np
 
 from .sgs import _axes, cov_norm
 
-__all__ = ["VariogramMap", "variogram_map", "bin_map", "experimental", "fit", "variograms"]
+__all__ = ["VariogramMap", "variogram_map", "bin_map", "experimental", "fit", "variograms", "LocalVariogramMap", "LocalVariogram",
+           "local_variogram_map", "fit_anisotropic", "fit_local", "local_variograms"]
 
 
 @dataclass
@@ -297,3 +307,286 @@ def variograms(xx, yy, grid, bin_func='even', maxlag=100e3, n_lags=70, covmodels
     bins, gamma, counts = experimental(xx, yy, grid, maxlag=maxlag, n_lags=n_lags, bin_func=bin_func, normal_score=True, device=device)
     vgrams = {m: fit(bins, gamma[0], counts[0], m) for m in covmodels}
     return vgrams, gamma[0], bins
+
+
+# ---- local variogram maps and anisotropic fits per window ------------------------------------------------------------------------
+
+@dataclass
+class LocalVariogramMap:
+    """VariogramMap's offset arrays (di, dj, hx, hy, dist, each [mi + 1, 2 mj + 1]), the lattice of tiles -- `tile` cells per
+    side, Ty = ceil(H / tile) by Tx = ceil(W / tile), centres xc, yc [Ty, Tx] (the mean coordinate of a tile's cells, the ragged
+    last tiles included) -- and per field and WINDOW [R, Ty, Tx, mi + 1, 2 mj + 1]: sum, count (int64), gamma = sum / (2 count),
+    NaN where count == 0.  A pair belongs to the tile that holds its midpoint; the window of a tile is the (2 half_window + 1)^2
+    tiles centred on it, clipped at the lattice's edge (half_window 0: the tile alone).  total_sum, total_count
+    [R, mi + 1, 2 mj + 1]: the map of the whole field (gsm_variogram_map), which is also the sum of all tiles."""
+    di: np.ndarray
+    dj: np.ndarray
+    hx: np.ndarray
+    hy: np.ndarray
+    dist: np.ndarray
+    xc: np.ndarray
+    yc: np.ndarray
+    sum: np.ndarray
+    count: np.ndarray
+    gamma: np.ndarray
+    total_sum: np.ndarray
+    total_count: np.ndarray
+    tile: int
+    half_window: int
+    shape: tuple
+
+
+def _tile_centres(xs, ys, tile):
+    """Mean coordinate of the cells of every tile: ([Ty], [Tx]) along y and x."""
+    def centres(c):
+        n = c.size
+        return np.array([0.5 * (c[a] + c[min(a + tile, n) - 1]) for a in range(0, n, tile)])
+    return centres(ys), centres(xs)
+
+
+def _local_result(xs, ys, dx, dy, mi, mj, tile, half_window, s, c, total_s, total_c):
+    yc, xc = _tile_centres(xs, ys, tile)
+    xc2, yc2 = np.meshgrid(xc, yc)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gamma = np.where(c > 0, s / (2.0 * c), np.nan)
+    return LocalVariogramMap(*_offsets(mi, mj, dx, dy), xc2, yc2, s, c, gamma, total_s, total_c, int(tile), int(half_window),
+                             (ys.size, xs.size))
+
+
+def local_variogram_map(xx, yy, fields, maxlag, tile, half_window=0, mask=None, device=None, _fields_per_part=None):
+    """Variogram maps per window of tiles (gsm_variogram_local): `fields`, `maxlag`, `mask`, `device` and the grid as
+    variogram_map; `tile` >= 2 cells per side of a tile, `half_window` >= 0 tiles on each side of a window's centre tile.
+    Returns a LocalVariogramMap.  Every pair is counted once, in the tile of its midpoint, and a window adds its tiles' tables,
+    so overlapping windows cost no pair work.  Bits as variogram_map: the same call twice gives the same bits, row r of a batch
+    gives the bits of the call on fields[r] alone, and the slices a large batch is sent in change nothing."""
+    import torch
+    from .engine import GsmEngine, _ptr
+    xx, yy = np.asarray(xx, dtype=np.float64), np.asarray(yy, dtype=np.float64)
+    if xx.ndim != 2 or xx.shape != yy.shape:
+        raise ValueError("xx and yy must be 2D arrays of the same shape")
+    H, W = xx.shape
+    if H < 3 or W < 3:
+        raise ValueError(f"the grid must have at least 3 rows and 3 columns, got {(H, W)}")
+    if int(tile) != tile or tile < 2:
+        raise ValueError("tile must be an integer >= 2 (cells per side of a tile)")
+    if int(half_window) != half_window or half_window < 0:
+        raise ValueError("half_window must be an integer >= 0 (tiles on each side of a window's centre)")
+    tile, half_window = int(tile), int(half_window)
+    xs, ys, dx, dy = _axes(xx, yy)
+    on_device = isinstance(fields, torch.Tensor)
+    f3 = _fields3(fields if on_device else np.asarray(fields, dtype=np.float64), (H, W))
+    R = f3.shape[0]
+    if R < 1:
+        raise ValueError("fields holds no field")
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (H, W):
+            raise ValueError(f"mask must have the grid's shape {(H, W)}, got {mask.shape}")
+    mi, mj = offset_extents(H, W, dx, dy, maxlag)
+    Ty, Tx = -(-H // tile), -(-W // tile)
+    table = (mi + 1, 2 * mj + 1)
+    n_off = table[0] * table[1]
+    s_out = np.empty((R, Ty, Tx) + table, dtype=np.float64)
+    c_out = np.empty((R, Ty, Tx) + table, dtype=np.int64)
+    ts_out = np.empty((R,) + table, dtype=np.float64)
+    tc_out = np.empty((R,) + table, dtype=np.int64)
+    eng = GsmEngine(H, W, 1, device)
+    try:
+        dev = eng.dev
+        d_mask = None if mask is None else torch.as_tensor(np.ascontiguousarray(mask != 0, dtype=np.uint8)).to(dev)
+        # a slice's own arrays: the fields (counted also when they are already on the device), the window tables and the whole
+        # field's.  The library adds its tile tables, at most 1 GiB or one field's; half of the free memory leaves room for them
+        per_field = 8 * H * W + 16 * n_off * (Ty * Tx + 1)
+        step = int(_fields_per_part or max(1, min(R, (torch.cuda.mem_get_info(dev)[0] // 2) // per_field)))
+        with torch.cuda.device(dev):
+            for r0 in range(0, R, step):
+                part = f3[r0:r0 + step]
+                d_f = (part if on_device else torch.as_tensor(np.ascontiguousarray(part))).to(device=dev, dtype=torch.float64).contiguous()
+                n = int(d_f.shape[0])
+                d_s = torch.empty((n, Ty, Tx) + table, dtype=torch.float64, device=dev)
+                d_c = torch.empty((n, Ty, Tx) + table, dtype=torch.int64, device=dev)
+                d_ts = torch.empty((n,) + table, dtype=torch.float64, device=dev)
+                d_tc = torch.empty((n,) + table, dtype=torch.int64, device=dev)
+                eng._check(eng.lib.gsm_variogram_local(eng.h, _ptr(d_f), n, _ptr(d_mask), mi, mj, tile, half_window, _ptr(d_s), _ptr(d_c),
+                                                       eng._stream()))
+                eng._check(eng.lib.gsm_variogram_map(eng.h, _ptr(d_f), n, _ptr(d_mask), mi, mj, 0, _ptr(d_ts), _ptr(d_tc), eng._stream()))
+                s_out[r0:r0 + n] = d_s.cpu().numpy()
+                c_out[r0:r0 + n] = d_c.cpu().numpy()
+                ts_out[r0:r0 + n] = d_ts.cpu().numpy()
+                tc_out[r0:r0 + n] = d_tc.cpu().numpy()
+    finally:
+        eng.close()
+    return _local_result(xs, ys, dx, dy, mi, mj, tile, half_window, s_out, c_out, ts_out, tc_out)
+
+
+_VTYPES = ("exponential", "gaussian", "spherical", "matern")
+
+
+def _aniso_gamma(hx, hy, q, vt, nugget, s):
+    """model_gamma at |h . R| with M = R R^T = [[a, b], [b, c]] and q = (a, b, c, sill): |h . R|^2 = a hx^2 + 2 b hx hy + c hy^2."""
+    a, b, c, sill = q
+    return model_gamma(np.sqrt(np.maximum(a * hx * hx + 2.0 * b * hx * hy + c * hy * hy, 0.0)), vt, 1.0, sill, nugget, s)
+
+
+def _aniso_polish(hx, hy, g, w, q, vt, nugget, s, rel_step=1e-4):
+    """_polish for the anisotropic model, on q = (a, b, c, sill) of _aniso_gamma: Gauss-Newton steps until the step is at rounding
+    level.  The central difference's step is relative to sqrt(a c) for the three entries of M (b may be zero) and to the sill.  A
+    step that is not finite, leaves the positive-definite matrices or the sills above the nugget ends the polish with the last
+    accepted q.  With residuals that are not zero (any measured table) the steps stop shrinking at about 1e-12, where the
+    difference quotient's rounding noise times the residual takes over; the polish ends there instead of wandering on."""
+    q = np.array(q, dtype=np.float64)
+    last = np.inf
+    for _ in range(100):
+        scale = np.array([math.sqrt(q[0] * q[2])] * 3 + [q[3]])
+        r = (_aniso_gamma(hx, hy, q, vt, nugget, s) - g) * w
+        J = np.empty((g.size, 4))
+        for k in range(4):
+            e = np.zeros(4)
+            e[k] = rel_step * scale[k]
+            J[:, k] = (_aniso_gamma(hx, hy, q + e, vt, nugget, s) - _aniso_gamma(hx, hy, q - e, vt, nugget, s)) / (2.0 * e[k]) * w
+        d = np.linalg.lstsq(J, -r, rcond=None)[0]
+        p = q + d
+        if not np.all(np.isfinite(p)) or p[0] <= 0 or p[2] <= 0 or p[0] * p[2] - p[1] * p[1] <= 0 or p[3] <= nugget:
+            break
+        q = p
+        step = float(np.max(np.abs(d) / scale))
+        if step < 1e-14 or (step < 1e-10 and step >= last):
+            break
+        last = step
+    return q
+
+
+def fit_anisotropic(hx, hy, gamma, counts, vtype, nugget=0.0, s=None, _start=None):
+    """The anisotropic counterpart of `fit`: major_range >= minor_range, azimuth in [0, 180) and sill of model_gamma(|h . R|, ...)
+    fitted to one table of offsets -- hx, hy, gamma, counts of the same shape, e.g. a VariogramMap's hx, hy, gamma[r], count[r] or
+    one window of a LocalVariogramMap -- by least squares weighted with the pair counts; the nugget (and Matern's s, required)
+    are held.  R is sgs.rotation_matrix's and the lag multiplies it from the left, as the kriging kernels do.
+    The fit runs on the symmetric positive-definite M = R R^T through its Cholesky factor (three numbers: no angle that wraps
+    around, no swap of the two ranges), then Gauss-Newton steps down to rounding (_aniso_polish); ranges and azimuth are read
+    from M's eigen-decomposition: eigenvalues 1 / range^2, the major axis along the eigenvector of the smaller one.  When the
+    ranges agree to 1e-9 relative they are returned equal with azimuth 0.0.  Empty offsets (NaN gamma or count 0) are left out.
+    Returns the `variogram` dict of interpolate.sgs / krige.  Spherical: the limitation stated in `fit`."""
+    from scipy.optimize import least_squares
+    vt = vtype.lower()
+    if vt not in _VTYPES:
+        raise ValueError("vtype must be exponential, gaussian, spherical, or matern")
+    if vt == "matern" and s is None:
+        raise ValueError("a Matern fit of an offset table holds the smoothness: pass s")
+    hx, hy, g, c = (np.asarray(a, dtype=np.float64).ravel() for a in (hx, hy, gamma, counts))
+    if not (hx.shape == hy.shape == g.shape == c.shape):
+        raise ValueError("hx, hy, gamma and counts must have the same shape (one table of offsets)")
+    ok = np.isfinite(g) & (c > 0)
+    if ok.sum() < 4 or np.linalg.matrix_rank(np.stack([hx[ok] ** 2, hx[ok] * hy[ok], hy[ok] ** 2], axis=1)) < 3:
+        raise ValueError("too few non-empty offsets to fit an anisotropic variogram model (four, in three directions)")
+    hx, hy, g, w = hx[ok], hy[ok], g[ok], np.sqrt(c[ok])
+    if _start is None:
+        def unpack(p):
+            l0, l1, l2, sill = p
+            return np.array([l0 * l0, l0 * l1, l1 * l1 + l2 * l2, sill])
+        r0 = np.hypot(hx, hy).max() / 3.0
+        p0 = [1.0 / r0, 0.0, 1.0 / r0, max(float(np.max(g)), nugget + 1e-9)]
+        out = least_squares(lambda p: (_aniso_gamma(hx, hy, unpack(p), vt, nugget, s) - g) * w, p0, x_scale="jac", xtol=1e-15,
+                            ftol=1e-15, gtol=1e-15, max_nfev=5000)
+        q = unpack(out.x)
+    else:
+        q = np.asarray(_start, dtype=np.float64)
+    if not np.all(np.isfinite(q)) or q[0] <= 0 or q[2] <= 0 or q[0] * q[2] - q[1] * q[1] <= 0 or q[3] <= nugget:
+        raise ValueError("the anisotropic fit left the admissible models (M positive definite, sill above the nugget)")
+    q = _aniso_polish(hx, hy, g, w, q, vt, nugget, s)
+    ev, evec = np.linalg.eigh(np.array([[q[0], q[1]], [q[1], q[2]]]))
+    major, minor = 1.0 / math.sqrt(ev[0]), 1.0 / math.sqrt(ev[1])
+    azimuth = math.degrees(math.atan2(evec[1, 0], evec[0, 0])) % 180.0
+    if major - minor <= 1e-9 * major:
+        minor, azimuth = major, 0.0
+    out = {"major_range": float(major), "minor_range": float(minor), "azimuth": float(azimuth), "sill": float(q[3]),
+           "nugget": float(nugget), "vtype": vt}
+    if vt == "matern":
+        out["s"] = float(s)
+    return out
+
+
+def _aniso_q(v):
+    """(a, b, c, sill) of _aniso_gamma for a variogram dict."""
+    th = math.radians(v["azimuth"])
+    cs, sn = math.cos(th), math.sin(th)
+    la, lb = 1.0 / v["major_range"] ** 2, 1.0 / v["minor_range"] ** 2
+    return np.array([cs * cs * la + sn * sn * lb, cs * sn * (la - lb), sn * sn * la + cs * cs * lb, v["sill"]])
+
+
+class LocalVariogram(dict):
+    """The `variogram` dict of interpolate.sgs / krige with [H, W] parameter maps; `fitted` [Ty, Tx] bool says which windows
+    carry their own fit (the others took the whole field's), `windows` [Ty, Tx] holds every window's fitted dict."""
+    fitted = None
+    windows = None
+
+
+def _expand(P, shape, tile, how, angle=False):
+    """A [Ty, Tx] lattice of window values as an [H, W] map.  'nearest': every cell takes its own tile's.  'bilinear': linear
+    between the tile centres along each axis (in cell indices; the ragged last tiles have their own centres), constant outside
+    the outermost centres; an angle (degrees, modulo 180) goes through cos 2 theta, sin 2 theta."""
+    H, W = shape
+    if how == "nearest":
+        return np.ascontiguousarray(P[np.arange(H)[:, None] // tile, np.arange(W)[None, :] // tile], dtype=np.float64)
+    if angle:
+        th = np.radians(2.0 * P)
+        cs, sn = _expand(np.cos(th), shape, tile, how), _expand(np.sin(th), shape, tile, how)
+        return (0.5 * np.degrees(np.arctan2(sn, cs))) % 180.0
+    ci, cj = _tile_centres(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64), tile)
+    rows = np.stack([np.interp(np.arange(W), cj, P[a]) for a in range(P.shape[0])])              # [Ty, W]
+    return np.ascontiguousarray(np.stack([np.interp(np.arange(H), ci, rows[:, b]) for b in range(W)], axis=1))
+
+
+def fit_local(lmap, vtype, nugget=0.0, s=None, min_pairs=500, field=0, expand="nearest", _start=None):
+    """fit_anisotropic on every window of a LocalVariogramMap (host), expanded to parameter maps of the grid's shape.
+    A window with fewer than min_pairs pairs in all, or whose fit fails (too few offsets, or a fit that leaves the admissible
+    models), takes the fit of the whole field's table, lmap.total_*; that fit failing is an error.
+    expand: 'nearest' -- every cell takes the window centred on its own tile -- or 'bilinear' -- linear between the tile centres,
+    the azimuth through cos 2 theta and sin 2 theta, constant outside the outermost centres.
+    Returns a LocalVariogram: the dict interpolate.sgs / krige take as is, major_range, minor_range, azimuth, sill as [H, W] maps
+    without NaN, nugget, vtype (and s) as given, with `fitted` [Ty, Tx] bool as an attribute.  _start ([Ty, Tx] fitted dicts, e.g.
+    an earlier result's `windows`): the windows' Gauss-Newton steps start there and the global search is left out.  Parameter maps go with vtype
+    exponential, gaussian or spherical there (interpolate._local_table); a Matern result serves as a table of fits."""
+    if expand not in ("nearest", "bilinear"):
+        raise ValueError("expand must be 'nearest' or 'bilinear'")
+    R, Ty, Tx = lmap.count.shape[:3]
+    if not 0 <= int(field) < R:
+        raise ValueError(f"field must be in [0, {R})")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tg = np.where(lmap.total_count[field] > 0, lmap.total_sum[field] / (2.0 * lmap.total_count[field]), np.nan)
+    whole = fit_anisotropic(lmap.hx, lmap.hy, tg, lmap.total_count[field], vtype, nugget, s)
+    fitted = np.zeros((Ty, Tx), dtype=bool)
+    windows = np.empty((Ty, Tx), dtype=object)
+    for a in range(Ty):
+        for b in range(Tx):
+            windows[a, b] = whole
+            if lmap.count[field, a, b].sum() < min_pairs:
+                continue
+            try:
+                windows[a, b] = fit_anisotropic(lmap.hx, lmap.hy, lmap.gamma[field, a, b], lmap.count[field, a, b], vtype, nugget, s,
+                                                _start=None if _start is None else _aniso_q(_start[a, b]))
+                fitted[a, b] = True
+            except (ValueError, np.linalg.LinAlgError):
+                pass
+    out = LocalVariogram()
+    for key in ("major_range", "minor_range", "azimuth", "sill"):
+        P = np.array([[windows[a, b][key] for b in range(Tx)] for a in range(Ty)], dtype=np.float64)
+        out[key] = _expand(P, lmap.shape, lmap.tile, expand, angle=key == "azimuth")
+    out["nugget"], out["vtype"] = float(nugget), whole["vtype"]
+    if "s" in whole:
+        out["s"] = whole["s"]
+    out.fitted, out.windows = fitted, windows
+    return out
+
+
+def local_variograms(xx, yy, grid, vtype, maxlag, tile, half_window=1, normal_score=True, mask=None, device=None, **fit_kw):
+    """Parameter maps for non-stationary interpolate.sgs / krige in one call: the normal-score transform of the conditioning
+    values of `grid` (NaN where there is none) as `variograms` makes it (normal_score=False: the values as they are), their
+    local_variogram_map on the device, and fit_local (fit_kw: nugget, s, min_pairs, expand).  Returns fit_local's LocalVariogram."""
+    grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim != 2 or grid.shape != np.shape(xx) or grid.shape != np.shape(yy):
+        raise ValueError("xx, yy, and grid must be 2D arrays of the same shape")
+    if "field" in fit_kw:
+        raise TypeError("local_variograms fits its one grid: `field` is not an argument")
+    values = _normal_scores(grid[None])[0] if normal_score else grid
+    lmap = local_variogram_map(xx, yy, values, maxlag, tile, half_window, mask=mask, device=device)
+    return fit_local(lmap, vtype, **fit_kw)
