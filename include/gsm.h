@@ -207,7 +207,7 @@ int gsm_spectral_from_noise(gsm_handle h, int32_t n_fields, const int32_t* size_
 /* Philox mode end to end.  Spectral generator: the fused chain kernel (per chain-step the proposal is generated and
  * consumed inside one workgroup; nothing but chain state touches HBM), launched once per segment of at most 4096 steps
  * (scratch: one 140-byte scalar record per chain and step of a SEGMENT; `batch` is not used).  Cholesky generator, block
- * tables beyond the fused kernel's LDS budget, or gsm_set_fused(h, 0): batches of `batch` steps, proposals of
+ * tables beyond the fused kernel's LDS budget, or gsm_set_option(h, GSM_OPT_FUSED, 0): batches of `batch` steps, proposals of
  * batch k+1 generated on a second stream while batch k is stepped, scratch owned by the handle.
  * Both forms give bit-identical results, whatever the segment / batch size.  Outputs as gsm_run_replay plus blocks
  * [dev, n_chains*n_steps*4] = (row, col, bh, bw) (blocks_cache, MCMC.py:1264).  Synchronises the stream before returning.
@@ -217,17 +217,25 @@ int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int32_t batch, 
                    const gsm_rf_params* rf, void* beds, void* energy, uint32_t* resampled, double* loss_sum,
                    double* loss, uint8_t* accept, int32_t* blocks, void* stream);
 
-/* Select the launch structure of gsm_run_philox for the spectral generator on this handle: 1 = fused chain kernel
- * (default), 0 = two-kernel pipeline.  Identical results; kept for A/B measurements and tests. */
-int gsm_set_fused(gsm_handle h, int32_t on);
+/* Which kernels the calls that follow on this handle run.  Every setting computes the same chain (bit for bit, or to the bound
+ * its test states); the options exist for A/B measurements and because a test uses each selected path as the reference of another.
+ *   GSM_OPT_FUSED          0 / 1, default 1   gsm_run_philox, spectral generator: 1 = fused chain kernel, 0 = two-kernel pipeline
+ *   GSM_OPT_STRIP          0 / 1, default 1   0 = never the strip kernels on this handle (gsm_strip_active)
+ *   GSM_OPT_SPLIT2         0 / 1, default 1   0 = direct sums in stage 2 of the proposal DFT instead of the sums split by the parity
+ *                                             of kx; has an effect on handles that run the strip kernels only
+ *   GSM_OPT_FUSED_SEGMENT  >= 1, default 4096 steps per launch of the fused chain kernel
+ * May be set at any time between calls and takes effect at the next call.  GSM_E_ARG for a NULL handle, an unknown option or
+ * a value outside its range (nothing changes then). */
+enum { GSM_OPT_FUSED = 0, GSM_OPT_STRIP = 1, GSM_OPT_SPLIT2 = 2, GSM_OPT_FUSED_SEGMENT = 3 };
+int gsm_set_option(gsm_handle h, int32_t which, int32_t value);
 /* Which form the last gsm_run_philox call on this handle ran: 1 = fused chain kernel, 0 = the two-kernel pipeline. */
 int gsm_last_run_fused(gsm_handle h);
-/* Which step kernels this handle's static fields and block table select (decided once per table, for gsm_run_replay and
+/* Which step kernels this handle's static fields, block table and GSM_OPT_STRIP select (one decision for gsm_run_replay and
  * gsm_run_philox alike, so that fused == propose + replay holds bit for bit): 1 = the strip kernels (chain_strip_kernel.hip:
  * 512-thread workgroups, two chains per CU, candidate bed in a (bh + 2) x (bw + 2) LDS tile), 0 = the flux-tile kernels
  * (1024-thread workgroups, one chain per CU: grids whose packed static operands, 48 bytes per cell, exceed an XCD's 4 MiB L2
  * -- more than 87 381 cells --, block tables whose strips would exceed 16 rows or whose proposal work area exceeds 80 KiB,
- * GSM_STRIP=0).  Needs gsm_set_static and gsm_set_blocks.  Same arithmetic per cell (MCMC.py:1279-1360,
+ * GSM_OPT_STRIP = 0).  Needs gsm_set_static and gsm_set_blocks.  Same arithmetic per cell (MCMC.py:1279-1360,
  * Topography.py:592-600); the window sums of a step are taken in another order (loss within 1e-15 relative). */
 int gsm_strip_active(gsm_handle h);
 
@@ -611,7 +619,11 @@ int gsm_sgs_grid_draw_pcg64(gsm_handle h, uint64_t* states, const int32_t* cells
  * grid value, the records name their cells, and the records of iteration j + 1 are made on a second stream of the handle while
  * iteration j runs its value pass, transforms, loss and decision (the longest kernel of an iteration leaves the critical path;
  * the value pass then reads the neighbours' values from the grid).  Same numbers as without the promise.  With NaN cells in
- * `cur` the promise is false and the neighbour sets would be wrong: leave it 0. */
+ * `cur` the promise is false and the neighbour sets would be wrong: leave it 0.
+ * tail_qt: with a transformer, whether both transforms of an iteration run inside the launch that ends it (where its tables
+ * and the map's parts fit) or as launches of their own -- same numbers.  GSM_TAIL_QT_AUTO (0, a zeroed struct): inside from 12
+ * chains on, where that is faster; GSM_TAIL_QT_ON / GSM_TAIL_QT_OFF: always / never.  Anything else is GSM_E_ARG. */
+enum { GSM_TAIL_QT_AUTO = 0, GSM_TAIL_QT_ON = 1, GSM_TAIL_QT_OFF = 2 };
 typedef struct gsm_sgs_batch {
   double* cur; double* next; double* proposed;            /* proposed: only with a transformer */
   const double* zcond; const double* trend;               /* trend NULL: not detrended */
@@ -626,6 +638,7 @@ typedef struct gsm_sgs_batch {
   int64_t cell_off_stride;
   int32_t qt_n, windowed, lag_mi, lag_mj, hw, num_points, max_cells;
   int32_t grid_finite;                                    /* the caller's promise: no NaN in cur (see below) */
+  int32_t tail_qt;                                        /* GSM_TAIL_QT_* */
 } gsm_sgs_batch;
 int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* batch, int32_t n_iters, void* stream);
 

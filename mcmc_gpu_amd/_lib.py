@@ -132,7 +132,7 @@ class SgsBatch(C.Structure):
                                           "x_axis", "y_axis", "lag_cov", "windows", "cell_off", "cell_cnt", "cells", "z", "cell_base", "u",
                                           "resampled", "loss", "bad", "loss_prev", "accept", "loss_rec", "acc_rec")] +
                 [("radius", C.c_double), ("sill", C.c_double), ("cell_off_stride", C.c_int64)] +
-                [(k, C.c_int32) for k in ("qt_n", "windowed", "lag_mi", "lag_mj", "hw", "num_points", "max_cells", "grid_finite")])
+                [(k, C.c_int32) for k in ("qt_n", "windowed", "lag_mi", "lag_mj", "hw", "num_points", "max_cells", "grid_finite", "tail_qt")])
 
 
 class Vario(C.Structure):
@@ -146,6 +146,28 @@ VTYPE_IDS = {"exponential": 0, "gaussian": 1, "spherical": 2, "matern": 3}
 
 
 MODEL_IDS = {"Gaussian": 0, "Exponential": 1, "Matern": 2}
+
+OPTION_IDS = {"fused": 0, "strip": 1, "split2": 2, "fused_segment": 3}      # GSM_OPT_* (include/gsm.h)
+TAIL_QT_AUTO, TAIL_QT_ON, TAIL_QT_OFF = 0, 1, 2                              # GSM_TAIL_QT_*
+
+
+def options_from_env(env) -> dict:
+    """The gsm_set_option settings that an environment mapping (os.environ where GsmEngine makes a handle) asks for, as {option name: int}:
+    GSM_STRIP and GSM_SPLIT2 (0 = off, any other integer = on) and GSM_FUSED_SEGMENT (steps per launch; below 1 = the default).
+    Unset variables are left out; a value that is not an integer raises ValueError."""
+    out = {}
+    for var, name in (("GSM_STRIP", "strip"), ("GSM_SPLIT2", "split2"), ("GSM_FUSED_SEGMENT", "fused_segment")):
+        if var not in env:
+            continue
+        try:
+            v = int(env[var])
+        except ValueError:
+            raise ValueError(f"{var}={env[var]!r}: not an integer") from None
+        if name != "fused_segment":
+            out[name] = int(v != 0)
+        elif v >= 1:
+            out[name] = v
+    return out
 
 _lib = None
 
@@ -189,7 +211,7 @@ def load() -> C.CDLL:
     lib.gsm_run_noise.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RfParams), vp, vp, vp, i64, vp, vp, vp]
     lib.gsm_run_philox.argtypes = [vp, i32, i64, i32, vp, C.POINTER(RfParams), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.gsm_enable_timing.argtypes = [vp, i32]
-    lib.gsm_set_fused.argtypes = [vp, i32]
+    lib.gsm_set_option.argtypes = [vp, i32, i32]
     lib.gsm_last_run_fused.argtypes = [vp]
     lib.gsm_strip_active.argtypes = [vp]
     lib.gsm_last_timing.argtypes = [vp, C.POINTER(dbl), C.POINTER(i32), C.POINTER(dbl), C.POINTER(i32)]

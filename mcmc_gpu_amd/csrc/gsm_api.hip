@@ -47,6 +47,17 @@ extern "C" int gsm_destroy(gsm_handle h) {
   return GSM_OK;
 }
 
+extern "C" int gsm_set_option(gsm_handle h, int32_t which, int32_t value) {
+  if (!h) return GSM_E_ARG;
+  int* const opt = which == GSM_OPT_FUSED ? &h->use_fused : which == GSM_OPT_STRIP ? &h->use_strip : which == GSM_OPT_SPLIT2 ? &h->use_split2 :
+                   which == GSM_OPT_FUSED_SEGMENT ? &h->fused_segment : nullptr;
+  if (!opt) return fail(h, GSM_E_ARG, "gsm_set_option: unknown option " + std::to_string(which));
+  if (which == GSM_OPT_FUSED_SEGMENT ? value < 1 : (value != 0 && value != 1))
+    return fail(h, GSM_E_ARG, "gsm_set_option: value " + std::to_string(value) + " out of range for option " + std::to_string(which));
+  *opt = value;
+  return GSM_OK;
+}
+
 extern "C" int gsm_set_static(gsm_handle h, const double* surf, const double* velx, const double* vely,
                               const double* dhdt, const double* smb, const double* crf_weight,
                               const uint8_t* update_mask, const uint8_t* mc_mask, double resolution,
@@ -319,7 +330,7 @@ extern "C" int gsm_residual(gsm_handle h, const double* beds, double* residual, 
 
 // 1 when this handle's static fields and block table go to the strip kernels (chain_strip_kernel.hip)
 int gsm::strip_for(gsm_handle h) {
-  return (h->have_static && h->have_blocks &&
+  return (h->use_strip && h->have_static && h->have_blocks &&
           strip_table_ok(h->S, h->B, std::max(4 * h->lds_x_half, h->lds_tt), h->prop_tiles1, h->prop_tiles)) ? 1 : 0;
 }
 

@@ -2,12 +2,9 @@
 #include "gsm_context.h"
 #include "math_tables.h"
 #include <string.h>
-#include <stdlib.h>
 #include <algorithm>
 
 using namespace gsm;
-
-static constexpr int kFusedSegment = 4096;   // steps per launch of the fused chain kernel
 
 static int check_device_flag(gsm_handle h, hipStream_t st, const char* who) {
   int32_t flag = 0;
@@ -122,8 +119,8 @@ static ProposeArgs make_propose(gsm_handle h, const gsm_rf_params* rf, int n_ste
   p.lds_main = std::max(4 * h->lds_x_half, h->lds_tt);
   p.tiles1_max = h->prop_tiles1; p.tiles2_max = h->prop_tiles;
   // stage 2 split by the parity of kx: on handles whose kernels hold two tile slots per wave (the strip kernels and the stand-alone proposal
-  // kernel beside them); GSM_SPLIT2=0 keeps the direct sums (tests/test_gpu_strip.py compares the step kernels of the two families on equal fields)
-  { static int on = -1; if (on < 0) { const char* v = getenv("GSM_SPLIT2"); on = v ? atoi(v) : 1; } p.split2 = (on && strip_for(h)) ? 1 : 0; p.parseval = p.split2; }
+  // kernel beside them); GSM_OPT_SPLIT2 = 0 keeps the direct sums (tests/test_gpu_strip.py compares the step kernels of the two families on equal fields)
+  p.split2 = (h->use_split2 && strip_for(h)) ? 1 : 0; p.parseval = p.split2;
   return p;
 }
 
@@ -205,12 +202,6 @@ extern "C" int gsm_run_noise(gsm_handle h, int32_t n_steps, void* beds, void* en
 }
 
 extern "C" int gsm_last_run_fused(gsm_handle h) { return h ? h->last_fused : GSM_E_ARG; }
-
-extern "C" int gsm_set_fused(gsm_handle h, int32_t on) {
-  GSM_GRID_HANDLE(h);
-  h->use_fused = on ? 1 : 0;
-  return GSM_OK;
-}
 
 extern "C" int gsm_enable_timing(gsm_handle h, int32_t on) {
   GSM_GRID_HANDLE(h);
@@ -295,7 +286,7 @@ static int run_philox_fused(gsm_handle h, FusedArgs& fa, int seg_max, int32_t n_
   return rc;
 }
 
-// The two-kernel pipeline (the Cholesky generator, gsm_set_fused(h, 0) and block tables beyond the fused kernel's LDS budget): the proposals
+// The two-kernel pipeline (the Cholesky generator, GSM_OPT_FUSED = 0 and block tables beyond the fused kernel's LDS budget): the proposals
 // of batch k + 1 are generated on the handle's second stream while the caller's stream steps through batch k; two scratch slots.
 static int run_philox_pipelined(gsm_handle h, int32_t n_steps, int64_t step0, int32_t batch, const uint64_t* seeds, const gsm_rf_params* rf,
                                 void* beds, void* energy, uint32_t* resampled, double* loss_sum, double* loss, uint8_t* accept,
@@ -368,12 +359,10 @@ extern "C" int gsm_run_philox(gsm_handle h, int32_t n_steps, int64_t step0, int3
   HIPCHK(h, hipSetDevice(h->device));
   if (batch > n_steps) batch = n_steps;
   if ((rc = ensure_k2(h, rf, st))) return rc;
-  // one fused launch per segment where the generator and the block table allow it; gsm_set_fused(h, 0) keeps the two-kernel pipeline
+  // one fused launch per segment where the generator and the block table allow it; GSM_OPT_FUSED = 0 keeps the two-kernel pipeline
   h->last_fused = 0;
   if (h->use_fused && rf->generator == GSM_GEN_SPECTRAL) {
-    int seg_cap = kFusedSegment;
-    if (const char* v = getenv("GSM_FUSED_SEGMENT")) { const int q = atoi(v); if (q >= 1) seg_cap = q; }
-    const int seg_max = std::min(n_steps, seg_cap);
+    const int seg_max = std::min(n_steps, h->fused_segment);
     FusedArgs fa{};
     fa.T = make_step(h, seg_max, beds, energy, resampled, loss_sum, loss, accept, blocks);
     fa.T.rec_stride = n_steps;

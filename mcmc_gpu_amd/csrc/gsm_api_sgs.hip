@@ -1,6 +1,5 @@
 // C ABI of libgsm_hip.so, sequential Gaussian simulation: the small-scale chain (gsm_sgs_* on blocks, gsm_sgs_iterate), whole-grid gsm_sgs_grid, gsm_krige_grid and the cross-validation gsm_krige_cv, each with its per-cell-variogram twin (gsm_*_local), and gsm_sgs_grid's draws from NumPy generators (gsm_sgs_grid_draw_pcg64).
 #include "gsm_context.h"
-#include <stdlib.h>
 #include <algorithm>
 
 using namespace gsm;
@@ -549,10 +548,9 @@ static int sgs_issue(gsm_handle h, const gsm_sgs_batch* b, int32_t n_iters, void
   // with a transformer: both transforms of an iteration inside the tail launch where its tables and the map's parts fit
   // (sgs_loss_tail_kernel<true>); the forward transform of the batch's first iteration is the stand-alone launch
   // Measured (same box): 16 chains +4.8 %, 32 chains +9.5 %, 64 chains +4.1 %, 256 chains +2.9 %, 8 chains -7 %, 4 chains -19 % (a thread of the tail launch then makes ~8 transforms one after
-  // the other where the stand-alone launches make one per thread: with a few chains latency is what counts).  GSM_SGS_TAIL_QT=0 / 1 forces.
-  const char* tail_env = getenv("GSM_SGS_TAIL_QT");
-  const bool tail_qt_env = tail_env ? tail_env[0] != '0' : h->n_chains >= 12;
-  const bool tail_qt = qt && !b->windowed && tail_qt_env && h->have_static && sgs_tail_takes_qt(h->S, b->qt_n);
+  // the other where the stand-alone launches make one per thread: with a few chains latency is what counts).  batch->tail_qt = GSM_TAIL_QT_ON / GSM_TAIL_QT_OFF forces.
+  const bool tail_qt_wanted = b->tail_qt == GSM_TAIL_QT_AUTO ? h->n_chains >= 12 : b->tail_qt == GSM_TAIL_QT_ON;
+  const bool tail_qt = qt && !b->windowed && tail_qt_wanted && h->have_static && sgs_tail_takes_qt(h->S, b->qt_n);
   const auto [qt_clip_min, qt_clip_max] = tail_qt ? qt_clip() : std::pair<double, double>(0.0, 0.0);
   if (tail_qt) HIPCHK(h, h->d_sgs_next_acc.ensure((size_t)map));
   for (int32_t j = 0; j < n_iters; ++j) {
@@ -606,6 +604,7 @@ extern "C" int gsm_sgs_iterate(gsm_handle h, const gsm_sgs_batch* b, int32_t n_i
     return fail(h, GSM_E_ARG, "gsm_sgs_iterate: the windowed finish needs energy / state and no transformer");
   if (!b->windowed && (!b->loss || !b->bad || !b->loss_prev)) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: loss / bad / loss_prev are NULL");
   if (b->cell_off_stride < h->n_chains) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: cell_off_stride must be >= n_chains");
+  if (b->tail_qt < GSM_TAIL_QT_AUTO || b->tail_qt > GSM_TAIL_QT_OFF) return fail(h, GSM_E_ARG, "gsm_sgs_iterate: tail_qt must be GSM_TAIL_QT_AUTO, _ON or _OFF");
   HIPCHK(h, hipSetDevice(h->device));
   return sgs_issue(h, b, n_iters, stream);
 }

@@ -116,7 +116,11 @@ struct gsm_context {
   // timing
   bool timing = false;
   int last_fused = 0;     // 1 when the last gsm_run_philox call went through the fused chain kernel
-  int use_fused = 1;      // 0 / 1: set by gsm_set_fused
+  // gsm_set_option (include/gsm.h: GSM_OPT_*), read at every call
+  int use_fused = 1;      // GSM_OPT_FUSED
+  int use_strip = 1;      // GSM_OPT_STRIP: 0 = never the strip kernels on this handle (strip_for)
+  int use_split2 = 1;     // GSM_OPT_SPLIT2: effective on strip handles only (make_propose)
+  int fused_segment = 4096;   // GSM_OPT_FUSED_SEGMENT: steps per launch of the fused chain kernel
   double t_step_ms = 0, t_prop_ms = 0;
   int n_step_launch = 0, n_prop_launch = 0;
 };

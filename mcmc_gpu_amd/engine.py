@@ -6,6 +6,7 @@ is in the HIP library behind the C ABI of include/gsm.h.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -45,6 +46,8 @@ class GsmEngine:
         if rc != 0:
             raise GsmError(rc, self.lib.gsm_last_error(None).decode())
         self.h = h
+        for name, value in _lib.options_from_env(os.environ).items():      # GSM_STRIP, GSM_SPLIT2, GSM_FUSED_SEGMENT: read here, per handle
+            self.set_option(name, value)
         self.beds = self.energy = self.resampled = self.loss_sum = self.static = None
         self.field_stride = 0
         self.n_sizes = 0
@@ -543,7 +546,11 @@ class GsmEngine:
 
     def set_fused(self, on: bool):
         """Philox mode, spectral generator: fused chain kernel (default) or the two-kernel pipeline (same results)."""
-        self._check(self.lib.gsm_set_fused(self.h, int(bool(on))))
+        self.set_option("fused", int(bool(on)))
+
+    def set_option(self, name: str, value: int):
+        """gsm_set_option (include/gsm.h): 'fused', 'strip', 'split2' (0 / 1) or 'fused_segment' (>= 1); from the next call on."""
+        self._check(self.lib.gsm_set_option(self.h, _lib.OPTION_IDS[name], int(value)))
 
     def last_run_fused(self) -> int:
         return int(self.lib.gsm_last_run_fused(self.h))

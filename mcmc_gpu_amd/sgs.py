@@ -33,6 +33,8 @@ from copy import deepcopy
 
 import numpy as np
 
+from ._lib import TAIL_QT_AUTO, TAIL_QT_OFF, TAIL_QT_ON
+
 __all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "batch_plan", "sgs", "cov_norm", "lag_cov_table", "trend_of",
            "gaussian_weights", "check_groups", "slice_groups", "handoff"]
 
@@ -657,6 +659,9 @@ class _SgsRun:
         # no NaN in the beds (and none can appear: every cell of a block is simulated): gsm_sgs_iterate may then make the records of
         # iteration j + 1 while iteration j is still running (include/gsm.h: grid_finite).  GSM_SGS_OVERLAP=0 turns that off.
         self.grid_finite = os.environ.get('GSM_SGS_OVERLAP', '1') != '0' and bool(np.isfinite(self.bed0).all())
+        # the transforms inside the launch that ends an iteration (include/gsm.h: tail_qt): GSM_SGS_TAIL_QT=0 never, any other value wherever they fit
+        tail_env = os.environ.get('GSM_SGS_TAIL_QT')
+        self.tail_qt = TAIL_QT_AUTO if tail_env is None else TAIL_QT_OFF if tail_env == '0' else TAIL_QT_ON
         # records; every driver starts at iteration 0 and overwrites the record of the initial state there (module docstring)
         self.loss_cache = np.zeros((n, n_iter)); self.step_cache = np.zeros((n, n_iter)); self.blocks_cache = np.full((n, n_iter, 4), np.nan)
         self.bed_cache = self.sample_values = self.ij = None
@@ -823,7 +828,7 @@ class _SgsRun:
         b.loss_rec, b.acc_rec = pv(d_lrec), pv(d_arec)
         b.radius, b.sill = self.rad, float(self.vario["sill"])
         b.lag_mi, b.lag_mj, b.hw, b.num_points, b.max_cells = self.lag_mi, self.lag_mj, self.hw, self.npts, self.max_cells
-        b.grid_finite = int(self.grid_finite)
+        b.grid_finite, b.tail_qt = int(self.grid_finite), self.tail_qt
         return b
 
     def iterate(self, d, kb, d_lrec, d_arec, st):

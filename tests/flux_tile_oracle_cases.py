@@ -1,18 +1,15 @@
 """Cases of tests/test_gpu_flux_tile_oracle.py: the oracle parity checks on the flux-tile and bed-tile step kernels.
 
 The strip kernels take every block table that `strip_table_ok` admits, so with GSM_STRIP at its default the oracle tests of
-test_gpu_parity / test_gpu_fullsize / test_gpu_fused / test_gpu_philox run the strip family.  GSM_STRIP is read once per process:
-`main(group)` is what a child process started with GSM_STRIP=0 runs.  It prints every case before running it and stops at the first
-exception, so that nothing touches the device after a failure.
+test_gpu_parity / test_gpu_fullsize / test_gpu_fused / test_gpu_philox run the strip family.  GSM_STRIP is read when an engine is
+made: the test runs `run_cases(group_cases(group))` with GSM_STRIP=0 set, and every engine the cases make is off the strip kernels.
+`run_cases` prints every case before running it and stops at the first exception.
 
 Dispatch rule restated here (step_kernel.hip: launch_step, step_flux_kernel.hip: launch_step_flux, chain_fused_kernel.hip:
 launch_chain_fused), with tile_cap = max (bh + 2)(bw + 2) and max_win = max(max_bh * max_bw, tile_cap - 1024):
   tile_cap <= 7168: flux-tile, KT = 2 (tile_cap <= 2048), 4 (<= 4096) or 7;
   otherwise:        bed-tile,  KMAX = 7 (max_win <= 7168), 12 (<= 12288) or 20 (<= 20480)."""
-import os
-import sys
 import time
-import traceback
 from pathlib import Path
 
 import numpy as np
@@ -314,18 +311,3 @@ def run_cases(cases):
         fn()
         print(f"  ok {time.perf_counter() - t0:.2f} s", flush=True)
 
-
-def main(group):
-    """Child process, GSM_STRIP=0: the standard 64 engine must be off the strip kernels, then the group's cases in order."""
-    try:
-        from gpu_common import make_engine
-        eng, *_ = make_engine(64, 1)
-        assert eng.strip_active() == 0, "GSM_STRIP=0 did not take the standard 64 table off the strip kernels"
-        eng.close()
-        run_cases(group_cases(group))
-    except BaseException:
-        traceback.print_exc()
-        sys.stdout.flush()
-        sys.stderr.flush()
-        os._exit(1)            # no interpreter teardown: no engine destructor, no torch shutdown on a device that may have faulted
-    print(f"GROUP {group} done", flush=True)

@@ -3,8 +3,8 @@
 
 The oracle cannot run such a grid in seconds, and at the 16-256 grids of the oracle tests the strip kernels take every table
 (tests/test_gpu_strip.py), so those tests pin the strip family only (table by table: tests/test_gpu_strip_oracle.py).  GSM_STRIP=0
-routes a small grid to the other two; the
-switch is read once per process, so each group of cases runs in a fresh child (tests/flux_tile_oracle_cases.py: main).
+routes a small grid to the other two: every engine made while it is set takes it as its option strip = 0, so each group of cases
+runs under monkeypatch.setenv (tests/flux_tile_oracle_cases.py: run_cases).
 
   group A  the bodies of the oracle tests of test_gpu_parity, test_gpu_fullsize, test_gpu_fused and test_gpu_philox, unchanged
   group B  one block table per instantiation against the oracle in replay mode, windows clipped on every edge:
@@ -16,52 +16,37 @@ switch is read once per process, so each group of cases runs in a fresh child (t
 
 Bars (the project's standing ones): accept masks, final beds and resampled counts bit-exact, losses within 1e-10 relative;
 Philox-mode comparisons between device paths bit for bit; proposal fields within philox_oracle.field_atol."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import pytest
 
 import flux_tile_oracle_cases as cases
+from gpu_common import make_engine
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-
-_CHILD = r"""
-import sys
-for p in ({root!r} + '/tests', {root!r} + '/oracle', {root!r}):
-    sys.path.insert(0, p)
-import flux_tile_oracle_cases
-flux_tile_oracle_cases.main({group!r})
-"""
 
 
-def _run_child(group):
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(root=str(ROOT), group=group)], env=dict(os.environ, GSM_STRIP="0"),
-                       capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, f"child for group {group!r} exited with {r.returncode}\n{r.stdout}\n{r.stderr}"
-    names = [n for n, _ in cases.group_cases(group)]
-    ran = [line[5:] for line in r.stdout.splitlines() if line.startswith("CASE ")]
-    assert ran == names and f"GROUP {group} done" in r.stdout, f"cases run: {ran}, expected: {names}"
+def _run_group(monkeypatch, group):
+    monkeypatch.setenv("GSM_STRIP", "0")
+    eng, *_ = make_engine(64, 1)
+    assert eng.strip_active() == 0, "GSM_STRIP=0 did not take the standard 64 table off the strip kernels"
+    eng.close()
+    cases.run_cases(cases.group_cases(group))
 
 
 @pytest.mark.parametrize("group", ["parity", "fused", "philox_oracle"])
-def test_existing_oracle_tests_on_the_flux_tile_kernels(group):
-    _run_child(group)
+def test_existing_oracle_tests_on_the_flux_tile_kernels(monkeypatch, group):
+    _run_group(monkeypatch, group)
 
 
 @pytest.mark.parametrize("name", cases.STRIP_ELIGIBLE)
-def test_table_against_oracle(name):
-    _run_child("table:" + name)
+def test_table_against_oracle(monkeypatch, name):
+    _run_group(monkeypatch, "table:" + name)
 
 
 @pytest.mark.parametrize("name", ["bed_kmax12", "bed_kmax20"])
 def test_large_table_against_oracle(name):
-    """Tiles above 80 KiB never go to the strip kernels: no child needed (every case still asserts strip_active() == 0)."""
+    """Tiles above 80 KiB never go to the strip kernels: no GSM_STRIP needed (every case still asserts strip_active() == 0)."""
     cases.run_cases(cases.table_cases(name))
 
 
-def test_philox_mode_on_the_flux_tile_tables():
-    _run_child("philox_tables")
+def test_philox_mode_on_the_flux_tile_tables(monkeypatch):
+    _run_group(monkeypatch, "philox_tables")

@@ -4,7 +4,7 @@ generates every proposal inside the workgroup that consumes it, with the same ar
 
 Which kernels these are: every block table here passes strip_table_ok, so with GSM_STRIP at its default both sides of every
 comparison below are the strip family (chain_strip_kernel against step_strip_kernel + propose_kernel).  The flux-tile pairing
-(chain_fused_kernel against step_flux_kernel) runs the same bodies in a GSM_STRIP=0 child of tests/test_gpu_flux_tile_oracle.py,
+(chain_fused_kernel against step_flux_kernel) runs the same bodies under GSM_STRIP=0 in tests/test_gpu_flux_tile_oracle.py,
 which also pins step_flux_kernel's NaN rule and thickness guard to the oracle.  The tables here are 8-16 cell blocks and the
 50-80 headline blocks: the strip family's fused == replay == two-kernel comparison on every decomposition of strip::config, and
 its NaN rule and thickness guard against the oracle on strips deeper than 2 rows, are in tests/test_gpu_strip_oracle.py."""
@@ -117,7 +117,7 @@ def test_fused_nan_fields_and_thickness_guard_equal_two_kernel_pipeline():
     lowered so far in one corner that proposals there trip the thickness guard (loss = inf, MCMC.py:1321-1329): the fused
     kernel must give what the two-kernel pipeline gives.  By default both are strip kernels (this 64 x 64 table passes
     strip_table_ok), whose replay side test_gpu_parity pins to the oracle.  The flux-tile pairing -- chain_fused_kernel's NaN-coded
-    operands against step_flux_kernel's -- is this same body in the GSM_STRIP=0 child of tests/test_gpu_flux_tile_oracle.py, where
+    operands against step_flux_kernel's -- is this same body under GSM_STRIP=0 in tests/test_gpu_flux_tile_oracle.py, where
     test_nan_cells_follow_nansum_semantics and test_thickness_guard_rejects pin step_flux_kernel to the oracle."""
     from mcmc_gpu_amd.engine import GsmEngine
     rfp = orc.standard_rf_params()
@@ -172,27 +172,26 @@ def test_fused_nan_fields_and_thickness_guard_equal_two_kernel_pipeline():
     eng.close()
 
 
-def test_fused_internal_segments_are_invisible(monkeypatch):
+def test_fused_internal_segments_are_invisible():
     """gsm_run_philox cuts a long call into launches of at most 4096 steps (scratch sized by the segment, ADVICE r1);
-    GSM_FUSED_SEGMENT lowers the cap: 7-step segments (a ragged last one) must reproduce the single-launch run exactly."""
+    the option fused_segment lowers the cap: 7-step segments (a ragged last one) must reproduce the single-launch run exactly."""
     rfp = orc.standard_rf_params()
     eng, prob, cfg, pairs, masks, _ = make_engine(64, 3)
     rfp.resolution = prob["resolution"]
     seeds = [81, 82, 83]
     beds0 = np.stack([orc.chain_initial_bed(prob, c) for c in range(3)])
     res = []
-    for cap in (None, "7"):
+    for cap in (None, 7):
         if cap:
-            monkeypatch.setenv("GSM_FUSED_SEGMENT", cap)
+            eng.set_option("fused_segment", cap)
         eng.set_state(beds0)
         loss, acc, blk = eng.run_philox(45, 2 ** 33 + 5, seeds, rfp)
         assert eng.last_run_fused() == 1
         res.append((loss, acc, blk, eng.beds.cpu().numpy().copy(), eng.resampled.cpu().numpy().copy(), eng.loss_sum.cpu().numpy().copy()))
-    monkeypatch.delenv("GSM_FUSED_SEGMENT")
     for x, y in zip(*res):
         assert np.array_equal(x, y)
     eng.enable_timing(True)
-    monkeypatch.setenv("GSM_FUSED_SEGMENT", "10")
+    eng.set_option("fused_segment", 10)
     eng.run_philox(45, 0, seeds, rfp)
     assert eng.last_timing()["step_launches"] == 5
     eng.close()

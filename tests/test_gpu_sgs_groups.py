@@ -7,10 +7,6 @@ Run level: run_many_sgs(groups=) equals one run_many_sgs call per group on a tem
 and the same generators or seeds per chain: beds, accept masks, blocks, counts, generator states bit for bit, losses bit for bit
 with device draws and to 1e-12 relative with host draws."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -19,7 +15,6 @@ import posterior_common as pc
 import sgs_groups_common as gc
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 GSM_E_ARG = -1
 N_ITER = 16
 
@@ -119,24 +114,13 @@ def test_grouped_run_equals_separate_runs(monkeypatch, cfg, source):
     assert not np.array_equal(res[0][0], res[1][0])
 
 
-_CHILD = """
-import sys
-sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
-import sgs_groups_common as gc
-for source in ("pcg64", "replay"):
-    out = gc.grouped_and_separate("qt", source, {n_iter})
-    gc.assert_same_chains(*out, source)
-    assert 0.05 < gc.acceptance(out[0]) < 0.95
-print("groups child done")
-"""
-
-
-def test_stand_alone_transforms_in_a_child_process():
-    """trend + transformer with GSM_SGS_TAIL_QT=0 (the transforms as launches of their own), in a fresh process as tests/test_gpu_sgs_iter.py
-    sets the switch"""
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), n_iter=N_ITER)],
-                       env=dict(os.environ, GSM_SGS_TAIL_QT="0"), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "groups child done" in r.stdout, f"child exited with {r.returncode}\n{r.stdout}\n{r.stderr}"
+def test_stand_alone_transforms(monkeypatch):
+    """trend + transformer with GSM_SGS_TAIL_QT=0 (the transforms as launches of their own)"""
+    monkeypatch.setenv("GSM_SGS_TAIL_QT", "0")
+    for source in ("pcg64", "replay"):
+        out = gc.grouped_and_separate("qt", source, N_ITER)
+        gc.assert_same_chains(*out, source)
+        assert 0.05 < gc.acceptance(out[0]) < 0.95
 
 
 @pytest.mark.parametrize("cfg", ("qt", "trend"))

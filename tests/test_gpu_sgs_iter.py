@@ -12,18 +12,12 @@ round trip inverse(transform(.)) is the identity up to that, so after k round tr
 reference's.  A bed error d on every cell moves a residual by at most dv = d AV, AV = (|velx_r| + |velx_l|) / den_x +
 (|vely_d| + |vely_u|) / den_y, and the loss by sum over the cells that enter of (2 |v| dv + dv^2) / (2 sigma^2): that is added to
 LOSS_BOUND of the reference's plane."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import sgs_iter_common as ic
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 LD = ic.LD
 E_ARG, E_STATE, E_UNSUPPORTED, E_DEVICE_DATA = -1, -2, -4, -5
 NAN = float("nan")
@@ -653,9 +647,9 @@ def qt_reference(case, cur, trend, qt, wins):
     return dict(lp0=lp0, u=u, acc=acc, rec=rec, rec_b=rec_b, cur=cur, res=res, bad=bad)
 
 
-def qt_child(out_path):
-    """Runs in a fresh process with GSM_SGS_TAIL_QT set in its environment (as tests/test_gpu_flux_tile_oracle.py sets GSM_STRIP): every
-    grid and table size through gsm_sgs_iterate with a transformer, every output plane saved."""
+def qt_child(tail_qt):
+    """Every grid and table size through gsm_sgs_iterate with a transformer and the batch's tail_qt (include/gsm.h: GSM_TAIL_QT_ON /
+    GSM_TAIL_QT_OFF), every output plane kept."""
     saved = {}
     for H, W in QT_GRIDS:
         for nq in QT_NQ:
@@ -673,44 +667,28 @@ def qt_child(out_path):
                            loss_rec=w.f64(np.full(n * QT_ITERS, NAN)), acc_rec=t.full((n * QT_ITERS,), 9, dtype=t.uint8, device=w.dev))
                 keep = dict(empty_lists(w, QT_ITERS), trend=w.f64(trend), windows=w.i32(np.repeat(np.array(wins), n, axis=0)), u=w.f64(ref["u"]),
                             qt_quantiles=w.f64(qt.quantiles_[:, 0]), qt_references=w.f64(qt.references_))
-                iterate(w, dict(keep, cell_off_stride=n, qt_n=nq, windowed=0, grid_finite=0, **out), QT_ITERS)
+                iterate(w, dict(keep, cell_off_stride=n, qt_n=nq, windowed=0, grid_finite=0, tail_qt=tail_qt, **out), QT_ITERS)
                 assert w.refused("gsm_sgs_check") == (0, "")
                 for k, v in out.items():
                     saved[f"{H}x{W}_{nq}_{k}"] = v.cpu().numpy()
             finally:
                 w.close()
             print(f"CASE {H}x{W} nq={nq}")
-    np.savez(out_path, **saved)
-    print("QT child done")
-
-
-_CHILD = r"""
-import sys
-for p in ({root!r} + '/tests', {root!r} + '/oracle', {root!r}):
-    sys.path.insert(0, p)
-import test_gpu_sgs_iter
-test_gpu_sgs_iter.qt_child({out!r})
-"""
+    return saved
 
 
 @pytest.fixture(scope="module")
-def qt_runs(tmp_path_factory):
+def qt_runs():
     pytest.importorskip("sklearn.preprocessing")
-    runs = {}
-    for flag in ("1", "0"):
-        out = str(tmp_path_factory.mktemp("qt") / f"tail_qt_{flag}.npz")
-        r = subprocess.run([sys.executable, "-c", _CHILD.format(root=str(ROOT), out=out)], env=dict(os.environ, GSM_SGS_TAIL_QT=flag),
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "QT child done" in r.stdout, f"child with GSM_SGS_TAIL_QT={flag} exited with {r.returncode}\n{r.stdout}\n{r.stderr}"
-        runs[flag] = dict(np.load(out))
-    return runs
+    from mcmc_gpu_amd._lib import TAIL_QT_OFF, TAIL_QT_ON
+    return {"1": qt_child(TAIL_QT_ON), "0": qt_child(TAIL_QT_OFF)}
 
 
 @pytest.mark.parametrize("nq", QT_NQ)
 @pytest.mark.parametrize("H,W", QT_GRIDS)
 def test_tail_launch_with_a_transformer(qt_runs, H, W, nq):
     """8 x 512 with nq <= 1024 takes the transforms into the tail launch (per + 2 W = 2048), 20 x 600 and nq = 1025 fall back to the
-    stand-alone transforms: either way both settings of GSM_SGS_TAIL_QT give the same bits, and both agree with scikit-learn.  `next`
+    stand-alone transforms: either way both settings of the batch's tail_qt give the same bits, and both agree with scikit-learn.  `next`
     is compared where the last iteration was rejected: after an accepted one the tail launch leaves T(proposed) there, ready for the
     next batch, and the stand-alone path T(cur) of before the iteration."""
     case, cur, trend, qt = qt_inputs(H, W, nq)

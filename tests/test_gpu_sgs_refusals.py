@@ -146,7 +146,9 @@ class _Refusals:
             "gsm_sgs_blocks": null("grids", "lag_cov", "z") + SEARCH + LAG + MAXC,
             "gsm_sgs_blocks_batch": null("grids", "x_axis", "cell_off") + SEARCH + LAG + MAXC,
             "gsm_sgs_iterate": null("next", "y_axis", "lag_cov") + SEARCH + LAG + MAXC +
-                               [(dict(cell_off_stride=self.w.n - 1), E_ARG, "cell_off_stride must be >= n_chains")],
+                               [(dict(cell_off_stride=self.w.n - 1), E_ARG, "cell_off_stride must be >= n_chains"),
+                                (dict(tail_qt=3), E_ARG, "tail_qt must be GSM_TAIL_QT_AUTO, _ON or _OFF"),
+                                (dict(tail_qt=-1), E_ARG, "tail_qt must be GSM_TAIL_QT_AUTO, _ON or _OFF")],
             "gsm_sgs_grid": null("grids", "draws", "lag_cov") + bounds + SEARCH + LAG + path,
             "gsm_sgs_grid_local": null("grids", "path_off", "local") + bounds + SEARCH + path + matern,
             "gsm_krige_grid": n_cells + null("grid", "lag_cov", "est") + SEARCH + LAG,

@@ -5,14 +5,9 @@ its bounding box matters) and windows that the trimming leaves empty.  The loss 
 are left out carry non-zero energies.
 
 Bars, the project's standing ones.  Against the NumPy oracle (tests/test_gpu_strip_oracle.py): accept masks, final beds and
-resampled counts bit-exact, losses within 1e-10 relative.  Against the flux-tile kernels, which do not trim, in a child process with
-GSM_STRIP=0 (tests/test_gpu_strip.py): accept masks, beds, the ENERGY plane and resampled counts identical, losses within 1e-12
+resampled counts bit-exact, losses within 1e-10 relative.  Against the flux-tile kernels, which do not trim, on a second engine with
+the option strip = 0 (tests/test_gpu_strip.py): accept masks, beds, the ENERGY plane and resampled counts identical, losses within 1e-12
 relative.  Philox mode: fused chain kernel == propose + replay == two-kernel pipeline, bit for bit."""
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
@@ -22,36 +17,23 @@ from flux_tile_oracle_cases import _bars
 from gpu_common import replay_inputs
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-
-_CHILD = r"""
-import sys, numpy as np
-sys.path.insert(0, {root!r}); sys.path.insert(0, {root!r} + '/oracle'); sys.path.insert(0, {root!r} + '/tests')
-import mcmc_oracle as orc
-import strip_trim_cases as cases
-from gpu_common import replay_inputs
-name, state = {name!r}, {state!r}
-outs = cases.oracle_outs(name, state == "f32")
-eng, prob, *_ = cases.engine(name, cases.N_CHAINS, state)
-eng.set_state(np.stack([orc.chain_initial_bed(prob, c) for c in range(cases.N_CHAINS)]))
-loss, acc = eng.run_replay(*replay_inputs(eng, outs))
-np.savez({out!r}, strip=int(eng.strip_active()), loss=loss, acc=acc, beds=eng.beds.cpu().numpy(), energy=eng.energy.cpu().numpy(),
-         res=eng.resampled.cpu().numpy())
-"""
 
 
-def _flux_tile(tmp_path, name, state):
-    """The same replay on the flux-tile kernels: GSM_STRIP is read once per process, so a child."""
-    out = str(tmp_path / f"flux_{name}_{state}.npz")
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(root=str(ROOT), name=name, state=state, out=out)], env=dict(os.environ, GSM_STRIP="0"),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return np.load(out)
+def _flux_tile(name, state, outs):
+    """The same replay on the flux-tile kernels: a second engine with the option strip = 0."""
+    eng, prob, *_ = cases.engine(name, cases.N_CHAINS, state)
+    eng.set_option("strip", 0)
+    eng.set_state(np.stack([orc.chain_initial_bed(prob, c) for c in range(cases.N_CHAINS)]))
+    loss, acc = eng.run_replay(*replay_inputs(eng, outs))
+    b = dict(strip=int(eng.strip_active()), loss=loss, acc=acc, beds=eng.beds.cpu().numpy(), energy=eng.energy.cpu().numpy(),
+             res=eng.resampled.cpu().numpy())
+    eng.close()
+    return b
 
 
 @pytest.mark.parametrize("name,state", [("regroup", "f64"), ("regroup", "f32"), ("deeper", "f64"), ("deeper_some_whole", "f64"), ("l_shape", "f64"),
                                         ("empty", "f64")])
-def test_trimmed_windows_replay_the_oracle_and_equal_the_flux_tile_kernels(tmp_path, name, state):
+def test_trimmed_windows_replay_the_oracle_and_equal_the_flux_tile_kernels(name, state):
     f32 = state == "f32"
     outs = cases.oracle_outs(name, f32)
     cases.conditions(name, *cases.oracle_blocks(outs))
@@ -66,7 +48,7 @@ def test_trimmed_windows_replay_the_oracle_and_equal_the_flux_tile_kernels(tmp_p
     # the cells the trimming leaves out carry energy: outside the update mask, inside the loss mask
     outside = np.asarray(cfg.grounded_ice_mask) == 0
     assert outside.any() and (a["energy"][:, outside] != 0).mean() > 0.9
-    b = _flux_tile(tmp_path, name, state)
+    b = _flux_tile(name, state, outs)
     assert int(b["strip"]) == 0                                    # the untrimmed kernels really ran
     for k in ("acc", "beds", "energy", "res"):
         if not np.array_equal(a[k], b[k]):

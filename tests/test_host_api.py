@@ -43,21 +43,37 @@ def test_struct_restatements_have_the_librarys_layout():
 
 
 def test_environment_switches_are_the_listed_ones():
-    """The GSM_* variables the package reads (getenv in csrc/, os.environ in its Python modules) are exactly the part of DESIGN.md
-    §1's list that the package reads: switches that a test uses as its reference, and GSM_LIB / GSM_DIST_BACKEND."""
+    """The library reads no environment variable (no getenv in csrc/: its switches are gsm_set_option and gsm_sgs_batch.tail_qt), and
+    the GSM_* variables the package's Python modules name are exactly the part of DESIGN.md §1's list that the package reads:
+    switches that a test uses as its reference, and GSM_LIB / GSM_DIST_BACKEND."""
     import re
     found = set()
     for p in sorted(_lib.CSRC.iterdir()):
-        found |= set(re.findall(r'getenv\(\s*"(GSM_\w+)"', p.read_text()))
-    for p in sorted(_lib.PKG_DIR.glob("*.py")):
-        for line in p.read_text().splitlines():
-            if "os.environ" in line:
-                found |= set(re.findall(r"""['"](GSM_\w+)['"]""", line))
+        assert "getenv" not in p.read_text(), p.name
+    for p in sorted(_lib.PKG_DIR.glob("*.py")):       # a variable is read by its quoted name, through os.environ or through _lib.options_from_env's mapping
+        found |= set(re.findall(r"""['"](GSM_\w+)['"]""", p.read_text()))
     listed = {"GSM_STRIP", "GSM_SPLIT2", "GSM_FUSED_SEGMENT", "GSM_SGS_BATCH", "GSM_SGS_OVERLAP", "GSM_SGS_DRAW_AHEAD",
               "GSM_SGS_TAIL_QT", "GSM_SGS_WINDOWED", "GSM_LIB", "GSM_DIST_BACKEND"}
     assert found == listed
     design = (_lib.PKG_DIR.parent / "DESIGN.md").read_text()
     assert all(f"`{name}`" in design for name in listed)
+
+
+def test_set_option_is_declared_and_refuses_a_null_handle():
+    lib = _lib.load()
+    names = _lib.declared_symbols()
+    assert "gsm_set_option" in names and "gsm_set_fused" not in names
+    assert lib.gsm_set_option(None, 0, 0) == -1                          # GSM_E_ARG
+
+
+def test_options_from_env():
+    assert _lib.options_from_env({}) == {}
+    assert _lib.options_from_env({"GSM_STRIP": "0", "GSM_SPLIT2": "0", "GSM_FUSED_SEGMENT": "7", "HOME": "/"}) == \
+        {"strip": 0, "split2": 0, "fused_segment": 7}
+    assert _lib.options_from_env({"GSM_STRIP": "3", "GSM_FUSED_SEGMENT": "0"}) == {"strip": 1}     # atoi's meaning of integers, as before
+    assert set(_lib.options_from_env({"GSM_STRIP": "1"})) <= set(_lib.OPTION_IDS)
+    with pytest.raises(ValueError, match="GSM_STRIP"):
+        _lib.options_from_env({"GSM_STRIP": "yes"})
 
 
 def test_create_without_gpu_fails_loudly():
