@@ -674,6 +674,38 @@ int gsm_min_dist_from_mask(gsm_handle h, const double* xx, const double* yy, con
 int gsm_gaussian_filter(gsm_handle h, const double* x, double* out, int32_t n, int32_t H, int32_t W, const double* w0, int32_t lw0,
                         const double* w1, int32_t lw1, void* stream);
 
+/* Fit of the normal-score transformers of a stack of fields: quantiles[r] = the table quantiles_[:, 0] that
+ * QuantileTransformer(n_quantiles=nq, subsample=None).fit(x[r].reshape(-1, 1)) of scikit-learn holds, for the n fields x [dev, n*cells]
+ * at once, fp64, bit for bit.  n and cells are the call's own: cells need not be the handle's H*W (a caller may fit on the cells of
+ * a mask), and the handle's grid may have any size.  x is only read.  Asynchronous on `stream`.
+ *   q [HOST, nq]             the probabilities, read before the call returns.  The caller makes them as scikit-learn and NumPy do:
+ *                            q = (np.linspace(0, 1, nq, endpoint=True) * 100) / 100 (references_ to percent and back).
+ *   quantiles [dev, n*nq]    the tables
+ *   n_valid, n_inf [dev, n]  int64: the values of field r that are not NaN, and those that are +inf or -inf
+ *   sorted [dev, n*cells]    or NULL: the values of field r that are not NaN in ascending order, then NaN up to `cells`
+ * Arithmetic, with s the ascending values of a field that are not NaN and m = n_valid[r], for every k < nq:
+ *   v = (m - 1) * q[k]                                  one fp64 multiply
+ *   lo = floor(v);  g = v - lo;  hi = min(lo + 1, m - 1);  a = s[lo];  b = s[hi];  d = b - a
+ *   t[k] = g >= 0.5 ? b - d * (1 - g) : a + d * g       every operation rounded on its own: nothing is fused
+ *   quantiles[r][k] = max(t[0..k])                      the running maximum, np.maximum.accumulate (NaN stays)
+ * which is np.nanpercentile(x[r], q * 100, method='linear') with NumPy's _lerp, then scikit-learn's np.maximum.accumulate.
+ * m == 0 gives a row of NaN, as NumPy does.
+ * Order: each field is sorted on its own by order-preserving 64-bit keys, -inf < .. < -0 < +0 < .. < +inf < NaN (every NaN is one
+ * key); a tile sort in LDS, then ceil(log2(ceil(cells / 4096))) merge passes.  Keys carry nothing else, so the sorted sequence is
+ * the one ascending arrangement of the values: field r of a batch has the bits of the one-field call, the same call twice gives the
+ * same bits, and nothing depends on the tiling or the batch.  No atomics.
+ * Scratch: two key buffers of n*cells 64-bit keys (the second only when cells > 4096) and q's copy are owned by the handle
+ * (grow-only, released by gsm_destroy; growing one frees the smaller buffer, which waits for the device).
+ * Errors (GSM_E_ARG, nothing launched): a NULL pointer other than sorted, quantiles or sorted == x, n < 1, cells outside [1, 2^24],
+ * nq outside [2, 2^20], a q that does not ascend within [0, 1] (NaN included), n * ceil(cells / 4096) beyond one launch's 2^31
+ * workgroups.
+ * Replaces: nst_trans = QuantileTransformer(n_quantiles=1000, output_distribution="normal", subsample=None,
+ * random_state=rng_seed).fit(data) (smallScaleChain_multiprocessing.py:493-494) for every large-scale bed of an ensemble at once;
+ * sklearn/preprocessing/_data.py QuantileTransformer._dense_fit.  references_ = np.linspace(0, 1, nq) and n_quantiles_ = nq are
+ * the caller's. */
+int gsm_qt_fit(gsm_handle h, const double* x, int32_t n, int64_t cells, const double* q, int32_t nq, double* quantiles,
+               int64_t* n_valid, int64_t* n_inf, double* sorted, void* stream);
+
 /* ---- posterior accumulator: moments of the bed over all chains and a thinned set of iterations --------------------------
  * The reference looks inside a run through host caches of one chain: bed_cache[i] = bed_c (only_save_last_bed=False,
  * MCMC.py:1198, :1362-1363) and sample_values[:, i] = bed_c at the sample points (set_sample_points_locations,

@@ -104,6 +104,8 @@ struct gsm_context {
   gsm::DevBuf<double> d_post_slab;                            // gsm_posterior_*: per-part sums before they are combined in part order
   gsm::DevBuf<double> d_vario_sum; gsm::DevBuf<int64_t> d_vario_count;   // gsm_variogram_map: per-part sums and counts before they are combined in part order
   gsm::DevBuf<double> d_trend_tmp;                            // gsm_gaussian_filter: the axis-0 pass of every field (grow-only)
+  gsm::DevBuf<uint64_t> d_sort_keys[2];                       // gsm_qt_fit: the sort's two key buffers, n * cells keys each (grow-only)
+  gsm::DevBuf<double> d_qt_fit_q;                             // gsm_qt_fit: the caller's q on the device (grow-only)
   // philox-mode scratch (two buffers)
   struct Scratch {
     gsm::DevBuf<int32_t> size_idx, centre;

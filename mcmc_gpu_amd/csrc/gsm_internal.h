@@ -447,6 +447,12 @@ constexpr int kTrendMaxLw = 128;
 struct TrendTaps { double w[2 * kTrendMaxLw + 1]; int lw; };
 hipError_t launch_gaussian_filter(const TrendTaps& t0, const TrendTaps& t1, const double* x, double* tmp, double* out, int n, int H, int W,
                                   hipStream_t st);
+// qt_fit_kernel.hip: the quantile tables of n fields of `cells` doubles; q [dev, nq]; keys0, keys1: n * cells keys each (sort_device.h).
+// hipErrorInvalidValue: more workgroups than one launch takes
+constexpr int64_t kQtFitMaxCells = int64_t(1) << 24;
+constexpr int kQtFitMaxQuantiles = 1 << 20;
+hipError_t launch_qt_fit(const double* x, int n, int64_t cells, const double* q, int nq, uint64_t* keys0, uint64_t* keys1, double* quantiles,
+                         int64_t* n_valid, int64_t* n_inf, double* sorted, hipStream_t st);
 // variogram_kernel.hip
 constexpr int kVariogramMaxLag = 1 << 20;
 int64_t variogram_workgroups(int mi, int mj);                           // workgroups per field and part

@@ -186,6 +186,24 @@ class GsmEngine:
                   w1.ctypes.data_as(dp), w1.size // 2)
         return out
 
+    def qt_fit(self, fields, q, want_sorted=False):
+        """gsm_qt_fit of n fields [n, cells] (array or device tensor; `cells` need not be the handle's H * W) at the probabilities q
+        (host array, ascending in [0, 1]).  Returns device tensors (quantiles [n, nq], n_valid [n] int64, n_inf [n] int64, sorted
+        [n, cells] or None)."""
+        x = fields.to(device=self.dev, dtype=torch.float64).contiguous() if isinstance(fields, torch.Tensor) else self._f64(fields)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("fields must have shape (n, cells)")
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.ndim != 1:
+            raise ValueError("q is a 1-D array")
+        n, cells = int(x.shape[0]), int(x.shape[1])
+        quantiles = torch.empty((n, q.size), dtype=torch.float64, device=self.dev)
+        n_valid = torch.empty(n, dtype=torch.int64, device=self.dev)
+        n_inf = torch.empty(n, dtype=torch.int64, device=self.dev)
+        srt = torch.empty_like(x) if want_sorted else None
+        self.call(self.lib.gsm_qt_fit, x, n, cells, q.ctypes.data_as(C.POINTER(C.c_double)), int(q.size), quantiles, n_valid, n_inf, srt)
+        return quantiles, n_valid, n_inf, srt
+
     def residual(self, beds):
         b = beds.to(device=self.dev, dtype=torch.float64).contiguous() if isinstance(beds, torch.Tensor) else self._f64(beds)
         if tuple(b.shape) != (self.n_chains, self.H, self.W):

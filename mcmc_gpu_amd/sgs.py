@@ -36,7 +36,7 @@ import numpy as np
 from ._lib import TAIL_QT_AUTO, TAIL_QT_OFF, TAIL_QT_ON
 
 __all__ = ["chain_sgs_gpu", "init_msc_chain_by_instance", "run_many_sgs", "batch_plan", "sgs", "cov_norm", "lag_cov_table", "trend_of",
-           "gaussian_weights", "check_groups", "slice_groups", "handoff"]
+           "gaussian_weights", "check_groups", "slice_groups", "handoff", "fit_normal_scores", "quantile_probabilities"]
 
 
 def gaussian_weights(sigma, truncate=4.0):
@@ -92,6 +92,65 @@ def trend_of(beds, sigma=10, truncate=4.0, device=None, mode="reflect"):
     if x.ndim == 2:
         return gaussian_filter(x, sigma=(s0, s1), truncate=float(truncate), mode="reflect")
     return np.stack([gaussian_filter(b, sigma=(s0, s1), truncate=float(truncate), mode="reflect") for b in x])
+
+
+def quantile_probabilities(n_quantiles):
+    """The probabilities at which QuantileTransformer._dense_fit takes its quantiles, after the round trip scikit-learn and NumPy make:
+    references_ * 100 (scikit-learn, to percent) / 100 (np.nanpercentile, back).  Not always references_ itself."""
+    return (np.linspace(0, 1, int(n_quantiles), endpoint=True) * 100) / 100
+
+
+def fit_normal_scores(fields, n_quantiles=1000, random_state=None, device=None, stack=False):
+    """The normal-score transformers the reference's driver fits on a detrended bed,
+        QuantileTransformer(n_quantiles, output_distribution='normal', subsample=None, random_state).fit(field.reshape(-1, 1))
+    (smallScaleChain_multiprocessing.py:493-494), each field on its own.  `fields` is one field [H, W], a stack [n, H, W], or -- with
+    stack=True, which tells the two 2-D readings apart -- a stack [n, cells] (the cells of a mask, say).
+    Returns a list of n fitted scikit-learn QuantileTransformer objects (one field: a list of one).
+    device=True: one gsm_qt_fit call for the whole stack; each object is an unfitted QuantileTransformer given n_quantiles_,
+    references_, quantiles_ and n_features_in_.  The tables have the bits of scikit-learn's fit.  Raises without a GPU.
+    device=False: scikit-learn's fit, field by field.
+    device=None (default): the device when a GPU is visible, else scikit-learn (trend_of's rule).
+    A device tensor is taken on the device path only.  NaN cells are left out of a field's fit, as scikit-learn leaves them out.
+    ValueError: n_quantiles above the number of cells of a field (scikit-learn clips with a warning; the device holds one table
+    length for all fields of a run), n_quantiles below 2, a field that holds +inf or -inf (scikit-learn's own refusal)."""
+    import torch
+    from sklearn.preprocessing import QuantileTransformer
+    is_tensor = isinstance(fields, torch.Tensor)
+    shape = tuple(fields.shape)
+    if len(shape) not in (2, 3) or 0 in shape or (stack and len(shape) != 2):
+        raise ValueError("fit_normal_scores: fields must be one field [H, W], a stack [n, H, W] or (stack=True) a stack [n, cells]")
+    n = shape[0] if (stack or len(shape) == 3) else 1
+    nq = int(n_quantiles)
+    if nq < 2:
+        raise ValueError("fit_normal_scores: n_quantiles must be at least 2")
+    if device is None:
+        device = torch.cuda.is_available()
+    if not device and is_tensor:
+        raise ValueError("fit_normal_scores: a tensor goes through the device path (device=True)")
+    x = (fields if is_tensor else np.asarray(fields, dtype=np.float64)).reshape(n, -1)
+    if nq > x.shape[1]:
+        raise ValueError(f"fit_normal_scores: n_quantiles = {nq} is above the {x.shape[1]} cells of a field")
+    make = lambda: QuantileTransformer(n_quantiles=nq, output_distribution='normal', subsample=None, random_state=random_state)
+    if not device:
+        if np.isinf(x).any():
+            raise ValueError("fit_normal_scores: a field holds infinity")
+        return [make().fit(f.reshape(-1, 1)) for f in x]
+    from .engine import GsmEngine
+    eng = GsmEngine(1, 1, 1, device=x.device.index if is_tensor and x.is_cuda else None)      # `cells` is the call's own: any handle serves
+    try:
+        quantiles, _, n_inf, _ = eng.qt_fit(x, quantile_probabilities(nq))
+        quantiles, n_inf = quantiles.cpu().numpy(), n_inf.cpu().numpy()
+    finally:
+        eng.close()
+    if n_inf.any():
+        raise ValueError("fit_normal_scores: a field holds infinity")
+    out = []
+    for row in quantiles:
+        t = make()
+        t.n_quantiles_, t.references_, t.n_features_in_ = nq, np.linspace(0, 1, nq, endpoint=True), 1
+        t.quantiles_ = np.ascontiguousarray(row.reshape(nq, 1))
+        out.append(t)
+    return out
 
 
 def cov_norm(h, vtype, sill, nugget, s=None):
@@ -512,7 +571,7 @@ def slice_groups(groups, lo, hi):
     return out
 
 
-def handoff(chain, lsc_beds, of, sigma=10, n_quantiles=1000, random_state=None, device=None):
+def handoff(chain, lsc_beds, of, sigma=10, n_quantiles=1000, random_state=None, device=None, fit='host'):
     """From large-scale beds to small-scale chains, the lines of the reference's driver that sit between the two samplers
     (smallScaleChain_multiprocessing.py:479-496), once per large-scale bed:
         bed = where((surf - bed <= 0) & (grounded_ice_mask == 1), surf - 1, bed)       the bed clamped under the surface
@@ -522,7 +581,14 @@ def handoff(chain, lsc_beds, of, sigma=10, n_quantiles=1000, random_state=None, 
     continues.  `chain` is the small-scale template (its surf and grounded_ice_mask are used; set detrend_map / do_transform on it
     as the run should have them: a key the template does not call for is left out of the dict).
     Returns (initial_beds, groups): initial_beds[c] is the clamped bed of group of[c], and run_many_sgs(chain, initial_beds, rngs,
-    n_iter, groups=groups) continues every bed with its own trend and transformer."""
+    n_iter, groups=groups) continues every bed with its own trend and transformer.
+    fit='host' (default): the transformers are fitted by scikit-learn, bed by bed.  fit='device': trend and transformers of all beds
+    on the device (trend_of and fit_normal_scores with device=True, the detrended stack formed there by one fp64 subtraction per cell,
+    NumPy's bits); the tables have the bits of the host fit of the same trend.  ValueError with device=False."""
+    if fit not in ('host', 'device'):
+        raise ValueError("handoff: fit must be 'host' or 'device'")
+    if fit == 'device' and device is not None and not device:
+        raise ValueError("handoff: fit='device' needs the device path (device=True or None)")
     beds = np.array(lsc_beds, dtype=np.float64)
     if beds.ndim != 3 or beds.shape[1:] != np.asarray(chain.xx).shape:
         raise ValueError("lsc_beds must have shape (G, H, W) of the chain's grid")
@@ -533,6 +599,17 @@ def handoff(chain, lsc_beds, of, sigma=10, n_quantiles=1000, random_state=None, 
     clamp = ((surf[None] - beds) <= 0) & (np.asarray(chain.grounded_ice_mask)[None] == 1)
     beds = np.where(clamp, surf[None] - 1, beds)
     groups = dict(of=np.ascontiguousarray(of, dtype=np.int32))
+    if fit == 'device':
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("no ROCm/HIP device visible to torch: handoff(fit='device') has no CPU fallback")
+        d_beds = torch.as_tensor(beds).to(torch.device("cuda", torch.cuda.current_device()))
+        d_trend = trend_of(d_beds, sigma=sigma, device=True)
+        if chain.detrend_map:
+            groups['trend'] = d_trend.cpu().numpy()
+        if chain.do_transform:
+            groups['nst_trans'] = fit_normal_scores(d_beds - d_trend, n_quantiles=n_quantiles, random_state=random_state, device=True)
+        return [beds[int(g)].copy() for g in of], groups
     trend = trend_of(beds, sigma=sigma, device=device)
     if chain.detrend_map:
         groups['trend'] = trend

@@ -15,7 +15,16 @@ within every repeat; the ranges are kept in the JSON.
   (c) --parent-tree DIR (a checkout of the parent commit with its library built): scripts/sgs_bench.py --pcg64 at 256 and at 4 chains,
       run from DIR and from this tree in turn, each in a fresh process; the rates printed by the script.
 
+  (d) --fit: the normal-score transformers of the same two stacks, 1000 quantiles (profiles/handoff_bench_fit.json):
+        - gsm_qt_fit, HIP events around whole calls, beside
+        - gsm_debug_stream_copy of one plane-stack: the bytes one read and one write of the keys move (the sort makes
+          2 + ceil(log2(cells / 4096)) such passes and a read);
+        - the scikit-learn loop on the host, QuantileTransformer(1000, subsample=None).fit per field, wall clock, arrays already there;
+        - sgs.handoff(fit='device') against sgs.handoff(fit='host') on those stacks as beds, wall clock of whole calls (clamp, trend,
+          transformers; the trend on the device in both).
+
     python scripts/handoff_bench.py [--repeats 7] [--iters 2000] [--skip-host] [--parent-tree DIR] [--out profiles/handoff_bench.json]
+    python scripts/handoff_bench.py --fit --skip-filter --skip-chain --out profiles/handoff_bench_fit.json
 """
 import argparse
 import json
@@ -98,6 +107,76 @@ def filter_rows(repeats, skip_host):
     return rows
 
 
+def fit_rows(repeats, skip_host):
+    import torch
+    from sklearn.preprocessing import QuantileTransformer
+    from mcmc_gpu_amd import sgs, synthetic
+    from mcmc_gpu_amd.engine import GsmEngine, _ptr
+    nq = 1000
+    rows = []
+    for n, H, W in FILTER_SHAPES:
+        eng = GsmEngine(H, W, 1)
+        try:
+            dev = eng.dev
+            gen = torch.Generator(device=dev).manual_seed(5)
+            x = 40.0 * torch.randn((n, H * W), dtype=torch.float64, device=dev, generator=gen)
+            b = torch.empty_like(x)
+            q = sgs.quantile_probabilities(nq)
+
+            def timed(fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); out = fn(); e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1), out
+
+            fit = lambda: eng.qt_fit(x, q)
+            copy = lambda: eng._check(eng.lib.gsm_debug_stream_copy(_ptr(x), _ptr(b), x.numel(), eng._stream()))
+            timed(copy); timed(fit)                            # warm-up: first launches, the handle's key buffers
+            xh = x.cpu().numpy()
+
+            def host():
+                t0 = time.perf_counter()
+                fits = [QuantileTransformer(n_quantiles=nq, output_distribution="normal", subsample=None, random_state=0).fit(f.reshape(-1, 1))
+                        for f in xh]
+                return 1e3 * (time.perf_counter() - t0), fits
+
+            t_f, t_c, t_h, tables, fits = [], [], [], None, None
+            for _ in range(repeats):
+                t, out = timed(fit); t_f.append(t); tables = out[0]
+                t_c.append(timed(copy)[0])
+                if not skip_host:
+                    t, fits = host(); t_h.append(t)
+        finally:
+            eng.close()
+        row = {"fields": n, "grid": f"{H}x{W}", "n_quantiles": nq, "merge_passes": int(np.ceil(np.log2(np.ceil(H * W / 4096)))),
+               "qt_fit_ms": _summary(t_f), "copy_one_plane_stack_ms": _summary(t_c), "fit_over_copy": float(np.median(t_f) / np.median(t_c)),
+               "copy_TB_per_s": 16 * x.numel() / (1e-3 * np.median(t_c)) / 1e12, "keys_per_s": x.numel() / (1e-3 * np.median(t_f))}
+        if t_h:
+            tab = tables.cpu().numpy()
+            row.update(host_sklearn_loop_ms=_summary(t_h), host_over_fit=float(np.median(t_h) / np.median(t_f)),
+                       tables_equal_sklearn=bool(all(np.array_equal(tab[r], fits[r].quantiles_[:, 0]) for r in range(n))))
+        # whole hand-offs: the stack as large-scale beds of a template on this grid (H == W)
+        del x, b
+        torch.cuda.empty_cache()
+        _, ch = synthetic.sgs_template(H)
+        lsc = np.asarray(ch.surf)[None] - 300.0 + xh.reshape(n, H, W)
+        of = np.arange(n)
+        sides = {"device": [], "host": []}
+        sgs.handoff(ch, lsc[:2], of[:2], fit="device")          # warm-up
+        for _ in range(repeats):
+            for side in (("device",) if skip_host else ("device", "host")):
+                t0 = time.perf_counter()
+                sgs.handoff(ch, lsc, of, sigma=10, n_quantiles=nq, random_state=0, fit=side)
+                sides[side].append(1e3 * (time.perf_counter() - t0))
+        row["handoff_fit_device_ms"] = _summary(sides["device"])
+        if sides["host"]:
+            row.update(handoff_fit_host_ms=_summary(sides["host"]),
+                       handoff_host_over_device=float(np.median(sides["host"]) / np.median(sides["device"])))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def chain_rows(repeats, iters):
     from mcmc_gpu_amd import sgs, synthetic
     H, n_groups, per = 64, 64, 4
@@ -172,12 +251,18 @@ def main():
     ap.add_argument("--iters", type=int, default=2000, help="iterations per chain in (b): the set-up of a call (per group: the conditioning data through its transformer on the host) is in the wall time")
     ap.add_argument("--skip-host", action="store_true", help="leave scipy on the host out of (a)")
     ap.add_argument("--skip-chain", action="store_true", help="leave (b) out")
+    ap.add_argument("--skip-filter", action="store_true", help="leave (a) out")
+    ap.add_argument("--fit", action="store_true", help="add (d): gsm_qt_fit beside a stream copy, the scikit-learn loop and whole hand-offs")
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its library built: adds (c)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.repeats < 7:
         ap.error("--repeats must be at least 7")
-    res = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "filter": filter_rows(args.repeats, args.skip_host)}
+    res = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats}
+    if not args.skip_filter:
+        res["filter"] = filter_rows(args.repeats, args.skip_host)
+    if args.fit:
+        res["fit"] = fit_rows(args.repeats, args.skip_host)
     if not args.skip_chain:
         res["chain"] = chain_rows(args.repeats, args.iters)
     if args.parent_tree:
