@@ -847,7 +847,37 @@ int gsm_qt_fit(gsm_handle h, const double* x, int32_t n, int64_t cells, const do
  * Errors: GSM_E_ARG for a NULL beds, g or cross, reach outside [1, 4], beds not 16-byte aligned; GSM_E_UNSUPPORTED where K x H x W
  * doubles exceed 1 GiB; nothing is written then.
  * Replaces: np.cov between neighbouring cells of bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
- * All eleven are asynchronous on `stream`. */
+ *
+ * gsm_posterior_regions: one snapshot into non-linear functionals of EVERY chain's bed per region -- the scalars an ensemble is
+ * published as: ice volume, volume above flotation (the sea-level contribution), area below sea level, area grounded below sea
+ * level, the deepest and the highest point, and the hypsometric (area-elevation) curve.  None follows from per-cell moments or from
+ * a projection.  region_bits [dev, H*W] uint8: bit k of a cell says that the cell belongs to region k < n_regions, 1 <= n_regions
+ * <= 8; regions may overlap (a basin, its sub-basin, the whole domain); bits at or above n_regions are ignored.  surf is the plane
+ * given to gsm_set_static.  Per chain c and cell, all fp64 with either state type and without fused multiply-adds, in this order:
+ *   x = (double)bed;  s = surf[cell];  valid = isfinite(x) && isfinite(s)
+ *   h = s - x;  t_thick = h > 0 ? h : 0
+ *   b = x - sea_level;  p = density_ratio * (b < 0 ? b : 0);  q = h + p;  t_haf = q > 0 ? q : 0
+ * so that the same expressions in any IEEE arithmetic give every term bit for bit (density_ratio = rho_water / rho_ice).
+ * func [dev, n_chains*n_regions*8] fp64 is WRITTEN: func[(c*n_regions + k)*8 + f] over the valid cells of region k,
+ *   f = 0  their number          f = 1  sum x            f = 2  sum t_thick        f = 3  sum t_haf
+ *   f = 4  the number with b < 0    f = 5  the number with b < 0 and t_haf > 0 (grounded below sea level)
+ *   f = 6  min x, +inf without a valid cell            f = 7  max x, -inf without a valid cell
+ * Counts are exact integers in fp64.  A cell that is not valid enters nothing: it does not make its region NaN.
+ * Hypsometry: n_bins = 0 (none; hyps may be NULL) or even in [2, 64].  kf = floor((x - hyps_lo) * hyps_inv_width) in double, a
+ * difference, a product and a floor; kf < 0 -> slot 0, kf >= n_bins -> slot n_bins + 1, otherwise slot (int)kf + 1 (the slot rule
+ * of gsm_posterior_histogram).  hyps [dev, n_chains*n_regions*(n_bins + 2)] int32, at (c*n_regions + k)*(n_bins + 2) + slot, is
+ * ADDED to: zero it once, call once per snapshot; only valid cells are counted; the caller keeps a counter below 2^31.
+ * One pass: each bed value is read from memory once per call and serves every region it belongs to (8 bytes per chain-cell with
+ * fp64 state, 4 with fp32); the bit plane and surf, 9 bytes per cell, are re-read by every chain and are expected to stay in the
+ * caches.  No floating-point atomics: the four sums are taken in a fixed tree (lane, wave, workgroup, then the plane parts in part
+ * order, a second kernel), so func is bit-reproducible from run to run; the integer hypsometry counts are combined in LDS and with
+ * integer atomics, exact in any order.
+ * Errors: GSM_E_ARG for a NULL beds, region_bits or func, n_regions outside [1, 8], n_bins odd or outside {0} and [2, 64], a NULL
+ * hyps with n_bins > 0, a sea_level that is not finite, a density_ratio that is not finite and > 0, with n_bins > 0 an
+ * hyps_inv_width that is not finite and > 0 or an hyps_lo that is not finite, beds not 16-byte aligned; GSM_E_STATE before
+ * gsm_set_static; GSM_E_UNSUPPORTED with more than 65535 chains; nothing is written then.
+ * Replaces: region statistics over bed_cache[burn_in::thin] of every chain of a pool (MCMC.py:1198, :1363).
+ * All twelve are asynchronous on `stream`. */
 int gsm_posterior_accumulate(gsm_handle h, const void* beds, void* ref, double* s1, double* s2, int32_t first,
                              const int32_t* sample_cells, int32_t n_samples, double* sample_out, void* stream);
 int gsm_posterior_accumulate_pooled(gsm_handle h, const void* beds, const double* g, double* s1, double* s2,
@@ -870,6 +900,12 @@ int gsm_posterior_residual(gsm_handle h, const void* beds, const double* rg, con
                            double* sums /* [dev, (3+n_levels)*H*W], ADDED to */, void* stream);
 int gsm_posterior_local(gsm_handle h, const void* beds, const double* g, int32_t reach,
                         double* cross /* [dev, K*H*W], ADDED to */, void* stream);
+int gsm_posterior_regions(gsm_handle h, const void* beds, const uint8_t* region_bits, int32_t n_regions,
+                          double sea_level, double density_ratio,
+                          double* func /* [dev, n_chains*n_regions*8], written */,
+                          double hyps_lo, double hyps_inv_width, int32_t n_bins,
+                          int32_t* hyps /* [dev, n_chains*n_regions*(n_bins+2)], ADDED to; NULL with n_bins 0 */,
+                          void* stream);
 
 /* ---- variogram map of gridded fields ---------------------------------------------------------------------------------------
  * On an axis-aligned uniform grid the separation of two cells depends on their integer offset (di, dj) alone, so an

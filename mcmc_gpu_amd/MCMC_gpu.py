@@ -595,7 +595,7 @@ def _accumulator(chain, eng, n_iter, opt):
     ij = chain._sample_indices() if chain.sample_loc is not None else None
     return PosteriorAccumulator(eng, n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
                                 sample_cells=None if ij is None else ij[:, 0] * eng.W + ij[:, 1], sample_loc=chain.sample_loc, hist=opt['hist'],
-                                ess=opt['ess'], cov=opt['cov'], residual=opt['residual'], local=opt['local'])
+                                ess=opt['ess'], cov=opt['cov'], residual=opt['residual'], local=opt['local'], regions=opt['regions'])
 
 
 def _run_with_posterior(chain, eng, RF, seeds, n_iter, batch, step0, opt):

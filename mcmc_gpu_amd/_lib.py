@@ -16,7 +16,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libgsm_hip.so"
 HEADER = PKG_DIR.parent / "include" / "gsm.h"
-SOURCES = ["gsm_api.hip", "gsm_api_chain.hip", "gsm_api_sgs.hip", "gsm_api_posterior.hip", "gsm_api_variogram.hip", "gsm_api_qt.hip", "gsm_version.hip", "step_kernel.hip", "step_flux_kernel.hip", "chain_fused_kernel.hip", "chain_strip_kernel.hip", "proposal_kernel.hip", "cholesky_kernel.hip", "sgs_kernel.hip", "sgs_iter_kernel.hip", "sgs_grid_kernel.hip", "sgs_grid_draw_kernel.hip", "krige_grid_kernel.hip", "krige_cv_kernel.hip", "pcg64_kernel.hip", "posterior_kernel.hip", "posterior_hist_kernel.hip", "posterior_lag_kernel.hip", "posterior_cov_kernel.hip", "posterior_residual_kernel.hip", "posterior_local_kernel.hip", "variogram_kernel.hip", "variogram_local_kernel.hip", "trend_kernel.hip", "qt_fit_kernel.hip"]
+SOURCES = ["gsm_api.hip", "gsm_api_chain.hip", "gsm_api_sgs.hip", "gsm_api_posterior.hip", "gsm_api_variogram.hip", "gsm_api_qt.hip", "gsm_version.hip", "step_kernel.hip", "step_flux_kernel.hip", "chain_fused_kernel.hip", "chain_strip_kernel.hip", "proposal_kernel.hip", "cholesky_kernel.hip", "sgs_kernel.hip", "sgs_iter_kernel.hip", "sgs_grid_kernel.hip", "sgs_grid_draw_kernel.hip", "krige_grid_kernel.hip", "krige_cv_kernel.hip", "pcg64_kernel.hip", "posterior_kernel.hip", "posterior_hist_kernel.hip", "posterior_lag_kernel.hip", "posterior_cov_kernel.hip", "posterior_residual_kernel.hip", "posterior_local_kernel.hip", "posterior_regions_kernel.hip", "variogram_kernel.hip", "variogram_local_kernel.hip", "trend_kernel.hip", "qt_fit_kernel.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                "-Wno-unused-value", "-Wno-unused-result"]
 # per-file extras.  step_flux_kernel: without machine LICM the fp64 polynomial constants of exp() are materialised at
@@ -256,6 +256,7 @@ def load() -> C.CDLL:
     lib.gsm_posterior_cross.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     lib.gsm_posterior_residual.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     lib.gsm_posterior_local.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.gsm_posterior_regions.argtypes = [vp, vp, vp, i32, dbl, dbl, vp, dbl, dbl, i32, vp, vp]
     lib.gsm_variogram_map.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
     lib.gsm_variogram_local.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.gsm_debug_stream_copy.argtypes = [vp, vp, i64, vp]

@@ -1,5 +1,5 @@
 // C ABI of libgsm_hip.so, the posterior accumulator (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip,
-// posterior_cov_kernel.hip, posterior_residual_kernel.hip, posterior_local_kernel.hip).  Every
+// posterior_cov_kernel.hip, posterior_residual_kernel.hip, posterior_local_kernel.hip, posterior_regions_kernel.hip).  Every
 // argument is validated here, once, where the error text is; the launchers take what they are given.
 #include "gsm_context.h"
 #include "posterior_device.h"
@@ -189,6 +189,32 @@ extern "C" int gsm_posterior_local(gsm_handle h, const void* beds, const double*
   HIPCHK(h, h->d_post_slab.ensure((size_t)parts * K * h->H * h->W));
   HIPCHK(h, launch_posterior_local(beds, g, h->d_post_slab.get(), cross, h->H, h->W, h->n_chains, parts, reach, h->f32_state, h->n_cu,
                                    (hipStream_t)stream));
+  return GSM_OK;
+}
+
+extern "C" int gsm_posterior_regions(gsm_handle h, const void* beds, const uint8_t* region_bits, int32_t n_regions, double sea_level,
+                                     double density_ratio, double* func, double hyps_lo, double hyps_inv_width, int32_t n_bins,
+                                     int32_t* hyps, void* stream) {
+  GSM_GRID_HANDLE(h);
+  if (!beds || !region_bits || !func) return fail(h, GSM_E_ARG, "gsm_posterior_regions: NULL pointer");
+  if (n_regions < 1 || n_regions > kRegMaxRegions) return fail(h, GSM_E_ARG, "gsm_posterior_regions: n_regions must be in [1, 8]");
+  if (n_bins != 0 && (n_bins < 2 || n_bins > kRegMaxBins || n_bins % 2))
+    return fail(h, GSM_E_ARG, "gsm_posterior_regions: n_bins must be 0 or even and in [2, 64]");
+  if (n_bins > 0 && !hyps) return fail(h, GSM_E_ARG, "gsm_posterior_regions: NULL hyps with n_bins > 0");
+  if (!std::isfinite(sea_level)) return fail(h, GSM_E_ARG, "gsm_posterior_regions: sea_level must be finite");
+  if (!(density_ratio > 0.0) || !std::isfinite(density_ratio))
+    return fail(h, GSM_E_ARG, "gsm_posterior_regions: density_ratio must be finite and > 0");
+  if (n_bins > 0 && (!(hyps_inv_width > 0.0) || !std::isfinite(hyps_inv_width) || !std::isfinite(hyps_lo)))
+    return fail(h, GSM_E_ARG, "gsm_posterior_regions: hyps_inv_width must be finite and > 0 and hyps_lo finite");
+  if (!aligned16(beds)) return fail(h, GSM_E_ARG, "gsm_posterior_regions: beds must be 16-byte aligned");
+  if (!h->have_static) return fail(h, GSM_E_STATE, "gsm_posterior_regions: call gsm_set_static first");
+  if (h->n_chains > 65535) return fail(h, GSM_E_UNSUPPORTED, "gsm_posterior_regions: more than 65535 chains");
+  int rc = posterior_device(h);
+  if (rc != GSM_OK) return rc;
+  const int64_t plane = (int64_t)h->H * h->W;
+  HIPCHK(h, h->d_post_slab.ensure((size_t)h->n_chains * posterior_regions_parts(plane, h->n_chains, h->f32_state, h->n_cu) * n_regions * 8));
+  HIPCHK(h, launch_posterior_regions(beds, h->S.surf, region_bits, n_regions, sea_level, density_ratio, h->d_post_slab.get(), func, hyps_lo,
+                                     hyps_inv_width, n_bins, hyps, plane, h->n_chains, h->f32_state, h->n_cu, (hipStream_t)stream));
   return GSM_OK;
 }
 

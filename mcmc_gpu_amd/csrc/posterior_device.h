@@ -1,5 +1,5 @@
 // What the posterior kernels share (posterior_kernel.hip, posterior_hist_kernel.hip, posterior_lag_kernel.hip, posterior_cov_kernel.hip,
-// posterior_residual_kernel.hip, posterior_local_kernel.hip) and what
+// posterior_residual_kernel.hip, posterior_local_kernel.hip, posterior_regions_kernel.hip) and what
 // gsm_api_posterior.hip sizes the slab by: the workgroup size, the 16-byte pack, the cut of the chain axis into parts, the cells
 // per lane and the choice of a kernel's instantiation by state type and cells per lane.
 #pragma once
@@ -132,5 +132,14 @@ int64_t posterior_local_tiles(int H, int W);
 int posterior_local_parts(int H, int W, int reach, int n_chains, int n_cu);
 hipError_t launch_posterior_local(const void* beds, const double* g, double* slab, double* cross, int H, int W, int n_chains, int parts,
                                   int reach, int f32_state, int n_cu, hipStream_t st);
+// posterior_regions_kernel.hip.  n_regions in [1, 8], n_bins 0 or even in [2, 64]
+constexpr int kRegMaxRegions = 8;
+constexpr int kRegMaxBins = 64;
+// the most parts the regions kernel cuts the plane into, so that parts * n_chains workgroups fill the CUs about eight times over;
+// its slab holds n_chains * parts * n_regions * 8 partial slots
+int posterior_regions_parts(int64_t plane, int n_chains, int f32_state, int n_cu);
+hipError_t launch_posterior_regions(const void* beds, const double* surf, const uint8_t* bits, int n_regions, double sea_level,
+                                    double density_ratio, double* slab, double* func, double hyps_lo, double hyps_inv_w, int n_bins,
+                                    int32_t* hyps, int64_t plane, int n_chains, int f32_state, int n_cu, hipStream_t st);
 
 }  // namespace gsm

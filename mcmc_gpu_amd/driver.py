@@ -149,9 +149,17 @@ def _merge_posterior(accum, local_sums, n_chains, base, label):
     pv = None
     if accum.d_proj is not None:                   # [T, local chains, probes] on the device -> [n_chains, probes, T]
         pv = parallel.all_gather_chains(accum.d_proj.permute(1, 2, 0).contiguous(), n_chains).cpu().numpy()
+    rf = rh = None
+    if accum.d_func is not None:                   # per chain, small: every rank's pair as it is, concatenated in rank order
+        from .posterior import merge_regions
+        parts = [(accum.region_functionals(), accum.region_hypsometry())]
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, (accum.region_functionals(), accum.region_hypsometry()))
+        rf, rh = merge_regions(parts)
     if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
         base.mkdir(parents=True, exist_ok=True)
-        accum.finalize(sample_values=sv, projections=pv, **sums).save(base / f'posterior_{label}.npz')
+        accum.finalize(sample_values=sv, projections=pv, region_func=rf, region_hyps=rh, **sums).save(base / f'posterior_{label}.npz')
 
 
 def _run_shard(lo, hi, largeScaleChain, rf, initial_beds, rng_seeds, n_iters, output_path, mode, batch, n_workers,

@@ -363,6 +363,37 @@ class GsmEngine:
         self._check_sums(K * self.H * self.W, cross=cross)
         self.call(self.lib.gsm_posterior_local, self.beds, g, int(reach), cross)
 
+    def posterior_regions(self, region_bits, n_regions, sea_level, density_ratio, func, hyps_lo=0.0, hyps_inv_width=0.0, n_bins=0, hyps=None):
+        """One snapshot of self.beds into the per-chain, per-region functionals func [n_chains, K, 8] float64 (written): over the cells
+        of region k (bit k of region_bits [H, W] uint8) whose bed x and set_static surf s are finite, 0 their number, 1 sum x, 2 sum
+        max(s - x, 0), 3 sum max((s - x) + density_ratio * min(x - sea_level, 0), 0), 4 the number with x < sea_level, 5 the number of
+        those with slot 3's term > 0, 6 min x, 7 max x.  With n_bins > 0 (even, <= 64) the hypsometry of the same cells is ADDED to hyps
+        [n_chains, K, n_bins + 2] int32: slot 0 below hyps_lo, then n_bins bins of width 1 / hyps_inv_width, then the overflow.
+        Asynchronous."""
+        self._need_beds()
+        if self.static is None:
+            raise RuntimeError("set_static() first")
+        K, B = int(n_regions), int(n_bins)
+        if not 1 <= K <= 8:
+            raise ValueError(f"n_regions must be in [1, 8], got {K}")
+        if B != 0 and (B < 2 or B > 64 or B % 2):
+            raise ValueError(f"n_bins must be 0 or an even integer in [2, 64], got {B}")
+        if not np.isfinite(sea_level) or not (np.isfinite(density_ratio) and density_ratio > 0):
+            raise ValueError("sea_level must be finite and density_ratio finite and > 0")
+        if region_bits.dtype != torch.uint8 or region_bits.numel() != self.H * self.W or not region_bits.is_contiguous() or region_bits.device != self.dev:
+            raise ValueError(f"region_bits must be a contiguous uint8 tensor of H x W = {self.H * self.W} elements on {self.dev}")
+        if func.numel() != self.n_chains * K * 8:
+            raise ValueError(f"func must hold n_chains x K x 8 = {self.n_chains * K * 8} elements")
+        self._check_sums(self.n_chains * K * 8, func=func)
+        if B:
+            if not (np.isfinite(hyps_lo) and np.isfinite(hyps_inv_width) and hyps_inv_width > 0):
+                raise ValueError("hyps_lo must be finite and hyps_inv_width finite and > 0")
+            n = self.n_chains * K * (B + 2)
+            if hyps is None or hyps.dtype != torch.int32 or hyps.numel() != n or not hyps.is_contiguous() or hyps.device != self.dev:
+                raise ValueError(f"hyps must be a contiguous int32 tensor of n_chains x K x (n_bins + 2) = {n} elements on {self.dev}")
+        self.call(self.lib.gsm_posterior_regions, self.beds, region_bits, K, float(sea_level), float(density_ratio), func, float(hyps_lo),
+                  float(hyps_inv_width), B, hyps if B else None)
+
     # ------------------------------------------------------------------------------------------
     def pack_fields(self, fields):
         """fields[c][s] = masked proposal (bh, bw) -> (n_chains, n_steps, field_stride) float64."""

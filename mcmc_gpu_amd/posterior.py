@@ -58,6 +58,16 @@ Definitions.  Iterations are numbered as in the reference's caches: 0 is the ini
               (X_k - n m m') / (n - 1), pooled over all chains and snapshots, ddof=1 -- the expression that gives sd^2 at offset
               (0, 0) --, NaN where the partner is outside the grid.  From it local_correlation, difference_sd(di, dj),
               gradient_sd(resolution) and block_mean_sd(k).  A NaN bed makes NaN exactly the entries that pair its cell.
+  regions     optional non-linear functionals of every chain's bed over K <= 8 regions (masks that may overlap, or a label map): the
+              scalars an ensemble is published as.  Per snapshot (all T of them), chain and region the device writes eight slots
+              (gsm_posterior_regions) over the cells whose bed x and surface s are finite: their number, sum x, sum max(s - x, 0) (ice
+              thickness), sum max((s - x) + (rho_water / rho_ice) min(x - sea_level, 0), 0) (thickness above flotation), the number with x <
+              sea_level, the number of those that are grounded (thickness above flotation > 0), min x and max x; fp64, no fused
+              multiply-adds, a fixed summation tree.  region_values(what)[c, k, t] turns them into counts, volumes and areas (x
+              resolution^2), region_stats() into mean, sd, 2.5 / 50 / 97.5 % quantiles and split-R-hat over the M N values.  With hyps=
+              dict(lo, hi, bins) the device also counts, per chain and region, the valid cells per elevation bin (int32, an underflow and
+              an overflow slot) over the snapshots that belong to a sequence: hypsometry().  Both are per chain: over ranks they are
+              gathered in rank order (merge_regions), not summed.  Needs eng.set_static (the surface).
 """
 from __future__ import annotations
 
@@ -136,6 +146,79 @@ class PosteriorSummary:
     local_cross: np.ndarray | None = None
     local_reach: int | None = None
     local_centre: np.ndarray | None = None
+    # with regions=: region_func [n_chains, K, T, 8] float64, the eight slots of gsm_posterior_regions of every chain and region at
+    # all T snapshots; region_masks [K, H, W] bool, region_names K strings; region_sea_level, region_density_ratio (rho_water /
+    # rho_ice) and region_resolution (metres per cell) that the slots were made with; region_hyps [n_chains, K, B + 2] int64 cell
+    # counts over the snapshots that belong to a sequence (slot 0 below region_hyps_range[0], B + 1 at or above region_hyps_range[1])
+    region_func: np.ndarray | None = None
+    region_masks: np.ndarray | None = None
+    region_names: tuple | None = None
+    region_sea_level: float | None = None
+    region_density_ratio: float | None = None
+    region_resolution: float | None = None
+    region_hyps: np.ndarray | None = None
+    region_hyps_range: np.ndarray | None = None
+
+    def _need_regions(self):
+        if self.region_func is None or self.region_resolution is None:
+            raise ValueError("this summary holds no region functionals: run with posterior=dict(..., regions=dict(masks=...))")
+        return np.asarray(self.region_func, dtype=np.float64)
+
+    def region_values(self, what):
+        """[n_chains, K, T] the quantity `what` (one of REGION_QUANTITIES) of every chain and region at all T snapshots: count (valid
+        cells), mean_bed (NaN for a region without a valid cell), volume (ice thickness summed, x resolution^2), volume_above_flotation,
+        area_below_sea_level, area_marine_grounded (below sea level and grounded: thickness above flotation > 0), min_bed and max_bed
+        (NaN for a region without a valid cell)."""
+        F = self._need_regions()
+        a = float(self.region_resolution) ** 2
+        if what not in REGION_QUANTITIES:
+            raise KeyError(f"unknown region quantity {what!r}; the quantities are {REGION_QUANTITIES}")
+        if what == "count":
+            return F[..., 0].copy()
+        if what == "mean_bed":
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.where(F[..., 0] > 0, F[..., 1] / F[..., 0], np.nan)
+        if what in ("min_bed", "max_bed"):
+            v = F[..., 6 if what == "min_bed" else 7]
+            return np.where(F[..., 0] > 0, v, np.nan)
+        return F[..., {"volume": 2, "volume_above_flotation": 3, "area_below_sea_level": 4, "area_marine_grounded": 5}[what]] * a
+
+    def region_stats(self):
+        """{quantity: dict(mean, sd, q025, q50, q975, rhat)}, each [K], of every quantity of REGION_QUANTITIES over the M N values
+        that mean and sd describe (the snapshots that split drops are left out, every chain cut into the summary's sequences): mean,
+        ddof=1 sd, the 2.5 / 50 / 97.5 % quantiles (NumPy's default, linear) and the split R-hat of probe_stats()."""
+        self._need_regions()
+        out = {}
+        for what in REGION_QUANTITIES:
+            s = self._sequences(self.region_values(what))
+            st = _sequence_stats(s)
+            with np.errstate(invalid="ignore"):
+                q = np.quantile(s.reshape(-1, s.shape[2]), (0.025, 0.5, 0.975), axis=0)
+            out[what] = dict(mean=st["mean"], sd=st["sd"], q025=q[0], q50=q[1], q975=q[2], rhat=st["rhat"])
+        return out
+
+    def hypsometry(self):
+        """dict(edges [B + 1] the bin edges in metres; area [n_chains, K, B + 2] every chain's mean area per slot over its snapshots
+        that belong to a sequence (slot 0: below edges[0], slots 1 .. B the bins, slot B + 1: at or above edges[B]), in resolution^2;
+        mean [K, B + 2] the mean of `area` over the chains: the pooled hypsometric curve)."""
+        self._need_regions()
+        if self.region_hyps is None or self.region_hyps_range is None:
+            raise ValueError("this summary holds no hypsometry: run with regions=dict(..., hyps=dict(lo=, hi=, bins=))")
+        cnt = np.asarray(self.region_hyps, dtype=np.float64)
+        B = cnt.shape[2] - 2
+        lo, hi = (float(v) for v in np.asarray(self.region_hyps_range).ravel())
+        n = self.n_per_sequence * (2 if self.split else 1)
+        area = cnt / n * float(self.region_resolution) ** 2
+        return dict(edges=lo + np.arange(B + 1) * ((hi - lo) / B), area=area, mean=area.mean(axis=0))
+
+    def _sequences(self, v):
+        """[M, N, K] from per-chain traces v [C, K, T]: the M N values that mean and sd describe -- v without the snapshots that split
+        drops, every chain cut into its sequences."""
+        v = np.asarray(v, dtype=np.float64)
+        C, K, T = v.shape
+        N = self.n_per_sequence
+        n_seq = 2 if self.split else 1
+        return v[:, :, T - n_seq * N:].transpose(0, 2, 1).reshape(C * n_seq, N, K)
 
     def _need_local(self, reach=1, what=None):
         if self.local_cross is None or self.local_reach is None or self.local_centre is None:
@@ -294,11 +377,7 @@ class PosteriorSummary:
     def _probe_sequences(self):
         """[M, N, K] the functionals at the M N values that mean and sd describe: probe_values without the snapshots that split drops,
         every chain cut into its sequences."""
-        v = np.asarray(self.probe_values, dtype=np.float64)
-        C, K, T = v.shape
-        N = self.n_per_sequence
-        n_seq = 2 if self.split else 1
-        return v[:, :, T - n_seq * N:].transpose(0, 2, 1).reshape(C * n_seq, N, K)
+        return self._sequences(self.probe_values)
 
     def covariance(self):
         """[K, H, W] covariance of every cell with every functional over the M N values, ddof=1: (Y_k - S1 q_k / n) / (n - 1) with
@@ -318,20 +397,8 @@ class PosteriorSummary:
         """dict of host statistics of the functionals over the same M N values: mean [K], sd [K] (ddof=1), rhat [K] (split R-hat over
         the summary's sequences, NaN where the within-sequence variance is 0 or there is one sequence) and cov [K, K], the ddof=1
         covariance of the functionals with each other."""
-        n = self._need_cov()
-        s = self._probe_sequences()
-        M, N, K = s.shape
-        flat = s.reshape(n, K)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            mean = flat.mean(axis=0)
-            dev = flat - mean
-            cov = dev.T @ dev / (n - 1)
-            mu = s.mean(axis=1)
-            v = np.where((s == s[:, :1]).all(axis=1), 0.0, s.var(axis=1, ddof=1))
-            W = v.mean(axis=0)
-            B_over_N = mu.var(axis=0, ddof=1) if M > 1 else np.full(K, np.nan)
-            rhat = np.where(W == 0, np.nan, np.sqrt(((N - 1) / N * W + B_over_N) / W))
-        return dict(mean=mean, sd=np.sqrt(np.diagonal(cov)), rhat=rhat, cov=cov)
+        self._need_cov()
+        return _sequence_stats(self._probe_sequences())
 
     def correlation(self):
         """[K, H, W] covariance() / (sd of the cell * sd of the functional).  NaN where either sd is 0."""
@@ -443,7 +510,30 @@ class PosteriorSummary:
             kw["residual_sigma_mc"] = float(kw["residual_sigma_mc"])
         if kw["local_reach"] is not None:
             kw["local_reach"] = int(kw["local_reach"])
+        if kw["region_names"] is not None:
+            kw["region_names"] = tuple(str(v) for v in kw["region_names"])
+        for k in ("region_sea_level", "region_density_ratio", "region_resolution"):
+            if kw[k] is not None:
+                kw[k] = float(kw[k])
         return cls(**kw)
+
+
+def _sequence_stats(s):
+    """dict(mean [K], sd [K] (ddof=1), rhat [K], cov [K, K]) of K scalar quantities over M sequences of N values, s [M, N, K]: pooled
+    over all M N values, and the split R-hat over the sequences (NaN where the within-sequence variance is 0 or there is one sequence)."""
+    M, N, K = s.shape
+    n = M * N
+    flat = s.reshape(n, K)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = flat.mean(axis=0)
+        dev = flat - mean
+        cov = dev.T @ dev / (n - 1)
+        mu = s.mean(axis=1)
+        v = np.where((s == s[:, :1]).all(axis=1), 0.0, s.var(axis=1, ddof=1))
+        W = v.mean(axis=0)
+        B_over_N = mu.var(axis=0, ddof=1) if M > 1 else np.full(K, np.nan)
+        rhat = np.where(W == 0, np.nan, np.sqrt(((N - 1) / N * W + B_over_N) / W))
+    return dict(mean=mean, sd=np.sqrt(np.diagonal(cov)), rhat=rhat, cov=cov)
 
 
 def _host_array(x, shape, dtype, what):
@@ -652,6 +742,125 @@ def _shifted(a, di, dj):
     return b
 
 
+REGION_KEYS = ("masks", "names", "sea_level", "rho_ice", "rho_water", "hyps")
+REGION_HYPS_KEYS = ("lo", "hi", "bins")
+REGION_MAX, REGION_MAX_BINS = 8, 64
+REGION_QUANTITIES = ("count", "mean_bed", "volume", "volume_above_flotation", "area_below_sea_level", "area_marine_grounded", "min_bed",
+                     "max_bed")
+
+
+def check_regions(regions, H=None, W=None):
+    """Validate the `regions` option: None, or dict(masks=, names=None, sea_level=0.0, rho_ice=917.0, rho_water=1028.0, hyps=None).
+    masks: [K, H, W] (or [H, W], K = 1) bool or numbers, non-zero = inside, regions may overlap and may be empty; or an integer label
+    map [H, W], label k in 1 .. K = region k - 1 and label 0 = no region; K <= 8.  names: K strings.  hyps: None or dict(lo=, hi=,
+    bins=) with finite lo < hi (metres) and bins even in [2, 64].  Returns None or dict(masks=<[K, h, w] bool>, names=<tuple of K str>,
+    sea_level, rho_ice, rho_water, hyps=<None or dict(lo, hi, bins)>); with H and W given the masks must have the grid's shape."""
+    if regions is None:
+        return None
+    if not isinstance(regions, dict):
+        raise ValueError("regions must be None or a dict with the key masks and optionally names, sea_level, rho_ice, rho_water, hyps")
+    unknown = set(regions) - set(REGION_KEYS)
+    if unknown:
+        raise ValueError(f"unknown regions option(s) {sorted(unknown)}; the options are {REGION_KEYS}")
+    if "masks" not in regions:
+        raise ValueError("regions needs masks: a bool array [K, H, W] or an integer label map [H, W]")
+    m = np.asarray(regions["masks"])
+    if m.dtype == object or not (m.dtype == bool or np.issubdtype(m.dtype, np.number)):
+        raise ValueError("regions masks must be an array of bools or numbers")
+    if m.ndim == 2 and np.issubdtype(m.dtype, np.integer):
+        if m.size and m.min() < 0:
+            raise ValueError("regions labels must be >= 0 (0 = no region)")
+        K = int(m.max()) if m.size else 0
+        if K > REGION_MAX:
+            raise ValueError(f"regions takes at most {REGION_MAX} regions, the label map goes up to {K}")
+        m = np.stack([m == k for k in range(1, K + 1)]) if K else np.zeros((0,) + m.shape, dtype=bool)
+    else:
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim == 3 and m.shape[0] > REGION_MAX:
+            raise ValueError(f"regions takes at most {REGION_MAX} regions, got {m.shape[0]}")
+        with np.errstate(invalid="ignore"):
+            m = m != 0
+    if m.ndim != 3 or 0 in m.shape:
+        raise ValueError(f"regions masks must have shape [K, H, W] with 1 <= K <= {REGION_MAX}, or be an integer label map [H, W] with a label "
+                         f"above 0; got {np.asarray(regions['masks']).shape}")
+    if H is not None and m.shape[1:] != (int(H), int(W)):
+        raise ValueError(f"regions masks of shape {m.shape}, the grid is {(int(H), int(W))}")
+    K = m.shape[0]
+    names = regions.get("names")
+    if names is None:
+        names = tuple(f"region{k}" for k in range(K))
+    elif isinstance(names, str) or not all(isinstance(v, str) for v in names) or len(names) != K:
+        raise ValueError(f"regions names must be a sequence of {K} strings, one per region")
+    out = dict(masks=np.ascontiguousarray(m), names=tuple(names))
+    for key, default, positive in (("sea_level", 0.0, False), ("rho_ice", 917.0, True), ("rho_water", 1028.0, True)):
+        try:
+            v = float(regions.get(key, default))
+        except (TypeError, ValueError):
+            raise ValueError(f"regions {key} must be a number, got {regions.get(key)!r}") from None
+        if not np.isfinite(v) or (positive and not v > 0.0):
+            raise ValueError(f"regions {key} must be finite{' and > 0' if positive else ''}, got {v}")
+        out[key] = v
+    hyps = regions.get("hyps")
+    if hyps is not None:
+        if not isinstance(hyps, dict) or set(hyps) != set(REGION_HYPS_KEYS):
+            raise ValueError(f"regions hyps must be None or a dict with exactly the keys {REGION_HYPS_KEYS}")
+        bins = hyps["bins"]
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 2 or bins > REGION_MAX_BINS or bins % 2:
+            raise ValueError(f"regions hyps bins must be an even integer in [2, {REGION_MAX_BINS}], got {bins!r}")
+        try:
+            lo, hi = float(hyps["lo"]), float(hyps["hi"])
+        except (TypeError, ValueError):
+            raise ValueError("regions hyps lo and hi must be numbers") from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and hi > lo):
+            raise ValueError(f"regions hyps needs finite lo < hi, got lo={lo}, hi={hi}")
+        hyps = dict(lo=lo, hi=hi, bins=int(bins))
+    out["hyps"] = hyps
+    return out
+
+
+def region_bits(masks):
+    """[H, W] uint8 bit plane of the masks [K, H, W], K <= 8: bit k of a cell is set where masks[k] is (gsm_posterior_regions)."""
+    m = np.asarray(masks) != 0
+    if m.ndim != 3 or not 1 <= m.shape[0] <= REGION_MAX:
+        raise ValueError(f"region_bits: masks must be [K, H, W] with 1 <= K <= {REGION_MAX}")
+    bits = np.zeros(m.shape[1:], dtype=np.uint8)
+    for k in range(m.shape[0]):
+        bits |= m[k].astype(np.uint8) << np.uint8(k)
+    return bits
+
+
+def check_region_count(H, W, n_iter, burn_in, thin, split=True):
+    """Refuse a hypsometry whose largest possible counter, H W cells x the snapshots of a chain that belong to a sequence, does not
+    fit the int32 counters."""
+    _, N, _ = sequence_plan(n_iter, burn_in, thin, split)
+    total = int(H) * int(W) * N * (2 if split else 1)
+    if total > HIST_MAX_COUNT:
+        raise ValueError(f"regions hyps: {int(H) * int(W)} cells x {N * (2 if split else 1)} snapshots = {total} exceed the int32 counters "
+                         f"({HIST_MAX_COUNT}): thin more")
+
+
+def merge_regions(parts):
+    """The per-chain region arrays of all ranks from the ranks' own, `parts` = [(func [c_r, K, T, 8], hyps [c_r, K, B + 2] or None),
+    ...] in rank order: both are per chain, so they are concatenated along the chain axis in rank order (the order of the gathered
+    traces and projections), never summed.  Returns (func [n_chains, K, T, 8] float64, hyps [n_chains, K, B + 2] int64 or None)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_regions: no rank")
+    func = [np.asarray(f, dtype=np.float64) for f, _ in parts]
+    hyps = [h for _, h in parts]
+    if any(f.ndim != 4 or f.shape[1:] != func[0].shape[1:] or f.shape[3] != 8 for f in func):
+        raise ValueError(f"merge_regions: the ranks' func arrays must be [chains, K, T, 8] with the same K and T, got {[f.shape for f in func]}")
+    if any((h is None) != (hyps[0] is None) for h in hyps):
+        raise ValueError("merge_regions: some ranks hold a hypsometry and some do not")
+    if hyps[0] is None:
+        return np.concatenate(func, axis=0), None
+    hyps = [np.asarray(h, dtype=np.int64) for h in hyps]
+    if any(h.ndim != 3 or h.shape[1:] != hyps[0].shape[1:] or h.shape[0] != f.shape[0] or h.shape[1] != f.shape[1] for h, f in zip(hyps, func)):
+        raise ValueError(f"merge_regions: the ranks' hyps arrays must be [chains, K, B + 2] beside their func, got {[h.shape for h in hyps]}")
+    return np.concatenate(func, axis=0), np.concatenate(hyps, axis=0)
+
+
 HIST_KEYS = ("bins", "half_width", "levels")
 HIST_MAX_BINS, HIST_MAX_LEVELS = 128, 8
 HIST_MAX_COUNT = 2 ** 31 - 1
@@ -722,10 +931,13 @@ class PosteriorAccumulator:
     [3 + L, H, W], to which add() adds the residual sums of every snapshot that belongs to a sequence (sum it over ranks with
     all_reduce_sum).
     local (see check_local): also, float64, `local_cross` [K, H, W], K = 2 reach^2 + 2 reach, to which add() adds the cross sums with
-    the neighbours of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_sum)."""
+    the neighbours of every snapshot that belongs to a sequence (sum it over ranks with all_reduce_sum).
+    regions (see check_regions; needs eng.set_static): also `d_region_bits` [H, W] uint8, `d_func` [T, n_chains, K, 8] float64, the
+    region slots of all T snapshots, and with hyps `region_hyps` [n_chains, K, B + 2] int32, to which add() adds the hypsometry of
+    every snapshot that belongs to a sequence.  Both are per chain: gather them over ranks in rank order (merge_regions)."""
 
     def __init__(self, eng, n_iter, burn_in, thin, split=True, rhat=True, common_ref=None, sample_cells=None, sample_loc=None, hist=None,
-                 ess=None, cov=None, residual=None, local=None):
+                 ess=None, cov=None, residual=None, local=None, regions=None):
         import torch
         self.eng = eng
         self.n_iter, self.burn_in, self.thin, self.split, self.rhat = int(n_iter), int(burn_in), int(thin), bool(split), bool(rhat)
@@ -747,6 +959,18 @@ class PosteriorAccumulator:
         self.residual = check_residual(residual)
         if self.residual is not None and getattr(eng, "static", None) is None:
             raise ValueError("residual needs the engine's static fields: call set_static() first")
+        self.regions = check_regions(regions, H, W)
+        self.n_regions = 0 if self.regions is None else int(self.regions["masks"].shape[0])
+        self.region_bins = 0
+        if self.regions is not None:
+            if getattr(eng, "static", None) is None:
+                raise ValueError("regions needs the engine's static fields (the surface): call set_static() first")
+            hy = self.regions["hyps"]
+            if hy is not None:
+                check_region_count(H, W, n_iter, burn_in, thin, self.split)
+                self.region_bins = hy["bins"]
+                self.region_hyps_lo, self.region_hyps_inv_w = hy["lo"], hy["bins"] / (hy["hi"] - hy["lo"])
+            self.region_density_ratio = self.regions["rho_water"] / self.regions["rho_ice"]
         # common_ref None: a zero field (run_many passes default_common_ref(chain.initial_bed))
         g = np.zeros((H, W)) if common_ref is None else np.ascontiguousarray(common_ref, dtype=np.float64)
         if g.shape != (H, W) or not np.isfinite(g).all():
@@ -778,6 +1002,10 @@ class PosteriorAccumulator:
             table += [("d_rg", (H, W), f64, False), ("residual_sums", (3 + len(self.residual["levels"]), H, W), f64, True)]
         if self.n_local:
             table += [("local_cross", (self.n_local, H, W), f64, True)]
+        if self.n_regions:
+            table += [("d_region_bits", (H, W), torch.uint8, False), ("d_func", (self.T, n, self.n_regions, 8), f64, False)]
+            if self.region_bins:
+                table += [("region_hyps", (n, self.n_regions, self.region_bins + 2), torch.int32, True)]
         self.device_bytes = need = sum(math.prod(shape) * dtype.itemsize for _, shape, dtype, _ in table)
         free = torch.cuda.mem_get_info(eng.dev)[0]
         if need > free:
@@ -785,6 +1013,7 @@ class PosteriorAccumulator:
                               f"{free / 2**30:.2f} GiB of device memory are free: use rhat=False (two [H, W] arrays) or fewer chains")
         self.ref = self.d_cells = self.d_samples = self.hist_counts = self.ring = self.lag_sqdiff = None
         self.d_probes = self.d_proj = self.probe_cross = self.d_rg = self.residual_sums = self.local_cross = None
+        self.d_region_bits = self.d_func = self.region_hyps = None
         for name, shape, dtype, zeroed in table:
             setattr(self, name, (torch.zeros if zeroed else torch.empty)(shape, dtype=dtype, device=eng.dev))
         self.d_g.copy_(torch.as_tensor(g))
@@ -798,6 +1027,8 @@ class PosteriorAccumulator:
             rg[~np.isfinite(rg)] = 0.0
             self.residual_ref = rg
             self.d_rg.copy_(torch.as_tensor(rg))
+        if self.n_regions:
+            self.d_region_bits.copy_(torch.as_tensor(region_bits(self.regions["masks"])))
         self.ring_head = self.ring_valid = 0
         self.n_added = 0
         self._partials = None
@@ -844,6 +1075,13 @@ class PosteriorAccumulator:
             eng.posterior_residual(self.d_rg, self.residual["levels"], self.residual_sums)
         if self.n_local and t >= self.dropped:               # the values that mean and sd describe, each paired once
             eng.posterior_local(self.d_g, self.local["reach"], self.local_cross)
+        if self.n_regions:                 # the functionals of every snapshot, the hypsometry of those that mean and sd describe
+            r, counted = self.regions, self.region_bins and t >= self.dropped
+            if counted:
+                eng.posterior_regions(self.d_region_bits, self.n_regions, r["sea_level"], self.region_density_ratio, self.d_func[t],
+                                      self.region_hyps_lo, self.region_hyps_inv_w, self.region_bins, self.region_hyps)
+            else:
+                eng.posterior_regions(self.d_region_bits, self.n_regions, r["sea_level"], self.region_density_ratio, self.d_func[t])
         self.n_added += 1
         self._partials = None
 
@@ -890,10 +1128,19 @@ class PosteriorAccumulator:
         """[n_chains, K, T] numpy array of the projections p of all snapshots, or None."""
         return None if self.d_proj is None else np.ascontiguousarray(self.d_proj.permute(1, 2, 0).cpu().numpy())
 
+    def region_functionals(self):
+        """[n_chains, K, T, 8] numpy array of the region slots of all snapshots, or None."""
+        return None if self.d_func is None else np.ascontiguousarray(self.d_func.permute(1, 2, 0, 3).cpu().numpy())
+
+    def region_hypsometry(self):
+        """[n_chains, K, B + 2] int64 numpy array of the hypsometry counts, or None."""
+        return None if self.region_hyps is None else self.region_hyps.cpu().numpy().astype(np.int64)
+
     def finalize(self, partials_sum=None, M=None, sample_values=None, hist_counts=None, lag_sqdiff=None, probe_cross=None, projections=None,
-                 residual_sums=None, local_cross=None):
+                 residual_sums=None, local_cross=None, region_func=None, region_hyps=None):
         """PosteriorSummary from the sums of local_sums() added over ranks (all_reduce_posterior, all_reduce_counts, all_reduce_sum);
-        each defaults to this accumulator's own.  projections: [n_chains, K, T] of all ranks' chains (projections(), gathered)."""
+        each defaults to this accumulator's own.  projections: [n_chains, K, T] of all ranks' chains (projections(), gathered);
+        region_func and region_hyps: those of all ranks' chains (merge_regions of region_functionals(), region_hypsometry())."""
         self._require_complete()
         if partials_sum is None:
             partials_sum, M = self.partials(), self.n_sequences
@@ -926,23 +1173,33 @@ class PosteriorAccumulator:
             meta.update(local_cross=_host_array(self.local_cross if local_cross is None else local_cross, (self.n_local,) + grid, np.float64,
                                                 "local cross sums"),
                         local_reach=self.local["reach"], local_centre=self.common_ref.copy())
+        if self.n_regions:
+            C, K, r = M // self.n_seq, self.n_regions, self.regions
+            meta.update(region_func=_host_array(self.region_functionals() if region_func is None else region_func, (C, K, self.T, 8), np.float64,
+                                                "region functionals"),
+                        region_masks=r["masks"].copy(), region_names=r["names"], region_sea_level=r["sea_level"],
+                        region_density_ratio=self.region_density_ratio, region_resolution=float(self.eng.static["resolution"]))
+            if self.region_bins:
+                meta.update(region_hyps=_host_array(self.region_hypsometry() if region_hyps is None else region_hyps, (C, K, self.region_bins + 2),
+                                                    np.int64, "hypsometry counts"),
+                            region_hyps_range=np.array([r["hyps"]["lo"], r["hyps"]["hi"]], dtype=np.float64))
         return finalize(partials_sum, M, self.N, self.common_ref, rhat=self.rhat, n_chains=M // self.n_seq,
                         snapshot_iterations=self.snapshot_iterations, burn_in=self.burn_in, thin=self.thin, split=self.split,
                         sample_values=self.sample_values() if sample_values is None else sample_values, sample_loc=self.sample_loc, **meta)
 
 
-POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov", "residual", "local")
+POSTERIOR_KEYS = ("burn_in", "thin", "split", "rhat", "common_ref", "hist", "ess", "cov", "residual", "local", "regions")
 
 
 def check_options(posterior, n_iter, n_chains=None):
     """Validate the `posterior=` dict of run_many / largeScaleChain_mp before anything runs; returns it with defaults filled in.
     n_chains: the chains of all ranks, for the histogram's count limit."""
     if not isinstance(posterior, dict):
-        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov, residual, local")
+        raise TypeError("posterior must be a dict with the keys burn_in, thin and optionally split, rhat, common_ref, hist, ess, cov, residual, local, regions")
     unknown = set(posterior) - set(POSTERIOR_KEYS)
     if unknown:
         raise ValueError(f"unknown posterior option(s) {sorted(unknown)}; the options are {POSTERIOR_KEYS}")
-    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None, residual=None, local=None)
+    opt = dict(burn_in=0, thin=1, split=True, rhat=True, common_ref=None, hist=None, ess=None, cov=None, residual=None, local=None, regions=None)
     opt.update(posterior)
     _, N, _ = sequence_plan(n_iter, opt["burn_in"], opt["thin"], opt["split"])
     opt["ess"] = check_ess(opt["ess"], N, opt["rhat"])
@@ -950,6 +1207,7 @@ def check_options(posterior, n_iter, n_chains=None):
     opt["cov"] = check_cov(opt["cov"])
     opt["residual"] = check_residual(opt["residual"])
     opt["local"] = check_local(opt["local"])
+    opt["regions"] = check_regions(opt["regions"])
     if opt["hist"] is not None and n_chains is not None:
         check_hist_count(n_chains, n_iter, opt["burn_in"], opt["thin"], opt["split"])
     return opt

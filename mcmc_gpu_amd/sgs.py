@@ -819,7 +819,7 @@ class _SgsRun:
         self.accum = PosteriorAccumulator(eng, self.n_iter, opt['burn_in'], opt['thin'], split=opt['split'], rhat=opt['rhat'], common_ref=g,
                                           sample_cells=None if self.ij is None else self.ij[:, 0] * self.W + self.ij[:, 1],
                                           sample_loc=chain.sample_loc, hist=opt['hist'], ess=opt['ess'], cov=opt['cov'],
-                                          residual=opt['residual'], local=opt['local'])
+                                          residual=opt['residual'], local=opt['local'], regions=opt['regions'])
         if self.trend is not None or self.bed_host is not None:
             self.snap = torch.empty((self.n, self.H, self.W), dtype=torch.float64, device=self.dev)
         if self.of is not None and self.d_trend is not None:

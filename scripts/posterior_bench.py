@@ -39,7 +39,16 @@
               (--no-end-to-end leaves that out).  Counted bytes of (a): the beds, every part's [K, H, W] slab written and read back,
               `cross` read and written.  The default --out is profiles/posterior_bench_local.json.
 
-    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K | --residual | --local R ...]
+  --regions K [--hyps B]  only the pass of the region functionals (gsm_posterior_regions) with K regions (the whole domain and K - 1
+              overlapping rectangles) and B hypsometry bins at 1024 chains of 256 x 256, fp64 and fp32 state: (a) the pass, (b)
+              gsm_debug_stream_copy moving the beds' bytes, (c) gsm_posterior_project with K probes and (d) the composition that needs no
+              new kernel, torch clamp and masked sums, counts, amin and amax over the same beds (without the hypsometry).  (a), (b), (c)
+              the median of 20 calls, (d) of 5, three repeats, the four alternating; then the wall time of MCMC_gpu.run_many without
+              `posterior`, with it, and with `regions` at thin=100 (--no-end-to-end leaves that out).  Counted bytes: the beds alone.
+              The default --out is profiles/posterior_bench_regions.json.
+
+    python scripts/posterior_bench.py [--out profiles/posterior_bench.json] [--quick] [--hist | --ess | --cov K | --residual | --local R ... |
+                                      --regions K [--hyps B]]
 """
 import argparse
 import json
@@ -417,13 +426,122 @@ def local_rows(n_chains, H, state, reaches, reps, repeats):
     return rows
 
 
-def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None, residual=False, local=None):
+def _bench_regions(H, W, K):
+    """[K, H, W] bool: the whole domain, then nested and overlapping rectangles -- a basin, its sub-basins, as an ensemble is reported"""
+    m = np.zeros((K, H, W), dtype=bool)
+    m[0] = True
+    for k in range(1, K):
+        i0, j0 = (k * H) // (2 * K), (k * W) // (3 * K)
+        m[k, i0: i0 + H // 2, j0: j0 + (2 * W) // 3] = True
+    return m
+
+
+def regions_rows(n_chains, H, state, K, bins, reps, repeats):
+    """The region pass (a) with K regions (and `bins` hypsometry bins, 0 = none) beside (b) a stream copy of the beds' bytes, (c)
+    gsm_posterior_project with K probes (the linear functionals of the same regions: their mean-bed weights) and (d) the composition
+    that needs no new kernel, in torch on the same beds: thickness and thickness above flotation by clamp, then per region masked
+    sums, counts, amin and amax over the plane (the hypsometry is left out of (d)).  (a), (b) and (c) are the median of `reps` calls,
+    (d) of 5, `repeats` times over, the four alternating within a repeat.  (a) and (d) are compared on their results."""
+    import ctypes as C
+    import torch
+    from mcmc_gpu_amd import posterior, synthetic
+    from mcmc_gpu_amd.engine import GsmEngine
+    prob, ch, rf = synthetic.template(H)
+    W = H
+    eng = GsmEngine(H, W, n_chains, state_dtype=state)
+    rows = []
+    try:
+        eng.set_static(ch.surf, ch.velx, ch.vely, ch.dhdt, ch.smb, None, np.ones((H, W), dtype=np.uint8), ch.mc_region_mask, ch.resolution, ch.sigma_mc)
+        dev, plane, sb = eng.dev, H * W, 8 if state == "f64" else 4
+        n = n_chains * plane
+        bed0 = torch.as_tensor(np.ascontiguousarray(prob["bed"], dtype=np.float64)).to(dev)
+        eng.beds = (bed0[None] + 20.0 * torch.randn((n_chains, H, W), dtype=torch.float64, device=dev)).to(eng.state_dtype)
+        shape = f"{n_chains}x{H}x{W} {state}"
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        masks = _bench_regions(H, W, K)
+        sea, ratio = float(np.median(prob["bed"])), 1028.0 / 917.0            # the beds straddle it: every branch is taken
+        lo, hi = float(prob["bed"].min()) - 50.0, float(prob["bed"].max()) + 50.0
+        d_bits = torch.as_tensor(posterior.region_bits(masks)).to(dev)
+        func = torch.empty((n_chains, K, 8), dtype=torch.float64, device=dev)
+        hyps = torch.zeros((n_chains, K, bins + 2), dtype=torch.int32, device=dev) if bins else None
+        g = bed0.clone()
+        probes = torch.as_tensor(posterior.region_mean_probes(masks)).to(dev)
+        proj = torch.empty((n_chains, K), dtype=torch.float64, device=dev)
+        d_masks = torch.as_tensor(masks).to(dev)
+        surf = torch.as_tensor(np.ascontiguousarray(ch.surf, dtype=np.float64)).to(dev)
+        comp = torch.empty((n_chains, K, 8), dtype=torch.float64, device=dev)
+        m = sb * n // 16
+        src = torch.ones(m, dtype=torch.float64, device=dev)
+        dst = torch.empty(m, dtype=torch.float64, device=dev)
+
+        def fused():
+            if bins:
+                eng.posterior_regions(d_bits, K, sea, ratio, func, lo, bins / (hi - lo), bins, hyps)
+            else:
+                eng.posterior_regions(d_bits, K, sea, ratio, func)
+
+        def composition():
+            x = eng.beds.to(torch.float64)
+            h = surf - x
+            b = x - sea
+            thick = h.clamp(min=0.0)
+            haf = (h + ratio * b.clamp(max=0.0)).clamp(min=0.0)
+            below = b < 0
+            marine = below & (haf > 0)
+            inf = torch.tensor(float("inf"), dtype=torch.float64, device=dev)
+            for k in range(K):
+                mk = d_masks[k]
+                comp[:, k, 0] = float(mk.sum().item())
+                comp[:, k, 1] = (x * mk).sum(dim=(1, 2))
+                comp[:, k, 2] = (thick * mk).sum(dim=(1, 2))
+                comp[:, k, 3] = (haf * mk).sum(dim=(1, 2))
+                comp[:, k, 4] = (below & mk).sum(dim=(1, 2))
+                comp[:, k, 5] = (marine & mk).sum(dim=(1, 2))
+                comp[:, k, 6] = torch.where(mk, x, inf).amin(dim=(1, 2))
+                comp[:, k, 7] = torch.where(mk, x, -inf).amax(dim=(1, 2))
+
+        calls = {"a region pass": (sb * n, reps, fused),
+                 "b stream copy of the beds' bytes": (16 * m, reps, lambda: eng._check(eng.lib.gsm_debug_stream_copy(
+                     C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), m, st))),
+                 "c project pass, K probes": (sb * n, reps, lambda: eng.posterior_project(g, probes, proj)),
+                 "d torch composition, clamp and masked sums": (sb * n, min(reps, 5), composition)}
+        med = {name: [] for name in calls}
+        for _ in range(repeats):
+            for name, (nbytes, r, fn) in calls.items():
+                row = _rate(f"{name} ({K} regions, {bins} bins, {shape})", nbytes, _timed(fn, r))
+                med[name].append(row["ms_median"])
+                rows.append(row)
+        names = list(calls)
+        mm = {name: statistics.median(v) for name, v in med.items()}
+        exact = bool(all(torch.equal(func[..., f], comp[..., f]) for f in (0, 4, 5, 6, 7)))
+        scale = comp[..., 1:4].abs().amax().item()
+        rows.append({"what": f"region pass summary {K} regions {bins} bins {shape}", "regions": K, "bins": bins, "bed_bytes": sb * n,
+                     "ms_median_per_repeat": med, "pass_over_copy": mm[names[0]] / mm[names[1]], "pass_over_project": mm[names[0]] / mm[names[2]],
+                     "composition_over_pass": mm[names[3]] / mm[names[0]],
+                     "pass_faster_than_composition_in_all_repeats": all(x < y for x, y in zip(med[names[0]], med[names[3]])),
+                     "counts_min_max_equal_composition": exact,
+                     "largest_sum_difference_from_composition_over_largest_sum": (func[..., 1:4] - comp[..., 1:4]).abs().amax().item() / scale})
+    finally:
+        eng.close()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+def end_to_end_rows(H, n_chains, n_iter, thins, repeats, ess_lags=None, cov_probes=None, residual=False, local=None, regions=None):
     import torch
     from mcmc_gpu_amd import MCMC_gpu, synthetic
     prob, ch, rf = synthetic.template(H)
     beds = synthetic.initial_beds(prob, n_chains)
     seeds = list(range(1000, 1000 + n_chains))
-    if local:
+    if regions is not None:
+        K, bins = regions
+        m = _bench_regions(H, H, K)
+        sea = float(np.median(prob["bed"]))
+        ropt = dict(masks=m, sea_level=sea, hyps=dict(lo=float(prob["bed"].min()) - 50.0, hi=float(prob["bed"].max()) + 50.0, bins=bins) if bins else None)
+        configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
+                  [(f"thin={t} rhat=True regions {K} hyps {bins}", dict(burn_in=0, thin=t, regions=ropt)) for t in thins]
+    elif local:
         configs = [("no posterior", None)] + [(f"thin={t} rhat=True", dict(burn_in=0, thin=t)) for t in thins] + \
                   [(f"thin={t} rhat=True local reach {R}", dict(burn_in=0, thin=t, local=dict(reach=R))) for t in thins for R in local]
     elif residual:
@@ -489,7 +607,10 @@ def main():
                     "composition of existing entry points, and run_many with and without residual")
     ap.add_argument("--local", type=int, nargs="+", default=None, metavar="R", help="only the pass of the covariance with the neighbours at "
                     "every reach given, beside the stream copy of the beds and the torch composition, and run_many with and without local")
-    ap.add_argument("--no-end-to-end", action="store_true", help="with --residual or --local: the kernel rows alone")
+    ap.add_argument("--regions", type=int, default=0, metavar="K", help="only the region pass with K regions beside the stream copy of the beds, "
+                    "the project pass at the same K and the torch composition, and run_many with and without regions")
+    ap.add_argument("--hyps", type=int, default=0, metavar="B", help="with --regions: B hypsometry bins (even, <= 64; 0 = none)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --residual, --local or --regions: the kernel rows alone")
     args = ap.parse_args()
     if args.cov and not 1 <= args.cov <= 15:
         raise SystemExit("--cov takes 1 .. 15 probes")
@@ -501,10 +622,21 @@ def main():
         raise SystemExit("--local takes reaches in 1 .. 4")
     if args.local and args.out is None and not args.quick:
         args.out = str(ROOT / "profiles" / "posterior_bench_local.json")
+    if args.regions and not (1 <= args.regions <= 8 and (args.hyps == 0 or (2 <= args.hyps <= 64 and args.hyps % 2 == 0))):
+        raise SystemExit("--regions takes 1 .. 8 regions and --hyps 0 or an even number of bins in 2 .. 64")
+    if args.regions and args.out is None and not args.quick:
+        args.out = str(ROOT / "profiles" / "posterior_bench_regions.json")
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured (there is no CPU fallback)")
     rows = []
-    if args.hist:
+    if args.regions:
+        for state in ("f64", "f32"):
+            rows += regions_rows(8, 64, state, args.regions, args.hyps, 3, 1) if args.quick else \
+                regions_rows(1024, 256, state, args.regions, args.hyps, max(args.reps, 20), args.repeats)
+        if not args.no_end_to_end:
+            rows += end_to_end_rows(64, 8, 1701, [100], 1, regions=(args.regions, args.hyps)) if args.quick else \
+                end_to_end_rows(256, 1024, 20001, [100], args.repeats, regions=(args.regions, args.hyps))
+    elif args.hist:
         for state in ("f64", "f32"):
             rows += hist_rows(8, 64, 64, state, 3) if args.quick else hist_rows(1024, 256, 256, state, args.reps)
     elif args.local:
